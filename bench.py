@@ -2,7 +2,7 @@
 """bench.py — aggregate emulated DSP MIPS of the MI355X batch FX8010 interpreter.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--config config5] [--samples S]
-                    [--instances M] [--sharded] [--no-extras] [--parity-instances P]
+                    [--instances M] [--sharded] [--dump-outputs DIR] [--full [--no-extras] [--parity-instances P]]
 
 One "step" = one pass of the hot path over one batch of synthetic PCM: fxb_process_block_dev()
 for S sample periods on this rank's instances (inputs already resident in HBM).  The default
@@ -24,11 +24,17 @@ handle (fxb_create_sharded: one host thread + stream per device, SURVEY.md secti
 Output: ONE JSON line (rank 0) with the contract fields plus
   roofline      HBM roofline of the kernel (algorithmic bytes / HIP-event kernel time / 8 TB/s), and next to it
                 roofline.valu: the vector-ALU issue roofline that actually bounds this path
+A plain run does nothing else: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.  --full adds
   cpu_baseline  the unmodified reference (oracle/_ref) timed on this box's host cores (N = 1 only)
   parity        instances of the timed run compared bit for bit with the CPU oracle after the timed region
   extra         (N = 1, default workload only) the other single-GPU configurations, the 1/8 shard of configs[4]
                 (what every GPU of an 8-GPU job runs) and the reference's own real-time measure (32-sample blocks
                 against 666.667 us, tools/realtime_capacity.py)
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of fxb_process_block_dev receives it: DIR/pcm_out.npy,
+float32 [S, k], the output PCM of k instances of this rank's range (all of them, or a fixed seeded sample of at most 32 MiB that
+always holds the first and the last).  The stimulus is a counter-based hash of (instance, sample), so the same arguments give
+the same inputs in every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -59,9 +65,13 @@ def parse():
                     help="strong (default): the config's instance count is the WHOLE job, split over the GPUs (configs[4]: 2 097 152 'sharded across 8'); "
                          "weak: every GPU runs the config's per-GPU share (config5: 262 144) whatever their number")
     ap.add_argument("--instances", type=int, default=0, help="instances (strong: of the whole job; weak: per GPU); 0 = BASELINE.json's count")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (rank 0, N=1 only); 0 disables")
-    ap.add_argument("--parity-instances", type=int, default=1024, help="instances checked against the oracle after the timed region (0 disables)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other configurations (they run by default for N=1, default workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the parity check against the oracle "
+                         "and (N=1, default workload) the other configurations and the real-time measure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the output PCM of the last timed step (a fixed seeded sample of it) to DIR/pcm_out.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (rank 0, N=1 only); 0 disables")
+    ap.add_argument("--parity-instances", type=int, default=1024, help="--full: instances checked against the oracle after the timed region (0 disables)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the other configurations (they run by default for N=1, default workload)")
     ap.add_argument("--sharded", action="store_true", help="one process, --gpus devices through fxb_create_sharded")
     ap.add_argument("--cpu-baseline", default="reference", choices=["reference", "port"],
                     help="what is timed on the host cores: 'reference' = oracle/_ref/libfxref.so, the UNMODIFIED reference compiled by `make -C oracle ref` "
@@ -233,6 +243,30 @@ def parity_check(text, y_last, n_inst, first_instance, n_samples, blocks, want, 
             "seconds": round(time.perf_counter() - t0, 1)}
 
 
+DUMP_MAX_WORDS = 8 << 20   # 32 MiB of float32 per dump
+
+
+def dump_outputs(torch, dirname, ys, cuts, n_local, n_samples):
+    """--dump-outputs: the output PCM of the last launch, [S, k] float32, for k instances of [0, n_local) - all of them when
+    they fit in DUMP_MAX_WORDS, else a sample fixed by a constant seed and n_local (the first and the last always in it).
+    ys: the output buffers of the shards, cuts: (first instance, count) of each."""
+    import numpy as np
+
+    k = max(1, DUMP_MAX_WORDS // n_samples)
+    if n_local <= k:
+        picks = np.arange(n_local)
+    else:
+        rng = np.random.default_rng(0xF8010)
+        picks = np.unique(np.concatenate([[0, n_local - 1], rng.choice(n_local, k - 2, replace=False)]))
+    cols = []
+    for y, (f, c) in zip(ys, cuts):
+        sel = picks[(picks >= f) & (picks < f + c)] - f
+        if len(sel):
+            cols.append(y.index_select(1, torch.as_tensor(sel, device=y.device)).cpu().numpy())
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pcm_out.npy"), np.ascontiguousarray(np.concatenate(cols, axis=1), dtype=np.float32))
+
+
 def kernel_name(batch):
     kid = batch.info("kernel")
     vg = (0, 0, 64, 72, 80, 96, 128, 168, 256)
@@ -301,7 +335,8 @@ class ClockSampler:
         return (round(sum(f) / len(f) / 1e6, 1) if f else None), (round(sum(w) / len(w) / 1e6, 1) if w else None)
 
 
-def run_workload(torch, fx8010_amd, progs, shard, config, n_local, first_instance, scaling, S, steps, warmup, devices, rank, dist, reduce_dev, parity_n):
+def run_workload(torch, fx8010_amd, progs, shard, config, n_local, first_instance, scaling, S, steps, warmup, devices, rank, dist, reduce_dev, parity_n,
+                 dump_dir=None):
     """One configuration on this process's device(s): instances [first_instance, first_instance + n_local) of the job
     (--sharded: split once more over this process's devices by the library).  Returns (fields for the JSON line, batch text)."""
     text = progs.CONFIGS[config]()
@@ -375,9 +410,12 @@ def run_workload(torch, fx8010_amd, progs, shard, config, n_local, first_instanc
     n_job = int(round(shard.reduce_scalar(dist, n_local, "sum", reduce_dev)))
     per_gpu_instances = [c for _, _, c in batch.shards()] if sharded else [int(round(v)) for v in shard.gather_scalars(dist, n_local, reduce_dev)]
 
+    cuts = [(f, c) for _, f, c in batch.shards()]
+    if rank == 0 and dump_dir:
+        dump_outputs(torch, dump_dir, ys, cuts, n_local, S)
+
     parity = None
     if rank == 0 and parity_n > 0:
-        cuts = [(f, c) for _, f, c in batch.shards()]
 
         def y_last(n):
             for k, (f, c) in enumerate(cuts):
@@ -515,7 +553,7 @@ def main():
     else:
         first, n_local, _ = plan_instances(args.config, args.scaling, args.instances, world, rank, progs, shard)
     res, text = run_workload(torch, fx8010_amd, progs, shard, args.config, n_local, first, args.scaling, S, args.steps, args.warmup, devices, rank, dist,
-                             reduce_dev, args.parity_instances)
+                             reduce_dev, args.parity_instances if args.full else 0, args.dump_outputs)
 
     if rank == 0:
         out = {
@@ -539,9 +577,9 @@ def main():
         if "parity" in res:
             out["parity"] = res["parity"]
         single = n_gpus == 1
-        if single and args.cpu_seconds > 0:
+        if args.full and single and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(text, args.cpu_seconds, args.cpu_baseline)
-        if single and not args.no_extras and args.config == "config5" and args.scaling == "strong" and not args.instances and S == 4096:
+        if args.full and single and not args.no_extras and args.config == "config5" and args.scaling == "strong" and not args.instances and S == 4096:
             # the other single-GPU configurations of BASELINE.json at their instance counts, and the 1/8 shard of configs[4]
             # (262 144 instances: what every GPU of the 8-GPU job runs - the N = 8 point of the strong-scaling curve is 8 x this);
             # fewer launches each, same block length

@@ -56,3 +56,33 @@ def test_the_default_is_strong_scaling_over_configs4():
     assert progs.CONFIG_TOTAL_INSTANCES["config5"] == 2097152 and progs.CONFIG_INSTANCES["config5"] * 8 == 2097152
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert "2097152 instances sharded across 8" in base["configs"][4]
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        plain = bench.parse()
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        full = bench.parse()
+    finally:
+        sys.argv = saved
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert full.full and full.dump_outputs == "out"
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_size_limit(tmp_path):
+    """--dump-outputs: the same columns of the output for the same instance count, whatever the shards, at most 32 MiB"""
+    import numpy as np
+    import torch
+
+    S, N = 4096, 5000
+    y = torch.arange(S * N, dtype=torch.float32).reshape(S, N) % 65521.0
+    bench.dump_outputs(torch, str(tmp_path / "a"), [y], [(0, N)], N, S)
+    bench.dump_outputs(torch, str(tmp_path / "b"), [y[:, :1234], y[:, 1234:]], [(0, 1234), (1234, N - 1234)], N, S)
+    a, b = np.load(tmp_path / "a" / "pcm_out.npy"), np.load(tmp_path / "b" / "pcm_out.npy")
+    assert a.dtype == np.float32 and a.nbytes <= bench.DUMP_MAX_WORDS * 4 and a.shape[0] == S and a.shape[1] <= bench.DUMP_MAX_WORDS // S
+    assert np.array_equal(a, b)
+    assert np.array_equal(a[:, 0], y[:, 0].numpy()) and np.array_equal(a[:, -1], y[:, N - 1].numpy())
+    bench.dump_outputs(torch, str(tmp_path / "c"), [y[:, :40]], [(0, 40)], 40, S)
+    assert np.array_equal(np.load(tmp_path / "c" / "pcm_out.npy"), y[:, :40].numpy())

@@ -687,7 +687,7 @@ def test_bench_through_rccl_with_one_rank(gpu, tmp_path):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
                         os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "config3", "--instances", "4096", "--samples", "256",
-                        "--parity-instances", "8", "--cpu-seconds", "0", "--no-extras"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+                        "--full", "--parity-instances", "8", "--cpu-seconds", "0", "--no-extras"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.split("\n") if l.startswith("{")][-1]
     d = json.loads(line)
@@ -710,7 +710,7 @@ def test_bench_splits_the_job_over_two_ranks(gpu, scaling):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
                         os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "config3", "--instances", "4100", "--samples", "128",
-                        "--scaling", scaling, "--parity-instances", "8", "--cpu-seconds", "0", "--no-extras"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--scaling", scaling, "--full", "--parity-instances", "8", "--cpu-seconds", "0", "--no-extras"], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])

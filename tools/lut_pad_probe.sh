@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 run() {
   local label=$1; shift
   local v
-  v=$(env "$@" python3 bench.py --config config4 --steps 5 --warmup 1 --no-extras --cpu-seconds 0 --parity-instances 64 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['roofline']['kernel_ms'], d['roofline']['valu']['valu_per_wave_sample'], d.get('parity',{}).get('parity_ok'))")
+  v=$(env "$@" python3 bench.py --config config4 --steps 5 --warmup 1 --full --no-extras --cpu-seconds 0 --parity-instances 64 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['roofline']['kernel_ms'], d['roofline']['valu']['valu_per_wave_sample'], d.get('parity',{}).get('parity_ok'))")
   echo "$label: MIPS kernel_ms valu/wave-sample parity = $v"
 }
 run "baseline            " FX_X=0

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for round in 1 2 3; do
   for w in 0 1; do
-    FX_XLATE_LUTWIDE=$w python3 $ROOT/bench.py --config config4 --steps 10 --warmup 2 --no-extras --cpu-seconds 0 --parity-instances 64 2>/dev/null | python3 -c "
+    FX_XLATE_LUTWIDE=$w python3 $ROOT/bench.py --config config4 --steps 10 --warmup 2 --full --no-extras --cpu-seconds 0 --parity-instances 64 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); v = d['roofline']['valu']
 print('round $round wide=$w: %.4e instr/s  kernel %.3f ms  %s MHz  %s W  valu/wave-sample %d  parity %s' % (d['value'] * 1e6, d['roofline']['kernel_ms'], v['clock_mhz'], v['power_w'], v['valu_per_wave_sample'], d['parity']['parity_ok']))"

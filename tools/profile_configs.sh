@@ -20,7 +20,7 @@ for spec in $CONFIGS; do
   cfg=${rest%%:*}; more=${rest#*:}; [ "$more" = "$rest" ] && more=""
   more=${more//,/ }
   echo "== $c: bench ($cfg $more)" 
-  python3 $ROOT/bench.py --config $cfg $more --cpu-seconds 0 --no-extras > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || exit 1
+  python3 $ROOT/bench.py --config $cfg $more --full --cpu-seconds 0 --no-extras > $OUT/${c}_bench.json 2> $OUT/${c}_bench.err || exit 1
   cat $OUT/${c}_bench.json
   echo "== $c: kernel trace"
   rocprofv3 --kernel-trace --stats -d $OUT/${c}_trace -o ${c} --output-format csv -- python3 $ROOT/bench.py --config $cfg $more --cpu-seconds 0 --no-extras --parity-instances 0 > $OUT/${c}_bench_under_rocprof.json 2> $OUT/${c}_trace.err || exit 1

@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 run() {
   local label=$1 cfg=$2; shift 2
   local v
-  v=$(env "$@" python3 bench.py --config $cfg --steps 20 --warmup 2 --no-extras --cpu-seconds 0 --parity-instances 16 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['roofline']['kernel_ms'], d['roofline']['valu']['valu_per_wave_sample'], d['roofline']['valu']['stages'], d.get('parity',{}).get('parity_ok'))")
+  v=$(env "$@" python3 bench.py --config $cfg --steps 20 --warmup 2 --full --no-extras --cpu-seconds 0 --parity-instances 16 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['roofline']['kernel_ms'], d['roofline']['valu']['valu_per_wave_sample'], d['roofline']['valu']['stages'], d.get('parity',{}).get('parity_ok'))")
   echo "$label: MIPS kernel_ms valu/group-sample stages parity = $v"
 }
 for cfg in config2 config3; do
