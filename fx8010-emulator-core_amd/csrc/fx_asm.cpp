@@ -232,6 +232,7 @@ const uint64_t* asmHandlerTable(AsmVariant variant, int device, hipError_t* err)
                 a.out = reinterpret_cast<float*>(dbuf);
                 a.n = 64;
                 a.nPad = 256;
+                a.pcmPitch = 64;
                 hipStream_t stream = nullptr;
                 e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);  // (a stream of its own: no device-wide wait)
                 if (e == hipSuccess) e = launchRaw(fn, a, 1, 0, stream);

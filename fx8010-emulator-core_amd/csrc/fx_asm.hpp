@@ -41,6 +41,7 @@ struct AsmArgs {
     int tramDane;            // interpreter builds, bit 0: the opt-in DANE delay-line model is in force (the address counters step once per sample
                              // period); bit 1: multi-pass program (END lies in a SKIP shadow: the kernel runs passes until every lane has executed it);
                              // bit 2: the wavefronts of a SIMD take turns at the top priority, 2^(bits 12:8) ticks of 10 ns each
+    long long pcmPitch;      // instances per PCM row of in / out (>= n; the kernels use channels * pcmPitch * 4 as a 32-bit stride)
 };
 static_assert(offsetof(AsmArgs, lut) == 0x40, "AsmArgs layout");
 static_assert(offsetof(AsmArgs, nLoad) == 0x58, "AsmArgs layout");
@@ -55,7 +56,8 @@ static_assert(offsetof(AsmArgs, tracks) == 0xb8, "AsmArgs layout");
 static_assert(offsetof(AsmArgs, stages) == 0xc0, "AsmArgs layout");
 static_assert(offsetof(AsmArgs, nStages) == 0xc8, "AsmArgs layout");
 static_assert(offsetof(AsmArgs, tramDane) == 0xcc, "AsmArgs layout");
-static_assert(sizeof(AsmArgs) == 0xd0, "AsmArgs layout");
+static_assert(offsetof(AsmArgs, pcmPitch) == 0xd0, "AsmArgs layout");
+static_assert(sizeof(AsmArgs) == 0xd8, "AsmArgs layout");
 
 // handler slots of fx_interp_gfx950.S (fx_interp_table.inc)
 enum AsmSlot : uint32_t {

@@ -34,6 +34,8 @@ const Luts& sharedLuts() {
 }
 constexpr size_t kScratchBytes = 1 << 16;
 inline uint32_t bitsOf(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+// the kernels step through PCM by two 32-bit byte strides: channels * pitch * 4 (a sample period) and pitch * 4 (a channel)
+inline bool pcmStrideTooWide(int channels, int64_t pitch) { return (uint64_t)std::max(channels, 1) * (uint64_t)pitch * 4u >= ((uint64_t)1 << 32); }
 }  // namespace
 
 Batch::Batch(int64_t nInstances, int channels, int device) : prog_(channels), knobs_(ReleaseKnobs::fromEnvironment()) {
@@ -1398,7 +1400,7 @@ int Batch::uploadTracks(int nSamples, hipStream_t s) {
 
 // Tiers without in-kernel tracks (interpreter, HIP C++ kernel): the same schedule by cutting the block at its change
 // points and writing the registers in between - what the caller would have had to do.
-int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream) {
+int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch) {
     std::vector<PendingTrack> tracks;
     tracks.swap(pendingTracks_);
     pendingTracks_.resize(trackRegs_.size());
@@ -1407,7 +1409,7 @@ int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples,
         for (int k = 0; k < t.steps && (int64_t)k * t.period < nSamples; ++k) cuts.push_back(k * t.period);
     std::sort(cuts.begin(), cuts.end());
     cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-    const size_t rowFloats = (size_t)prog_.numChannels * (size_t)n_;
+    const size_t rowFloats = (size_t)prog_.numChannels * (size_t)pitch;   // floats per sample period
     for (size_t c = 0; c + 1 < cuts.size(); ++c) {
         const int lo = cuts[c], hi = cuts[c + 1];
         for (size_t k = 0; k < tracks.size(); ++k) {
@@ -1418,7 +1420,7 @@ int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples,
             if (rc != 0) return rc < 0 ? rc : fail(FX_E_ARG, "track: register vanished");
         }
         controlHeat_ = 0;  // these writes are the schedule, not a moving slider
-        const int rc = processDevice(dIn + (size_t)lo * rowFloats, dOut + (size_t)lo * rowFloats, hi - lo, stream);
+        const int rc = processDevice(dIn + (size_t)lo * rowFloats, dOut + (size_t)lo * rowFloats, hi - lo, stream, pitch);
         if (rc != 0) return rc;
     }
     return 0;
@@ -1463,9 +1465,12 @@ void Batch::noteBlockLength(int nSamples) {
     wantedClass_ = was;
 }
 
-int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream) {
+int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch) {
     (void)hipSetDevice(device_);
     if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
+    if (pitch <= 0) pitch = n_;
+    if (pitch < n_) return fail(FX_E_ARG, "PCM row pitch below the instance count");
+    if (pcmStrideTooWide(prog_.numChannels, pitch)) return fail(FX_E_ARG, "PCM row pitch too wide: channels * pitch * 4 must stay below 2^32");
     if (!piecewise_) {   // (a piece of a pipelined host block: done once for the whole block)
         pendingSamples_ = nSamples;
         if (controlHeat_ > 0 && --controlHeat_ == 0 && c_.deferred) lowDirty_ = true;  // quiet again: translate
@@ -1479,7 +1484,7 @@ int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_
     everLowered_ = true;
     if (nSamples == 0) return 0;
     if (!dIn || !dOut) return fail(FX_E_ARG, "null buffer");
-    if (tracksArmed() && !c_.useXlate) return processWithTrackFallback(dIn, dOut, nSamples, stream);
+    if (tracksArmed() && !c_.useXlate) return processWithTrackFallback(dIn, dOut, nSamples, stream, pitch);
     hipStream_t s = pick(stream);
     if (c_.useXlate && !trackRegs_.empty() && (rc = uploadTracks(nSamples, s)) != 0) return rc;
     KernelArgs a{};
@@ -1495,6 +1500,7 @@ int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_
     a.lut = dLut_;
     a.n = n_;
     a.nPad = nPad_;
+    a.pcmPitch = pitch;
     a.nOps = (int)nOps;
     a.nLoad = (int)c_.low.loadRows.size();
     a.nStore = (int)c_.low.storeRows.size();
@@ -1529,7 +1535,7 @@ int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_
             AsmArgs g{};
             g.steady = a.steady; g.last = a.last; g.rowTable = a.rowTable; g.state = a.state;
             g.in = a.in; g.out = a.out; g.itram = a.itram; g.xtram = a.xtram; g.lut = a.lut;
-            g.n = a.n; g.nPad = a.nPad; g.nLoad = a.nLoad; g.nStore = a.nStore;
+            g.n = a.n; g.nPad = a.nPad; g.pcmPitch = a.pcmPitch; g.nLoad = a.nLoad; g.nStore = a.nStore;
             g.nSamples = a.nSamples; g.channels = a.channels;
             for (int c = 0; c < kMaxChannels; ++c) {
                 g.inOff[c] = a.inRow[c] >= 0 ? a.inRow[c] * (int)c_.low.rowPitch : -1;
@@ -1598,7 +1604,7 @@ int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_
         (void)hipGetLastError();   // (the launch's own error, just read: not a sticky one)
         stagingOff_ = true;
         lowDirty_ = true;
-        return processDevice(dIn, dOut, nSamples, stream);
+        return processDevice(dIn, dOut, nSamples, stream, pitch);
     }
     if (e != hipSuccess) return hipFail(e, "launch fx_step_block");
     launched_ = !untimed_;  // (an untimed launch is synchronised by its caller before anything else happens)
@@ -1653,22 +1659,78 @@ inline bool deviceVisibleRange(const void* host, size_t bytes, const void** devi
     return static_cast<const char*>(last) - static_cast<const char*>(*device) == static_cast<std::ptrdiff_t>(bytes - 1);
 }
 
-// in == out is fine in place (an instance reads its sample before it writes it, and no other instance touches that word); ranges
-// that overlap in any other way need the whole input read before the first output is written: the staged copies do that.
-inline bool overlapButNotEqual(const void* a, const void* b, size_t bytes) {
-    const char *x = static_cast<const char*>(a), *y = static_cast<const char*>(b);
-    return x != y && x < y + bytes && y < x + bytes;
+// Bytes from the first to the last element of a [rows][pitch] PCM block whose instances are columns 0..n-1.
+inline size_t pcmExtent(size_t rows, int64_t n, int64_t pitch) { return ((rows - 1) * (size_t)pitch + (size_t)n) * 4; }
+
+// in == out is fine in place (an instance reads its sample before it writes it, and no other instance touches that word), and so
+// are two footprints that share no element - e.g. two column ranges of one buffer.  Footprints that overlap in any other way need
+// the whole input read before the first output is written: the staged copies do that.  Both have the same pitch: element r * P + c
+// (c < n) of `out` is element r' * P + c' of `in` only if c - c' = m (mod P), m = (out - in) mod P, which |c - c'| < n rules out
+// for n <= m <= P - n.
+inline bool pcmDisjointOrSame(const float* in, const float* out, size_t rows, int64_t n, int64_t pitch) {
+    if (in == out) return true;
+    const size_t bytes = pcmExtent(rows, n, pitch);
+    const char *x = reinterpret_cast<const char*>(in), *y = reinterpret_cast<const char*>(out);
+    if (x + bytes <= y || y + bytes <= x) return true;
+    const std::ptrdiff_t d = y - x;
+    if (d % 4 != 0) return false;
+    int64_t m = (int64_t)(d / 4) % pitch;
+    if (m < 0) m += pitch;
+    return m >= n && m <= pitch - n;
 }
 }  // namespace
+
+int Batch::processDeviceChecked(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream) {
+    (void)hipSetDevice(device_);
+    if (pitch <= 0) pitch = n_;
+    if (pitch < n_) return fail(FX_E_ARG, "PCM row pitch below the instance count");
+    if (pcmStrideTooWide(prog_.numChannels, pitch)) return fail(FX_E_ARG, "PCM row pitch too wide: channels * pitch * 4 must stay below 2^32");
+    if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
+    if (nSamples > 0) {
+        if (!dIn || !dOut) return fail(FX_E_ARG, "null buffer");
+        const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels, bytes = pcmExtent(rows, n_, pitch);
+        if (dIn != checkedIn_ || dOut != checkedOut_ || bytes > checkedBytes_) {
+            checkedIn_ = checkedOut_ = nullptr;
+            if (!pcmDisjointOrSame(dIn, dOut, rows, n_, pitch)) return fail(FX_E_ARG, "input and output overlap without being one buffer");
+            // memory of this device (the runtime's record of the allocation holds the whole footprint), or pinned host memory (its
+            // device address goes to the kernel)
+            auto addressable = [&](const void* p, const void** dev) {
+                hipPointerAttribute_t attr;
+                std::memset(&attr, 0, sizeof(attr));
+                if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+                if (attr.type == hipMemoryTypeHost) return deviceVisibleRange(p, bytes, dev);
+                if (attr.type != hipMemoryTypeDevice || attr.device != device_) return false;
+                hipDeviceptr_t base = nullptr;
+                size_t size = 0;
+                if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess || !base) { (void)hipGetLastError(); return false; }
+                const char *lo = static_cast<const char*>(base), *at = static_cast<const char*>(p);
+                *dev = p;
+                return at >= lo && bytes <= size && static_cast<size_t>(at - lo) <= size - bytes;
+            };
+            const void *devIn = nullptr, *devOut = nullptr;
+            if (!addressable(dIn, &devIn) || (dOut == dIn ? (devOut = devIn, false) : !addressable(dOut, &devOut)))
+                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
+            checkedIn_ = dIn;
+            checkedOut_ = dOut;
+            checkedBytes_ = bytes;
+            checkedDevIn_ = static_cast<const float*>(devIn);
+            checkedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
+        }
+        return processDevice(checkedDevIn_, checkedDevOut_, nSamples, stream, pitch);
+    }
+    return processDevice(dIn, dOut, nSamples, stream, pitch);
+}
 
 int Batch::processHost(const float* in, float* out, int nSamples, int64_t pitch) {
     (void)hipSetDevice(device_);
     if (pitch <= 0) pitch = n_;
     if (pitch < n_) return fail(FX_E_ARG, "host row pitch below the instance count");
+    if (pcmStrideTooWide(prog_.numChannels, pitch)) return fail(FX_E_ARG, "PCM row pitch too wide: channels * pitch * 4 must stay below 2^32");
     if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
     if (nSamples == 0) return ensureLowered();
     if (!in || !out) return fail(FX_E_ARG, "null buffer");
     const size_t count = (size_t)nSamples * prog_.numChannels * (size_t)n_;
+    const size_t rows = (size_t)nSamples * prog_.numChannels;
     // A few KB of PCM (per-sample calls on a handful of instances): two staged copies cost more than the launch.  The kernel
     // reads and writes pinned host memory instead - one launch, one synchronisation.
     if (count <= kPinnedFloats && pitch == n_) {
@@ -1682,6 +1744,7 @@ int Batch::processHost(const float* in, float* out, int nSamples, int64_t pitch)
             }
         }
         if (hPinIn_ && hPinOut_) {
+            ++hostStagedBlocks_;
             std::memcpy(hPinIn_, in, count * 4);
             waitLastLaunch();
             // no event pair around a launch that is waited for right here (last_kernel_ms: -1) - unless schedules are armed:
@@ -1701,12 +1764,16 @@ int Batch::processHost(const float* in, float* out, int nSamples, int64_t pitch)
     // computes.  One launch, one wait.  Measured (tools/realtime_capacity.py, 32-sample blocks of config5): the staged path's
     // copy-out is a shader copy (__amd_rocclr_copyBuffer) that slows a kernel running beside it threefold
     // (profiles/r05_rt_timeline_131072.txt); in place, a block of 131 072 instances takes about what its 16.8 MB each way take the
-    // link.  FX_HOST_PIPELINE=0 keeps the staged copies.
-    if (knobs_.hostPipeline && pitch == n_) {
+    // link.  FX_HOST_PIPELINE=0 keeps the staged copies.  Any row pitch: the kernels address [sample][channel][pitch] - a shard of a
+    // larger batch works on its columns of the caller's buffers, on its own device (this runs on the shard's thread, the device
+    // current: the lookup below is that device's view of the memory).
+    if (knobs_.hostPipeline) {
         const void *dIn = nullptr, *dOut = nullptr;
-        if (!overlapButNotEqual(in, out, count * 4) && deviceVisibleRange(in, count * 4, &dIn) &&
-            (static_cast<const void*>(out) == in ? (dOut = dIn, true) : deviceVisibleRange(out, count * 4, &dOut))) {
-            const int rc = processDevice(static_cast<const float*>(dIn), static_cast<float*>(const_cast<void*>(dOut)), nSamples, stream_);
+        const size_t bytes = pcmExtent(rows, n_, pitch);
+        if (pcmDisjointOrSame(in, out, rows, n_, pitch) && deviceVisibleRange(in, bytes, &dIn) &&
+            (static_cast<const void*>(out) == in ? (dOut = dIn, true) : deviceVisibleRange(out, bytes, &dOut))) {
+            ++hostInplaceBlocks_;
+            const int rc = processDevice(static_cast<const float*>(dIn), static_cast<float*>(const_cast<void*>(dOut)), nSamples, stream_, pitch);
             const hipError_t se = hipStreamSynchronize(stream_);   // (also when the call failed: nothing of it may still touch the caller's memory)
             if (rc != 0) return rc;
             return se == hipSuccess ? 0 : hipFail(se, "synchronising a block on pinned host buffers");
@@ -1726,10 +1793,11 @@ int Batch::processHost(const float* in, float* out, int nSamples, int64_t pitch)
     // Large blocks: copy-in, kernel and copy-out of consecutive pieces overlap.  268 MB each way (tools/host_block_rate.py):
     // pinned caller buffers 6.5 ms instead of 12.7 (both DMA directions at once), pageable ones 9.7 instead of 12.9 (the driver
     // pins them on the fly; a freshly allocated, untouched output buffer costs 2-3 x that in page faults either way).
+    ++hostStagedBlocks_;
     const int pieces = hostPieces(count * 4, nSamples, kHostPieces);
     if (pieces >= 2 && !tracksArmed() && knobs_.hostPipeline)
         return processHostPipelined(in, out, nSamples, pitch, pieces);
-    const size_t rows = (size_t)nSamples * prog_.numChannels, width = (size_t)n_ * 4;
+    const size_t width = (size_t)n_ * 4;
     hipError_t e = pitch == n_ ? hipMemcpyAsync(dIn_, in, count * 4, hipMemcpyHostToDevice, stream_)
                                : hipMemcpy2DAsync(dIn_, width, in, (size_t)pitch * 4, width, rows, hipMemcpyHostToDevice, stream_);
     if (e != hipSuccess) return hipFail(e, "H2D");
@@ -2091,6 +2159,8 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_NUM_INSTRUCTIONS) return (int64_t)prog_.instrs.size();
     if (what == FXB_INFO_NUM_REGISTERS) return (int64_t)prog_.regs.size();
     if (what == FXB_INFO_GRID) return lastGrid_;
+    if (what == FXB_INFO_HOST_STAGED_BLOCKS) return hostStagedBlocks_;
+    if (what == FXB_INFO_HOST_INPLACE_BLOCKS) return hostInplaceBlocks_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

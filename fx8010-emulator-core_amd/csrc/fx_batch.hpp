@@ -42,7 +42,11 @@ public:
     int setRegisterTrack(const std::string& key, const float* values, int nSteps, int period, bool perInstance, int64_t pitch = 0);
 
     int processHost(const float* in, float* out, int nSamples, int64_t pitch = 0);  // synchronous; pitch: instances per host PCM row (0 = n)
-    int processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream);
+    // dIn / dOut: [nSamples][channels][pitch] floats the device can address, this batch's instances are columns 0..n-1 (pitch 0 = n)
+    int processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch = 0);
+    // the same for a caller's pointers: refused (FX_E_ARG, no launch) unless both footprints are memory of this handle's device or
+    // device-visible host memory, and in == out or the two share no element
+    int processDeviceChecked(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream);
     int sync();
     int prepare(int nSamples, bool wait);   // generate the code for blocks of this length now (and wait for the builder thread)
 
@@ -102,7 +106,7 @@ private:
     int ensureState();            // allocate / grow the state block for the current register count
     int ensureTram(const Lowered& low);
     int uploadTracks(int nSamples, hipStream_t s);   // translated tier: header + values -> dTracks_
-    int processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream);  // other tiers: cut the block
+    int processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch);  // other tiers: cut the block
     bool tracked(int reg) const;
     std::vector<uint8_t> laneForced() const;      // the registers with rows in the code that is wanted now: laneForcedFull(), minus the controls a lean variant in force has folded in
     std::vector<uint8_t> laneForcedFull() const;  // forcedLane_ plus the trackable registers
@@ -310,6 +314,13 @@ private:
     hipEvent_t evIn_[kHostPieces] = {}, evDone_[kHostPieces] = {};
     int processHostPipelined(const float* in, float* out, int nSamples, int64_t pitch, int pieces);
     unsigned lastGrid_ = 0;
+    int64_t hostStagedBlocks_ = 0, hostInplaceBlocks_ = 0;   // host blocks by route (FXB_INFO_HOST_STAGED_BLOCKS / _INPLACE_BLOCKS)
+    // processDeviceChecked: the last buffer pair that passed its checks (a real-time caller pays for the lookups once)
+    const float* checkedIn_ = nullptr;
+    const float* checkedOut_ = nullptr;
+    size_t checkedBytes_ = 0;
+    const float* checkedDevIn_ = nullptr;   // ... and the device addresses of the two
+    float* checkedDevOut_ = nullptr;
 #ifdef FX_DIAGNOSTICS
   public:
     // diagnostics build (fx_knobs.hpp): one word per wavefront, written by generated code behind its last sample when

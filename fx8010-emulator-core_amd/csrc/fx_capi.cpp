@@ -195,7 +195,7 @@ int fxb_seed_noise_i(fxb_handle* h, int64_t inst, int32_t x1, int32_t x2) { retu
 void* fxb_host_alloc(int64_t bytes) {
     if (bytes <= 0) { g_createError = "fxb_host_alloc: bytes must be positive"; return nullptr; }
     void* p = nullptr;
-    const hipError_t e = hipHostMalloc(&p, (size_t)bytes, hipHostMallocDefault);
+    const hipError_t e = hipHostMalloc(&p, (size_t)bytes, hipHostMallocPortable);   // (one buffer for every shard's device)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         g_createError = std::string("fxb_host_alloc: ") + hipGetErrorString(e);
@@ -209,6 +209,12 @@ void fxb_host_free(void* p) {
 int fxb_process_block(fxb_handle* h, const float* in, float* out, int n) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.processHost(in, out, n); }) : FX_E_ARG; }
 int fxb_process_block_dev(fxb_handle* h, const float* d_in, float* d_out, int n, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processDevice(d_in, d_out, n, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
+}
+int fxb_process_block_pitched(fxb_handle* h, const float* in, float* out, int n, int64_t pitch) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processHost(in, out, n, pitch > 0 ? pitch : -1); }) : FX_E_ARG;
+}
+int fxb_process_block_dev_pitched(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t pitch, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processDevicePitched(d_in, d_out, n, pitch, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
 }
 int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float* const* d_out, int n) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processDeviceShards(d_in, d_out, n); }) : FX_E_ARG;

@@ -89,7 +89,8 @@
 	.set KA_TRAMDANE, 0xcc      // interpreter builds, bit 0: the opt-in DANE delay-line model (address counters step once per sample period);
 	                            //  bit 1: multi-pass program (END inside a SKIP shadow: lanes that skipped it run the program again);
 	                            //  bit 2: the wavefronts of a SIMD take turns at the top priority, turns of 2^(bits 12:8) ticks of 10 ns
-	.set KA_SIZE,     0xd0
+	.set KA_PCMPITCH, 0xd0      // instances per PCM row of in / out (>= n; only its low dword is read: channels * pitch * 4 < 2^32)
+	.set KA_SIZE,     0xd8
 
 // ---- out-of-domain flag bits (fx_kernel.hpp) ----
 	.set OOD_TRAM_READ_NEG, 1
@@ -110,9 +111,9 @@
 //  s9 nSamples  s[10:11] state  s[12:13] in (this sample)  s[14:15] out (this sample)
 //  s[16:23] current record  s[24:31] next record  s[32:33] branch table  s[34:35] jump target
 //  s[36:37] iTRAM of this wave  s[38:39] xTRAM of this wave  s[40:41] LUT  s[42:43] last-sample stream
-//  s44 channels  s45 bytes per sample (channels*N*4)  s46 iSlots  s47 xSlots  s[48:51] input row offsets
+//  s44 channels  s45 bytes per sample (channels*P*4, P = PCM row pitch)  s46 iSlots  s47 xSlots  s[48:51] input row offsets
 //  s[52:55] latch row offsets  s56 iSize  s57 xSize  s[58:59] lanes with instance < N  s60 state row pitch (nPad*4)
-//  s61 byte offset of x1[] in the LUT blob  s62-s67 temporaries  s68 bytes per channel-sample (N*4)
+//  s61 byte offset of x1[] in the LUT blob  s62-s67 temporaries  s68 bytes per channel-sample (P*4)
 //  s[72:73] row table  s74 nLoad  s75 nStore  s76 cursor state row  s77 LFSR state row
 //  s70 (interpreter builds) bit 0 opt-in DANE delay-line model, bit 1 multi-pass program   s71 passes of this sample period
 //  s[96:97] (interpreter builds) lanes that run the passes of this sample period   s[98:99] lanes that have executed END in it
@@ -206,6 +207,7 @@ KNAME:
 	s_load_dwordx16 s[4:19], s[0:1], KA_STEADY            // steady last rowtab state in out itram xtram
 	s_load_dwordx8  s[40:47], s[0:1], KA_LUT              // lut n npad nload nstore
 	s_load_dwordx2  s[64:65], s[0:1], KA_NSAMPLES         // nSamples channels
+	s_load_dword    s66, s[0:1], KA_PCMPITCH              // instances per PCM row
 	v_lshlrev_b32 v1, 2, v0
 	s_lshl_b32 s62, s2, 6
 	v_add_u32 v27, s62, v0                                // instance
@@ -223,14 +225,14 @@ KNAME:
 	// s[40:41] lut, s[42:43] n, s[44:45] nPad, s46 nLoad, s47 nStore
 	v_cmp_gt_u32 s[58:59], s42, v27                       // lane has an instance (n < 2^31)
 	s_lshl_b32 s60, s44, 2                                // state row pitch in bytes
-	s_lshl_b32 s68, s42, 2                                // bytes of one channel of one sample (N*4)
+	s_lshl_b32 s68, s66, 2                                // bytes of one channel of one sample (P*4)
 	v_lshlrev_b32 v27, 2, v27                             // instance*4
 	s_mov_b32 s9, s64                                     // nSamples
 	s_mov_b32 s74, s46                                    // nLoad
 	s_mov_b32 s75, s47                                    // nStore
 	s_mov_b32 s44, s65                                    // channels
-	s_mul_i32 s45, s42, s44
-	s_lshl_b32 s45, s45, 2                                // bytes per sample of PCM = channels * N * 4
+	s_mul_i32 s45, s66, s44
+	s_lshl_b32 s45, s45, 2                                // bytes per sample of PCM = channels * P * 4
 	s_mov_b64 s[42:43], s[70:71]                          // last-sample stream
 #ifdef XLATE
 	// translated programs: `steady` / `last` are byte offsets of the two code streams from the kernel entry
@@ -1048,11 +1050,11 @@ PNAME:
 amdhsa.kernels:
   - .args:
       - .offset: 0
-        .size: 208
+        .size: 216
         .value_kind: by_value
     .group_segment_fixed_size: 0
     .kernarg_segment_align: 8
-    .kernarg_segment_size: 208
+    .kernarg_segment_size: 216
 #ifdef XLATE
     .max_flat_workgroup_size: 1024
 #else
@@ -1067,11 +1069,11 @@ amdhsa.kernels:
 #ifndef XLATE
   - .args:
       - .offset: 0
-        .size: 208
+        .size: 216
         .value_kind: by_value
     .group_segment_fixed_size: 0
     .kernarg_segment_align: 8
-    .kernarg_segment_size: 208
+    .kernarg_segment_size: 216
     .max_flat_workgroup_size: 64
     .name: PNAME
     .private_segment_fixed_size: 0

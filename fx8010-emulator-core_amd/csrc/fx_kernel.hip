@@ -506,7 +506,9 @@ __global__ __launch_bounds__(64) void fx_step_block(const KernelArgs a) {
     const long long inst0 = (wave * 64 + lane) * K;  // first of this lane's K instances
     const long long left = a.n - inst0;
     const int nValid = left >= K ? K : (left > 0 ? (int)left : 0);
-    const bool vecIo = (nValid == K) && ((a.n % K) == 0);  // aligned, complete run of K instances
+    // aligned, complete run of K instances: every PCM row starts on a K-instance boundary (a column range of a larger buffer
+    // may not: then the per-instance path)
+    const bool vecIo = (nValid == K) && ((a.pcmPitch % K) == 0) && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) % (4u * K) == 0);
 
     Ctx<K> c;
     c.lane = smem + lane * 4 * K;
@@ -525,12 +527,12 @@ __global__ __launch_bounds__(64) void fx_step_block(const KernelArgs a) {
     }
     for (int i = 0; i < a.nZero; ++i) ldsStore<K>(c.lane, rowTable[a.nLoad + a.nStore + i] * ROWB, splat<K>(0.0f));
 
-    const size_t n = (size_t)a.n;
+    const size_t pitch = (size_t)a.pcmPitch;  // PCM row: [S][CH][pitch], this batch's instances are columns 0..n-1
     const int CH = a.channels;
     Vec<K> nextIn[kMaxChannels];
 #pragma unroll
     for (int ch = 0; ch < kMaxChannels; ++ch)
-        nextIn[ch] = (ch < CH && a.inRow[ch] >= 0 && a.nSamples > 0) ? gLoad<K>(a.in + (size_t)ch * n + inst0, vecIo, nValid) : splat<K>(0.0f);
+        nextIn[ch] = (ch < CH && a.inRow[ch] >= 0 && a.nSamples > 0) ? gLoad<K>(a.in + (size_t)ch * pitch + inst0, vecIo, nValid) : splat<K>(0.0f);
 
     bool allRun[K];
 #pragma unroll
@@ -543,7 +545,7 @@ __global__ __launch_bounds__(64) void fx_step_block(const KernelArgs a) {
         if (s + 1 < a.nSamples) {
 #pragma unroll
             for (int ch = 0; ch < kMaxChannels; ++ch)
-                if (ch < CH && a.inRow[ch] >= 0) nextIn[ch] = gLoad<K>(a.in + ((size_t)(s + 1) * CH + ch) * n + inst0, vecIo, nValid);
+                if (ch < CH && a.inRow[ch] >= 0) nextIn[ch] = gLoad<K>(a.in + ((size_t)(s + 1) * CH + ch) * pitch + inst0, vecIo, nValid);
         }
 
         ConstU32 prog = (ConstU32)((s == a.nSamples - 1) ? a.last : a.steady);
@@ -619,7 +621,7 @@ __global__ __launch_bounds__(64) void fx_step_block(const KernelArgs a) {
 
 #pragma unroll
         for (int ch = 0; ch < kMaxChannels; ++ch)
-            if (ch < CH) gStore<K>(a.out + ((size_t)s * CH + ch) * n + inst0, ldsLoad<K>(c.lane, (uint32_t)a.latchRow[ch] * ROWB), vecIo, nValid);
+            if (ch < CH) gStore<K>(a.out + ((size_t)s * CH + ch) * pitch + inst0, ldsLoad<K>(c.lane, (uint32_t)a.latchRow[ch] * ROWB), vecIo, nValid);
         if (a.tramDane) {  // opt-in delay-line model: the address counters step once per sample period
             daneStep<K>(c, a.iSize, a.cursorOff);
             daneStep<K>(c, a.xSize, a.cursorOff + 2u * ROWB);

@@ -26,8 +26,8 @@ struct KernelArgs {
     const uint32_t* last;      // stream for the final sample of the block
     const uint32_t* rowTable;  // nLoad + nStore entries ldsRow | stateRow << 16, then nZero LDS rows to clear
     uint32_t* state;           // [rows][nPad] 32-bit words, instance-fastest
-    const float* in;           // [S][CH][N]
-    float* out;                // [S][CH][N]
+    const float* in;           // [S][CH][pcmPitch]: the batch's instances are columns 0..n-1
+    float* out;                // [S][CH][pcmPitch]
     float* itram;              // [wave][iSlots][64][K]
     float* xtram;              // [wave][xSlots][64][K]
     const double* lut;         // LutDevice blob (fx_model.hpp): thresholds, x1, per-table {slope, y1}
@@ -50,6 +50,7 @@ struct KernelArgs {
     int hasShadow;
     int instPerLane;     // K: 1, 2 or 4
     int tramDane;        // opt-in DANE delay-line model: the two write-cursor rows are per-sample address counters
+    long long pcmPitch;  // instances per PCM row (>= n; channels * pcmPitch * 4 < 2^32)
 };
 
 // grid = ceil(n / (64*K)) workgroups of one wavefront; dynamic LDS = nRows*256*K bytes.

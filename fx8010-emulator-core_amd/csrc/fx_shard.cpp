@@ -225,14 +225,18 @@ int Sharded::setRegisterTrack(const std::string& key, const float* values, int n
     return fan([&](int k, Batch& b) { return b.setRegisterTrack(key, perInstance ? values + shards_[(size_t)k]->first : values, nSteps, period, perInstance, n_); });
 }
 
-int Sharded::processHost(const float* in, float* out, int nSamples) {
+int Sharded::processHost(const float* in, float* out, int nSamples, int64_t pitch) {
     Serial serial(api_);
     lastError_.clear();
-    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.processHost(in, out, nSamples); });
+    if (pitch == 0) pitch = n_;
+    if (pitch < n_) { lastError_ = "host row pitch below the instance count"; return FX_E_ARG; }
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.processHost(in, out, nSamples, pitch); });
     if (nSamples > 0 && (!in || !out)) { lastError_ = "null buffer"; return FX_E_ARG; }
+    // each shard on its own thread, its device current: in place on its columns when that device can address the buffers, staged
+    // copies of its columns otherwise (only that shard)
     return fan([&](int k, Batch& b) {
         const int64_t first = shards_[(size_t)k]->first;
-        return b.processHost(in ? in + first : in, out ? out + first : out, nSamples, n_);
+        return b.processHost(in ? in + first : in, out ? out + first : out, nSamples, pitch);
     });
 }
 int Sharded::processDeviceShards(const float* const* dIn, float* const* dOut, int nSamples) {
@@ -246,6 +250,12 @@ int Sharded::processDevice(const float* dIn, float* dOut, int nSamples, hipStrea
     lastError_.clear();
     if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
     return runOn(0, [&](Batch& b) { return b.processDevice(dIn, dOut, nSamples, stream); });
+}
+int Sharded::processDevicePitched(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
+    return runOn(0, [&](Batch& b) { return b.processDeviceChecked(dIn, dOut, nSamples, pitch, stream); });
 }
 int Sharded::sync() {
     Serial serial(api_);
@@ -352,7 +362,7 @@ int64_t Sharded::info(int what) {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
-    if (what == FXB_INFO_GRID) {
+    if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

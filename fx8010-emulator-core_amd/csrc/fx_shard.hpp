@@ -57,13 +57,16 @@ public:
     void setChannels(int c);
     int setOption(unsigned option, bool on);
 
-    // host buffers [sample][channel][all instances]: every shard copies its columns in, runs, copies them out
-    int processHost(const float* in, float* out, int nSamples);
+    // host buffers [sample][channel][pitch] (pitch >= all instances; 0 = all of them, a negative one is refused): every shard works on its own columns - in
+    // place where the buffers are pinned memory its device can address, else it copies its columns in, runs, copies them out
+    int processHost(const float* in, float* out, int nSamples, int64_t pitch = 0);
     // device-resident buffers, one pair per shard: dIn[k] / dOut[k] are [sample][channel][count_k] on shard k's device;
     // asynchronous (pair with sync())
     int processDeviceShards(const float* const* dIn, float* const* dOut, int nSamples);
     // single shard only: the caller's stream
     int processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream);
+    // ... with a row pitch; the buffers are checked first (Batch::processDeviceChecked)
+    int processDevicePitched(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream);
     int sync();
     int prepare(int nSamples, bool wait);
 

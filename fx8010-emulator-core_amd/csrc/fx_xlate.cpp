@@ -603,9 +603,11 @@ class Translator {
         e_.sop2(SOP2_SUB_I32, "s_sub_i32", sreg(kSTemp + 2), sreg(kSNumSamples), sreg(kSSample));   // samples from s on
         if (first) {
             e_.sop2(SOP2_SUB_I32, "s_sub_i32", sreg(kSTemp + 2), sreg(kSTemp + 2), imm32((uint32_t)first));
+            // 8 samples ahead: 8 x bytes per sample, 64-bit (a PCM row pitch wider than the batch makes a sample up to 4 GB)
             e_.sop2(SOP2_LSHL_B32, "s_lshl_b32", sreg(kSTemp + 3), sreg(kSSampleBytes), imm32(3));
+            e_.sop2(SOP2_LSHR_B32, "s_lshr_b32", sreg(kSTemp + 4), sreg(kSSampleBytes), imm32(29));
             e_.sop2(SOP2_ADD_U32, "s_add_u32", sreg(kSAddr), sreg(kSPcmIn), sreg(kSTemp + 3));
-            e_.sop2(SOP2_ADDC_U32, "s_addc_u32", sreg(kSAddr + 1), sreg(kSPcmIn + 1), imm32(0));
+            e_.sop2(SOP2_ADDC_U32, "s_addc_u32", sreg(kSAddr + 1), sreg(kSPcmIn + 1), sreg(kSTemp + 4));
         } else {
             e_.sop1(SOP1_MOV_B64, "s_mov_b64", sreg64(kSAddr), sreg64(kSPcmIn));
         }

@@ -24,6 +24,7 @@ INFO = {
     "waves_per_wg": 5, "num_microops": 6, "itram_slots": 7, "xtram_slots": 8, "tram_ops": 9, "multipass": 10,
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
+    "host_staged_blocks": 33, "host_inplace_blocks": 34,
 }
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
@@ -33,6 +34,7 @@ SYMBOLS = [
     "fx_meta_get", "fx_set_option", "fxb_set_option", "fxp_set_option", "fx_set_channels", "fx_get_channels", "fx_ready", "fx_last_error", "fx_last_create_error",
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
+    "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -83,6 +85,7 @@ def load():
     sig("fxb_get_register_i", f32, vp, cp, i64); sig("fxb_seed_noise_i", i32, vp, i64, C.c_int32, C.c_int32)
     sig("fxb_process_block", i32, vp, _f32p, _f32p, i32)
     sig("fxb_process_block_dev", i32, vp, vp, vp, i32, vp); sig("fxb_sync", i32, vp)
+    sig("fxb_process_block_pitched", i32, vp, vp, vp, i32, i64); sig("fxb_process_block_dev_pitched", i32, vp, vp, vp, i32, i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -387,9 +390,30 @@ class Batch(_Reports):
         self._check(self._lib.fxb_get_cursors_i(self._h, int(inst), buf), "get_cursors_i")
         return list(buf)
 
+    def _row_pitch(self, shape, strides):
+        """P when strides (in floats) of an [S, channels, N] array walk a [S][channels][P] buffer, else None"""
+        S, ch, n = shape
+        if (ch, n) != (self.channels, self.n) or strides[2] != 1:
+            return None
+        if ch > 1:
+            p = strides[1]
+            return p if p >= n and (S <= 1 or strides[0] == ch * p) else None
+        return (strides[0] if strides[0] >= n else None) if S > 1 else n
+
     def process_block(self, x, out=None):
         """x: float32 [S, N] (mono) or [S, channels, N]; returns the same shape (into `out` when given: e.g. a view of pinned
-        memory - large blocks from pinned buffers are copied at DMA rate and overlap with the kernel)."""
+        memory - large blocks from pinned buffers are copied at DMA rate and overlap with the kernel).  Column slices of a
+        larger [S, channels, P] buffer (pin[:, :, lo:hi]) go to the library as they are, x and out with one common P: in place
+        when the buffer is pinned."""
+        if out is not None and isinstance(x, np.ndarray) and x.ndim == 3 and x.shape[0] > 0:
+            def pitch(a):
+                ok = isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 3 and all(t % 4 == 0 for t in a.strides)
+                return self._row_pitch(a.shape, [t // 4 for t in a.strides]) if ok else None
+            px, po = pitch(x), pitch(out)
+            if px is not None and px == po and out.flags["WRITEABLE"] and not (x.flags["C_CONTIGUOUS"] and out.flags["C_CONTIGUOUS"]):
+                self._check(self._lib.fxb_process_block_pitched(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), x.shape[0], px),
+                            "process_block")
+                return out
         x = np.ascontiguousarray(x, dtype=np.float32)
         S = x.shape[0]
         assert x.size == S * self.channels * self.n, "input must be [S, channels, N]"
@@ -402,6 +426,24 @@ class Batch(_Reports):
     def process_block_dev(self, d_in, d_out, n_samples, stream=None):
         """device pointers (ints); asynchronous."""
         return self._check(self._lib.fxb_process_block_dev(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n_samples, C.c_void_p(stream or 0)), "process_block_dev")
+
+    def process_block_dev_pitched(self, d_in, d_out, n_samples, pitch=None, stream=None):
+        """d_in / d_out: device pointers (ints) of [n_samples][channels][pitch] floats whose columns 0..N-1 are this handle's
+        instances, or torch device tensors [n_samples, channels, N] (column slices of a wider tensor included; the pitch comes
+        from stride()).  Buffers the handle's device cannot address are refused without a launch.  Asynchronous."""
+        def ptr(t):
+            if isinstance(t, int):
+                return t, None
+            assert t.element_size() == 4 and t.dim() == 3 and tuple(t.shape) == (n_samples, self.channels, self.n), "[S, channels, N] float32"
+            p = self._row_pitch(tuple(t.shape), tuple(t.stride()))
+            assert p is not None, "rows of one pitch: [S][channels][P]"
+            return t.data_ptr(), p
+        (a, pa), (b, pb) = ptr(d_in), ptr(d_out)
+        p = pitch if pitch is not None else (pa if pa is not None else pb)
+        assert p is not None, "pitch: give it with pointers"
+        assert pa in (None, p) and pb in (None, p), "d_in and d_out with one common pitch"
+        return self._check(self._lib.fxb_process_block_dev_pitched(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(p), C.c_void_p(stream or 0)),
+                           "process_block_dev_pitched")
 
     def sync(self):
         return self._check(self._lib.fxb_sync(self._h), "sync")

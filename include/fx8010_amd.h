@@ -125,8 +125,10 @@ fxb_handle* fxb_create(int64_t n_instances, int num_channels, int device);
  * much more DSP's" on many cores): contiguous instance ranges, whole wavefronts per shard, one host thread + one HIP
  * stream per shard inside the library, program / tables / broadcast controls replicated, NO exchange between shards.
  * Every fxb_* call works on such a handle unchanged (instances keep their global numbers; host PCM buffers keep the
- * [sample][channel][all instances] layout and each shard copies its own columns); device-resident PCM is per device and
- * goes through fxb_process_block_dev_shards.
+ * [sample][channel][all instances] layout and each shard works on its own columns: in place where the buffers are pinned
+ * memory its device can address - fxb_host_alloc asks for memory that every device may map - with staged copies of its
+ * columns otherwise);
+ * device-resident PCM is per device and goes through fxb_process_block_dev_shards.
  *   fxb_create_sharded     one shard per set bit of device_mask (bit d = HIP ordinal d), in ordinal order
  *   fxb_create_on_devices  one shard per list entry; an ordinal may repeat (several shards on one GPU) */
 fxb_handle* fxb_create_sharded(int64_t n_instances, int num_channels, uint64_t device_mask);
@@ -200,6 +202,11 @@ int fxb_get_cursors_i(fxb_handle* h, int64_t instance, int32_t* out4);
  * straddles the end of a hipHostRegister range is refused by the runtime's copy itself: FX_E_NODEVICE with its message;
  * the handle stays usable). */
 int fxb_process_block(fxb_handle* h, const float* in, float* out, int n_samples);
+/* in/out: [n_samples][num_channels][pitch] floats; the handle's instances are columns 0..N-1 from in/out (pass base + first
+ * column).  pitch >= N (N = all instances of a sharded handle); pitch == N is fxb_process_block.  Pinned buffers: in place,
+ * every shard on its own columns; columns outside the handle's range are never read or written.  Several handles may work on
+ * disjoint column ranges of one buffer at the same time.  num_channels * pitch * 4 must stay below 2^32 (FX_E_ARG otherwise). */
+int fxb_process_block_pitched(fxb_handle* h, const float* in, float* out, int n_samples, int64_t pitch);
 /* Pinned, device-visible host memory for PCM buffers - for hosts that do not link the HIP runtime themselves (the reference's
  * callers keep their audio in plain vectors: include/FX8010.h:57; such a buffer is what to copy it into once per block).
  * NULL when the allocation fails (fx_last_create_error says why).  Free with fxb_host_free; both are thread-safe. */
@@ -208,6 +215,10 @@ void fxb_host_free(void* p);
 /* Same with device-resident buffers (hipMalloc'ed, on h's device); asynchronous on `stream`
  * (a hipStream_t, NULL = the handle's own stream).  Pair with fxb_sync(). */
 int fxb_process_block_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, void* stream);
+/* single-shard handles; d_in/d_out must be device memory of h's device or device-visible host memory: anything else is
+ * FX_E_ARG without a launch (the last validated buffer pair is remembered, so a real-time caller pays once).  Layout as
+ * fxb_process_block_pitched; in == out or footprints that share no element.  Asynchronous like fxb_process_block_dev. */
+int fxb_process_block_dev_pitched(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t pitch, void* stream);
 /* Sharded batches: d_in[k] / d_out[k] are shard k's buffers on shard k's device, [n_samples][num_channels][n_instances of
  * the shard]; launched concurrently from the shards' own threads on their own streams.  Pair with fxb_sync(). */
 int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float* const* d_out, int n_samples);
@@ -273,11 +284,13 @@ enum {
                                       on the caller's own blocks; FX_STAGES_TUNE=0 turns that off, FX_STAGES=n pins the count) */
     FXB_INFO_XLATE_BACKGROUND_BUILDS = 29, /* translations on the handle's builder thread (ahead of time: the variant with the declared controls in
                                       rows, the lean variant, code for another class of block lengths); FX_BUILDER=0 in the environment turns the thread off */
-    FXB_INFO_CONTROL_ROWS = 32     /* declared controls that have a register row in the code in force: 0 until the host moves one (their values are
+    FXB_INFO_CONTROL_ROWS = 32,    /* declared controls that have a register row in the code in force: 0 until the host moves one (their values are
                                       folded into the code), then all of them (one change of code for the whole panel, generated ahead of time), then
                                       - a few blocks later, a pointer swap - only the ones that have been written lately (within 8192 sample periods;
                                       the others go back into the code, where a constant is cheaper than a row: e.g. INTERP with a constant X).  Same
                                       results in all three. */
+    FXB_INFO_HOST_STAGED_BLOCKS = 33,  /* host blocks that went through staging copies since creation (summed over shards) */
+    FXB_INFO_HOST_INPLACE_BLOCKS = 34  /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

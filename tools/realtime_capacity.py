@@ -47,9 +47,8 @@ def percentiles(us):
 def measure(torch, A, progs, n, blocks, warm, mode, check=4, config="config5", control="decay", shards=1):
     """one N, one mode ("host": pinned host PCM through fxb_process_block; "device": resident PCM, launch + sync per block).
     shards > 1 (host mode): the handle is made of that many shards ON THE SAME GPU (fxb_create_on_devices with the ordinal
-    repeated): each shard has its own host thread and stream and copies its own columns of the caller's [S][N] buffers, so the
-    copy-in of one shard, the kernel of another and the copy-out of a third overlap - the block's PCIe time is no longer
-    serialised around its kernel."""
+    repeated): each shard has its own host thread and stream and works on its own columns of the caller's pinned [S][N] buffers in
+    place (before row-pitched PCM: copied its columns in and out, staged)."""
     import numpy as np
     from pyoracle import Oracle
 
@@ -140,6 +139,8 @@ def measure(torch, A, progs, n, blocks, warm, mode, check=4, config="config5", c
         "emulated_mips_sustained": round(progs.count_instructions(text) * BLOCK * n * blocks / wall / 1e6, 1),
         "translations_in_timed_region": [builds1[0] - builds0[0], builds1[1] - builds0[1]],
         "tier": b.tier_note(), "parity_instances": len(picks), "parity_ok": ok, "blocks_replayed_by_oracle": total,
+        # host blocks by route, summed over the shards (FXB_INFO_HOST_STAGED_BLOCKS / _INPLACE_BLOCKS): 0 staged on pinned buffers
+        "host_staged_blocks": b.info("host_staged_blocks"), "host_inplace_blocks": b.info("host_inplace_blocks"),
     })
     b.close()
     del xin, yout
@@ -172,6 +173,7 @@ def run(torch, A, progs, instances, blocks, warm, modes=("host", "device"), log=
                 log(("%d shards " % shards if shards > 1 and mode == "host" else "") + "%-6s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  kernel %6.1f us  %s  parity %s" % (
                     mode, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], r["kernel_us_median"] or -1,
                     "REAL TIME" if r["within_budget_p999"] else "over budget", "ok" if r["parity_ok"] else "MISMATCH")
+                    + ("  staged %d in place %d" % (r["host_staged_blocks"], r["host_inplace_blocks"]) if mode == "host" else "")
                     + ("  (blocks that move the slider: median %.1f, the others %.1f, p99.9 %.1f)" % (
                         r["control_blocks"]["median_us"], r["other_blocks"]["median_us"], r["other_blocks"]["p999_us"]) if "control_blocks" in r else ""))
         out["capacity_%s_fed" % mode] = capacity([r for r in out["rows"] if r["mode"] == mode])
