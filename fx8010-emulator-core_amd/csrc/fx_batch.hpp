@@ -4,9 +4,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
+#include <condition_variable>
 #include <cstdint>
+#include <cstring>
+#include <deque>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "fx_asm.hpp"
@@ -17,6 +22,8 @@
 #include "fx_model.hpp"
 
 namespace fx {
+
+inline uint32_t bitsOf(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
 class Batch {
 public:
@@ -98,26 +105,26 @@ public:
     int setOption(unsigned option, bool on);
 
 private:
+    // ---- device state, registers, control tracks, snapshot, counters (fx_batch.cpp) -----------------------------------------------
     std::string tierNotePlain() const;
     int fail(int code, const std::string& what);
     int hipFail(hipError_t e, const char* where);
     int afterLoad(bool ok);
-    int ensureLowered();          // (re)lower + upload the stream when dirty
     int ensureState();            // allocate / grow the state block for the current register count
     int ensureTram(const Lowered& low);
     int uploadTracks(int nSamples, hipStream_t s);   // translated tier: header + values -> dTracks_
-    int processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch);  // other tiers: cut the block
     bool tracked(int reg) const;
-    std::vector<uint8_t> laneForced() const;      // the registers with rows in the code that is wanted now: laneForcedFull(), minus the controls a lean variant in force has folded in
     std::vector<uint8_t> laneForcedFull() const;  // forcedLane_ plus the trackable registers
-    std::vector<uint8_t> coldControls() const;    // the declared controls that have a row only for company and could be folded into the code (coldControl)
-    std::vector<uint8_t> forcedWithout(const std::vector<uint8_t>& folded) const;   // laneForcedFull() minus those
     int fillRows(const std::vector<uint32_t>& rows, const std::vector<uint32_t>& values);
     bool laneResident(int reg) const;
     bool intrinsicLane(int reg) const;
     int chooseInstPerLane() const;
     hipStream_t pick(hipStream_t s) const { return s ? s : stream_; }
     void waitLastLaunch();        // host waits for the most recent kernel (an event of ours, not the caller's stream handle)
+    bool readByProgram(int reg) const;
+    bool declaredControl(int reg) const;
+    void markControls();
+    bool movableControl(int reg) const;
 
     Program prog_;
     const ReleaseKnobs knobs_;          // the environment's release knobs as they were when the handle was created (fx_knobs.hpp)
@@ -142,7 +149,34 @@ private:
     float* dXTram_ = nullptr;
     int iSlotsAlloc_ = 0, xSlotsAlloc_ = 0;
     int instPerLane_ = 1;
+    std::vector<uint8_t> intrinsicLane_, readByProgram_;   // per register, as of the last load
+    double* dLut_ = nullptr;
+    // control tracks (fx_xlate.hpp TrackEvent): registers the generated loop can re-load by itself, and what is armed
+    struct PendingTrack { int period = 0, steps = 0; bool perInstance = false; std::vector<float> values; };
+    std::vector<int> trackRegs_;           // register of slot t
+    std::vector<PendingTrack> pendingTracks_;  // per slot; steps == 0: not armed
+    uint32_t* dTracks_ = nullptr;
+    size_t tracksCap_ = 0;                 // bytes
+    bool tracksClear_ = false;             // the device header holds no armed schedule
+    std::vector<uint32_t> trackStage_;     // host image of dTracks_ for the block being launched
+    bool tracksArmed() const { for (const PendingTrack& t : pendingTracks_) if (t.steps > 0) return true; return false; }
+    uint32_t* dScratch_ = nullptr;  // small device scratch: fill lists, reductions
+#ifdef FX_DIAGNOSTICS
+  public:
+    // diagnostics build (fx_knobs.hpp): one word per wavefront, written by generated code behind its last sample when
+    // FX_XLATE_ENDSTAMP is set (fx_xlate.cpp) - the low word of the 100 MHz clock at which the wavefront finished
+    int readEndStamps(uint32_t* out, int64_t nWords);
+  private:
+    uint32_t* dStamps_ = nullptr;
+    size_t stampWords_ = 0;
+#endif
+    std::string lastError_;
 
+    // ---- what runs: lowering, code cache, builder thread, stage tuner, control variants (fx_batch_code.cpp) ------------------------
+    int ensureLowered();          // (re)lower + upload the stream when dirty
+    std::vector<uint8_t> laneForced() const;      // the registers with rows in the code that is wanted now: laneForcedFull(), minus the controls a lean variant in force has folded in
+    std::vector<uint8_t> coldControls() const;    // the declared controls that have a row only for company and could be folded into the code (coldControl)
+    std::vector<uint8_t> forcedWithout(const std::vector<uint8_t>& folded) const;   // laneForcedFull() minus those
     struct StageOption { int wanted = 1, stages = 1, group = 0; double predicted = 0.0; };   // wanted: what planStages is asked for (1: the plain program)
     // Everything a lowering produces - the lowered streams, the tier that runs them, the loaded code object of a translated
     // program and the device copy of its tables.  It is a pure function of a KEY (codeKey(): the program, the values folded
@@ -187,9 +221,34 @@ private:
     int cacheHits_ = 0;
     std::string codeKey(int blockClass, bool defer) const;
     std::string codeKeyFor(const std::vector<uint8_t>& forced, int blockClass, bool defer, int pick) const;
-    struct Builder;                              // the thread that generates code off the caller's thread (fx_batch.cpp)
+    struct BuildInputs {                         // what a build reads of the batch's changing state (a snapshot: builds also run on the builder thread)
+        std::string key;
+        int blockClass = -1;
+        bool defer = false;
+        std::vector<float> hostValue;
+        std::vector<uint8_t> forced;             // laneForced()
+        std::vector<int> trackRegs;
+        int stagePick = 0;                       // stages to ask the planner for; 0: the cheapest by its costs (rankStages)
+        // the batch's device state as it was when the build was asked for: a build on the builder thread must not change any of
+        // it and reads only this copy (the caller's thread may be growing the state or the delay lines meanwhile)
+        int instPerLane = 1, iSlotsAlloc = 0, xSlotsAlloc = 0, stateRows = 0;
+        bool stagingOff = false;
+    };
+    BuildInputs buildInputs(const std::string& key, int blockClass, bool defer) const;
+    // the thread that generates code off the caller's thread (fx_batch_code.cpp: requestBuild and what follows it)
+    struct Builder {
+        std::thread thread;
+        std::mutex mu;
+        std::condition_variable cv;
+        std::deque<BuildInputs> jobs;
+        std::string running;                          // key being built
+        std::vector<std::unique_ptr<Code>> finished;
+        std::deque<std::string> failed;               // keys the offline path could not build (left to the caller's thread); the most recent kMaxFailed
+        static constexpr size_t kMaxFailed = 32;      // (a forgotten one is merely asked for again)
+        hipStream_t upload = nullptr;                 // the thread's own copy stream (created and destroyed by it; read by it only)
+        bool quit = false;
+    };
     std::unique_ptr<Builder> builder_;
-    struct BuildInputs;
     bool builderWanted() const;
     void requestBuild(BuildInputs&& in);
     void collectBuilt();                         // what the builder has finished -> cache_
@@ -206,26 +265,15 @@ private:
     bool adoptCode(const std::string& key);      // cache_ -> c_
     void releaseCode(Code& c);                   // unload / free what a Code holds on the device
     void clearCodeCache();
-    struct BuildInputs {                         // what a build reads of the batch's changing state (a snapshot: builds also run on the builder thread)
-        std::string key;
-        int blockClass = -1;
-        bool defer = false;
-        std::vector<float> hostValue;
-        std::vector<uint8_t> forced;             // laneForced()
-        std::vector<int> trackRegs;
-        int stagePick = 0;                       // stages to ask the planner for; 0: the cheapest by its costs (rankStages)
-        // the batch's device state as it was when the build was asked for: a build on the builder thread must not change any of
-        // it and reads only this copy (the caller's thread may be growing the state or the delay lines meanwhile)
-        int instPerLane = 1, iSlotsAlloc = 0, xSlotsAlloc = 0, stateRows = 0;
-        bool stagingOff = false;
-    };
-    BuildInputs buildInputs(const std::string& key, int blockClass, bool defer) const;
-    int buildCodeInto(Code& c, const BuildInputs& in, bool offline, std::string* err);
+    // the lowering, into an empty Code, in three steps.  `in` is the build's own copy: inline, the first step brings it up to date
+    // with the device state it has just grown, so that the later steps read nothing but `in` on either thread
+    int buildCodeInto(Code& c, BuildInputs in, bool offline, std::string* err);
+    int chooseTierAndLower(Code& c, BuildInputs& in, bool offline, std::string* err);   // tier, lowered streams, state rows and delay lines
+    int translateInto(Code& c, const BuildInputs& in, bool offline, std::string* err);  // generated code where the tier has it: image -> loaded module
+    int packStream(Code& c, const BuildInputs& in, bool offline, std::string* err);     // records, row table, stage descriptors -> the device
+    bool twoWavesPerSimd() const { return (n_ + 63) / 64 >= 2048; }   // 256 CUs x 4 SIMDs x 2
+    bool priorityTurns(AsmVariant variant) const;
     int wantedClass_ = -1;                       // block-length class the code should be for (sticky: see processDevice)
-    bool readByProgram(int reg) const;
-    bool declaredControl(int reg) const;
-    void markControls();
-    std::vector<uint8_t> intrinsicLane_, readByProgram_;   // per register, as of the last load
     bool controlMode_ = false;                   // the declared controls have rows (the host has moved one)
     // Control mode puts EVERY declared control in a row at the first touch of one (one change of code for the panel, built ahead:
     // no stall).  A row costs what the value folded into the code saves - config5 with `damp` in a row: 100 INTERPs that convert X
@@ -275,10 +323,6 @@ private:
     int pickFor(int blockClass) const { return (blockClass >= 0 && blockClass < 3) ? tune_[blockClass].pick : 0; }
     void adoptStageOptions();                    // after a build / an adoption: the options the code came with start the class's tuner
     void noteLaunchTime();                       // the previous launch's time -> the tuner; move to the next option / settle
-    int lastLaunchPick_ = 0, lastLaunchSamples_ = 0, lastLaunchClass_ = -1;
-    bool lastLaunchTimed_ = false;
-    bool movableControl(int reg) const;
-    bool piecewise_ = false;   // processDevice is being called for the pieces of one pipelined host block
     int xlateBuilds_ = 0;                    // translations on the caller's thread since the handle was created
     std::atomic<int> backgroundBuilds_{0};   // ... and on the builder thread
     // a pipeline fills and drains in 3 (K - 1) steps: short blocks get short steps and fewer stages (stageBlockClass); the code is
@@ -290,24 +334,27 @@ private:
     int controlHeat_ = 0;
     int pendingSamples_ = 0;  // block length of the call that triggered the lowering
     bool everLowered_ = false;
-    double* dLut_ = nullptr;
-    // control tracks (fx_xlate.hpp TrackEvent): registers the generated loop can re-load by itself, and what is armed
-    struct PendingTrack { int period = 0, steps = 0; bool perInstance = false; std::vector<float> values; };
-    std::vector<int> trackRegs_;           // register of slot t
-    std::vector<PendingTrack> pendingTracks_;  // per slot; steps == 0: not armed
-    uint32_t* dTracks_ = nullptr;
-    size_t tracksCap_ = 0;                 // bytes
-    bool tracksClear_ = false;             // the device header holds no armed schedule
-    std::vector<uint32_t> trackStage_;     // host image of dTracks_ for the block being launched
-    bool tracksArmed() const { for (const PendingTrack& t : pendingTracks_) if (t.steps > 0) return true; return false; }
-    uint32_t* dScratch_ = nullptr;  // small device scratch: fill lists, reductions
+
+    // ---- a block's path from the C ABI to the kernel launch (fx_batch_io.cpp) -----------------------------------------------------
+    int checkBlock(const float* in, const float* out, int nSamples, int64_t* pitch);   // the argument refusals of every entry point; *pitch <= 0 becomes n
+    void beginBlock(int nSamples, int pieces = 1);   // head of a caller-visible block: control heat, tuner, block-length class, lean variants, sample clock
+    // how launchBlock is called: for a block of its own, for a piece of a pipelined host block (never timed by the stage tuner), or
+    // without the event pair, by a caller that waits for the stream right behind the launch (last_kernel_ms: -1)
+    enum LaunchMode : unsigned { kWholeBlock = 0, kPiece = 1, kUntimed = 2 };
+    int launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch, unsigned mode);
+    KernelArgs kernelArgs(const float* dIn, float* dOut, int nSamples, int64_t pitch) const;
+    AsmArgs asmArgs(const KernelArgs& a) const;
+    static hipError_t copyRows(void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t stream);
+    int processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch);  // other tiers: cut the block
+    int lastLaunchPick_ = 0, lastLaunchSamples_ = 0, lastLaunchClass_ = -1;
+    bool lastLaunchTimed_ = false;
     float* dIn_ = nullptr;
     float* dOut_ = nullptr;
     size_t ioCap_ = 0;
     // small blocks (the reference's one process() per sample): pinned host buffers the kernel reads and writes directly
     float* hPinIn_ = nullptr;
     float* hPinOut_ = nullptr;
-    bool pinTried_ = false, untimed_ = false;
+    bool pinTried_ = false;
     // large host blocks: pieces of the block are copied in, processed and copied out concurrently
     static constexpr int kHostPieces = 8;
     hipStream_t copyIn_ = nullptr, copyOut_ = nullptr;
@@ -322,16 +369,8 @@ private:
     const float* checkedDevIn_ = nullptr;   // ... and the device addresses of the two
     float* checkedDevOut_ = nullptr;
 #ifdef FX_DIAGNOSTICS
-  public:
-    // diagnostics build (fx_knobs.hpp): one word per wavefront, written by generated code behind its last sample when
-    // FX_XLATE_ENDSTAMP is set (fx_xlate.cpp) - the low word of the 100 MHz clock at which the wavefront finished
-    int readEndStamps(uint32_t* out, int64_t nWords);
-  private:
-    uint32_t* dStamps_ = nullptr;
-    size_t stampWords_ = 0;
+    int ensureEndStamps();   // the end stamps' buffer (dStamps_), one word per wavefront
 #endif
-
-    std::string lastError_;
 };
 
 }  // namespace fx

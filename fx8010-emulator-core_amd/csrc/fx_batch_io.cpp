@@ -1,0 +1,507 @@
+// fx_batch_io.cpp — from "a block arrives" to "the kernel is launched": the host and device entry points, the routes a host block
+// can take (the library's small pinned pair, in place on the caller's pinned buffers, staged in one piece, staged in pieces on
+// three streams), the argument and addressability checks, the kernel arguments and the launch.
+#include "fx_batch.hpp"
+
+#include <cstddef>
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/fx8010_amd.h"
+
+namespace fx {
+
+// pitch: instances per PCM row of the HOST buffers (>= n_); a shard of a larger batch reads / writes its columns of the
+// caller's [sample][channel][all instances] arrays in place (fx_shard.cpp)
+namespace {
+constexpr size_t kPinnedFloats = 512;
+// the kernels step through PCM by two 32-bit byte strides: channels * pitch * 4 (a sample period) and pitch * 4 (a channel)
+inline bool pcmStrideTooWide(int channels, int64_t pitch) { return (uint64_t)std::max(channels, 1) * (uint64_t)pitch * 4u >= ((uint64_t)1 << 32); }
+// A host block of 32 MiB and more is cut into eight pieces (consecutive sample ranges) whose copy-in, kernel and copy-out overlap
+// on three streams (round 2: 268 MB each way in 6.5 instead of 12.7 ms from pinned buffers).  Smaller blocks were tried in pieces in
+// round 5 (by size, 2-8 of them) for real-time callers and gained little - 32 samples x 131 072 instances: 806 -> 622 us - because
+// the runtime's copy-OUT is a shader copy that slows a kernel running beside it threefold (profiles/r05_rt_timeline_131072.txt),
+// and pieces are not timed by the stage tuner; what serves those callers is the in-place path above (pinned buffers: 486 us).
+constexpr size_t kPipelinedBytes = (size_t)32 << 20;
+inline int hostPieces(size_t bytes, int nSamples, int most) { return (bytes >= kPipelinedBytes && nSamples >= 2 * most) ? most : 1; }
+
+inline bool pointerAttributes(const void* p, hipPointerAttribute_t* attr) {
+    std::memset(attr, 0, sizeof(*attr));
+    if (hipPointerGetAttributes(attr, p) == hipSuccess) return true;
+    (void)hipGetLastError();   // (pageable memory: the runtime says "invalid value", which must not stay behind as the thread's last error)
+    return false;
+}
+
+// Can the device address the whole of [p, p + bytes)?  Yes for pinned host memory (hipHostMalloc / hipHostRegister - e.g. a torch
+// pinned tensor) that lies inside ONE mapping, and - only when the caller allows device memory: device >= 0 - for memory of that
+// device whose allocation holds the range.  *dev: the address the kernel takes.  The range comes from the runtime's own record of
+// the allocation the address belongs to; where it keeps none for registered host memory, both ends pinned with one address offset
+// between them will do.  (A caller that registered part of a buffer takes the staged copies.)
+inline bool addressable(const void* p, size_t bytes, int device, const void** dev) {
+    hipPointerAttribute_t attr;
+    if (!pointerAttributes(p, &attr)) return false;
+    const bool host = attr.type == hipMemoryTypeHost;
+    if (host ? !attr.devicePointer : (device < 0 || attr.type != hipMemoryTypeDevice || attr.device != device)) return false;
+    *dev = host ? attr.devicePointer : p;
+    if (host && bytes <= 1) return true;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(*dev)) == hipSuccess && base && size) {
+        const char *lo = static_cast<const char*>(base), *at = static_cast<const char*>(*dev);
+        return at >= lo && bytes <= size && static_cast<size_t>(at - lo) <= size - bytes;
+    }
+    (void)hipGetLastError();   // (reported by the answer: not again by the next launch helper that asks)
+    hipPointerAttribute_t last;
+    if (!host || !pointerAttributes(static_cast<const char*>(p) + (bytes - 1), &last) || last.type != hipMemoryTypeHost || !last.devicePointer) return false;
+    return static_cast<const char*>(last.devicePointer) - static_cast<const char*>(*dev) == static_cast<std::ptrdiff_t>(bytes - 1);
+}
+
+// Bytes from the first to the last element of a [rows][pitch] PCM block whose instances are columns 0..n-1.
+inline size_t pcmExtent(size_t rows, int64_t n, int64_t pitch) { return ((rows - 1) * (size_t)pitch + (size_t)n) * 4; }
+
+// in == out is fine in place (an instance reads its sample before it writes it, and no other instance touches that word), and so
+// are two footprints that share no element - e.g. two column ranges of one buffer.  Footprints that overlap in any other way need
+// the whole input read before the first output is written: the staged copies do that.  Both have the same pitch: element r * P + c
+// (c < n) of `out` is element r' * P + c' of `in` only if c - c' = m (mod P), m = (out - in) mod P, which |c - c'| < n rules out
+// for n <= m <= P - n.
+inline bool pcmDisjointOrSame(const float* in, const float* out, size_t rows, int64_t n, int64_t pitch) {
+    if (in == out) return true;
+    const size_t bytes = pcmExtent(rows, n, pitch);
+    const char *x = reinterpret_cast<const char*>(in), *y = reinterpret_cast<const char*>(out);
+    if (x + bytes <= y || y + bytes <= x) return true;
+    const std::ptrdiff_t d = y - x;
+    if (d % 4 != 0) return false;
+    int64_t m = (int64_t)(d / 4) % pitch;
+    if (m < 0) m += pitch;
+    return m >= n && m <= pitch - n;
+}
+}  // namespace
+
+// Tiers without in-kernel tracks (interpreter, HIP C++ kernel): the same schedule by cutting the block at its change
+// points and writing the registers in between - what the caller would have had to do.
+int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch) {
+    std::vector<PendingTrack> tracks;
+    tracks.swap(pendingTracks_);
+    pendingTracks_.resize(trackRegs_.size());
+    std::vector<int> cuts{0, nSamples};
+    for (const PendingTrack& t : tracks)
+        for (int k = 0; k < t.steps && (int64_t)k * t.period < nSamples; ++k) cuts.push_back(k * t.period);
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    const size_t rowFloats = (size_t)prog_.numChannels * (size_t)pitch;   // floats per sample period
+    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+        const int lo = cuts[c], hi = cuts[c + 1];
+        for (size_t k = 0; k < tracks.size(); ++k) {
+            const PendingTrack& t = tracks[k];
+            if (t.steps <= 0 || lo % t.period != 0 || lo / t.period >= t.steps) continue;
+            const std::string& name = prog_.regs[(size_t)trackRegs_[k]].name;
+            const int rc = t.perInstance ? setRegisterArray(name, &t.values[(size_t)(lo / t.period) * (size_t)n_]) : setRegister(name, t.values[(size_t)(lo / t.period)]);
+            if (rc != 0) return rc < 0 ? rc : fail(FX_E_ARG, "track: register vanished");
+        }
+        controlHeat_ = 0;  // these writes are the schedule, not a moving slider
+        const int rc = processDevice(dIn + (size_t)lo * rowFloats, dOut + (size_t)lo * rowFloats, hi - lo, stream, pitch);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+// The refusals of every entry point, written once: a call that is refused has changed nothing and launches nothing.
+int Batch::checkBlock(const float* in, const float* out, int nSamples, int64_t* pitch) {
+    if (*pitch <= 0) *pitch = n_;
+    if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
+    if (*pitch < n_) return fail(FX_E_ARG, "PCM row pitch below the instance count");
+    if (pcmStrideTooWide(prog_.numChannels, *pitch)) return fail(FX_E_ARG, "PCM row pitch too wide: channels * pitch * 4 must stay below 2^32");
+    if (nSamples > 0 && (!in || !out)) return fail(FX_E_ARG, "null buffer");
+    return 0;
+}
+
+// Head of a block as the caller sees it (once for a host block that is launched in pieces: a translation must not fire between
+// two of them).  The class of block lengths goes by what the kernel is launched with - the piece -, the sample clock by the block.
+void Batch::beginBlock(int nSamples, int pieces) {
+    pendingSamples_ = nSamples / pieces;
+    if (controlHeat_ > 0 && --controlHeat_ == 0 && c_.deferred) lowDirty_ = true;  // quiet again: translate
+    // (as it has been: pieces are not timed, and the stage tuner does not move on at the head of a block in pieces either - whether
+    // it should is a question of its own)
+    if (pieces == 1) noteLaunchTime();
+    noteBlockLength(pendingSamples_);
+    leanStep();
+    sampleClock_ += nSamples;
+}
+
+int Batch::processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch) {
+    (void)hipSetDevice(device_);
+    const int rc = checkBlock(dIn, dOut, nSamples, &pitch);
+    if (rc != 0) return rc;
+    beginBlock(nSamples);
+    return launchBlock(dIn, dOut, nSamples, stream, pitch, kWholeBlock);
+}
+
+KernelArgs Batch::kernelArgs(const float* dIn, float* dOut, int nSamples, int64_t pitch) const {
+    KernelArgs a{};
+    const size_t nOps = c_.low.steady.size();
+    a.steady = c_.dStream;
+    a.last = c_.dStream + nOps * 8;
+    a.rowTable = c_.dStream + nOps * 16;
+    a.state = dState_;
+    a.in = dIn;
+    a.out = dOut;
+    a.itram = dITram_;
+    a.xtram = dXTram_;
+    a.lut = dLut_;
+    a.n = n_;
+    a.nPad = nPad_;
+    a.pcmPitch = pitch;
+    a.nOps = (int)nOps;
+    a.nLoad = (int)c_.low.loadRows.size();
+    a.nStore = (int)c_.low.storeRows.size();
+    a.nSamples = nSamples;
+    a.channels = prog_.numChannels;
+    for (int c = 0; c < kMaxChannels; ++c) {
+        a.inRow[c] = c < prog_.numChannels ? c_.low.inRow[c] : -1;
+        a.latchRow[c] = c < prog_.numChannels ? c_.low.latchRow[c] : 0;
+    }
+    a.iSlots = iSlotsAlloc_;
+    a.xSlots = xSlotsAlloc_;
+    a.iSize = prog_.iTramSize;
+    a.xSize = prog_.xTramSize;
+    a.nZero = (int)c_.low.zeroRows.size();
+    const uint32_t rowBytes = 256u * (uint32_t)instPerLane_;
+    a.skipOff = c_.low.skipRow >= 0 ? (uint32_t)c_.low.skipRow * rowBytes : 0;
+    a.cursorOff = c_.low.cursorRow >= 0 ? (uint32_t)c_.low.cursorRow * rowBytes : 0;
+    a.noiseOff = c_.low.noiseRow >= 0 ? (uint32_t)c_.low.noiseRow * rowBytes : 0;
+    a.oodOff = c_.low.oodRow >= 0 ? (uint32_t)c_.low.oodRow * rowBytes : 0;
+    a.aliveOff = c_.low.aliveRow >= 0 ? (uint32_t)c_.low.aliveRow * rowBytes : 0;
+    a.hasShadow = c_.low.skipRow >= 0 ? 1 : 0;
+    a.instPerLane = instPerLane_;
+    a.tramDane = (c_.low.tramDane && c_.low.cursorRow >= 0) ? 1 : 0;
+    a.oodRow = stateLayout_.oodRow;
+    a.countLo = stateLayout_.countLo;
+    a.countHi = stateLayout_.countHi;
+    a.staticCount = c_.low.staticCount;
+    a.nRows = c_.low.nRows;
+    return a;
+}
+
+// the same block for the assembly tiers (interpreter and generated code)
+AsmArgs Batch::asmArgs(const KernelArgs& a) const {
+    AsmArgs g{};
+    g.steady = a.steady; g.last = a.last; g.rowTable = a.rowTable; g.state = a.state;
+    g.in = a.in; g.out = a.out; g.itram = a.itram; g.xtram = a.xtram; g.lut = a.lut;
+    g.n = a.n; g.nPad = a.nPad; g.pcmPitch = a.pcmPitch; g.nLoad = a.nLoad; g.nStore = a.nStore;
+    g.nSamples = a.nSamples; g.channels = a.channels;
+    for (int c = 0; c < kMaxChannels; ++c) {
+        g.inOff[c] = a.inRow[c] >= 0 ? a.inRow[c] * (int)c_.low.rowPitch : -1;
+        g.latchOff[c] = a.latchRow[c] * (int)c_.low.rowPitch;
+    }
+    g.iSlots = a.iSlots; g.xSlots = a.xSlots; g.iSize = a.iSize; g.xSize = a.xSize;
+    g.cursorRow = stateLayout_.cursorBase; g.noiseRow = stateLayout_.noiseBase;
+    g.oodRow = a.oodRow; g.countLo = a.countLo; g.countHi = a.countHi; g.staticCount = a.staticCount;
+    g.lutX1Off = kLutX1Off * 8;
+    g.tramDane = (c_.low.tramDane && (c_.low.usesITram || c_.low.usesXTram)) ? 1 : 0;   // (like the other tiers: counters step where the program has taps)
+    if (c_.low.multipass) g.tramDane |= 2;
+    if (!c_.useXlate && c_.variant != ASM_LDS && priorityTurns(c_.variant)) {
+        // the interpreter's wavefronts take turns like generated code's: a turn = 1/24 of the block at about 20 us per sample and
+        // four wavefronts, between 0.66 and 10 ms
+        int shift = 6;
+        while ((1 << (shift - 6 + 1)) <= a.nSamples) ++shift;   // floor(log2(samples of the launch)) + 6
+        g.tramDane |= 4 | (std::min(std::max(shift, 16), 20) << 8);
+    }
+    if (c_.useXlate) {
+        // code streams are named by their byte offset from the kernel entry: {fast, exact} per argument
+        g.steady = reinterpret_cast<const uint32_t*>((uintptr_t)c_.steady);
+        g.last = reinterpret_cast<const uint32_t*>((uintptr_t)c_.last);
+        g.initOff = (int)c_.initOff;
+        g.tracks = trackRegs_.empty() ? nullptr : dTracks_;
+        if (c_.stages > 1) {
+            g.stages = a.rowTable + c_.low.loadRows.size() + c_.low.storeRows.size() + c_.low.zeroRows.size();
+            g.nStages = c_.stages;
+        }
+    }
+    return g;
+}
+
+#ifdef FX_DIAGNOSTICS
+// the end stamps' own buffer rides in the kernarg slot of the stage descriptors, which an unstaged launch leaves unused (nStages
+// stays 0: the template never looks at the pointer)
+int Batch::ensureEndStamps() {
+    const size_t words = ((size_t)n_ + 63) / 64;
+    if (words <= stampWords_) return 0;
+    waitLastLaunch();
+    (void)hipFree(dStamps_);
+    dStamps_ = nullptr;
+    stampWords_ = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&dStamps_), words * 4) != hipSuccess) return fail(FX_E_MEMORY, "end stamps");
+    stampWords_ = words;
+    return 0;
+}
+#endif
+
+// Lower if need be and launch: the block has been checked and counted (beginBlock) by the caller.
+int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch, unsigned mode) {
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    everLowered_ = true;
+    if (nSamples == 0) return 0;
+    if (tracksArmed() && !c_.useXlate) return processWithTrackFallback(dIn, dOut, nSamples, stream, pitch);
+    hipStream_t s = pick(stream);
+    if (c_.useXlate && !trackRegs_.empty() && (rc = uploadTracks(nSamples, s)) != 0) return rc;
+    const bool timed = !(mode & kUntimed);
+    hipError_t e = hipSuccess;
+    for (;;) {
+        const KernelArgs a = kernelArgs(dIn, dOut, nSamples, pitch);
+        e = timed ? hipEventRecord(ev0_, s) : hipSuccess;
+        if (e == hipSuccess && c_.useAsm) {
+            AsmArgs g = asmArgs(a);
+#ifdef FX_DIAGNOSTICS
+            if (c_.useXlate && c_.stages <= 1 && FX_DIAG_KNOB("FX_XLATE_ENDSTAMP")) {
+                if ((rc = ensureEndStamps()) != 0) return rc;
+                g.stages = dStamps_;
+            }
+#endif
+            e = c_.useXlate ? launchAsmFunction(c_.fn, g, (unsigned)((n_ + 63) / 64), c_.ldsBytes, s, (unsigned)c_.stages)
+                            : launchAsmInterp(g, c_.variant, c_.variant == ASM_LDS ? (size_t)a.nRows * 256 : 0, device_, s);
+        } else if (e == hipSuccess) {
+            e = launchStepBlock(a, c_.low.multipass, s);
+        }
+        const hipError_t launchError = e;   // (of the event record in front of the launch or of the launch itself)
+        if (e == hipSuccess && timed) e = hipEventRecord(ev1_, s);
+        // A workgroup of several wavefronts that the device will not start (registers x wavefronts beyond a CU, LDS): the plain
+        // program runs everywhere - no stages for this handle from now on, and a second pass for this block.  Only for what a launch
+        // CONFIGURATION can cause: any other error (a fault of an earlier kernel that this call merely inherits, a lost device) is
+        // reported as it is and leaves the handle's choice of code alone.  Nothing has been consumed at this point that the second
+        // pass needs: a staged program has no control tracks (planStages refuses them), so uploadTracks has not run.
+        const bool configError = launchError == hipErrorInvalidValue || launchError == hipErrorInvalidConfiguration || launchError == hipErrorLaunchOutOfResources;
+        if (!(configError && c_.useXlate && c_.stages > 1 && !stagingOff_ && trackRegs_.empty())) break;
+        (void)hipGetLastError();   // (the launch's own error, just read: not a sticky one)
+        stagingOff_ = true;
+        lowDirty_ = true;
+        if ((rc = ensureLowered()) != 0) return rc;
+    }
+    if (e != hipSuccess) return hipFail(e, "launch fx_step_block");
+    launched_ = timed;  // (an untimed launch is synchronised by its caller before anything else happens)
+    timed_ = timed;
+    lastLaunchTimed_ = timed && !(mode & kPiece);
+    lastLaunchPick_ = c_.stagePick;
+    lastLaunchSamples_ = nSamples;
+    lastLaunchClass_ = c_.useXlate ? c_.blockClass : -1;
+    lastGrid_ = (unsigned)((n_ + 64 * instPerLane_ - 1) / (64 * instPerLane_));
+    return 0;
+}
+
+// rows of `width` bytes; one plain copy when neither side has a gap between its rows
+hipError_t Batch::copyRows(void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t stream) {
+    if (dstPitch == width && srcPitch == width) return hipMemcpyAsync(dst, src, rows * width, kind, stream);
+    return hipMemcpy2DAsync(dst, dstPitch, src, srcPitch, width, rows, kind, stream);
+}
+
+int Batch::processDeviceChecked(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream) {
+    (void)hipSetDevice(device_);
+    const int rc = checkBlock(dIn, dOut, nSamples, &pitch);
+    if (rc != 0) return rc;
+    if (nSamples > 0) {
+        const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels, bytes = pcmExtent(rows, n_, pitch);
+        if (dIn != checkedIn_ || dOut != checkedOut_ || bytes > checkedBytes_) {
+            checkedIn_ = checkedOut_ = nullptr;
+            if (!pcmDisjointOrSame(dIn, dOut, rows, n_, pitch)) return fail(FX_E_ARG, "input and output overlap without being one buffer");
+            // memory of this device, or pinned host memory (its device address goes to the kernel)
+            const void *devIn = nullptr, *devOut = nullptr;
+            if (!addressable(dIn, bytes, device_, &devIn) || (dOut == dIn ? (devOut = devIn, false) : !addressable(dOut, bytes, device_, &devOut)))
+                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
+            checkedIn_ = dIn;
+            checkedOut_ = dOut;
+            checkedBytes_ = bytes;
+            checkedDevIn_ = static_cast<const float*>(devIn);
+            checkedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
+        }
+        dIn = checkedDevIn_;
+        dOut = checkedDevOut_;
+    }
+    beginBlock(nSamples);
+    return launchBlock(dIn, dOut, nSamples, stream, pitch, kWholeBlock);
+}
+
+int Batch::processHost(const float* in, float* out, int nSamples, int64_t pitch) {
+    (void)hipSetDevice(device_);
+    int rc = checkBlock(in, out, nSamples, &pitch);
+    if (rc != 0) return rc;
+    if (nSamples == 0) return ensureLowered();
+    const size_t count = (size_t)nSamples * prog_.numChannels * (size_t)n_;
+    const size_t rows = (size_t)nSamples * prog_.numChannels;
+    // A few KB of PCM (per-sample calls on a handful of instances): two staged copies cost more than the launch.  The kernel
+    // reads and writes pinned host memory instead - one launch, one synchronisation.
+    if (count <= kPinnedFloats && pitch == n_) {
+        if (!pinTried_) {
+            pinTried_ = true;
+            if (hipHostMalloc(reinterpret_cast<void**>(&hPinIn_), kPinnedFloats * 4, hipHostMallocDefault) != hipSuccess ||
+                hipHostMalloc(reinterpret_cast<void**>(&hPinOut_), kPinnedFloats * 4, hipHostMallocDefault) != hipSuccess) {
+                if (hPinIn_) (void)hipHostFree(hPinIn_);
+                hPinIn_ = hPinOut_ = nullptr;
+                (void)hipGetLastError();
+            }
+        }
+        if (hPinIn_ && hPinOut_) {
+            ++hostStagedBlocks_;
+            std::memcpy(hPinIn_, in, count * 4);
+            waitLastLaunch();
+            // no event pair around a launch that is waited for right here (last_kernel_ms: -1) - unless schedules are armed:
+            // the tiers that cut the block at every step launch several times and wait for each launch through its event
+            beginBlock(nSamples);
+            rc = launchBlock(hPinIn_, hPinOut_, nSamples, stream_, n_, tracksArmed() ? kWholeBlock : kUntimed);
+            if (rc != 0) return rc;
+            hipError_t se = hipStreamSynchronize(stream_);
+            if (se != hipSuccess) return hipFail(se, "synchronising a small block");
+            std::memcpy(out, hPinOut_, count * 4);
+            return 0;
+        }
+    }
+    // The caller's buffers are pinned host memory (a real-time host keeps its PCM in such buffers): NO copies at all - the kernel
+    // reads its input from and stores its output to the caller's memory over PCIe, in both directions at once, while it
+    // computes.  One launch, one wait.  Measured (tools/realtime_capacity.py, 32-sample blocks of config5): the staged path's
+    // copy-out is a shader copy (__amd_rocclr_copyBuffer) that slows a kernel running beside it threefold
+    // (profiles/r05_rt_timeline_131072.txt); in place, a block of 131 072 instances takes about what its 16.8 MB each way take the
+    // link.  FX_HOST_PIPELINE=0 keeps the staged copies.  Any row pitch: the kernels address [sample][channel][pitch] - a shard of a
+    // larger batch works on its columns of the caller's buffers, on its own device (this runs on the shard's thread, the device
+    // current: the lookup below is that device's view of the memory).
+    if (knobs_.hostPipeline) {
+        const void *dIn = nullptr, *dOut = nullptr;
+        const size_t bytes = pcmExtent(rows, n_, pitch);
+        // (pinned HOST memory only: anything else handed to this entry, memory of the device included, is staged)
+        if (pcmDisjointOrSame(in, out, rows, n_, pitch) && addressable(in, bytes, -1, &dIn) &&
+            (static_cast<const void*>(out) == in ? (dOut = dIn, true) : addressable(out, bytes, -1, &dOut))) {
+            ++hostInplaceBlocks_;
+            rc = processDevice(static_cast<const float*>(dIn), static_cast<float*>(const_cast<void*>(dOut)), nSamples, stream_, pitch);
+            const hipError_t se = hipStreamSynchronize(stream_);   // (also when the call failed: nothing of it may still touch the caller's memory)
+            if (rc != 0) return rc;
+            return se == hipSuccess ? 0 : hipFail(se, "synchronising a block on pinned host buffers");
+        }
+    }
+    if (count > ioCap_) {
+        (void)hipStreamSynchronize(stream_);
+        (void)hipFree(dIn_);
+        (void)hipFree(dOut_);
+        dIn_ = dOut_ = nullptr;
+        ioCap_ = 0;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dIn_), count * 4);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dOut_), count * 4);
+        if (e != hipSuccess) return hipFail(e, "hipMalloc io");
+        ioCap_ = count;
+    }
+    // Large blocks: copy-in, kernel and copy-out of consecutive pieces overlap.  268 MB each way (tools/host_block_rate.py):
+    // pinned caller buffers 6.5 ms instead of 12.7 (both DMA directions at once), pageable ones 9.7 instead of 12.9 (the driver
+    // pins them on the fly; a freshly allocated, untouched output buffer costs 2-3 x that in page faults either way).
+    ++hostStagedBlocks_;
+    const int pieces = hostPieces(count * 4, nSamples, kHostPieces);
+    if (pieces >= 2 && !tracksArmed() && knobs_.hostPipeline)
+        return processHostPipelined(in, out, nSamples, pitch, pieces);
+    const size_t width = (size_t)n_ * 4;
+    hipError_t e = copyRows(dIn_, width, in, (size_t)pitch * 4, width, rows, hipMemcpyHostToDevice, stream_);
+    if (e != hipSuccess) return hipFail(e, "H2D");
+    rc = processDevice(dIn_, dOut_, nSamples, stream_);
+    if (rc != 0) {
+        (void)hipStreamSynchronize(stream_);   // (whatever went wrong: no copy may still read the caller's buffer when this returns)
+        return rc;
+    }
+    e = copyRows(out, (size_t)pitch * 4, dOut_, width, width, rows, hipMemcpyDeviceToHost, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        return hipFail(e, "D2H");
+    }
+    return 0;
+}
+
+// A large host block in pieces (dIn_ / dOut_ hold the whole block): while the kernel works on piece p, piece p + 1 is on its way
+// in and piece p - 1 on its way out - two copy streams beside the compute stream, ordered by events.  The pieces are
+// consecutive blocks to the kernel: state carries over exactly as between two calls.
+int Batch::processHostPipelined(const float* in, float* out, int nSamples, int64_t pitch, int pieces) {
+    if (!copyIn_) {
+        hipError_t c = hipStreamCreateWithFlags(&copyIn_, hipStreamNonBlocking);
+        if (c == hipSuccess) c = hipStreamCreateWithFlags(&copyOut_, hipStreamNonBlocking);
+        for (int k = 0; k < kHostPieces && c == hipSuccess; ++k) {
+            c = hipEventCreateWithFlags(&evIn_[k], hipEventDisableTiming);
+            if (c == hipSuccess) c = hipEventCreateWithFlags(&evDone_[k], hipEventDisableTiming);
+        }
+        if (c != hipSuccess) return hipFail(c, "streams for the pipelined host block");
+    }
+    const size_t ch = (size_t)prog_.numChannels, width = (size_t)n_ * 4;
+    auto lo = [&](int p) { return (int)((int64_t)nSamples * p / pieces); };
+    auto copyIn = [&](int p) {
+        const size_t first = (size_t)lo(p) * ch, rows = (size_t)(lo(p + 1) - lo(p)) * ch;
+        hipError_t e = copyRows(dIn_ + first * (size_t)n_, width, in + first * (size_t)pitch, (size_t)pitch * 4, width, rows, hipMemcpyHostToDevice, copyIn_);
+        if (e == hipSuccess) e = hipEventRecord(evIn_[p], copyIn_);
+        return e;
+    };
+    auto launch = [&](int p) -> int {
+        hipError_t e = hipStreamWaitEvent(stream_, evIn_[p], 0);
+        if (e != hipSuccess) return hipFail(e, "pipelined host block");
+        const size_t first = (size_t)lo(p) * ch * (size_t)n_;
+        const int rc = launchBlock(dIn_ + first, dOut_ + first, lo(p + 1) - lo(p), stream_, n_, kPiece);
+        if (rc != 0) return rc;
+        e = hipEventRecord(evDone_[p], stream_);
+        return e == hipSuccess ? 0 : hipFail(e, "pipelined host block");
+    };
+    auto copyOut = [&](int p) {
+        const size_t first = (size_t)lo(p) * ch, rows = (size_t)(lo(p + 1) - lo(p)) * ch;
+        hipError_t e = hipStreamWaitEvent(copyOut_, evDone_[p], 0);
+        if (e != hipSuccess) return e;
+        return copyRows(out + first * (size_t)pitch, (size_t)pitch * 4, dOut_ + first * (size_t)n_, width, width, rows, hipMemcpyDeviceToHost, copyOut_);
+    };
+    // (whatever goes wrong: no copy may still touch the caller's buffers when this returns)
+    auto drain = [&]() {
+        (void)hipStreamSynchronize(copyIn_);
+        (void)hipStreamSynchronize(stream_);
+        (void)hipStreamSynchronize(copyOut_);
+    };
+    waitLastLaunch();
+    // the block is ONE call to the bookkeeping of control changes and to the lowering, not kHostPieces
+    beginBlock(nSamples, pieces);
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    hipError_t e = copyIn(0);
+    if (e != hipSuccess) { drain(); return hipFail(e, "H2D"); }
+    rc = launch(0);
+    if (rc != 0) { drain(); return rc; }
+    for (int p = 0; p < pieces; ++p) {
+        if (p + 1 < pieces) {
+            if ((e = copyIn(p + 1)) != hipSuccess) { drain(); return hipFail(e, "H2D"); }
+            if ((rc = launch(p + 1)) != 0) { drain(); return rc; }
+        }
+        if ((e = copyOut(p)) != hipSuccess) { drain(); return hipFail(e, "D2H"); }
+    }
+    e = hipStreamSynchronize(copyOut_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    return e == hipSuccess ? 0 : hipFail(e, "pipelined host block");
+}
+
+// Generate the code a stream of `nSamples`-sample blocks will run, now - a real-time caller does this after loading, before the
+// stream starts, instead of paying for the translation in its first block.  wait: also until the builder thread has finished
+// what it was asked for (the variant with the controls in rows, other stage counts on trial).
+int Batch::prepare(int nSamples, bool wait) {
+    (void)hipSetDevice(device_);
+    if (nSamples < 1) return fail(FX_E_ARG, "prepare: n_samples >= 1");
+    pendingSamples_ = nSamples;
+    noteBlockLength(nSamples);
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    everLowered_ = true;
+    leanStep();   // (controls have rows and some of them rest: their variant is asked for now)
+    if (wait && builder_) {
+        std::unique_lock<std::mutex> lock(builder_->mu);
+        builder_->cv.wait(lock, [&] { return builder_->running.empty() && builder_->jobs.empty(); });
+        lock.unlock();
+        collectBuilt();
+        leanStep();   // ... and in force when this returns
+        rc = ensureLowered();
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+int Batch::sync() {
+    (void)hipSetDevice(device_);
+    hipError_t e = hipStreamSynchronize(stream_);
+    if (e == hipSuccess && launched_) e = hipEventSynchronize(ev1_);
+    return e == hipSuccess ? 0 : hipFail(e, "sync");
+}
+
+}  // namespace fx

@@ -228,10 +228,10 @@ int Sharded::setRegisterTrack(const std::string& key, const float* values, int n
 int Sharded::processHost(const float* in, float* out, int nSamples, int64_t pitch) {
     Serial serial(api_);
     lastError_.clear();
+    // what goes by the instance count of the WHOLE batch, before any shard is posted: the default pitch and the refusal of a
+    // narrower one (a shard would compare with its own count); every other refusal is the shards' (Batch::checkBlock)
     if (pitch == 0) pitch = n_;
-    if (pitch < n_) { lastError_ = "host row pitch below the instance count"; return FX_E_ARG; }
-    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.processHost(in, out, nSamples, pitch); });
-    if (nSamples > 0 && (!in || !out)) { lastError_ = "null buffer"; return FX_E_ARG; }
+    if (pitch < n_) { lastError_ = "PCM row pitch below the instance count"; return FX_E_ARG; }
     // each shard on its own thread, its device current: in place on its columns when that device can address the buffers, staged
     // copies of its columns otherwise (only that shard)
     return fan([&](int k, Batch& b) {

@@ -291,7 +291,7 @@ class Translator {
         {
             // diagnostics build only (FX_XLATE_ENDSTAMP=1): when does each wavefront finish?  Behind the last sample's PCM store the
             // low word of the 100 MHz clock goes to word [wavefront] of a buffer of ITS OWN - the batch hands it over in the kernarg
-            // slot of the stage descriptors, which an unstaged launch does not use (fx_batch.cpp; read back with
+            // slot of the stage descriptors, which an unstaged launch does not use (fx_batch_io.cpp launchBlock; read back with
             // fxb_diag_read_stamps, tools/wave_end_probe.py) - never into an output element (MI355X_MICROARCH.md on stamps)
             static const bool stamp = FX_DIAG_KNOB("FX_XLATE_ENDSTAMP") != nullptr;
             if (stamp && isLast_ && !staged) {

@@ -1,6 +1,6 @@
 // hip_stub.cpp — a device-free stand-in for the HIP runtime calls the host side of libfx8010_amd.so makes (TEST INFRASTRUCTURE).
 //
-// The product's host engine (fx_batch.cpp, fx_shard.cpp, fx_asm.cpp: code cache, builder thread, launch-timing tuner, shard
+// The product's host engine (fx_batch*.cpp, fx_shard.cpp, fx_asm.cpp: code cache, builder thread, launch-timing tuner, shard
 // mailboxes) is ordinary multi-threaded C++ whose only contact with the GPU is the HIP runtime API.  This file implements
 // that API - the ~40 functions the library calls, nothing more - on the host, so that the SAME host sources, untouched, can be
 // linked into a library that runs without a GPU under ThreadSanitizer / AddressSanitizer (csrc/Makefile `tsan`, `stubasan`;

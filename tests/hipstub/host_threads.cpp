@@ -2,7 +2,7 @@
 // (TEST INFRASTRUCTURE: csrc/Makefile `tsan` / `stubasan` link this file with the library's host sources and tests/hipstub/).
 //
 // The reference is single-threaded (/root/reference/include/FX8010.h:47-75: plain members, no locks); everything concurrent in
-// this library is its own: a builder thread per handle that generates code ahead of the caller (fx_batch.cpp Batch::Builder), a
+// this library is its own: a builder thread per handle that generates code ahead of the caller (fx_batch_code.cpp, Batch::Builder), a
 // cache of finished code handed across threads, a tuner that times the caller's launches while the builder loads modules, one
 // worker thread + mailbox per shard of a multi-device handle (fx_shard.cpp) - and the stand-in's stream threads, which play the
 // GPU.  Scenarios:
@@ -10,7 +10,8 @@
 //                 values that change the key (eviction), fxb_prepare with and without waiting, a load while builds are queued
 //                 (drainBuilder), destruction with the builder busy
 //   queued        tuner trials with launches queued back to back on device-resident buffers (no sync per block)
-//   hostpipe      a host block cut into pieces on three streams (copy-in, kernel, copy-out overlapping), a launch failing in the middle
+//   hostpipe      a host block cut into pieces on three streams (copy-in, kernel, copy-out overlapping) at the natural and at a wider
+//                 pitch; a launch failing in the middle of it, in a staged block of one piece and in a block in place
 //   shards        a 3-shard handle with two host threads posting: blocks on one, register / counter reads on the other
 //   handles       independent handles on independent threads (process-wide tables: templates, interpreter module, LUTs)
 //   memory        a load whose delay memory cannot be allocated -> FX_E_MEMORY, handle stays usable; 50 create / load / run /
@@ -206,9 +207,42 @@ void scenarioHostPipe() {
         const int rc = fxb_process_block(h, xin.data(), yout.data(), S);
         CHECK(rc == FX_E_NODEVICE);
     }   // (freed here)
+    // ... the same on the other routes: pieces at a wider pitch (2-D copies), staged in one piece, in place on pinned buffers
+    fxstub_fail_launches(3, 1, (int)hipErrorLaunchFailure);
+    {
+        std::vector<float> xin((size_t)(N + 32) * S, 0.5f), yout(xin.size());
+        CHECK(fxb_process_block_pitched(h, xin.data() + 8, yout.data() + 8, S, N + 32) == FX_E_NODEVICE);
+    }
+    fxstub_fail_launches(0, 1, (int)hipErrorLaunchFailure);
+    {
+        std::vector<float> xin((size_t)(N + 32) * 64, 0.5f), yout(xin.size());
+        CHECK(fxb_process_block_pitched(h, xin.data() + 8, yout.data() + 8, 64, N + 32) == FX_E_NODEVICE);
+    }
+    fxstub_fail_launches(0, 1, (int)hipErrorLaunchFailure);
+    {
+        float* px = static_cast<float*>(fxb_host_alloc((int64_t)N * 32 * 4));
+        CHECK(px && fxb_process_block(h, px, px, 32) == FX_E_NODEVICE);
+        fxb_host_free(px);
+    }
     fxstub_fail_launches(-1, 0, 0);
     std::vector<float> y(x.size());
     CHECK(fxb_process_block(h, x.data(), y.data(), S) == 0);
+    // pieces at a wider pitch: every piece comes back, nothing outside the handle's columns is written
+    {
+        const size_t P = (size_t)N + 32;
+        std::vector<float> xin(P * S, 0.5f), yout(P * S, -7.0f);
+        for (size_t r = 0; r < (size_t)S; ++r) std::memcpy(&xin[r * P + 8], &x[r * (size_t)N], (size_t)N * 4);
+        const long before = fxstub_kernels_run();
+        CHECK(fxb_process_block_pitched(h, xin.data() + 8, yout.data() + 8, S, (int64_t)P) == 0);
+        CHECK(fxstub_kernels_run() == before + 8);
+        bool same = true, clean = true;
+        for (size_t r = 0; r < (size_t)S; ++r) {
+            same = same && std::memcmp(&yout[r * P + 8], &x[r * (size_t)N], (size_t)N * 4) == 0;
+            for (size_t c = 0; c < 8; ++c) clean = clean && yout[r * P + c] == -7.0f;
+            for (size_t c = 8 + (size_t)N; c < P; ++c) clean = clean && yout[r * P + c] == -7.0f;
+        }
+        CHECK(same && clean);
+    }
     fxb_destroy(h);
 }
 

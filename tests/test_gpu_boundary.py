@@ -386,7 +386,7 @@ def test_many_tracks_in_one_block(gpu, track_tier):
 
 @pytest.mark.parametrize("channels", [1, 2])
 def test_small_host_blocks_take_the_pinned_path_and_large_ones_the_staged_copies(gpu, channels):
-    """Host blocks of up to 2 KB of PCM are read and written by the kernel in pinned host memory (fx_batch.cpp processHost);
+    """Host blocks of up to 2 KB of PCM are read and written by the kernel in pinned host memory (fx_batch_io.cpp processHost);
     larger ones are copied.  The same instances fed in blocks of both sizes, interleaved, must follow the oracle bit for bit."""
     if channels == 1:
         text = progs.config3()
@@ -471,7 +471,7 @@ def test_schedules_in_small_host_blocks_on_the_tiers_that_cut_the_block(gpu, tra
 @pytest.mark.parametrize("shards", [1, 2])
 def test_large_host_block_in_pinned_buffers_is_processed_in_overlapping_pieces(gpu, shards):
     """fxb_process_block on large host blocks: pageable caller buffers go through staged copies in overlapping pieces on three
-    streams (fx_batch.cpp processHostPipelined: 42 MB each way = five pieces), pinned buffers of a single-shard handle are
+    streams (fx_batch_io.cpp processHostPipelined: 42 MB each way = five pieces), pinned buffers of a single-shard handle are
     processed in place (no copies), the shards of a multi-shard handle copy their columns of the caller's rows (2-D copies, in
     pieces).  All of them are consecutive blocks to the kernel: state, delay lines and counters must come out exactly alike, and
     as the oracle says."""
@@ -1073,7 +1073,7 @@ def test_delay_memory_that_cannot_be_allocated(gpu):
 @pytest.mark.parametrize("channels", [1, 2])
 def test_pinned_caller_buffers_are_processed_in_place(gpu, channels, monkeypatch):
     """A real-time host keeps its PCM in pinned memory; fxb_process_block then runs the kernel on the caller's buffers themselves
-    (hipPointerGetAttributes says they are device-visible: no staging copies, one launch - fx_batch.cpp processHost).  Same words
+    (hipPointerGetAttributes says they are device-visible: no staging copies, one launch - fx_batch_io.cpp processHost).  Same words
     as through pageable buffers (staged copies) and as with FX_HOST_PIPELINE=0 (the knob that turns the in-place path off):
     uneven blocks from 1 sample up, a slider moving in between, a control schedule inside a block, a buffer that starts in the middle of a pinned allocation, input
     and output in ONE buffer (in place in the caller's sense too), mono and stereo; the mono run against the oracle."""
@@ -1142,7 +1142,7 @@ def test_overlapping_and_partly_pinned_buffers_take_the_staged_copies(gpu, monke
     """The in-place path is for buffers the kernel can work on sample by sample: one buffer (in == out) or two that do not
     overlap, each WHOLLY inside one pinned mapping.  An output range shifted against the input by a few sample periods would be
     overwritten while other wavefronts still read it, and a buffer only the front of which is registered would fault the GPU at its
-    first unpinned page: both take the staged copies (fx_batch.cpp processHost: overlapButNotEqual, deviceVisibleRange), so the
+    first unpinned page: both take the staged copies (fx_batch_io.cpp processHost: pcmDisjointOrSame, addressable), so the
     words are those of pageable buffers (or, where the runtime cannot copy from a half-registered buffer either, the call says so).  The reference's caller owns one float per call (/root/reference/include/FX8010.h:57);
     blocks and their aliasing rules are this library's, written in include/fx8010_amd.h."""
     import torch

@@ -154,10 +154,10 @@ def test_committed_counter_passes_name_the_code_generated_today():
             fe.set_option(option)
         assert fe.load_text(P.CONFIGS[config]())
         slots = {"config5": 8192, "config3": 1000, "tram_bound": 8192, "config5_dane": 8192}.get(config, 0)
-        streaming = slots * ((b["instances"] + 63) // 64) * 256 > (512 << 20)   # (fx_batch.cpp: delay lines beyond the caches)
+        streaming = slots * ((b["instances"] + 63) // 64) * 256 > (512 << 20)   # (fx_batch_code.cpp translateInto: delay lines beyond the caches)
         waves = (b["instances"] + 63) // 64
         resident = {64: 8, 72: 7, 80: 6, 96: 5, 128: 4, 168: 3, 256: 2}[int(m.group(1))]
-        slices = (b.get("stages") or 1) == 1 and waves >= 2048 and resident <= 4   # (fx_batch.cpp: two or more wavefronts per SIMD on a build of at most four slots)
+        slices = (b.get("stages") or 1) == 1 and waves >= 2048 and resident <= 4   # (fx_batch_code.cpp priorityTurns: two or more wavefronts per SIMD on a build of at most four slots)
         now = "%016x" % fe.code_hash(int(m.group(1)), b.get("stages") or 1, streaming, slices)
         assert now == b["code_hash"], "%s was collected on other code than is generated today (%s vs %s): run tools/profile_configs.sh again" % (os.path.basename(f), b["code_hash"], now)
 
@@ -268,7 +268,7 @@ def test_dane_model_listing_reassembles_and_has_no_cursor_advance():
 
 @needs_llvm
 def test_priority_turns_listing_reassembles(monkeypatch):
-    """what a batch of two or more wavefronts per SIMD generates (fx_batch.cpp; on a build of at most four wave slots): every
+    """what a batch of two or more wavefronts per SIMD generates (fx_batch_code.cpp priorityTurns; on a build of at most four wave slots): every
     fourth sample the wavefront reads the 100 MHz clock and takes the priority ((clock >> s8) + wave-buffer slot) & 3; s8 comes from
     the run-once code (log2 of the block length + log2 of the modelled sample period / 24, at least 16).  The new encodings
     (s_memrealtime, s_getreg_b32, s_setprio, s_flbit_i32_b32, s_max_i32, s_lshr_b32) against llvm-mc; off by default here."""
