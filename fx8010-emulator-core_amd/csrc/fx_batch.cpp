@@ -73,6 +73,9 @@ Batch::~Batch() {
     (void)hipFree(dTracks_);
     (void)hipFree(dIn_);
     (void)hipFree(dOut_);
+    (void)hipFree(dBus_);
+    (void)hipFree(dBusStage_);
+    if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS
     (void)hipFree(dStamps_);
 #endif
@@ -93,6 +96,8 @@ Batch::~Batch() {
 // garbage-collected): wait on the event recorded behind that launch instead of holding the foreign handle.
 void Batch::waitLastLaunch() {
     if (launched_) (void)hipEventSynchronize(ev1_);
+    // (a bus block ends behind its emulation launch: the mix kernel, or the copy out of the scratch block)
+    if (busLaunched_) (void)hipEventSynchronize(evBus_);
 }
 
 int Batch::fail(int code, const std::string& what) {
@@ -770,6 +775,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_GRID) return lastGrid_;
     if (what == FXB_INFO_HOST_STAGED_BLOCKS) return hostStagedBlocks_;
     if (what == FXB_INFO_HOST_INPLACE_BLOCKS) return hostInplaceBlocks_;
+    if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fx_asm.hpp"
+#include "fx_bus.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -54,6 +55,16 @@ public:
     // the same for a caller's pointers: refused (FX_E_ARG, no launch) unless both footprints are memory of this handle's device or
     // device-visible host memory, and in == out or the two share no element
     int processDeviceChecked(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream);
+    // Group buses (fx_bus.hpp; include/fx8010_amd.h FXB_BUS_*): with kBusSharedIn `in` is [nSamples][channels][inPitch] with one
+    // column per group of `group` instances, with kBusMixOut `out` is the same shape and takes every group's sum; a side without
+    // its flag is [nSamples][channels][pitch] with one column per instance as in processHost.  Pitch 0: the side's own width.  A
+    // shard of a larger batch passes the caller's full-width buffers from its own first column on.  kBusHost: synchronous, in
+    // place on pinned buffers or staged; kBusDevice: the buffers are checked like processDeviceChecked's, asynchronous on `stream`.
+    enum : unsigned { kBusSharedIn = 1u << 0, kBusMixOut = 1u << 1, kBusFlags = 3u };
+    enum BusEntry { kBusHost, kBusDevice };
+    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream);
+    // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
+    static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     int sync();
     int prepare(int nSamples, bool wait);   // generate the code for blocks of this length now (and wait for the builder thread)
 
@@ -368,6 +379,26 @@ private:
     size_t checkedBytes_ = 0;
     const float* checkedDevIn_ = nullptr;   // ... and the device addresses of the two
     float* checkedDevOut_ = nullptr;
+    // bus blocks: expand -> the ordinary launch in place on the scratch -> mix, piece by piece on one stream
+    struct BusShape { int64_t group = 1, groups = 1, inWidth = 0, outWidth = 0, inPitch = 0, outPitch = 0; };
+    static constexpr size_t kBusScratchBytes = (size_t)64 << 20;   // 32 samples of 524 288 instances: real-time blocks are never cut
+    int checkBus(const float* in, const float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
+    int ensureBusScratch(size_t floats);
+    int ensureBusStage(size_t floats);
+    int runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
+               const BusShape& shape, hipStream_t stream);
+    float* dBus_ = nullptr;         // the per-instance scratch [samples of a piece][channels][n]
+    size_t busCap_ = 0;             // floats
+    float* dBusStage_ = nullptr;    // pageable host buffers: the [samples][channels][groups] sides of a block
+    size_t busStageCap_ = 0;
+    hipEvent_t evBus_ = nullptr;    // behind the last kernel of the most recent bus block
+    bool busLaunched_ = false;
+    int64_t busBlocks_ = 0;         // FXB_INFO_BUS_BLOCKS
+    const float* busCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one
+    const float* busCheckedOut_ = nullptr;
+    size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;
+    const float* busCheckedDevIn_ = nullptr;
+    float* busCheckedDevOut_ = nullptr;
 #ifdef FX_DIAGNOSTICS
     int ensureEndStamps();   // the end stamps' buffer (dStamps_), one word per wavefront
 #endif

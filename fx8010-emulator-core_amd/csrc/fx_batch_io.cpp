@@ -473,6 +473,189 @@ int Batch::processHostPipelined(const float* in, float* out, int nSamples, int64
     return e == hipSuccess ? 0 : hipFail(e, "pipelined host block");
 }
 
+// ---- group buses: a shared input and / or a mixed output per group of instances (fx_bus.hpp) ---------------------------------------
+//
+// None of the three kernel tiers knows about groups: a bus block is expand -> the ordinary launch, in place on a per-instance
+// scratch block in device memory -> mix, ordered on one stream.  What crosses PCIe is the [sample][channel][group] side only.
+
+bool Batch::busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch) {
+    const bool oneLayout = inWidth == outWidth && inPitch == outPitch;
+    if (in == out) return oneLayout;
+    const char *x = reinterpret_cast<const char*>(in), *y = reinterpret_cast<const char*>(out);
+    if (x + pcmExtent(rows, inWidth, inPitch) <= y || y + pcmExtent(rows, outWidth, outPitch) <= x) return true;
+    return oneLayout && pcmDisjointOrSame(in, out, rows, inWidth, inPitch);   // (two column ranges of one buffer)
+}
+
+// The refusals of the bus entries, in front of everything else: a refused call has launched nothing and changed nothing.
+int Batch::checkBus(const float* in, const float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
+    if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
+    if (group < 1) return fail(FX_E_ARG, "bus: group must be at least 1");
+    if (flags & ~(unsigned)kBusFlags) return fail(FX_E_ARG, "bus: unknown flag bits");
+    BusShape s;
+    s.group = std::min(group, n_);   // (a larger group is the one group of everything)
+    s.groups = (n_ + s.group - 1) / s.group;
+    s.inWidth = (flags & kBusSharedIn) ? s.groups : n_;
+    s.outWidth = (flags & kBusMixOut) ? s.groups : n_;
+    s.inPitch = inPitch > 0 ? inPitch : s.inWidth;
+    s.outPitch = outPitch > 0 ? outPitch : s.outWidth;
+    if (s.inPitch < s.inWidth || s.outPitch < s.outWidth) return fail(FX_E_ARG, "bus: row pitch below the width of the layout");
+    if (pcmStrideTooWide(prog_.numChannels, s.inPitch) || pcmStrideTooWide(prog_.numChannels, s.outPitch) || pcmStrideTooWide(prog_.numChannels, n_))
+        return fail(FX_E_ARG, "bus: PCM row too wide: channels * row length * 4 must stay below 2^32 in every layout");
+    if (nSamples > 0 && (!in || !out)) return fail(FX_E_ARG, "null buffer");
+    if (nSamples > 0 && !busBuffersApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
+        return fail(FX_E_ARG, "bus: input and output overlap without being one buffer with one layout");
+    *shape = s;
+    return 0;
+}
+
+int Batch::ensureBusScratch(size_t floats) {
+    if (!evBus_) {
+        const hipError_t e = hipEventCreateWithFlags(&evBus_, hipEventDisableTiming);
+        if (e != hipSuccess) { evBus_ = nullptr; return hipFail(e, "bus event"); }
+    }
+    if (floats <= busCap_) return 0;
+    // (a block on the caller's stream may still be working on the old one)
+    if (busLaunched_) (void)hipEventSynchronize(evBus_);
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dBus_);
+    dBus_ = nullptr;
+    busCap_ = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBus_), floats * 4);
+    if (e != hipSuccess) { dBus_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc bus scratch"); }
+    busCap_ = floats;
+    return 0;
+}
+
+int Batch::ensureBusStage(size_t floats) {
+    if (floats <= busStageCap_) return 0;
+    (void)hipStreamSynchronize(stream_);
+    (void)hipFree(dBusStage_);
+    dBusStage_ = nullptr;
+    busStageCap_ = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBusStage_), floats * 4);
+    if (e != hipSuccess) { dBusStage_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc bus staging"); }
+    busStageCap_ = floats;
+    return 0;
+}
+
+// The block itself, asynchronous on `stream`.  in / out: the per-instance sides as the caller gave them (copied to / from the
+// scratch by the runtime), narrowIn / narrowOut: the per-group sides as the device addresses them.  A block whose scratch would
+// exceed kBusScratchBytes runs in consecutive sample ranges that fit - consecutive blocks to the kernel, like the pieces of
+// processHostPipelined; with control tracks armed the block stays whole (a schedule counts samples from the head of ONE launch).
+int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
+                  const BusShape& shape, hipStream_t stream) {
+    const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
+    const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
+    const int pieces = (nSamples + most - 1) / most;
+    int rc = ensureBusScratch((size_t)((nSamples + pieces - 1) / pieces) * perSample);
+    if (rc != 0) return rc;
+    hipStream_t s = pick(stream);
+    // The scratch is one buffer: the previous bus block, on whatever stream it ran, must have emptied it before this one fills it
+    // (the host entry has waited for it on the host already: waitLastLaunch).
+    if (busLaunched_) {
+        const hipError_t we = hipStreamWaitEvent(s, evBus_, 0);
+        if (we != hipSuccess) return hipFail(we, "bus: waiting for the previous bus block");
+    }
+    beginBlock(nSamples, pieces);   // ONE block to the bookkeeping of control changes and to the lowering
+    if ((rc = ensureLowered()) != 0) return rc;
+    auto lo = [&](int p) { return (int)((int64_t)nSamples * p / pieces); };
+    const size_t width = (size_t)n_ * 4;
+    for (int p = 0; p < pieces; ++p) {
+        const int count = lo(p + 1) - lo(p);
+        const size_t first = (size_t)lo(p) * ch;
+        BusArgs a{};
+        a.wide = dBus_;
+        a.rows = (long long)count * (long long)ch;
+        a.n = n_;
+        a.group = shape.group;
+        a.groups = shape.groups;
+        hipError_t e;
+        if (flags & kBusSharedIn) {
+            a.narrowIn = narrowIn + first * (size_t)narrowInPitch;
+            a.narrowPitch = narrowInPitch;
+            e = launchBusExpand(a, s);
+        } else {
+            e = copyRows(dBus_, width, in + first * (size_t)shape.inPitch, (size_t)shape.inPitch * 4, width, (size_t)a.rows, hipMemcpyDefault, s);
+        }
+        if (e != hipSuccess) return hipFail(e, "bus: filling the scratch block");
+        if ((rc = launchBlock(dBus_, dBus_, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) {
+            if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
+            return rc;
+        }
+        if (flags & kBusMixOut) {
+            a.narrowIn = nullptr;
+            a.narrowOut = narrowOut + first * (size_t)narrowOutPitch;
+            a.narrowPitch = narrowOutPitch;
+            e = launchBusMix(a, s);
+        } else {
+            e = copyRows(out + first * (size_t)shape.outPitch, (size_t)shape.outPitch * 4, dBus_, width, width, (size_t)a.rows, hipMemcpyDefault, s);
+        }
+        if (e == hipSuccess) e = hipEventRecord(evBus_, s);
+        if (e != hipSuccess) return hipFail(e, "bus: emptying the scratch block");
+        busLaunched_ = true;
+    }
+    ++busBlocks_;   // (blocks whose every piece was queued)
+    return 0;
+}
+
+int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream) {
+    (void)hipSetDevice(device_);
+    BusShape shape;
+    int rc = checkBus(in, out, nSamples, group, flags, inPitch, outPitch, &shape);
+    if (rc != 0) return rc;
+    if (nSamples == 0) return ensureLowered();
+    const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels;
+    const size_t inBytes = pcmExtent(rows, shape.inWidth, shape.inPitch), outBytes = pcmExtent(rows, shape.outWidth, shape.outPitch);
+    const void *devIn = nullptr, *devOut = nullptr;
+    if (entry == kBusDevice) {
+        if (in != busCheckedIn_ || out != busCheckedOut_ || inBytes > busCheckedInBytes_ || outBytes > busCheckedOutBytes_) {
+            busCheckedIn_ = busCheckedOut_ = nullptr;
+            if (!addressable(in, inBytes, device_, &devIn) || !addressable(out, outBytes, device_, &devOut))
+                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
+            busCheckedIn_ = in;
+            busCheckedOut_ = out;
+            busCheckedInBytes_ = inBytes;
+            busCheckedOutBytes_ = outBytes;
+            busCheckedDevIn_ = static_cast<const float*>(devIn);
+            busCheckedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
+        }
+        return runBus(busCheckedDevIn_, busCheckedDevOut_, busCheckedDevIn_, shape.inPitch, busCheckedDevOut_, shape.outPitch, nSamples, flags, shape, stream);
+    }
+    // Host entry.  Pinned buffers: the bus kernels read the group words from and store the sums to the caller's memory over PCIe
+    // (256 bytes per wavefront access), no copies.  Anything else: the [sample][channel][group] sides are staged.  Whatever
+    // happens, nothing of the call may still touch the caller's memory when it returns.
+    waitLastLaunch();
+    if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && addressable(out, outBytes, -1, &devOut)) {
+        const float* dIn = static_cast<const float*>(devIn);
+        float* dOut = static_cast<float*>(const_cast<void*>(devOut));
+        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_);
+        const hipError_t se = hipStreamSynchronize(stream_);
+        if (rc != 0) return rc;
+        if (se != hipSuccess) return hipFail(se, "synchronising a bus block on pinned host buffers");
+        ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
+        return 0;
+    }
+    const size_t side = rows * (size_t)shape.groups;
+    const bool sharedIn = (flags & kBusSharedIn) != 0, mixOut = (flags & kBusMixOut) != 0;
+    if ((rc = ensureBusStage(side * ((sharedIn ? 1 : 0) + (mixOut ? 1 : 0)))) != 0) return rc;
+    float* stageIn = dBusStage_;
+    float* stageOut = dBusStage_ + (sharedIn ? side : 0);
+    const size_t narrow = (size_t)shape.groups * 4;
+    hipError_t e = hipSuccess;
+    if (sharedIn) e = copyRows(stageIn, narrow, in, (size_t)shape.inPitch * 4, narrow, rows, hipMemcpyDefault, stream_);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        return hipFail(e, "bus H2D");
+    }
+    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_);
+    if (rc == 0 && mixOut) e = copyRows(out, (size_t)shape.outPitch * 4, stageOut, narrow, narrow, rows, hipMemcpyDefault, stream_);
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (rc != 0) return rc;
+    if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "bus D2H");
+    ++hostStagedBlocks_;
+    return 0;
+}
+
 // Generate the code a stream of `nSamples`-sample blocks will run, now - a real-time caller does this after loading, before the
 // stream starts, instead of paying for the translation in its first block.  wait: also until the builder thread has finished
 // what it was asked for (the variant with the controls in rows, other stage counts on trial).
@@ -501,6 +684,7 @@ int Batch::sync() {
     (void)hipSetDevice(device_);
     hipError_t e = hipStreamSynchronize(stream_);
     if (e == hipSuccess && launched_) e = hipEventSynchronize(ev1_);
+    if (e == hipSuccess && busLaunched_) e = hipEventSynchronize(evBus_);   // (the last kernel of a bus block on the caller's stream)
     return e == hipSuccess ? 0 : hipFail(e, "sync");
 }
 

@@ -1,0 +1,153 @@
+// fx_bus.hip — the two kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
+// per-instance scratch, mix the scratch down to one word per group.  gfx950, wave64, one wavefront per workgroup.  The narrow side,
+// which may be pinned host memory behind PCIe, sees exactly one 256-byte access per wavefront and row.  The wide side: the expand
+// stores 1 KiB per wavefront access; the mix loads 256 contiguous bytes per access for groups of 64 instances and more, and ONE
+// PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
+// 64 trees on 256 bytes; packing several short groups into one load with a segmented tree of the same bits is open).  Groups above
+// 64 are summed by one wavefront, four loads in flight: a group of a whole row (K = N) is one wavefront walking the row.
+#include <hip/hip_runtime.h>
+
+#include "fx_bus.hpp"
+
+namespace fx {
+
+namespace {
+
+constexpr unsigned kExpandSpan = 2048;   // floats of a row one wavefront writes: 8 stores of 1 KiB
+
+__device__ __forceinline__ uint32_t laneWord(uint32_t v, unsigned src) { return (uint32_t)__shfl((int)v, (int)(src & 63u)); }
+
+// grid.x = blocks of 64 groups x slices of kExpandSpan instances, grid.y strides over the rows.  Words are moved as bits: a NaN
+// keeps its payload.
+__global__ __launch_bounds__(64) void fx_bus_expand(BusArgs a, unsigned slices) {
+    const unsigned lane = threadIdx.x;
+    const unsigned K = (unsigned)a.group, n = (unsigned)a.n;
+    const long long g0 = (long long)(blockIdx.x / slices) * 64;
+    const long long lo = g0 * (long long)K + (long long)(blockIdx.x % slices) * kExpandSpan;
+    long long hi = (g0 + 64) * (long long)K;
+    if (hi > (long long)n) hi = n;
+    if (hi > lo + (long long)kExpandSpan) hi = lo + kExpandSpan;
+    if (lo >= hi) return;   // (the whole wavefront)
+    const unsigned first = (unsigned)lo, end = (unsigned)hi, gFirst = (unsigned)g0;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.narrowIn);
+    uint32_t* wide = reinterpret_cast<uint32_t*>(a.wide);
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        uint32_t v = 0;
+        if (g0 + lane < a.groups) v = src[row * a.narrowPitch + g0 + lane];   // one 256-byte load
+        uint32_t* dst = wide + row * a.n;
+        // up to three words in front of the first 16-byte boundary, then whole uint4 stores, the ragged end word by word
+        const unsigned head = (unsigned)((4u - (unsigned)((reinterpret_cast<uintptr_t>(dst + first) >> 2) & 3u)) & 3u);
+        {
+            const unsigned i = first + lane;
+            const uint32_t w = laneWord(v, i / K - gFirst);
+            if (lane < head && i < end) dst[i] = w;
+        }
+        for (unsigned base = first + head; base < end; base += 256u) {
+            const unsigned i = base + lane * 4u;
+            const unsigned at = i < end ? i : end - 1u;
+            unsigned q = at / K, r = at - q * K;
+            uint32_t w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                w[e] = laneWord(v, q - gFirst);
+                if (++r == K) { r = 0; ++q; }
+            }
+            if (i + 4u <= end) {
+                *reinterpret_cast<uint4*>(dst + i) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (i + (unsigned)e < end) dst[i + e] = w[e];
+            }
+        }
+    }
+}
+
+// the 64-lane shuffle-down tree; lanes at and beyond 64 - step take a value nobody reads
+__device__ __forceinline__ float treeSum(float p) {
+#pragma unroll
+    for (int step = 32; step > 0; step >>= 1) p = p + __shfl_down(p, step);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p)));
+}
+
+// grid.x = blocks of 64 groups, grid.y strides over the rows: group g0 + k's sum ends in lane k, one 256-byte store per row
+__global__ __launch_bounds__(64) void fx_bus_mix(BusArgs a) {
+    const unsigned lane = threadIdx.x;
+    const long long K = a.group;
+    const long long g0 = (long long)blockIdx.x * 64;
+    const int here = (int)(a.groups - g0 < 64 ? a.groups - g0 : 64);
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        const float* y = a.wide + row * a.n;
+        float res = 0.0f;
+        if (K <= 64) {
+            // a group is one partial wavefront load: eight of them in flight at a time
+            for (int k0 = 0; k0 < here; k0 += 8) {
+                float v[8];
+                bool have[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const long long first = (g0 + k0 + u) * K;
+                    const long long count = a.n - first < K ? a.n - first : K;
+                    have[u] = k0 + u < here && (long long)lane < count;
+                    v[u] = have[u] ? y[first + lane] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    float p = 0.0f;
+                    p = have[u] ? p + v[u] : p;
+                    const float sum = treeSum(p);
+                    if ((int)lane == k0 + u) res = sum;
+                }
+            }
+        } else {
+            for (int k = 0; k < here; ++k) {
+                const long long first = (g0 + k) * K;
+                const long long count = a.n - first < K ? a.n - first : K;
+                float p = 0.0f;
+                for (long long m0 = 0; m0 < count; m0 += 256) {
+                    float v[4];
+                    bool have[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const long long m = m0 + u * 64 + lane;
+                        have[u] = m < count;
+                        v[u] = have[u] ? y[first + m] : 0.0f;   // 256 contiguous bytes per load
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) p = have[u] ? p + v[u] : p;
+                }
+                const float sum = treeSum(p);
+                if ((int)lane == k) res = sum;
+            }
+        }
+        if ((int)lane < here) a.narrowOut[row * a.narrowPitch + g0 + lane] = res;
+    }
+}
+
+inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
+
+}  // namespace
+
+hipError_t launchBusExpand(const BusArgs& a, hipStream_t stream) {
+    if (badArgs(a) || !a.narrowIn || a.n >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    const long long blocks = (a.groups + 63) / 64;
+    const long long widest = 64 * a.group < a.n ? 64 * a.group : a.n;   // instances of a block of 64 groups
+    const long long slices = (widest + kExpandSpan - 1) / kExpandSpan;
+    if (blocks * slices >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(blocks * slices), (unsigned)(a.rows < 65535 ? a.rows : 65535));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_bus_expand, grid, dim3(64), 0, stream, a, (unsigned)slices);
+    return hipGetLastError();
+}
+
+hipError_t launchBusMix(const BusArgs& a, hipStream_t stream) {
+    if (badArgs(a) || !a.narrowOut) return hipErrorInvalidValue;
+    const long long blocks = (a.groups + 63) / 64;
+    if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks, (unsigned)(a.rows < 65535 ? a.rows : 65535));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_bus_mix, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace fx

@@ -219,6 +219,17 @@ int fxb_process_block_dev_pitched(fxb_handle* h, const float* d_in, float* d_out
 int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float* const* d_out, int n) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processDeviceShards(d_in, d_out, n); }) : FX_E_ARG;
 }
+int64_t fxb_bus_groups(fxb_handle* h, int64_t group) { 
+    if (!h || group < 1) return FX_E_ARG;
+    const int64_t n = h->batch.instances(), k = std::min(group, n);   // (a larger group is the one group of everything; no overflow)
+    return (n + k - 1) / k;
+}
+int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n, int64_t group, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(in, out, n, group, flags, false, nullptr); }) : FX_E_ARG;
+}
+int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t group, unsigned flags, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
+}
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }
 int64_t fxb_state_size(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.stateBytes(); }) : FX_E_ARG; }

@@ -257,6 +257,31 @@ int Sharded::processDevicePitched(const float* dIn, float* dOut, int nSamples, i
     if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
     return runOn(0, [&](Batch& b) { return b.processDeviceChecked(dIn, dOut, nSamples, pitch, stream); });
 }
+int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream) {
+    Serial serial(api_);
+    lastError_.clear();
+    // the refusals that go by the WHOLE batch, before any shard is posted (a refused call launches nothing on any shard)
+    if (group < 1) { lastError_ = "bus: group must be at least 1"; return FX_E_ARG; }
+    if (flags & ~(unsigned)Batch::kBusFlags) { lastError_ = "bus: unknown flag bits"; return FX_E_ARG; }
+    if (device && shards_.size() != 1) { lastError_ = "the device entry of a bus block is for handles of one shard"; return FX_E_ARG; }
+    if (flags == 0) return device ? processDevicePitched(in, out, nSamples, n_, stream) : processHost(in, out, nSamples, 0);
+    if (shards_.size() == 1)
+        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream); });
+    for (auto& w : shards_)
+        if (w->first % group != 0) { lastError_ = "bus: a group straddles shards (every shard must begin at a multiple of the group size: fxb_shard_plan)"; return FX_E_ARG; }
+    const int64_t groups = (n_ + group - 1) / group;
+    const int64_t inPitch = (flags & Batch::kBusSharedIn) ? groups : n_, outPitch = (flags & Batch::kBusMixOut) ? groups : n_;
+    if (nSamples > 0 && in && out && !Batch::busBuffersApart(in, out, (size_t)nSamples * (size_t)front().channels(), inPitch, inPitch, outPitch, outPitch)) {
+        lastError_ = "bus: input and output overlap without being one buffer with one layout";
+        return FX_E_ARG;
+    }
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        const float* shardIn = in ? in + ((flags & Batch::kBusSharedIn) ? first / group : first) : in;
+        float* shardOut = out ? out + ((flags & Batch::kBusMixOut) ? first / group : first) : out;
+        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr);
+    });
+}
 int Sharded::sync() {
     Serial serial(api_);
     lastError_.clear();
@@ -362,7 +387,7 @@ int64_t Sharded::info(int what) {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
-    if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS) {
+    if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

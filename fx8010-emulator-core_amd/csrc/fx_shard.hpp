@@ -67,6 +67,10 @@ public:
     int processDevice(const float* dIn, float* dOut, int nSamples, hipStream_t stream);
     // ... with a row pitch; the buffers are checked first (Batch::processDeviceChecked)
     int processDevicePitched(const float* dIn, float* dOut, int nSamples, int64_t pitch, hipStream_t stream);
+    // group buses (Batch::processBus): `in` / `out` are the caller's full-width buffers, [sample][channel][groups of the whole batch]
+    // on a side with its flag.  Every shard must begin at a multiple of `group` (fxb_shard_plan tells the boundaries) and works on
+    // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
+    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream);
     int sync();
     int prepare(int nSamples, bool wait);
 

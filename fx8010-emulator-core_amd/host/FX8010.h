@@ -205,6 +205,14 @@ public:
     void process(const float* in, float* out, int nSamples) {
         if (fxb_process_block(h_, in, out, nSamples) < 0) throw std::runtime_error(std::string("FX8010Batch::process: ") + fxb_last_error(h_));
     }
+    // a shared input (in: [nSamples][channels][busGroups(group)], instance n hears column n / group) and / or a mixed output
+    // (out: the same shape, every group's sum in the order include/fx8010_amd.h fixes) per group of `group` instances; a side
+    // whose flag is false is [nSamples][channels][instances] as in process().  Host buffers, synchronous.
+    int64_t busGroups(int64_t group) { return fxb_bus_groups(h_, group); }
+    void processBlockBus(const float* in, float* out, int nSamples, int64_t group, bool sharedIn = true, bool mixOut = true) {
+        const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
+        if (fxb_process_block_bus(h_, in, out, nSamples, group, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::processBlockBus: ") + fxb_last_error(h_));
+    }
     // device-resident buffers, asynchronous on `stream` (hipStream_t)
     void processDevice(const float* dIn, float* dOut, int nSamples, void* stream = nullptr) {
         if (fxb_process_block_dev(h_, dIn, dOut, nSamples, stream) < 0) throw std::runtime_error(std::string("FX8010Batch::processDevice: ") + fxb_last_error(h_));

@@ -24,8 +24,10 @@ INFO = {
     "waves_per_wg": 5, "num_microops": 6, "itram_slots": 7, "xtram_slots": 8, "tram_ops": 9, "multipass": 10,
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
-    "host_staged_blocks": 33, "host_inplace_blocks": 34,
+    "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35,
 }
+
+BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -35,6 +37,7 @@ SYMBOLS = [
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
+    "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -86,6 +89,8 @@ def load():
     sig("fxb_process_block", i32, vp, _f32p, _f32p, i32)
     sig("fxb_process_block_dev", i32, vp, vp, vp, i32, vp); sig("fxb_sync", i32, vp)
     sig("fxb_process_block_pitched", i32, vp, vp, vp, i32, i64); sig("fxb_process_block_dev_pitched", i32, vp, vp, vp, i32, i64, vp)
+    sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
+    sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -444,6 +449,42 @@ class Batch(_Reports):
         assert pa in (None, p) and pb in (None, p), "d_in and d_out with one common pitch"
         return self._check(self._lib.fxb_process_block_dev_pitched(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(p), C.c_void_p(stream or 0)),
                            "process_block_dev_pitched")
+
+    def bus_groups(self, group):
+        """G = ceil(N / group): the columns of a shared input / a mixed output"""
+        return self._check(int(self._lib.fxb_bus_groups(self._h, int(group))), "bus_groups")
+
+    def process_block_bus(self, x, group, shared_in=True, mix_out=True, out=None):
+        """A block with a shared input and / or a mixed output per group of `group` consecutive instances.  x: float32
+        [S, channels, G] with shared_in (instance n hears column n // group), else [S, channels, N]; returns [S, channels, G] with
+        mix_out (every group's sum, in the order include/fx8010_amd.h fixes), else [S, channels, N] (mono: the channel axis may be
+        left out).  Into `out` when given; x and out in pinned memory (HostBuffer.array) are read and written in place."""
+        G = self.bus_groups(group)
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        S = x.shape[0]
+        assert x.size == S * self.channels * (G if shared_in else self.n), "input must be [S, channels, %s]" % ("G" if shared_in else "N")
+        shape = ((S,) if x.ndim == 2 else (S, self.channels)) + ((G if mix_out else self.n),)
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == int(np.prod(shape))
+        flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        self._check(self._lib.fxb_process_block_bus(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), S, int(group), flags), "process_block_bus")
+        return out
+
+    def process_block_bus_dev(self, d_in, d_out, n_samples, group, shared_in=True, mix_out=True, stream=None):
+        """d_in / d_out: device pointers (ints) or contiguous float32 torch tensors, [n_samples, channels, G] on a side with its
+        flag and [n_samples, channels, N] on the other; single-shard handles; asynchronous on `stream` (a hipStream_t as int)."""
+        G = self.bus_groups(group)
+
+        def ptr(t, width):
+            if isinstance(t, int):
+                return t
+            assert t.element_size() == 4 and t.is_contiguous() and t.numel() == n_samples * self.channels * width, "[S, channels, %d] float32" % width
+            return t.data_ptr()
+        a, b = ptr(d_in, G if shared_in else self.n), ptr(d_out, G if mix_out else self.n)
+        flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        return self._check(self._lib.fxb_process_block_bus_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(group), flags, C.c_void_p(stream or 0)),
+                           "process_block_bus_dev")
 
     def sync(self):
         return self._check(self._lib.fxb_sync(self._h), "sync")

@@ -222,6 +222,28 @@ int fxb_process_block_dev_pitched(fxb_handle* h, const float* d_in, float* d_out
 /* Sharded batches: d_in[k] / d_out[k] are shard k's buffers on shard k's device, [n_samples][num_channels][n_instances of
  * the shard]; launched concurrently from the shards' own threads on their own streams.  Pair with fxb_sync(). */
 int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float* const* d_out, int n_samples);
+/* Group buses: a shared input and / or a mixed output per group of `group` consecutive instances.  G = fxb_bus_groups(h, group) =
+ * ceil(N / group); group g holds instances g*group .. min((g+1)*group, N) - 1 (the last one may be short; group >= N is one group).
+ *   FXB_BUS_SHARED_IN  `in` is [n_samples][num_channels][G]: instance n reads column n / group (one signal through `group`
+ *                      instances that differ in their controls - a parameter sweep).  Without it `in` is [..][N] as ever.
+ *   FXB_BUS_MIX_OUT    `out` is [n_samples][num_channels][G]: column g is the sum of the group's outputs (voices onto a bus), in
+ *                      fp32, round to nearest, never fused, denormals kept, in exactly this order: 64 partial sums p[0..63] start
+ *                      at +0.0f; for j = 0, 1, ... every member m = j*64 + l of the group that exists is added to p[l]; then for
+ *                      step = 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l + step] for l < step; the sum is p[0].  Without it `out` is
+ *                      [..][N].
+ * flags == 0 is fxb_process_block.  The instances' state afterwards is what fxb_process_block on the expanded input leaves; control
+ * tracks armed for the block apply.  Only the [..][G] sides cross PCIe: a small kernel expands the input into a per-instance block
+ * in device memory, the program runs on it in place, a second kernel adds the groups up.
+ * Host entry: synchronous; pinned buffers (fxb_host_alloc ...) are read and written in place by those kernels, others are staged.
+ * Device entry: single-shard handles, buffers checked like fxb_process_block_dev_pitched's, asynchronous on `stream`.
+ * Sharded handles: every shard must begin at a multiple of `group` (fxb_shard_plan), else FX_E_ARG.
+ * FX_E_ARG (nothing launched, nothing changed): group < 1, unknown flag bits, a null buffer with n_samples > 0, `in` and `out`
+ * overlapping without being the same buffer with the same layout, num_channels * row length * 4 >= 2^32 in any layout. */
+#define FXB_BUS_SHARED_IN (1u << 0)
+#define FXB_BUS_MIX_OUT   (1u << 1)
+int64_t fxb_bus_groups(fxb_handle* h, int64_t group);   /* G, or FX_E_ARG */
+int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n_samples, int64_t group, unsigned flags);
+int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t group, unsigned flags, void* stream);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -290,7 +312,8 @@ enum {
                                       the others go back into the code, where a constant is cheaper than a row: e.g. INTERP with a constant X).  Same
                                       results in all three. */
     FXB_INFO_HOST_STAGED_BLOCKS = 33,  /* host blocks that went through staging copies since creation (summed over shards) */
-    FXB_INFO_HOST_INPLACE_BLOCKS = 34  /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
+    FXB_INFO_HOST_INPLACE_BLOCKS = 34, /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
+    FXB_INFO_BUS_BLOCKS = 35           /* bus blocks (fxb_process_block_bus* with a flag set) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

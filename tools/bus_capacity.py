@@ -1,0 +1,264 @@
+#!/usr/bin/env python3
+"""What a group bus buys a real-time host: 32-sample blocks of config5 from pinned host buffers, the plain in-place
+fxb_process_block ([32][N] in and out over PCIe) beside fxb_process_block_bus with a shared input and a mixed output per group
+of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel around the unchanged emulation launch).
+
+1. The condition: at 131 072 instances, stretches of blocks of the two paths take turns in ONE process on ONE build; the bus
+   path's median block time must not exceed the plain path's.  It moves 1/64 of the PCIe bytes and adds two passes over the
+   16.8 MB per-instance block in device memory: if it is slower, the bus kernels are at fault.  The exit status is 1 then.
+2. Capacity: the instance count goes up for the bus path; the largest count whose p99.9 block time (and every smaller count's)
+   stays inside 666.667 us is reported beside the plain path's, measured by tools/realtime_capacity.py's own routine.
+3. `--trace-run`: nothing is timed, a stretch of bus blocks at --trace-instances runs - the program to put behind
+   `rocprofv3 --kernel-trace --stats ... --` in a run of its own, without counters.  `--kernel-stats FILE.csv` then reads the
+   table that run wrote: the expand and mix kernels' share of device time, and their achieved bytes/s (the bytes the two must
+   move, from the shapes) against the 6.3 TB/s an MI355X's HBM gives a streaming kernel.
+
+Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
+path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
+
+    python tools/bus_capacity.py [--blocks 4000] [--json profiles/bus_realtime.json] [--kernel-stats bus_kernel_stats.csv]
+"""
+import argparse
+import csv
+import ctypes as C
+import gc
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+import realtime_capacity as rt   # (sets the import paths of the binding and the oracle)
+
+BLOCK, BUDGET_US, SLIDER, SLIDER_EVERY, RING = rt.BLOCK, rt.BUDGET_US, rt.SLIDER, rt.SLIDER_EVERY, rt.RING
+GROUP = 64
+HBM_ACHIEVABLE_BPS = 6.3e12
+
+
+def mix_model(y, K):
+    """[..., N] -> [..., G] in the order include/fx8010_amd.h fixes (K <= 64 here: one member per lane, then the tree)"""
+    import numpy as np
+    N = y.shape[-1]
+    assert K <= 64 and N % K == 0
+    p = np.zeros(y.shape[:-1] + (N // K, 64), dtype=np.float32)
+    p[..., :K] = p[..., :K] + y.reshape(y.shape[:-1] + (N // K, K))
+    for step in (32, 16, 8, 4, 2, 1):
+        p[..., :step] = p[..., :step] + p[..., step:2 * step]
+    return p[..., 0]
+
+
+class Path:
+    """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
+
+    def __init__(self, A, progs, n, bus):
+        import numpy as np
+        self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
+        self.b = A.Batch(n, 1, 0)
+        if not self.b.load_text(progs.CONFIGS["config5"]()):
+            raise RuntimeError("load failed: %s" % self.b.errors())
+        self.width = self.b.bus_groups(GROUP) if bus else n
+        self.ring = [A.HostBuffer((BLOCK, 1, self.width)) for _ in range(RING)]
+        for k, h in enumerate(self.ring):
+            g = progs.stimulus(self.b.bus_groups(GROUP), BLOCK, first_sample=k * BLOCK)
+            h.array[:, 0, :] = g if bus else np.repeat(g, GROUP, axis=1)[:, :n]
+        self.out = A.HostBuffer((BLOCK, 1, self.width))
+        self.xp = [C.c_void_p(h.array.ctypes.data) for h in self.ring]
+        self.yp = C.c_void_p(self.out.array.ctypes.data)
+        self.b.prepare(BLOCK, True)
+        self.k = 0
+        self.times = []
+
+    def block(self):
+        k, h = self.k, self.b._h
+        if k % SLIDER_EVERY == 0:
+            assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
+        if self.bus:
+            rc = self.lib.fxb_process_block_bus(h, self.xp[k % RING], self.yp, BLOCK, GROUP, 3)
+        else:
+            rc = self.lib.fxb_process_block_pitched(h, self.xp[k % RING], self.yp, BLOCK, self.n)
+        if rc != 0:
+            raise RuntimeError("block %d failed (%d): %s" % (k, rc, self.b.last_error()))
+        self.k = k + 1
+
+    def stretch(self, blocks, timed=True):
+        for _ in range(blocks):
+            t0 = time.perf_counter_ns()
+            self.block()
+            if timed:
+                self.times.append((time.perf_counter_ns() - t0) * 1e-3)
+
+    def close(self):
+        self.b.close()
+        for h in self.ring + [self.out]:
+            h.close()
+
+
+def check_words(A, progs, n):
+    """two blocks on fresh handles: the bus path's words are the model's, applied to the plain path's"""
+    import numpy as np
+    plain, bus = Path(A, progs, n, False), Path(A, progs, n, True)
+    for _ in range(2):
+        plain.block()
+        bus.block()
+        want, got = mix_model(plain.out.array, GROUP), bus.out.array
+        nan = np.isnan(want)
+        if not ((np.isnan(got) == nan).all() and (got.view(np.uint32)[~nan] == want.view(np.uint32)[~nan]).all()):
+            raise RuntimeError("the bus path's output differs from the model of the plain path's at %d instances" % n)
+    plain.close()
+    bus.close()
+
+
+def shader_clock_reader(torch):
+    """-> a function that reads the shader clock of device 0 in MHz from the amdgpu hwmon file of its PCI address (None where
+    that file cannot be found: the clock is extra information)"""
+    import glob
+    path = None
+    try:
+        p = torch.cuda.get_device_properties(0)
+        bdf = "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)
+        for d in glob.glob("/sys/bus/pci/devices/%s/hwmon/hwmon*" % bdf):
+            if os.path.exists(os.path.join(d, "freq1_input")):
+                path = os.path.join(d, "freq1_input")
+    except Exception:
+        pass
+
+    def read():
+        try:
+            with open(path) as fh:
+                return float(fh.read().strip()) / 1e6 or None
+        except Exception:
+            return None
+    return read
+
+
+def side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None):
+    plain, bus = Path(A, progs, n, False), Path(A, progs, n, True)
+    clocks = {"plain": [], "bus": []}
+    for p in (plain, bus):
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    staged0 = [p.b.info("host_staged_blocks") for p in (plain, bus)]
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in (("plain", plain), ("bus", bus)):   # by turns: what else happens on the host and the device meets both
+                p.stretch(stretch)
+                clocks[name].append(clock())   # (one reading right behind the stretch's last block, outside every timed block)
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "stretch_blocks": stretch}
+    for name, p, s0 in (("plain", plain, staged0[0]), ("bus", bus, staged0[1])):
+        r = rt.percentiles(p.times)
+        half = len(p.times) // 2
+        r.update({"median_us_first_half": rt.percentiles(p.times[:half])["median_us"], "median_us_second_half": rt.percentiles(p.times[half:])["median_us"],
+                  "pcie_bytes_each_way_per_block": BLOCK * p.width * 4, "host_staged_blocks_in_timed_region": p.b.info("host_staged_blocks") - s0,
+                  "kernel_us_last": round(p.b.last_kernel_ms() * 1e3, 1), "tier": p.b.tier_note()})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-5s N=%7d  median %7.1f (halves %7.1f / %7.1f)  p99 %7.1f  p99.9 %7.1f  max %8.1f us  emulation kernel %6.1f us" % (
+            name, n, r["median_us"], r["median_us_first_half"], r["median_us_second_half"], r["p99_us"], r["p999_us"], r["max_us"], r["kernel_us_last"]))
+    out["condition_bus_median_not_above_plain_median"] = out["bus"]["median_us"] <= out["plain"]["median_us"]
+    plain.close()
+    bus.close()
+    return out
+
+
+def bus_row(A, progs, n, blocks, warm, log):
+    """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
+    block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
+    summation order applied to the plain path's last block; the instruction counters of sampled instances must agree too."""
+    import numpy as np
+    p = Path(A, progs, n, True)
+    p.stretch(warm, timed=False)
+    p.b.prepare(BLOCK, True)
+    gc.collect()
+    gc.disable()
+    try:
+        p.stretch(blocks)
+    finally:
+        gc.enable()
+    r = rt.percentiles(p.times)
+    r.update({"instances": n, "mode": "bus", "group": GROUP, "within_budget_p999": r["p999_us"] <= BUDGET_US,
+              "kernel_us_last": round(p.b.last_kernel_ms() * 1e3, 1), "host_inplace_blocks": p.b.info("host_inplace_blocks"), "host_staged_blocks": p.b.info("host_staged_blocks")})
+    plain = Path(A, progs, n, False)
+    plain.stretch(p.k, timed=False)
+    want, got = mix_model(plain.out.array, GROUP), p.out.array
+    nan = np.isnan(want)
+    ok = bool((np.isnan(got) == nan).all() and (got.view(np.uint32)[~nan] == want.view(np.uint32)[~nan]).all())
+    picks = sorted({0, 63, 64, n // 2, n - 1})
+    ok = ok and all(p.b.instruction_counter_i(i) == plain.b.instruction_counter_i(i) for i in picks)
+    r.update({"parity_ok": ok, "parity": "last of %d blocks against the summation order applied to a plain handle's replay of the run; instruction counters of %d instances" % (p.k, len(picks))})
+    log("bus   N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  parity %s" % (n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"],
+        "REAL TIME" if r["within_budget_p999"] else "over budget", "ok" if ok else "MISMATCH"))
+    plain.close()
+    p.close()
+    return r
+
+
+def kernel_shares(path, n):
+    """the --stats table of a `--trace-run` under rocprofv3: share of device time and achieved bytes/s of the two bus kernels"""
+    rows = list(csv.DictReader(open(path)))
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    groups = -(-n // GROUP)
+    need = {"fx_bus_expand": BLOCK * (groups + n) * 4, "fx_bus_mix": BLOCK * (n + groups) * 4}   # bytes read + written per launch
+    out = {"instances": n, "device_time_ns": total, "kernels": {}}
+    for r in rows:
+        for key, bytes_ in need.items():
+            if key in r["Name"]:
+                avg = float(r["AverageNs"])
+                out["kernels"][key] = {"calls": int(r["Calls"]), "average_ns": round(avg, 1), "share_of_device_time": round(float(r["TotalDurationNs"]) / total, 4),
+                                       "bytes_per_launch": bytes_, "achieved_TBps": round(bytes_ / avg / 1e3, 3),
+                                       "share_of_achievable_hbm": round(bytes_ / (avg * 1e-9) / HBM_ACHIEVABLE_BPS, 3)}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=4000)
+    ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--stretch", type=int, default=250, help="blocks of one path before the other takes its turn")
+    ap.add_argument("--instances", type=int, default=131072)
+    ap.add_argument("--sweep", default="131072,196608,262144,327680,393216,458752,524288")
+    ap.add_argument("--plain-sweep", default="65536,98304,131072,147456,163840,180224")
+    ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--trace-instances", type=int, default=524288)
+    ap.add_argument("--kernel-stats", default="")
+    ap.add_argument("--json", default="")
+    args = ap.parse_args()
+    import torch  # first: its HIP runtime is the one the library binds to
+
+    import fx8010_amd as A
+    import fx8010_programs as progs
+    log = lambda s: print(s, flush=True)
+    if args.trace_run:
+        p = Path(A, progs, args.trace_instances, True)
+        p.stretch(200, timed=False)
+        p.close()
+        return 0
+    out = {"what": "32-sample blocks of config5 at 48 kHz against %.3f us, pinned host buffers, call -> output in host memory on the caller's clock; plain: "
+                   "fxb_process_block in place; bus: fxb_process_block_bus, shared input and mixed output per %d instances" % (BUDGET_US, GROUP),
+           "gpu": torch.cuda.get_device_name(0), "budget_us": round(BUDGET_US, 3), "blocks_per_point": args.blocks, "warmup_blocks": args.warmup}
+    check_words(A, progs, args.instances)
+    out["side_by_side"] = side_by_side(A, progs, args.instances, args.blocks, args.warmup, args.stretch, log, shader_clock_reader(torch))
+    rows = [bus_row(A, progs, int(v), args.blocks, args.warmup, log) for v in args.sweep.split(",") if v]
+    out["bus_rows"], out["capacity_bus"] = rows, rt.capacity(rows)
+    plain = rt.run(torch, A, progs, [int(v) for v in args.plain_sweep.split(",") if v], args.blocks, args.warmup, ("host",), log)
+    out["plain_rows"], out["capacity_plain"] = plain["rows"], plain["capacity_host_fed"]
+    if args.kernel_stats:
+        out["device_time"] = kernel_shares(args.kernel_stats, args.trace_instances)
+    log("largest N within %.3f us at p99.9: bus %s, plain %s; bus median <= plain median at %d: %s" % (
+        BUDGET_US, out["capacity_bus"], out["capacity_plain"], args.instances, out["side_by_side"]["condition_bus_median_not_above_plain_median"]))
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+    return 0 if out["side_by_side"]["condition_bus_median_not_above_plain_median"] and all(r["parity_ok"] for r in rows) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
