@@ -75,6 +75,7 @@ Batch::~Batch() {
     (void)hipFree(dOut_);
     (void)hipFree(dBus_);
     (void)hipFree(dBusStage_);
+    (void)hipFree(dMeter_);
     if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS
     (void)hipFree(dStamps_);
@@ -126,6 +127,7 @@ int Batch::setOption(unsigned option, bool on) {
 
 int Batch::afterLoad(bool ok) {
     (void)hipSetDevice(device_);
+    if (dMeter_) (void)meterReset();   // a program load resets the meters and keeps them enabled
     // registers may have been created even when the load failed; keep host mirrors in step
     const size_t old = hostValue_.size();
     hostValue_.resize(prog_.regs.size());
@@ -738,6 +740,58 @@ float Batch::lastKernelMs() {
     return ms;
 }
 
+// ---- output meters (fx_meter.hpp): accumulator rows in device memory, carried from launch to launch ---------------------------------
+
+int Batch::meterReset() {
+    waitLastLaunch();
+    hipError_t e = hipMemsetAsync(dMeter_, 0, meterChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    meterSamples_ = 0;
+    return e == hipSuccess ? 0 : hipFail(e, "zeroing the meter rows");
+}
+
+int Batch::meterEnable(bool on) {
+    (void)hipSetDevice(device_);
+    if (on == (dMeter_ != nullptr)) return 0;   // (on twice: the values stay)
+    waitLastLaunch();
+    (void)hipStreamSynchronize(stream_);
+    if (!on) {
+        (void)hipFree(dMeter_);
+        dMeter_ = nullptr;
+        meterSamples_ = 0;
+        return 0;
+    }
+    const hipError_t e = hipMalloc(&dMeter_, meterChannelBytes(nPad_) * (size_t)prog_.numChannels);
+    if (e != hipSuccess) { dMeter_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc meter rows"); }
+    const int rc = meterReset();
+    if (rc != 0) {
+        (void)hipFree(dMeter_);
+        dMeter_ = nullptr;
+    }
+    return rc;
+}
+
+int Batch::meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset, int64_t rowPitch) {
+    (void)hipSetDevice(device_);
+    if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (rowPitch <= 0) rowPitch = n_;
+    if (rowPitch < n_) return fail(FX_E_ARG, "meters: row pitch below the instance count");
+    int rc = sync();
+    if (rc != 0) return rc;
+    const char* rows = static_cast<const char*>(dMeter_);
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < prog_.numChannels && e == hipSuccess; ++c) {
+        const char* ch = rows + (size_t)c * meterChannelBytes(nPad_);
+        const size_t at = (size_t)c * (size_t)rowPitch;
+        if (energy) e = hipMemcpy(energy + at, ch + meterEnergyOff(nPad_), (size_t)n_ * 8, hipMemcpyDeviceToHost);
+        if (peak && e == hipSuccess) e = hipMemcpy(peak + at, ch + meterPeakOff(nPad_), (size_t)n_ * 4, hipMemcpyDeviceToHost);
+        if (fullScale && e == hipSuccess) e = hipMemcpy(fullScale + at, ch + meterFullScaleOff(nPad_), (size_t)n_ * 4, hipMemcpyDeviceToHost);
+        if (nonfinite && e == hipSuccess) e = hipMemcpy(nonfinite + at, ch + meterNonfiniteOff(nPad_), (size_t)n_ * 4, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return hipFail(e, "reading the meter rows");
+    return reset ? meterReset() : 0;
+}
+
 #ifdef FX_DIAGNOSTICS
 int Batch::readEndStamps(uint32_t* out, int64_t nWords) {
     (void)hipSetDevice(device_);
@@ -776,6 +830,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_HOST_STAGED_BLOCKS) return hostStagedBlocks_;
     if (what == FXB_INFO_HOST_INPLACE_BLOCKS) return hostInplaceBlocks_;
     if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
+    if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

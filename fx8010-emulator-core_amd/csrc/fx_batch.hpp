@@ -19,6 +19,7 @@
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
+#include "fx_meter.hpp"
 #include "fx_knobs.hpp"
 #include "fx_model.hpp"
 
@@ -66,6 +67,14 @@ public:
     // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
     static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     int sync();
+    // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
+    // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
+    // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
+    // every array is [channels][rowPitch] with this batch's instances in columns 0..n-1 (rowPitch 0 = n), any pointer may be null.
+    int meterEnable(bool on);
+    int meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset, int64_t rowPitch = 0);
+    int64_t meterSamples() const { return dMeter_ ? meterSamples_ : (int64_t)-3; }   // (FX_E_ARG while metering is off)
+    bool metering() const { return dMeter_ != nullptr; }
     int prepare(int nSamples, bool wait);   // generate the code for blocks of this length now (and wait for the builder thread)
 
     // State snapshot (the reference keeps all DSP state in plain members, include/FX8010.h:162-217, 288-291: registers, output
@@ -172,6 +181,11 @@ private:
     std::vector<uint32_t> trackStage_;     // host image of dTracks_ for the block being launched
     bool tracksArmed() const { for (const PendingTrack& t : pendingTracks_) if (t.steps > 0) return true; return false; }
     uint32_t* dScratch_ = nullptr;  // small device scratch: fill lists, reductions
+    // output meters: the accumulator rows (fx_meter.hpp), null while metering is off
+    void* dMeter_ = nullptr;
+    int64_t meterSamples_ = 0;      // sample periods metered since the last reset
+    int64_t meterLaunches_ = 0;     // FXB_INFO_METER_LAUNCHES
+    int meterReset();               // waits for what has been queued, zeroes the rows
 #ifdef FX_DIAGNOSTICS
   public:
     // diagnostics build (fx_knobs.hpp): one word per wavefront, written by generated code behind its last sample when

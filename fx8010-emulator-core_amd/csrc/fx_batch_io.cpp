@@ -264,6 +264,21 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
             e = launchStepBlock(a, c_.low.multipass, s);
         }
         const hipError_t launchError = e;   // (of the event record in front of the launch or of the launch itself)
+        // Metering: the meter kernel reads the block this launch writes, right behind it on the same stream and in front of the
+        // ev1_ record - every wait for "the last launch" covers its read of the caller's buffer, and the kernel time includes it.
+        if (e == hipSuccess && dMeter_) {
+            MeterArgs m{};
+            m.y = dOut;
+            m.rows = dMeter_;
+            m.n = n_;
+            m.nPad = nPad_;
+            m.pitch = pitch;
+            m.samples = nSamples;
+            m.channels = prog_.numChannels;
+            if ((e = launchMeter(m, s)) != hipSuccess) return hipFail(e, "launch fx_meter");
+            ++meterLaunches_;
+            meterSamples_ += nSamples;
+        }
         if (e == hipSuccess && timed) e = hipEventRecord(ev1_, s);
         // A workgroup of several wavefronts that the device will not start (registers x wavefronts beyond a CU, LDS): the plain
         // program runs everywhere - no stages for this handle from now on, and a second pass for this block.  Only for what a launch

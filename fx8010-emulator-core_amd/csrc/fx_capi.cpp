@@ -230,6 +230,11 @@ int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n, int
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t group, unsigned flags, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
 }
+int fxb_meter_enable(fxb_handle* h, int on) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterEnable(on != 0); }) : FX_E_ARG; }
+int fxb_meter_read(fxb_handle* h, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterRead(energy, peak, full_scale, nonfinite, reset != 0); }) : FX_E_ARG;
+}
+int64_t fxb_meter_samples(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSamples(); }) : FX_E_ARG; }
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }
 int64_t fxb_state_size(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.stateBytes(); }) : FX_E_ARG; }

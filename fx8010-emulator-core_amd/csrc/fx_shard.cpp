@@ -288,6 +288,35 @@ int Sharded::sync() {
     return fan([](int, Batch& b) { return b.sync(); });
 }
 
+int Sharded::meterEnable(bool on) {
+    Serial serial(api_);
+    lastError_.clear();
+    const bool was = front().metering();
+    const int rc = fan([&](int, Batch& b) { return b.meterEnable(on); });
+    if (rc != 0 && on && !was) {
+        const std::string why = lastError();
+        fan([](int, Batch& b) { return b.meterEnable(false); });
+        lastError_ = why;
+    }
+    return rc;
+}
+int Sharded::meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        return b.meterRead(energy ? energy + first : nullptr, peak ? peak + first : nullptr, fullScale ? fullScale + first : nullptr,
+                           nonfinite ? nonfinite + first : nullptr, reset, n_);
+    });
+}
+int64_t Sharded::meterSamples() {
+    Serial serial(api_);
+    lastError_.clear();
+    const int64_t s = front().meterSamples();
+    if (s < 0) lastError_ = "meters: metering is off (fxb_meter_enable)";
+    return s;
+}
+
 int64_t Sharded::instructionCounter() {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
@@ -387,7 +416,8 @@ int64_t Sharded::info(int what) {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
-    if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS) {
+    if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
+        what == FXB_INFO_METER_LAUNCHES) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

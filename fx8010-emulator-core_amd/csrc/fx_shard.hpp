@@ -72,6 +72,11 @@ public:
     // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream);
     int sync();
+    // output meters (Batch::meterEnable ...): enable fans out (a shard that cannot allocate leaves metering off on all of them),
+    // read gives each shard its columns of the caller's [channels][all instances] arrays, samples is shard 0's
+    int meterEnable(bool on);
+    int meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
+    int64_t meterSamples();
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

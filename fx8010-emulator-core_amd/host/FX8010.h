@@ -218,6 +218,20 @@ public:
         if (fxb_process_block_dev(h_, dIn, dOut, nSamples, stream) < 0) throw std::runtime_error(std::string("FX8010Batch::processDevice: ") + fxb_last_error(h_));
     }
     void sync() { fxb_sync(h_); }
+    // Output meters (include/fx8010_amd.h "Output meters"): per instance and channel the energy, the peak, the samples at the +-1
+    // rail and the non-finite ones, accumulated on the device over the blocks processed while metering is on.  meterRead fills
+    // [channels][instances] arrays (a null pointer skips one) and, with reset, zeroes the meters afterwards.
+    void meterEnable(bool on = true) {
+        if (fxb_meter_enable(h_, on ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterEnable: ") + fxb_last_error(h_));
+    }
+    void meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset = false) {
+        if (fxb_meter_read(h_, energy, peak, fullScale, nonfinite, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterRead: ") + fxb_last_error(h_));
+    }
+    int64_t meterSamples() {
+        const int64_t s = fxb_meter_samples(h_);
+        if (s < 0) throw std::runtime_error(std::string("FX8010Batch::meterSamples: ") + fxb_last_error(h_));
+        return s;
+    }
     // generate the code for blocks of nSamples samples now, not in the first process call (callers with a deadline per block)
     void prepare(int nSamples, bool wait = true) {
         if (fxb_prepare(h_, nSamples, wait ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::prepare: ") + fxb_last_error(h_));

@@ -24,7 +24,7 @@ INFO = {
     "waves_per_wg": 5, "num_microops": 6, "itram_slots": 7, "xtram_slots": 8, "tram_ops": 9, "multipass": 10,
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
-    "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35,
+    "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -38,6 +38,7 @@ SYMBOLS = [
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev",
+    "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -91,6 +92,7 @@ def load():
     sig("fxb_process_block_pitched", i32, vp, vp, vp, i32, i64); sig("fxb_process_block_dev_pitched", i32, vp, vp, vp, i32, i64, vp)
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
+    sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -485,6 +487,25 @@ class Batch(_Reports):
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
         return self._check(self._lib.fxb_process_block_bus_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(group), flags, C.c_void_p(stream or 0)),
                            "process_block_bus_dev")
+
+    def meter_enable(self, on=True):
+        """Output meters on (accumulator rows allocated and zeroed on every shard; on twice keeps the values) or off (freed).
+        While they are on, every launch of the program is followed by a small kernel that meters the block it wrote."""
+        return self._check(self._lib.fxb_meter_enable(self._h, 1 if on else 0), "meter_enable")
+
+    def meter_read(self, reset=False):
+        """{"energy": float64, "peak": float32, "full_scale": uint32, "nonfinite": uint32}, each [channels, N] by global instance:
+        what has accumulated since the last reset (include/fx8010_amd.h "Output meters").  Synchronous; reset: zero afterwards."""
+        shape = (self.channels, self.n)
+        out = {"energy": np.empty(shape, dtype=np.float64), "peak": np.empty(shape, dtype=np.float32),
+               "full_scale": np.empty(shape, dtype=np.uint32), "nonfinite": np.empty(shape, dtype=np.uint32)}
+        self._check(self._lib.fxb_meter_read(self._h, *[C.c_void_p(out[k].ctypes.data) for k in ("energy", "peak", "full_scale", "nonfinite")],
+                                             1 if reset else 0), "meter_read")
+        return out
+
+    def meter_samples(self):
+        """sample periods metered since the last reset"""
+        return self._check(int(self._lib.fxb_meter_samples(self._h)), "meter_samples")
 
     def sync(self):
         return self._check(self._lib.fxb_sync(self._h), "sync")

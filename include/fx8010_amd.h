@@ -244,6 +244,49 @@ int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float*
 int64_t fxb_bus_groups(fxb_handle* h, int64_t group);   /* G, or FX_E_ARG */
 int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n_samples, int64_t group, unsigned flags);
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t group, unsigned flags, void* stream);
+/* Output meters: per instance and channel the peak, the energy, how often the output sat at the FX8010's +-1 saturation rail and
+ * how many of its samples were non-finite - computed on the device, accumulated there across blocks, read when the host wants
+ * them.  Metering is a mode of the handle, off by default; with it off nothing below costs anything.
+ *
+ * The definition.  Each pair (channel c, instance n) has four accumulators.  After reset they are energy = +0.0 (fp64),
+ * peak = +0.0f, full_scale = 0 and nonfinite = 0 (both uint32).  For every output word y of that column, in sample order:
+ *   fin = |y| < +Inf.  This is false for NaN and +-Inf.
+ *   w = fin ? |y| : +0.0f.
+ *   energy = energy + (double)w * (double)w.  The product of two fp32 values is exact in fp64.  There is therefore one rounding
+ *     per sample, in the add, and fused or unfused arithmetic gives the same bits.
+ *   peak = max(peak, w).
+ *   full_scale += (fin && |y| >= 1.0f).
+ *   nonfinite += !fin.
+ * The two counters saturate at 0xFFFFFFFF.
+ * The order is sequential over the samples of a block, then over blocks in the order they were queued.  The accumulators are
+ * carried in device memory between launches.  A stream cut into blocks of 16 + 17 samples therefore gives the same bits as one
+ * block of 33.  The same holds for a block that the runtime cuts into pieces.  The pieces are those of the 64 MiB bus scratch and
+ * those of a pageable host block of 32 MB and more; a block with a control track armed that the interpreter and HIP C++ tiers cut
+ * at its change points is metered segment by segment, in order, to the same bits.
+ *
+ * Where the meters look.  A small kernel follows every launch of the program on the same stream and reads the per-instance
+ * output block exactly where that launch wrote it:
+ *   device entries            the caller's d_out, at its pitch;
+ *   staged host blocks        the library's device staging buffer;
+ *   pinned host blocks        processed in place: the caller's pinned memory, which the meter kernel reads BACK over PCIe (the
+ *                             block crosses the link a third time: real-time hosts that want meters use bus blocks);
+ *   bus blocks                the per-instance scratch block in device memory, between the program and the mix or the copy out:
+ *                             the per-instance output still never leaves the device, and every instance has its figures.
+ * While metering is on, fxb_last_kernel_ms and fxb_shard_kernel_ms cover the program's launch plus its meter launch (the meter
+ * is queued in front of the event that ends the measurement, so that every wait for a block also covers the meter's read of the
+ * caller's buffer).
+ *
+ * fxb_meter_enable: on != 0 allocates and zeroes the accumulator rows on every shard (20 bytes per instance and channel), 0 frees
+ *   them.  Enabling twice is a no-op that keeps the values.  FX_E_MEMORY leaves metering off and the handle usable.  All device
+ *   allocation for metering happens here, never inside a block.  Waits for the blocks that have been queued.
+ * fxb_meter_read: every array is [num_channels][N] by global instance; any pointer may be NULL.  Synchronous: waits as fxb_sync
+ *   does, copies, and with reset != 0 zeroes the accumulators after the copy.  FX_E_ARG while metering is off.
+ * fxb_meter_samples: the sample periods metered since the last reset, or FX_E_ARG while metering is off.
+ * A program load (fxb_load_file / fxb_load_text) resets the meters and keeps them enabled.  Meters are not part of the state
+ * image: fxb_save_state and fxb_load_state leave them alone.  FXB_INFO_METER_LAUNCHES counts the meter kernel's launches. */
+int fxb_meter_enable(fxb_handle* h, int on);
+int fxb_meter_read(fxb_handle* h, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset);
+int64_t fxb_meter_samples(fxb_handle* h);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -262,7 +305,8 @@ int fxb_meta_get(fxb_handle* h, const char* key, char* buf, int buflen);
 int fxb_ready(fxb_handle* h);
 const char* fxb_last_error(fxb_handle* h);
 /* HIP-event duration (ms) of the most recent interpreter-kernel launch, measured on the
- * stream it ran on; <0 if none.  Implies a sync on that stream. */
+ * stream it ran on; <0 if none.  Implies a sync on that stream.  While metering is on (fxb_meter_enable) the
+ * duration covers the launch and the meter launch behind it. */
 float fxb_last_kernel_ms(fxb_handle* h);
 
 /* introspection of the lowered program (what the kernel actually runs) */
@@ -313,7 +357,8 @@ enum {
                                       results in all three. */
     FXB_INFO_HOST_STAGED_BLOCKS = 33,  /* host blocks that went through staging copies since creation (summed over shards) */
     FXB_INFO_HOST_INPLACE_BLOCKS = 34, /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
-    FXB_INFO_BUS_BLOCKS = 35           /* bus blocks (fxb_process_block_bus* with a flag set) since creation (summed over shards) */
+    FXB_INFO_BUS_BLOCKS = 35,          /* bus blocks (fxb_process_block_bus* with a flag set) since creation (summed over shards) */
+    FXB_INFO_METER_LAUNCHES = 36       /* launches of the output-meter kernel (fxb_meter_enable) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -13,6 +13,12 @@ of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel a
    table that run wrote: the expand and mix kernels' share of device time, and their achieved bytes/s (the bytes the two must
    move, from the shapes) against the 6.3 TB/s an MI355X's HBM gives a streaming kernel.
 
+4. `--meter`: what the output meters (fxb_meter_enable) cost a real-time host.  At every count of --meter-instances two bus
+   handles, meters off and meters on, take turns in stretches in ONE process; median and p99.9 of both are reported with the
+   shader clock behind their stretches (`--meter-out FILE.txt` keeps the lines).  Their outputs must stay equal word for word.
+   With `--trace-run --meter` the traced stretch runs with meters on, and `--kernel-stats` then also reports the meter kernel
+   beside the mix kernel, which reads the same per-instance block.
+
 Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
@@ -52,7 +58,7 @@ def mix_model(y, K):
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus):
+    def __init__(self, A, progs, n, bus, meter=False):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -66,6 +72,8 @@ class Path:
         self.out = A.HostBuffer((BLOCK, 1, self.width))
         self.xp = [C.c_void_p(h.array.ctypes.data) for h in self.ring]
         self.yp = C.c_void_p(self.out.array.ctypes.data)
+        if meter:
+            self.b.meter_enable()
         self.b.prepare(BLOCK, True)
         self.k = 0
         self.times = []
@@ -169,6 +177,50 @@ def side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None):
     return out
 
 
+def meter_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None):
+    """bus blocks with meters off and on by turns, in stretches, in one process"""
+    import numpy as np
+    off, on = Path(A, progs, n, True), Path(A, progs, n, True, meter=True)
+    clocks = {"meters off": [], "meters on": []}
+    for p in (off, on):
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    launches0 = on.b.info("meter_launches")
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in (("meters off", off), ("meters on", on)):
+                p.stretch(stretch)
+                clocks[name].append(clock())
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "stretch_blocks": stretch}
+    for name, p in (("meters off", off), ("meters on", on)):
+        r = rt.percentiles(p.times)
+        r.update({"kernel_us_last": round(p.b.last_kernel_ms() * 1e3, 1), "blocks": len(p.times)})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-10s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  launch(es) behind the last block %6.1f us  shader clock %s MHz" % (
+            name, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["p999_us"] <= BUDGET_US else "over budget",
+            r["kernel_us_last"], r["shader_clock_mhz_behind_a_stretch"]))
+    # the two have heard the same blocks: same words out, and one meter launch per block
+    same = off.k == on.k and np.array_equal(off.out.array.view(np.uint32), on.out.array.view(np.uint32))
+    meters = on.b.meter_read()
+    out["outputs_equal"] = bool(same)
+    out["meter_launches_in_timed_region"] = on.b.info("meter_launches") - launches0
+    out["meter_samples"] = on.b.meter_samples()
+    log("           N=%7d  outputs of the two %s; %d meter launches for %d timed blocks; %d sample periods metered, %d instances with energy > 0, %d non-finite words" % (
+        n, "equal" if same else "DIFFER", out["meter_launches_in_timed_region"], len(on.times), out["meter_samples"],
+        int((meters["energy"] > 0).sum()), int(meters["nonfinite"].sum(dtype=np.uint64))))
+    off.close()
+    on.close()
+    return out
+
+
 def bus_row(A, progs, n, blocks, warm, log):
     """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
     block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
@@ -206,7 +258,8 @@ def kernel_shares(path, n):
     rows = list(csv.DictReader(open(path)))
     total = sum(float(r["TotalDurationNs"]) for r in rows)
     groups = -(-n // GROUP)
-    need = {"fx_bus_expand": BLOCK * (groups + n) * 4, "fx_bus_mix": BLOCK * (n + groups) * 4}   # bytes read + written per launch
+    # bytes read + written per launch (the meter: the block, and its 20-byte accumulators in and out)
+    need = {"fx_bus_expand": BLOCK * (groups + n) * 4, "fx_bus_mix": BLOCK * (n + groups) * 4, "fx_meter": BLOCK * n * 4 + 2 * 20 * n}
     out = {"instances": n, "device_time_ns": total, "kernels": {}}
     for r in rows:
         for key, bytes_ in need.items():
@@ -230,6 +283,9 @@ def main():
     ap.add_argument("--trace-instances", type=int, default=524288)
     ap.add_argument("--kernel-stats", default="")
     ap.add_argument("--json", default="")
+    ap.add_argument("--meter", action="store_true", help="bus blocks with output meters off and on by turns (with --trace-run: meters on)")
+    ap.add_argument("--meter-instances", default="131072,458752")
+    ap.add_argument("--meter-out", default="", help="keep the lines of --meter in this text file")
     args = ap.parse_args()
     import torch  # first: its HIP runtime is the one the library binds to
 
@@ -237,10 +293,29 @@ def main():
     import fx8010_programs as progs
     log = lambda s: print(s, flush=True)
     if args.trace_run:
-        p = Path(A, progs, args.trace_instances, True)
+        p = Path(A, progs, args.trace_instances, True, meter=args.meter)
         p.stretch(200, timed=False)
         p.close()
         return 0
+    if args.meter:
+        lines = []
+
+        def keep(s):
+            lines.append(s)
+            log(s)
+        keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us, output meters off and on "
+             "by turns in stretches of %d blocks in one process, %d blocks per point after %d warm-up blocks; %s" % (
+                 GROUP, BUDGET_US, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+        rows = [meter_side_by_side(A, progs, int(v), args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.meter_instances.split(",") if v]
+        if args.kernel_stats:
+            keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances)))
+        if args.meter_out:
+            with open(args.meter_out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump({"meter_rows": rows}, fh, indent=1)
+        return 0 if all(r["outputs_equal"] for r in rows) else 1
     out = {"what": "32-sample blocks of config5 at 48 kHz against %.3f us, pinned host buffers, call -> output in host memory on the caller's clock; plain: "
                    "fxb_process_block in place; bus: fxb_process_block_bus, shared input and mixed output per %d instances" % (BUDGET_US, GROUP),
            "gpu": torch.cuda.get_device_name(0), "budget_us": round(BUDGET_US, 3), "blocks_per_point": args.blocks, "warmup_blocks": args.warmup}
