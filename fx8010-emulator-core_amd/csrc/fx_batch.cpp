@@ -831,6 +831,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_HOST_INPLACE_BLOCKS) return hostInplaceBlocks_;
     if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
     if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
+    if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

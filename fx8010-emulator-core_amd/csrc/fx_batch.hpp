@@ -16,6 +16,7 @@
 
 #include "fx_asm.hpp"
 #include "fx_bus.hpp"
+#include "fx_imajor.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -66,6 +67,15 @@ public:
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream);
     // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
     static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
+    // Instance-major blocks (fx_imajor.hpp; include/fx8010_amd.h fxb_process_block_imajor): instance i's input is the run of
+    // nSamples * channels floats, [sample][channel], at in + i * inStride, its output the same at out + i * outStride (a stride in
+    // floats, 0 = packed).  in == out with one stride, or footprints that share no element.  A shard of a larger batch passes
+    // base + first * stride.  Entries as processBus's: kBusHost synchronous, in place on pinned buffers or staged; kBusDevice
+    // checked once, asynchronous on `stream`.
+    int processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, BusEntry entry, hipStream_t stream);
+    // the refusals that read nothing but the arguments (also asked by Sharded, for the whole batch): 0, or why not in *why; a stride
+    // of 0 becomes the run
+    static int checkImajorShape(const float* in, const float* out, int nSamples, int channels, int64_t n, int64_t* inStride, int64_t* outStride, const char** why);
     int sync();
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
@@ -413,6 +423,15 @@ private:
     size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;
     const float* busCheckedDevIn_ = nullptr;
     float* busCheckedDevOut_ = nullptr;
+    // instance-major blocks: gather -> the ordinary launch in place on the bus scratch -> scatter (the scratch, evBus_ and
+    // busLaunched_ are shared with bus blocks: the two kinds may alternate, on different streams)
+    int runImajor(const float* in, int64_t inStride, float* out, int64_t outStride, int nSamples, hipStream_t stream);
+    int64_t imajorBlocks_ = 0;      // FXB_INFO_IMAJOR_BLOCKS
+    const float* imajorCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks
+    const float* imajorCheckedOut_ = nullptr;
+    size_t imajorCheckedInBytes_ = 0, imajorCheckedOutBytes_ = 0;
+    const float* imajorCheckedDevIn_ = nullptr;
+    float* imajorCheckedDevOut_ = nullptr;
 #ifdef FX_DIAGNOSTICS
     int ensureEndStamps();   // the end stamps' buffer (dStamps_), one word per wavefront
 #endif

@@ -671,6 +671,152 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
     return 0;
 }
 
+// ---- instance-major blocks: one interleaved [sample][channel] stream per instance (fx_imajor.hpp) ---------------------------------
+//
+// The same sandwich as a bus block, on the same scratch: gather (a transposition of the n runs into [rows][n]) -> the ordinary
+// launch in place -> scatter.  What crosses PCIe is each stream's run, once each way.
+
+namespace {
+// Do the runs of `in` and of `out` - n runs of `run` floats at their strides - share an element?  Not when one footprint ends
+// before the other begins.  With one stride, run j of `out` lies d + (j - k) * stride floats behind run k of `in`: the distances
+// nearest to zero are m = d mod stride and m - stride, so no two runs meet iff run <= m <= stride - run.  With two strides the
+// runs of both, each in ascending order, are walked once.
+bool imajorFootprintsApart(const float* in, const float* out, int64_t run, int64_t n, int64_t inStride, int64_t outStride) {
+    const char *x = reinterpret_cast<const char*>(in), *y = reinterpret_cast<const char*>(out);
+    const size_t inBytes = ((size_t)(n - 1) * (size_t)inStride + (size_t)run) * 4, outBytes = ((size_t)(n - 1) * (size_t)outStride + (size_t)run) * 4;
+    if (x + inBytes <= y || y + outBytes <= x) return true;
+    if (inStride == outStride) {
+        const std::ptrdiff_t d = y - x;
+        if (d % 4 != 0) return false;
+        int64_t m = (int64_t)(d / 4) % inStride;
+        if (m < 0) m += inStride;
+        return m >= run && m <= inStride - run;
+    }
+    const size_t bytes = (size_t)run * 4;
+    for (int64_t i = 0, j = 0; i < n && j < n;) {
+        const char *a = x + (size_t)i * (size_t)inStride * 4, *b = y + (size_t)j * (size_t)outStride * 4;
+        if (a + bytes <= b) ++i;
+        else if (b + bytes <= a) ++j;
+        else return false;
+    }
+    return true;
+}
+}  // namespace
+
+int Batch::checkImajorShape(const float* in, const float* out, int nSamples, int channels, int64_t n, int64_t* inStride, int64_t* outStride, const char** why) {
+    *why = nullptr;
+    if (nSamples < 0) *why = "n_samples < 0";
+    const int64_t run = (int64_t)std::max(nSamples, 0) * (int64_t)std::max(channels, 1);
+    if (!*why && run >= ((int64_t)1 << 31)) *why = "instance-major block: n_samples * num_channels must stay below 2^31";
+    if (!*why && (*inStride < 0 || *outStride < 0)) *why = "instance-major block: negative stride";
+    if (*why) return FX_E_ARG;
+    if (*inStride == 0) *inStride = run;
+    if (*outStride == 0) *outStride = run;
+    if (*inStride < run || *outStride < run) *why = "instance-major block: stride below n_samples * num_channels";
+    else if (std::max(*inStride, *outStride) > (((int64_t)1 << 60) / std::max<int64_t>(n, 1))) *why = "instance-major block: stride too wide";
+    else if (nSamples > 0 && (!in || !out)) *why = "null buffer";
+    else if (nSamples > 0 && (in == out ? *inStride != *outStride : !imajorFootprintsApart(in, out, run, n, *inStride, *outStride)))
+        *why = "instance-major block: input and output overlap without being one buffer with one stride";
+    return *why ? FX_E_ARG : 0;
+}
+
+// The block itself, asynchronous on `stream`: in / out as the device addresses them.  Pieces as in runBus - consecutive sample
+// ranges that fit the scratch, every piece gathering and scattering its sub-run of every stream; a piece is wholly gathered before
+// anything of it is scattered and pieces are disjoint ranges, so in == out is safe.
+int Batch::runImajor(const float* in, int64_t inStride, float* out, int64_t outStride, int nSamples, hipStream_t stream) {
+    const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
+    const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
+    const int pieces = (nSamples + most - 1) / most;
+    int rc = ensureBusScratch((size_t)((nSamples + pieces - 1) / pieces) * perSample);
+    if (rc != 0) return rc;
+    hipStream_t s = pick(stream);
+    // (the scratch is the bus blocks': whatever filled it last, on whatever stream, must have emptied it)
+    if (busLaunched_) {
+        const hipError_t we = hipStreamWaitEvent(s, evBus_, 0);
+        if (we != hipSuccess) return hipFail(we, "instance-major block: waiting for the previous block on the scratch");
+    }
+    beginBlock(nSamples, pieces);   // ONE block to the bookkeeping of control changes and to the lowering
+    if ((rc = ensureLowered()) != 0) return rc;
+    auto lo = [&](int p) { return (int)((int64_t)nSamples * p / pieces); };
+    for (int p = 0; p < pieces; ++p) {
+        const int count = lo(p + 1) - lo(p);
+        ImajorArgs a{};
+        a.wide = dBus_;
+        a.first = (long long)lo(p) * (long long)ch;
+        a.rows = (long long)count * (long long)ch;
+        a.n = n_;
+        a.in = in;
+        a.stride = inStride;
+        hipError_t e = launchImajorGather(a, s);
+        if (e != hipSuccess) return hipFail(e, "instance-major block: filling the scratch block");
+        if ((rc = launchBlock(dBus_, dBus_, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) {
+            if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
+            return rc;
+        }
+        a.in = nullptr;
+        a.out = out;
+        a.stride = outStride;
+        e = launchImajorScatter(a, s);
+        if (e == hipSuccess) e = hipEventRecord(evBus_, s);
+        if (e != hipSuccess) return hipFail(e, "instance-major block: emptying the scratch block");
+        busLaunched_ = true;
+    }
+    ++imajorBlocks_;   // (blocks whose every piece was queued)
+    return 0;
+}
+
+int Batch::processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, BusEntry entry, hipStream_t stream) {
+    (void)hipSetDevice(device_);
+    const char* why = nullptr;
+    int rc = checkImajorShape(in, out, nSamples, prog_.numChannels, n_, &inStride, &outStride, &why);
+    if (rc != 0) return fail(rc, why);
+    if (pcmStrideTooWide(prog_.numChannels, n_)) return fail(FX_E_ARG, "instance-major block: channels * instances * 4 must stay below 2^32");
+    if (nSamples == 0) return ensureLowered();
+    const size_t run = (size_t)nSamples * (size_t)prog_.numChannels;
+    const size_t inBytes = ((size_t)(n_ - 1) * (size_t)inStride + run) * 4, outBytes = ((size_t)(n_ - 1) * (size_t)outStride + run) * 4;
+    const void *devIn = nullptr, *devOut = nullptr;
+    if (entry == kBusDevice) {
+        if (in != imajorCheckedIn_ || out != imajorCheckedOut_ || inBytes > imajorCheckedInBytes_ || outBytes > imajorCheckedOutBytes_) {
+            imajorCheckedIn_ = imajorCheckedOut_ = nullptr;
+            if (!addressable(in, inBytes, device_, &devIn) || !addressable(out, outBytes, device_, &devOut))
+                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
+            imajorCheckedIn_ = in;
+            imajorCheckedOut_ = out;
+            imajorCheckedInBytes_ = inBytes;
+            imajorCheckedOutBytes_ = outBytes;
+            imajorCheckedDevIn_ = static_cast<const float*>(devIn);
+            imajorCheckedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
+        }
+        return runImajor(imajorCheckedDevIn_, inStride, imajorCheckedDevOut_, outStride, nSamples, stream);
+    }
+    // Host entry.  Pinned buffers: the two kernels read the runs from and store them to the caller's memory over PCIe, no copies.
+    // Anything else: the n runs are staged as rows of a 2-D copy, [n][run] in device memory, and transposed from there.  Whatever
+    // happens, nothing of the call may still touch the caller's memory when it returns.
+    waitLastLaunch();
+    if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && (static_cast<const void*>(out) == in ? (devOut = devIn, true) : addressable(out, outBytes, -1, &devOut))) {
+        rc = runImajor(static_cast<const float*>(devIn), inStride, static_cast<float*>(const_cast<void*>(devOut)), outStride, nSamples, stream_);
+        const hipError_t se = hipStreamSynchronize(stream_);
+        if (rc != 0) return rc;
+        if (se != hipSuccess) return hipFail(se, "synchronising an instance-major block on pinned host buffers");
+        ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
+        return 0;
+    }
+    // (one staging block serves both directions: a piece's sub-runs are scattered to where they were gathered from)
+    if ((rc = ensureBusStage(run * (size_t)n_)) != 0) return rc;
+    hipError_t e = copyRows(dBusStage_, run * 4, in, (size_t)inStride * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        return hipFail(e, "instance-major H2D");
+    }
+    rc = runImajor(dBusStage_, (int64_t)run, dBusStage_, (int64_t)run, nSamples, stream_);
+    if (rc == 0) e = copyRows(out, (size_t)outStride * 4, dBusStage_, run * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (rc != 0) return rc;
+    if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "instance-major D2H");
+    ++hostStagedBlocks_;
+    return 0;
+}
+
 // Generate the code a stream of `nSamples`-sample blocks will run, now - a real-time caller does this after loading, before the
 // stream starts, instead of paying for the translation in its first block.  wait: also until the builder thread has finished
 // what it was asked for (the variant with the controls in rows, other stage counts on trial).

@@ -230,6 +230,12 @@ int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n, int
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t group, unsigned flags, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
 }
+int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n, int64_t in_stride, int64_t out_stride) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processImajor(in, out, n, in_stride, out_stride, false, nullptr); }) : FX_E_ARG;
+}
+int fxb_process_block_imajor_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t in_stride, int64_t out_stride, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processImajor(d_in, d_out, n, in_stride, out_stride, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
+}
 int fxb_meter_enable(fxb_handle* h, int on) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterEnable(on != 0); }) : FX_E_ARG; }
 int fxb_meter_read(fxb_handle* h, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterRead(energy, peak, full_scale, nonfinite, reset != 0); }) : FX_E_ARG;

@@ -282,6 +282,20 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
         return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr);
     });
 }
+int Sharded::processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream) {
+    Serial serial(api_);
+    lastError_.clear();
+    // the refusals that go by the WHOLE batch, before any shard is posted: the footprints of all instances, the packed stride
+    if (device && shards_.size() != 1) { lastError_ = "the device entry of an instance-major block is for handles of one shard"; return FX_E_ARG; }
+    const char* why = nullptr;
+    if (Batch::checkImajorShape(in, out, nSamples, front().channels(), n_, &inStride, &outStride, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    if (shards_.size() == 1)
+        return runOn(0, [&](Batch& b) { return b.processImajor(in, out, nSamples, inStride, outStride, device ? Batch::kBusDevice : Batch::kBusHost, stream); });
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        return b.processImajor(in ? in + first * inStride : in, out ? out + first * outStride : out, nSamples, inStride, outStride, Batch::kBusHost, nullptr);
+    });
+}
 int Sharded::sync() {
     Serial serial(api_);
     lastError_.clear();
@@ -417,7 +431,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_IMAJOR_BLOCKS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

@@ -71,6 +71,9 @@ public:
     // on a side with its flag.  Every shard must begin at a multiple of `group` (fxb_shard_plan tells the boundaries) and works on
     // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream);
+    // instance-major blocks (Batch::processImajor): shard k works on the runs from in + first_k * inStride on, on its own thread
+    // and device.  device: the caller's stream, single-shard handles only.
+    int processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream);
     int sync();
     // output meters (Batch::meterEnable ...): enable fans out (a shard that cannot allocate leaves metering off on all of them),
     // read gives each shard its columns of the caller's [channels][all instances] arrays, samples is shard 0's

@@ -213,6 +213,12 @@ public:
         const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
         if (fxb_process_block_bus(h_, in, out, nSamples, group, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::processBlockBus: ") + fxb_last_error(h_));
     }
+    // one interleaved stream per instance (include/fx8010_amd.h fxb_process_block_imajor): instance n's nSamples * channels floats,
+    // [sample][channel], at in + n * inStride, its output the same way at out + n * outStride (strides in floats, 0 = packed; a
+    // larger one walks a whole file or ring per instance in place).  Host buffers, synchronous; in == out with one stride is fine.
+    void processStreams(const float* in, float* out, int nSamples, int64_t inStride = 0, int64_t outStride = 0) {
+        if (fxb_process_block_imajor(h_, in, out, nSamples, inStride, outStride) < 0) throw std::runtime_error(std::string("FX8010Batch::processStreams: ") + fxb_last_error(h_));
+    }
     // device-resident buffers, asynchronous on `stream` (hipStream_t)
     void processDevice(const float* dIn, float* dOut, int nSamples, void* stream = nullptr) {
         if (fxb_process_block_dev(h_, dIn, dOut, nSamples, stream) < 0) throw std::runtime_error(std::string("FX8010Batch::processDevice: ") + fxb_last_error(h_));

@@ -138,18 +138,15 @@ int main(int argc, char** argv) {
         out.channels = ch;
         out.sampleRate = in.sampleRate;
         out.frames.resize(frames * ch);
-        std::vector<float> bin((size_t)block * ch * instances), bout(bin.size());
+        // every instance's block is its own interleaved [sample][channel] run, as the file holds it
+        const size_t run = (size_t)block * ch;
+        std::vector<float> bin(run * (size_t)instances), bout(bin.size());
         for (size_t f0 = 0; f0 < frames; f0 += (size_t)block) {
             const int S = (int)std::min<size_t>((size_t)block, frames - f0);
-            for (int s = 0; s < S; ++s)
-                for (int c = 0; c < ch; ++c) {
-                    const float v = in.frames[(f0 + s) * ch + c];
-                    float* row = &bin[((size_t)s * ch + c) * instances];
-                    for (int64_t i = 0; i < instances; ++i) row[i] = v;
-                }
-            dsp.process(bin.data(), bout.data(), S);
-            for (int s = 0; s < S; ++s)
-                for (int c = 0; c < ch; ++c) out.frames[(f0 + s) * ch + c] = bout[((size_t)s * ch + c) * instances + pick];
+            const size_t words = (size_t)S * ch;
+            for (int64_t i = 0; i < instances; ++i) std::memcpy(&bin[(size_t)i * run], &in.frames[f0 * ch], words * 4);
+            dsp.processStreams(bin.data(), bout.data(), S, (int64_t)run, (int64_t)run);
+            std::memcpy(&out.frames[f0 * ch], &bout[(size_t)pick * run], words * 4);
         }
         writeWavFloat(outPath, out);
         std::cout << frames << " frames x " << ch << " channel(s) x " << instances << " instance(s): " << dsp.getInstructionCounter()

@@ -24,7 +24,7 @@ INFO = {
     "waves_per_wg": 5, "num_microops": 6, "itram_slots": 7, "xtram_slots": 8, "tram_ops": 9, "multipass": 10,
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
-    "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36,
+    "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -38,6 +38,7 @@ SYMBOLS = [
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev",
+    "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
@@ -92,6 +93,7 @@ def load():
     sig("fxb_process_block_pitched", i32, vp, vp, vp, i32, i64); sig("fxb_process_block_dev_pitched", i32, vp, vp, vp, i32, i64, vp)
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
+    sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
@@ -487,6 +489,49 @@ class Batch(_Reports):
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
         return self._check(self._lib.fxb_process_block_bus_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(group), flags, C.c_void_p(stream or 0)),
                            "process_block_bus_dev")
+
+    def _stream_stride(self, shape, strides):
+        """the instance stride (in floats) when an [N, S, channels] array is N interleaved [S][channels] runs at one stride, else None"""
+        n, S, ch = shape
+        if (n, ch) != (self.n, self.channels) or (ch > 1 and strides[2] != 1) or (S > 1 and strides[1] != ch):
+            return None
+        return S * ch if n == 1 else (strides[0] if strides[0] >= S * ch else None)
+
+    def process_block_imajor(self, x, out=None):
+        """A block of per-instance streams.  x: float32 [N, S, channels] - instance n's interleaved [S][channels] run - returns the
+        same shape (into `out` when given).  A view with unit inner strides and one instance stride, e.g. whole[:, f0:f0 + S, :] of
+        a pinned [N, frames, channels] array, goes to the library as it is, with its stride: in place when the memory is pinned.
+        Other layouts are copied."""
+        def stride(a):
+            ok = isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 3 and all(t % 4 == 0 for t in a.strides)
+            return self._stream_stride(a.shape, [t // 4 for t in a.strides]) if ok else None
+        if stride(x) is None:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            assert x.ndim == 3 and x.shape[0] == self.n and x.shape[2] == self.channels, "input must be [N, S, channels]"
+        S = x.shape[1]
+        given = out
+        if out is None or stride(out) is None or not out.flags["WRITEABLE"] or out.shape != x.shape:
+            out = np.empty((self.n, S, self.channels), dtype=np.float32)
+        self._check(self._lib.fxb_process_block_imajor(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), S, stride(x), stride(out)), "process_block_imajor")
+        if given is not None and given is not out:
+            given[...] = out
+            return given
+        return out
+
+    def process_block_imajor_dev(self, d_in, d_out, n_samples, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: device pointers (ints) with strides in floats (None: packed), or float32 torch tensors [N, n_samples,
+        channels] whose inner strides are those of an interleaved run (views into a longer [N, frames, channels] tensor included;
+        the instance stride comes from stride()).  Single-shard handles; asynchronous on `stream` (a hipStream_t as int)."""
+        def ptr(t, given):
+            if isinstance(t, int):
+                return t, int(given or 0)
+            assert t.element_size() == 4 and t.dim() == 3 and tuple(t.shape) == (self.n, n_samples, self.channels), "[N, S, channels] float32"
+            st = self._stream_stride(tuple(t.shape), tuple(t.stride()))
+            assert st is not None and given in (None, st), "N interleaved runs at one stride"
+            return t.data_ptr(), st
+        (a, sa), (b, sb) = ptr(d_in, in_stride), ptr(d_out, out_stride)
+        return self._check(self._lib.fxb_process_block_imajor_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), sa, sb, C.c_void_p(stream or 0)),
+                           "process_block_imajor_dev")
 
     def meter_enable(self, on=True):
         """Output meters on (accumulator rows allocated and zeroed on every shard; on twice keeps the values) or off (freed).

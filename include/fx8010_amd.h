@@ -244,6 +244,36 @@ int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float*
 int64_t fxb_bus_groups(fxb_handle* h, int64_t group);   /* G, or FX_E_ARG */
 int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n_samples, int64_t group, unsigned flags);
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t group, unsigned flags, void* stream);
+/* Instance-major blocks: one interleaved stream per instance, transposed on the device.  Instance n's input is the
+ * n_samples * num_channels floats at in + n * in_stride, ordered [sample][channel] - what n_samples calls of the reference's
+ * process() consume and what a WAV file holds - and its output goes to out + n * out_stride the same way.
+ *   Strides are in floats.  0 means packed (n_samples * num_channels).  A stride above the run is the useful case: a host that
+ *   holds a whole file or a ring per instance passes base + f0 * num_channels with the stride of the whole allocation and walks
+ *   through it block by block without copying.  The words between two runs are never read and never written.
+ *   Nothing beyond 4-byte alignment is assumed of a base or a stride.  n * stride * 4 may exceed 2^32 (the offset of an instance
+ *   is 64-bit arithmetic); n_samples * num_channels must stay below 2^31.
+ * Results and instance state afterwards are exactly those of fxb_process_block on the transposed input: two small kernels
+ * surround the unchanged launch of the program - a gather from the streams into a per-instance [sample][channel][N] block in
+ * device memory (the scratch block of bus blocks), the program in place on it, a scatter back to the streams.  Every word is moved
+ * as a 32-bit pattern.  Control tracks armed for the block apply; n_samples == 0 lowers the program and returns 0.  Blocks whose
+ * scratch would exceed 64 MiB run in consecutive sample ranges (with a track armed the block stays whole).  Bus blocks and
+ * instance-major blocks may alternate on one handle, on different streams.  FXB_INFO_IMAJOR_BLOCKS counts these blocks,
+ * FXB_INFO_BUS_BLOCKS does not.
+ * Overlap: in == out with in_stride == out_stride is allowed (a range of samples is wholly gathered before anything of it is
+ * scattered); so are footprints - N runs of n_samples * num_channels floats at the stride - that share no element.  Any other
+ * overlap is FX_E_ARG.
+ * Host entry: synchronous.  Pinned buffers (fxb_host_alloc ...) are read and written in place by the two kernels, no copies
+ * (FXB_INFO_HOST_INPLACE_BLOCKS); other memory is staged with 2-D copies of the N runs and transposed from the staging block
+ * (FXB_INFO_HOST_STAGED_BLOCKS).
+ * Device entry: single-shard handles, buffers checked like fxb_process_block_bus_dev's and remembered, asynchronous on `stream`,
+ * covered by fxb_sync.
+ * Sharded handles: shard k works on the runs from in + first_k * in_stride on, on its own thread and stream; in place where its
+ * device can address the buffer, staged (that shard only) otherwise.  No condition on the shard boundaries.
+ * FX_E_ARG (nothing launched, nothing changed): n_samples < 0, a negative stride or one above 0 and below
+ * n_samples * num_channels, a null buffer with n_samples > 0, overlap as above, the device entry on a handle of several shards or
+ * with memory the device cannot address. */
+int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n_samples, int64_t in_stride, int64_t out_stride);
+int fxb_process_block_imajor_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t in_stride, int64_t out_stride, void* stream);
 /* Output meters: per instance and channel the peak, the energy, how often the output sat at the FX8010's +-1 saturation rail and
  * how many of its samples were non-finite - computed on the device, accumulated there across blocks, read when the host wants
  * them.  Metering is a mode of the handle, off by default; with it off nothing below costs anything.
@@ -272,6 +302,8 @@ int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, in
  *                             block crosses the link a third time: real-time hosts that want meters use bus blocks);
  *   bus blocks                the per-instance scratch block in device memory, between the program and the mix or the copy out:
  *                             the per-instance output still never leaves the device, and every instance has its figures.
+ *   instance-major blocks     the same scratch block, between the program and the scatter to the streams: the meter reads
+ *                             device memory, whichever memory the streams live in.
  * While metering is on, fxb_last_kernel_ms and fxb_shard_kernel_ms cover the program's launch plus its meter launch (the meter
  * is queued in front of the event that ends the measurement, so that every wait for a block also covers the meter's read of the
  * caller's buffer).
@@ -358,7 +390,8 @@ enum {
     FXB_INFO_HOST_STAGED_BLOCKS = 33,  /* host blocks that went through staging copies since creation (summed over shards) */
     FXB_INFO_HOST_INPLACE_BLOCKS = 34, /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
     FXB_INFO_BUS_BLOCKS = 35,          /* bus blocks (fxb_process_block_bus* with a flag set) since creation (summed over shards) */
-    FXB_INFO_METER_LAUNCHES = 36       /* launches of the output-meter kernel (fxb_meter_enable) since creation (summed over shards) */
+    FXB_INFO_METER_LAUNCHES = 36,      /* launches of the output-meter kernel (fxb_meter_enable) since creation (summed over shards) */
+    FXB_INFO_IMAJOR_BLOCKS = 37        /* instance-major blocks since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
