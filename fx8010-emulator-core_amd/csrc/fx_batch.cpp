@@ -76,6 +76,11 @@ Batch::~Batch() {
     (void)hipFree(dBus_);
     (void)hipFree(dBusStage_);
     (void)hipFree(dMeter_);
+    (void)hipFree(dInstList_);
+    (void)hipFree(dInstRec_);
+    if (hInstList_) (void)hipHostFree(hInstList_);
+    if (hInstRec_) (void)hipHostFree(hInstRec_);
+    if (evInst_) (void)hipEventDestroy(evInst_);
     if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS
     (void)hipFree(dStamps_);
@@ -99,6 +104,8 @@ void Batch::waitLastLaunch() {
     if (launched_) (void)hipEventSynchronize(ev1_);
     // (a bus block ends behind its emulation launch: the mix kernel, or the copy out of the scratch block)
     if (busLaunched_) (void)hipEventSynchronize(evBus_);
+    // (a copy or a reset of instances queued behind it: once it has been waited for no later launch needs to)
+    if (instLaunched_ && hipEventSynchronize(evInst_) == hipSuccess) instLaunched_ = false;
 }
 
 int Batch::fail(int code, const std::string& what) {
@@ -832,10 +839,13 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
     if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
+    if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
+    if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {
         case FXB_INFO_INST_PER_LANE: return instPerLane_;
+        case FXB_INFO_INSTANCE_WORDS: return (int64_t)stateRows_ + iSlotsAlloc_ + xSlotsAlloc_;
         case FXB_INFO_KERNEL: return c_.useAsm ? (c_.useXlate ? 8 + (int)c_.variant : 1 + (int)c_.variant) : 0;
         case FXB_INFO_XLATE_CODE_BYTES: return c_.useXlate ? (int64_t)c_.codeBytes : 0;
         case FXB_INFO_XLATE_INLINED: return c_.useXlate ? c_.inlined : 0;

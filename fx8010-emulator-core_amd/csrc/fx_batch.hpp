@@ -17,6 +17,7 @@
 #include "fx_asm.hpp"
 #include "fx_bus.hpp"
 #include "fx_imajor.hpp"
+#include "fx_instances.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -111,6 +112,31 @@ public:
     }
     int saveStateColumns(uint8_t* image, const SnapshotHeader& hdr, int64_t first);
     int loadStateColumns(const uint8_t* image, const SnapshotHeader& hdr, int64_t first);
+    // Per-instance state calls (fx_instances.hpp; include/fx8010_amd.h "Per-instance state").  A RECORD is the W = stateRows +
+    // iSlots + xSlots words of one instance, packed: the state rows in the order of the whole-batch image, then the iTRAM slots, then
+    // the xTRAM slots.  An instance image is a SnapshotHeader with kInstanceMagic and n = the number of records, then the records.
+    // Every list here holds instance numbers of THIS batch; Sharded splits the caller's global lists.  All of them lower the program
+    // first, run on the handle's own stream behind every block queued so far on whatever stream (ev1_, evBus_), and every later
+    // block, state access and sync is ordered behind them (evInst_).
+    static constexpr uint32_t kInstanceMagic = 0x49535846u;   // "FXSI"
+    // the refusals that read nothing but the lists (Sharded asks for the whole batch): 0, or FX_E_ARG and why.  dst null: one list
+    // whose entries must be distinct; else src may repeat, dst may not and may not appear in src
+    static int checkInstanceLists(const int64_t* src, const int64_t* dst, int64_t count, int64_t n, const char** why);
+    int instanceShape(SnapshotHeader* hdr, int64_t count);   // the header of an image of `count` records of this batch
+    static int64_t instanceWords(const SnapshotHeader& hdr) { return (int64_t)hdr.stateRows + hdr.iSlots + hdr.xSlots; }
+    // 0 when `hdr` (validated field by field) heads an instance image of `count` records this batch can take and `bytes` holds it
+    int checkInstanceImage(const SnapshotHeader& hdr, int64_t count, int64_t bytes);
+    int copyInstances(const int64_t* src, const int64_t* dst, int64_t count);   // stream-ordered
+    int resetInstances(const int64_t* list, int64_t count);                     // stream-ordered
+    // records to / from host memory, synchronous: the record of list[k] is the W words at buf + pos[k] * W (pos null: k)
+    int gatherRecords(const int64_t* list, const int64_t* pos, int64_t count, uint32_t* buf);
+    int scatterRecords(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf);
+    // the delay-line rule of a load: FX_E_ARG unless the program executes no delay-line instruction or the four position words of
+    // every record equal those the destination instance holds now.  Changes nothing.
+    int checkRecordCursors(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf);
+    // what the host knows about the registers follows a load of these `total` records (of all shards: every shard ends up with
+    // the same rows): a register with a value other than hostValue_ in any record becomes per-instance, as after setRegisterAt
+    void promoteLoaded(const uint32_t* buf, int64_t total);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -432,6 +458,26 @@ private:
     size_t imajorCheckedInBytes_ = 0, imajorCheckedOutBytes_ = 0;
     const float* imajorCheckedDevIn_ = nullptr;
     float* imajorCheckedDevOut_ = nullptr;
+    // per-instance state calls (fx_batch_instances.cpp): a device list and a record scratch of their own, allocated on first use,
+    // grown on demand and kept - the records up to kInstScratchBytes, the size of the bus scratch (not shared with it: a bus block
+    // on a caller's stream and a copy on the handle's stream then never wait for each other's scratch); a call whose records exceed
+    // it runs in pieces.  The lists go through pinned memory of the library, so the caller's arrays are free on return.
+    static constexpr size_t kInstScratchBytes = (size_t)64 << 20;
+    InstArgs instArgs() const;
+    int beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords);   // lower, range check, lists -> device, order behind the blocks
+    int endInstanceCall(bool wait);                           // evInst_ behind what was queued
+    int64_t recordsPerPiece() const;
+    long long* dInstList_ = nullptr;     // [2][instListCap_]
+    size_t instListCap_ = 0;
+    long long* hInstList_ = nullptr;     // pinned, same shape
+    size_t hInstListCap_ = 0;
+    uint32_t* dInstRec_ = nullptr;
+    size_t instRecCap_ = 0;              // words
+    uint32_t* hInstRec_ = nullptr;       // pinned: the one record of a reset
+    size_t hInstRecCap_ = 0;             // words
+    hipEvent_t evInst_ = nullptr;        // behind the last kernel or copy of the most recent instance call
+    bool instLaunched_ = false;          // ... which may still be running
+    int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS
 #ifdef FX_DIAGNOSTICS
     int ensureEndStamps();   // the end stamps' buffer (dStamps_), one word per wavefront
 #endif

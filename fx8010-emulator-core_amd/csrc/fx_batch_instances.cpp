@@ -1,0 +1,298 @@
+// fx_batch_instances.cpp — the per-instance state calls of one batch: copy, reset, records to and from the host (fx_batch.hpp
+// "Per-instance state calls", kernels: fx_instances.hip).
+//
+// Every call has the same frame.  beginInstanceCall lowers the program (the delay memory exists from then on), refuses instance
+// numbers outside the batch, waits on the HOST for the previous instance call (its lists and records are in the buffers this one
+// is about to fill - between two calls of a voice pool lies at least a block, so that wait is over before it starts), copies the
+// lists into pinned memory and from there to the device, and makes the handle's stream wait for every block queued so far on
+// whatever stream (ev1_, evBus_).  The kernels then run on the handle's stream, in pieces of at most recordsPerPiece() records on
+// the one record scratch - stream order alone keeps a piece's scatter in front of the next piece's gather.  endInstanceCall
+// records evInst_ behind the last of them: a block on another stream waits for it (launchBlock), the host does in waitLastLaunch
+// and sync.
+#include "fx_batch.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/fx8010_amd.h"
+
+namespace fx {
+
+namespace {
+// how many of the `most` positions from p on are consecutive: one copy moves their records
+int64_t recordRun(const int64_t* p, int64_t most) {
+    int64_t run = 1;
+    while (run < most && p[run] == p[run - 1] + 1) ++run;
+    return run;
+}
+}  // namespace
+
+int Batch::checkInstanceLists(const int64_t* src, const int64_t* dst, int64_t count, int64_t n, const char** why) {
+    *why = nullptr;
+    if (count < 0) *why = "instances: a negative count";
+    else if (count > 0 && !src && !dst) *why = "instances: a null list";
+    else if (count >= ((int64_t)1 << 31)) *why = "instances: more than 2^31 - 1 list entries";
+    if (*why) return FX_E_ARG;
+    for (const int64_t* list : {src, dst})
+        for (int64_t k = 0; list && k < count; ++k)
+            if (list[k] < 0 || list[k] >= n) { *why = "instances: an instance number outside the batch"; return FX_E_ARG; }
+    if (!dst || count == 0) return 0;
+    std::vector<int64_t> sorted(dst, dst + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { *why = "instances: a destination is listed twice"; return FX_E_ARG; }
+    for (int64_t k = 0; src && k < count; ++k)
+        if (std::binary_search(sorted.begin(), sorted.end(), src[k])) { *why = "instances: a destination is also a source"; return FX_E_ARG; }
+    return 0;
+}
+
+int Batch::instanceShape(SnapshotHeader* hdr, int64_t count) {
+    const int rc = snapshotShape(hdr);
+    if (rc != 0) return rc;
+    hdr->magic = kInstanceMagic;
+    hdr->n = count;
+    return 0;
+}
+
+int Batch::checkInstanceImage(const SnapshotHeader& hdr, int64_t count, int64_t bytes) {
+    SnapshotHeader mine;
+    const int rc = instanceShape(&mine, count);
+    if (rc != 0) return rc;
+    // (every field is compared before any of them enters an address: the image may be a damaged file.  Equal to ours, the
+    // counts are sane and count * W * 4 cannot overflow: count < 2^31, W < 2^22)
+    if (hdr.magic != mine.magic || hdr.version != mine.version) return fail(FX_E_ARG, "instance image: not an instance image of this library version");
+    if (hdr.n != count || count < 0 || count >= ((int64_t)1 << 31)) return fail(FX_E_ARG, "instance image: it holds another number of records than the list has entries");
+    if (hdr.channels != mine.channels || hdr.nRegs != mine.nRegs || hdr.stateRows != mine.stateRows || hdr.iSlots != mine.iSlots || hdr.xSlots != mine.xSlots)
+        return fail(FX_E_ARG, "instance image: the image is of another program (registers, channels or delay lines differ)");
+    if (bytes < (int64_t)sizeof(SnapshotHeader) + count * instanceWords(mine) * 4) return fail(FX_E_ARG, "instance image: truncated");
+    return 0;
+}
+
+InstArgs Batch::instArgs() const {
+    InstArgs a{};
+    a.state = dState_;
+    a.itram = reinterpret_cast<uint32_t*>(dITram_);
+    a.xtram = reinterpret_cast<uint32_t*>(dXTram_);
+    a.n = n_;
+    a.nPad = nPad_;
+    a.stateRows = stateRows_;
+    a.iSlots = iSlotsAlloc_;
+    a.xSlots = xSlotsAlloc_;
+    a.cols = 64 * instPerLane_;
+    a.recStride = fx::instanceWords(a);
+    return a;
+}
+
+int64_t Batch::recordsPerPiece() const {
+    const size_t w = (size_t)stateRows_ + (size_t)iSlotsAlloc_ + (size_t)xSlotsAlloc_;
+    return (int64_t)std::max<size_t>(kInstScratchBytes / (w * 4), 1);
+}
+
+int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords) {
+    (void)hipSetDevice(device_);
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    const char* why = nullptr;
+    if (checkInstanceLists(a, nullptr, count, n_, &why) != 0 || (b && checkInstanceLists(b, nullptr, count, n_, &why) != 0)) return fail(FX_E_ARG, why);
+    if (!a || count < 1) return fail(FX_E_ARG, "instances: a null list");
+    hipError_t e = hipSuccess;
+    if (!evInst_ && (e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming)) != hipSuccess) { evInst_ = nullptr; return hipFail(e, "instance event"); }
+    if (instLaunched_) {
+        if ((e = hipEventSynchronize(evInst_)) != hipSuccess) return hipFail(e, "waiting for the previous instance call");
+        instLaunched_ = false;
+    }
+    const size_t entries = (size_t)count;
+    if (entries > hInstListCap_) {
+        if (hInstList_) (void)hipHostFree(hInstList_);
+        hInstList_ = nullptr;
+        hInstListCap_ = 0;
+        if ((e = hipHostMalloc(reinterpret_cast<void**>(&hInstList_), entries * 2 * sizeof(long long), hipHostMallocDefault)) != hipSuccess) { hInstList_ = nullptr; return hipFail(hipErrorOutOfMemory, "pinned instance lists"); }
+        hInstListCap_ = entries;
+    }
+    if (entries > instListCap_) {
+        (void)hipFree(dInstList_);
+        dInstList_ = nullptr;
+        instListCap_ = 0;
+        if ((e = hipMalloc(reinterpret_cast<void**>(&dInstList_), entries * 2 * sizeof(long long))) != hipSuccess) { dInstList_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc instance lists"); }
+        instListCap_ = entries;
+    }
+    if (recordWords > instRecCap_) {
+        (void)hipFree(dInstRec_);
+        dInstRec_ = nullptr;
+        instRecCap_ = 0;
+        if ((e = hipMalloc(reinterpret_cast<void**>(&dInstRec_), recordWords * 4)) != hipSuccess) { dInstRec_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc instance records"); }
+        instRecCap_ = recordWords;
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "instance lists");
+    std::memcpy(hInstList_, a, entries * 8);
+    if (b) std::memcpy(hInstList_ + hInstListCap_, b, entries * 8);
+    e = hipMemcpyAsync(dInstList_, hInstList_, entries * 8, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && b) e = hipMemcpyAsync(dInstList_ + instListCap_, hInstList_ + hInstListCap_, entries * 8, hipMemcpyHostToDevice, stream_);
+    // behind every block queued so far, on whichever stream it was queued
+    if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
+    if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+    if (e != hipSuccess) {
+        (void)endInstanceCall(true);   // (the list copies may be on their way)
+        return hipFail(e, "instances: lists to the device");
+    }
+    return 0;
+}
+
+int Batch::endInstanceCall(bool wait) {
+    hipError_t e = hipEventRecord(evInst_, stream_);
+    if (e == hipSuccess) instLaunched_ = true;
+    if (wait || e != hipSuccess) {
+        const hipError_t se = hipStreamSynchronize(stream_);
+        if (se == hipSuccess) instLaunched_ = false;
+        if (e == hipSuccess) e = se;
+    }
+    return e == hipSuccess ? 0 : hipFail(e, "instances: end of the call");
+}
+
+int Batch::copyInstances(const int64_t* src, const int64_t* dst, int64_t count) {
+    if (count == 0) return ensureLowered();
+    if (!src || !dst) return fail(FX_E_ARG, "instances: a null list");
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    const int64_t per = recordsPerPiece();
+    InstArgs a = instArgs();
+    if ((rc = beginInstanceCall(src, dst, count, (size_t)std::min(count, per) * (size_t)a.recStride)) != 0) return rc;
+    a.records = dInstRec_;
+    hipError_t e = hipSuccess;
+    for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
+        a.count = std::min(per, count - off);
+        a.list = dInstList_ + off;
+        if ((e = launchInstGather(a, stream_)) != hipSuccess) break;
+        ++instGathers_;
+        a.list = dInstList_ + instListCap_ + off;
+        if ((e = launchInstScatter(a, stream_)) == hipSuccess) ++instScatters_;
+    }
+    rc = endInstanceCall(e != hipSuccess);
+    return e != hipSuccess ? hipFail(e, "launch fx_inst_gather / fx_inst_scatter") : rc;
+}
+
+int Batch::resetInstances(const int64_t* list, int64_t count) {
+    if (count == 0) return ensureLowered();
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    InstArgs a = instArgs();
+    const size_t W = (size_t)a.recStride;
+    if ((rc = beginInstanceCall(list, nullptr, count, W)) != 0) return rc;
+    hipError_t e = hipSuccess;
+    if (W > hInstRecCap_) {
+        if (hInstRec_) (void)hipHostFree(hInstRec_);
+        hInstRec_ = nullptr;
+        hInstRecCap_ = 0;
+        if ((e = hipHostMalloc(reinterpret_cast<void**>(&hInstRec_), W * 4, hipHostMallocDefault)) != hipSuccess) {
+            hInstRec_ = nullptr;
+            (void)endInstanceCall(true);
+            return hipFail(hipErrorOutOfMemory, "pinned reset record");
+        }
+        hInstRecCap_ = W;
+    }
+    // the record of a freshly created instance (ensureState): registers as the last broadcast write left them, latches 0, the
+    // reference's LFSR seeds, flags 0, counter 0, delay memory 0 - the four position words are skipped by the scatter
+    std::memset(hInstRec_, 0, W * 4);
+    for (int r = 0; r < stateLayout_.nRegs; ++r) hInstRec_[r] = bitsOf(hostValue_[(size_t)r]);
+    hInstRec_[stateLayout_.noiseBase + 0] = 0x70f4f854u;   // g_x1, include/FX8010.h:290
+    hInstRec_[stateLayout_.noiseBase + 1] = 0xe1e9f0a7u;   // g_x2, include/FX8010.h:291
+    e = hipMemcpyAsync(dInstRec_, hInstRec_, W * 4, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) {
+        a.records = dInstRec_;
+        a.recStride = 0;
+        a.list = dInstList_;
+        a.count = count;
+        a.skipLo = stateLayout_.cursorBase;
+        a.skipHi = stateLayout_.cursorBase + 4;
+        if ((e = launchInstScatter(a, stream_)) == hipSuccess) ++instScatters_;
+    }
+    rc = endInstanceCall(e != hipSuccess);
+    return e != hipSuccess ? hipFail(e, "launch fx_inst_scatter") : rc;
+}
+
+int Batch::gatherRecords(const int64_t* list, const int64_t* pos, int64_t count, uint32_t* buf) {
+    if (count == 0) return ensureLowered();
+    if (!buf) return fail(FX_E_ARG, "instances: a null buffer");
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    const int64_t per = recordsPerPiece();
+    InstArgs a = instArgs();
+    const size_t W = (size_t)a.recStride;
+    if ((rc = beginInstanceCall(list, nullptr, count, (size_t)std::min(count, per) * W)) != 0) return rc;
+    a.records = dInstRec_;
+    hipError_t e = hipSuccess;
+    for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
+        a.count = std::min(per, count - off);
+        a.list = dInstList_ + off;
+        if ((e = launchInstGather(a, stream_)) != hipSuccess) break;
+        ++instGathers_;
+        // one copy per piece, straight to where the records belong - with positions, one per run of consecutive positions
+        for (int64_t k = 0, run = 0; k < a.count && e == hipSuccess; k += run) {
+            run = pos ? recordRun(pos + off + k, a.count - k) : a.count;
+            e = hipMemcpyAsync(buf + (size_t)(pos ? pos[off + k] : off + k) * W, dInstRec_ + (size_t)k * W, (size_t)run * W * 4, hipMemcpyDeviceToHost, stream_);
+        }
+    }
+    rc = endInstanceCall(true);
+    return e != hipSuccess ? hipFail(e, "instances: records to the host") : rc;
+}
+
+int Batch::scatterRecords(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf) {
+    if (count == 0) return ensureLowered();
+    if (!buf) return fail(FX_E_ARG, "instances: a null buffer");
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    const int64_t per = recordsPerPiece();
+    InstArgs a = instArgs();
+    const size_t W = (size_t)a.recStride;
+    if ((rc = beginInstanceCall(list, nullptr, count, (size_t)std::min(count, per) * W)) != 0) return rc;
+    a.records = dInstRec_;
+    hipError_t e = hipSuccess;
+    for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
+        a.count = std::min(per, count - off);
+        a.list = dInstList_ + off;
+        for (int64_t k = 0, run = 0; k < a.count && e == hipSuccess; k += run) {
+            run = pos ? recordRun(pos + off + k, a.count - k) : a.count;
+            e = hipMemcpyAsync(dInstRec_ + (size_t)k * W, buf + (size_t)(pos ? pos[off + k] : off + k) * W, (size_t)run * W * 4, hipMemcpyHostToDevice, stream_);
+        }
+        if (e == hipSuccess && (e = launchInstScatter(a, stream_)) == hipSuccess) ++instScatters_;
+    }
+    rc = endInstanceCall(true);
+    return e != hipSuccess ? hipFail(e, "instances: records to the device") : rc;
+}
+
+int Batch::checkRecordCursors(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf) {
+    (void)hipSetDevice(device_);
+    int rc = ensureLowered();
+    if (rc != 0 || count == 0) return rc;
+    const char* why = nullptr;
+    if (!list || !buf || checkInstanceLists(list, nullptr, count, n_, &why) != 0) return fail(FX_E_ARG, why ? why : "instances: a null list or buffer");
+    if (c_.low.tramOpsPerSample == 0) return 0;   // (no delay-line instruction runs: the positions never move and nothing reads them)
+    waitLastLaunch();
+    std::vector<uint32_t> cur((size_t)4 * (size_t)n_);
+    const hipError_t e = hipMemcpy2D(cur.data(), (size_t)n_ * 4, dState_ + (size_t)stateLayout_.cursorBase * nPad_, (size_t)nPad_ * 4, (size_t)n_ * 4, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hipFail(e, "instances: reading the delay-line positions");
+    const size_t W = (size_t)stateRows_ + (size_t)iSlotsAlloc_ + (size_t)xSlotsAlloc_;
+    for (int64_t k = 0; k < count; ++k) {
+        const uint32_t* rec = buf + (size_t)(pos ? pos[k] : k) * W + (size_t)stateLayout_.cursorBase;
+        for (int j = 0; j < 4; ++j)
+            if (rec[j] != cur[(size_t)j * (size_t)n_ + (size_t)list[k]])
+                return fail(FX_E_ARG, "load_instances: a record's delay-line positions differ from those of its destination (the handles have not run the same number of samples)");
+    }
+    return 0;
+}
+
+void Batch::promoteLoaded(const uint32_t* buf, int64_t total) {
+    const size_t W = (size_t)stateRows_ + (size_t)iSlotsAlloc_ + (size_t)xSlotsAlloc_;
+    for (int r = 0; r < stateLayout_.nRegs; ++r) {
+        if (tracked(r) || intrinsicLane(r)) continue;
+        const uint32_t held = bitsOf(hostValue_[(size_t)r]);
+        bool differs = false;
+        for (int64_t k = 0; k < total && !differs; ++k) differs = buf[(size_t)k * W + (size_t)r] != held;
+        if (!differs) continue;
+        // as if setRegisterAt had written it (the row is valid for every other instance: setRegister's invariant)
+        if (coldControl(r)) coldSetChanged();
+        if (!forcedLane_[(size_t)r] && readByProgram(r)) { forcedLane_[(size_t)r] = 1; lowDirty_ = true; }
+        laneWritten_[(size_t)r] = 1;
+    }
+}
+
+}  // namespace fx

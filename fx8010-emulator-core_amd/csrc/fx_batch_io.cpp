@@ -244,6 +244,11 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
     if (nSamples == 0) return 0;
     if (tracksArmed() && !c_.useXlate) return processWithTrackFallback(dIn, dOut, nSamples, stream, pitch);
     hipStream_t s = pick(stream);
+    // (instance calls run on stream_: a block on another stream follows the last of them that may still be running)
+    if (instLaunched_ && s != stream_) {
+        const hipError_t we = hipStreamWaitEvent(s, evInst_, 0);
+        if (we != hipSuccess) return hipFail(we, "waiting for the instance call in front of the block");
+    }
     if (c_.useXlate && !trackRegs_.empty() && (rc = uploadTracks(nSamples, s)) != 0) return rc;
     const bool timed = !(mode & kUntimed);
     hipError_t e = hipSuccess;
@@ -846,6 +851,7 @@ int Batch::sync() {
     hipError_t e = hipStreamSynchronize(stream_);
     if (e == hipSuccess && launched_) e = hipEventSynchronize(ev1_);
     if (e == hipSuccess && busLaunched_) e = hipEventSynchronize(evBus_);   // (the last kernel of a bus block on the caller's stream)
+    if (e == hipSuccess && instLaunched_ && (e = hipEventSynchronize(evInst_)) == hipSuccess) instLaunched_ = false;
     return e == hipSuccess ? 0 : hipFail(e, "sync");
 }
 

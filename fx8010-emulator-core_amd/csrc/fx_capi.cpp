@@ -246,6 +246,17 @@ int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->b
 int64_t fxb_state_size(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.stateBytes(); }) : FX_E_ARG; }
 int fxb_save_state(fxb_handle* h, void* buf, int64_t cap) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.saveState(buf, cap); }) : FX_E_ARG; }
 int fxb_load_state(fxb_handle* h, const void* buf, int64_t bytes) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.loadState(buf, bytes); }) : FX_E_ARG; }
+int64_t fxb_instance_image_size(fxb_handle* h, int64_t count) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.instanceImageBytes(count); }) : FX_E_ARG; }
+int fxb_copy_instances(fxb_handle* h, const int64_t* src, const int64_t* dst, int64_t count) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.copyInstances(src, dst, count); }) : FX_E_ARG;
+}
+int fxb_reset_instances(fxb_handle* h, const int64_t* list, int64_t count) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.resetInstances(list, count); }) : FX_E_ARG; }
+int fxb_save_instances(fxb_handle* h, const int64_t* list, int64_t count, void* buf, int64_t cap) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.saveInstances(list, count, buf, cap); }) : FX_E_ARG;
+}
+int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.loadInstances(list, count, buf, bytes); }) : FX_E_ARG;
+}
 int fxb_get_tram_i(fxb_handle* h, int which, int64_t inst, float* out, int n_slots) {
     return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.getTramAt(which, inst, out, n_slots); }) : FX_E_ARG;
 }

@@ -77,6 +77,7 @@ Sharded::~Sharded() {
     // caller's current device is restored afterwards (found by the stand-in's multi-device scenario, tests/hipstub)
     DeviceGuard guard;
     shards_.clear();
+    if (hStage_ && hipHostFree(hStage_) != hipSuccess) (void)hipGetLastError();
 }
 
 void Sharded::loop(Worker* w) {
@@ -401,6 +402,138 @@ int Sharded::loadState(const void* buf, int64_t bytes) {
     }
     return fan([&](int k, Batch& b) { return b.loadStateColumns(static_cast<const uint8_t*>(buf), hdr, shards_[(size_t)k]->first); });
 }
+
+// ---- per-instance state calls -----------------------------------------------------------------------------------------------------
+std::vector<Sharded::ListPart> Sharded::splitList(const int64_t* list, int64_t count) const {
+    std::vector<ListPart> parts(shards_.size());
+    for (int64_t k = 0; k < count; ++k) {
+        const int s = shardOf(list[k]);   // (the list has been checked: every entry has a shard)
+        parts[(size_t)s].list.push_back(list[k] - shards_[(size_t)s]->first);
+        parts[(size_t)s].pos.push_back(k);
+    }
+    return parts;
+}
+
+int64_t Sharded::instanceImageBytes(int64_t count) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (count < 0 || count >= ((int64_t)1 << 31)) { lastError_ = "instance image: count out of range"; return FX_E_ARG; }
+    Batch::SnapshotHeader hdr;
+    const int rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, count); });
+    if (rc != 0) return rc;
+    return (int64_t)sizeof(hdr) + count * Batch::instanceWords(hdr) * 4;
+}
+
+int Sharded::copyInstances(const int64_t* src, const int64_t* dst, int64_t count) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* why = nullptr;
+    if (count > 0 && (!src || !dst)) { lastError_ = "instances: a null list"; return FX_E_ARG; }
+    if (Batch::checkInstanceLists(src, dst, count, n_, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.copyInstances(src, dst, count); });
+    // pairs inside a shard: local lists for that shard; the others: (source shard, local source, destination shard, local destination)
+    struct Pairs { std::vector<int64_t> src, dst; };
+    std::vector<Pairs> inside(shards_.size());
+    struct Cross { int from, to; int64_t src, dst; };
+    std::vector<Cross> cross;
+    for (int64_t k = 0; k < count; ++k) {
+        const int f = shardOf(src[k]), t = shardOf(dst[k]);
+        const int64_t ls = src[k] - shards_[(size_t)f]->first, ld = dst[k] - shards_[(size_t)t]->first;
+        if (f == t) { inside[(size_t)f].src.push_back(ls); inside[(size_t)f].dst.push_back(ld); }
+        else cross.push_back({f, t, ls, ld});
+    }
+    // (by source shard, then by destination shard: a shard's records are runs of the staging block, one copy each)
+    std::stable_sort(cross.begin(), cross.end(), [](const Cross& a, const Cross& b) { return a.from != b.from ? a.from < b.from : a.to < b.to; });
+    int rc = fan([&](int k, Batch& b) { return b.copyInstances(inside[(size_t)k].src.data(), inside[(size_t)k].dst.data(), (int64_t)inside[(size_t)k].src.size()); });
+    if (rc != 0 || cross.empty()) return rc;
+    Batch::SnapshotHeader hdr;
+    if ((rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, 0); })) != 0) return rc;
+    const size_t W = (size_t)Batch::instanceWords(hdr), chunk = std::max<size_t>(kStageBytes / (W * 4), 1);
+    const size_t want = std::min(chunk, cross.size()) * W;
+    if (want > stageWords_) {
+        if (hStage_ && hipHostFree(hStage_) != hipSuccess) (void)hipGetLastError();
+        hStage_ = nullptr;
+        stageWords_ = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&hStage_), want * 4, hipHostMallocPortable) != hipSuccess) {
+            (void)hipGetLastError();
+            hStage_ = nullptr;
+            lastError_ = "copy_instances: no pinned staging for the pairs that cross shards";
+            return FX_E_MEMORY;
+        }
+        stageWords_ = want;
+    }
+    for (size_t c0 = 0; c0 < cross.size() && rc == 0; c0 += chunk) {
+        const size_t m = std::min(chunk, cross.size() - c0);
+        std::vector<ListPart> from(shards_.size()), to(shards_.size());
+        for (size_t k = 0; k < m; ++k) {
+            const Cross& x = cross[c0 + k];
+            from[(size_t)x.from].list.push_back(x.src); from[(size_t)x.from].pos.push_back((int64_t)k);
+            to[(size_t)x.to].list.push_back(x.dst); to[(size_t)x.to].pos.push_back((int64_t)k);
+        }
+        // every gather of the chunk has finished (fan waits for all shards) before a scatter starts
+        rc = fan([&](int k, Batch& b) { return b.gatherRecords(from[(size_t)k].list.data(), from[(size_t)k].pos.data(), (int64_t)from[(size_t)k].list.size(), hStage_); });
+        if (rc == 0) rc = fan([&](int k, Batch& b) { return b.scatterRecords(to[(size_t)k].list.data(), to[(size_t)k].pos.data(), (int64_t)to[(size_t)k].list.size(), hStage_); });
+    }
+    return rc;
+}
+
+int Sharded::resetInstances(const int64_t* list, int64_t count) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* why = nullptr;
+    if (count > 0 && !list) { lastError_ = "instances: a null list"; return FX_E_ARG; }
+    if (Batch::checkInstanceLists(nullptr, list, count, n_, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.resetInstances(list, count); });
+    const std::vector<ListPart> parts = splitList(list, count);
+    return fan([&](int k, Batch& b) { return b.resetInstances(parts[(size_t)k].list.data(), (int64_t)parts[(size_t)k].list.size()); });
+}
+
+int Sharded::saveInstances(const int64_t* list, int64_t count, void* buf, int64_t cap) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* why = nullptr;
+    if (count > 0 && !list) { lastError_ = "instances: a null list"; return FX_E_ARG; }
+    if (Batch::checkInstanceLists(list, nullptr, count, n_, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    Batch::SnapshotHeader hdr;
+    int rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, count); });
+    if (rc != 0) return rc;
+    if (count == 0 && (!buf || cap < (int64_t)sizeof(hdr))) return 0;   // (nothing to save; a buffer that holds a header gets one)
+    if (!buf || cap < (int64_t)sizeof(hdr) + count * Batch::instanceWords(hdr) * 4) { lastError_ = "save_instances: buffer smaller than fxb_instance_image_size()"; return FX_E_ARG; }
+    std::memcpy(buf, &hdr, sizeof(hdr));
+    uint32_t* records = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + sizeof(hdr));
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.gatherRecords(list, nullptr, count, records); });
+    const std::vector<ListPart> parts = splitList(list, count);
+    return fan([&](int k, Batch& b) { return b.gatherRecords(parts[(size_t)k].list.data(), parts[(size_t)k].pos.data(), (int64_t)parts[(size_t)k].list.size(), records); });
+}
+
+int Sharded::loadInstances(const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* why = nullptr;
+    if (count > 0 && !list) { lastError_ = "instances: a null list"; return FX_E_ARG; }
+    if (Batch::checkInstanceLists(nullptr, list, count, n_, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    Batch::SnapshotHeader hdr;
+    if (count == 0) return runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, 0); });   // (nothing to load; FX_E_NOTREADY without a program)
+    if (!buf || bytes < (int64_t)sizeof(hdr)) { lastError_ = "load_instances: no image"; return FX_E_ARG; }
+    std::memcpy(&hdr, buf, sizeof(hdr));
+    int rc = runOn(0, [&](Batch& b) { return b.checkInstanceImage(hdr, count, bytes); });
+    if (rc != 0 || count == 0) return rc;
+    const uint32_t* records = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf) + sizeof(hdr));
+    const bool one = shards_.size() == 1;
+    std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    // the delay-line rule on every shard before any shard changes a word
+    rc = fan([&](int k, Batch& b) { return b.checkRecordCursors(listOf(k), posOf(k), countOf(k), records); });
+    if (rc != 0) return rc;
+    return fan([&](int k, Batch& b) {
+        const int r = b.scatterRecords(listOf(k), posOf(k), countOf(k), records);
+        if (r == 0) b.promoteLoaded(records, count);
+        return r;
+    });
+}
+
 int Sharded::getTramAt(int which, int64_t inst, float* out, int nSlots) {
     Serial serial(api_);
     lastError_.clear();
@@ -431,7 +564,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_IMAJOR_BLOCKS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

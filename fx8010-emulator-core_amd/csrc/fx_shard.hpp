@@ -87,6 +87,15 @@ public:
     int64_t stateBytes();
     int saveState(void* buf, int64_t cap);
     int loadState(const void* buf, int64_t bytes);
+    // per-instance state calls (Batch "Per-instance state calls"): the lists hold GLOBAL instance numbers and are checked for the
+    // whole batch before any shard is posted, then split by shard.  Pairs of a copy inside one shard run on that shard's thread
+    // and stream (stream-ordered); a pair that crosses shards goes gather -> pinned staging of the library -> scatter, in chunks
+    // of the staging block, every chunk's gathers finished before its scatters start: such a call blocks.
+    int64_t instanceImageBytes(int64_t count);
+    int copyInstances(const int64_t* src, const int64_t* dst, int64_t count);
+    int resetInstances(const int64_t* list, int64_t count);
+    int saveInstances(const int64_t* list, int64_t count, void* buf, int64_t cap);
+    int loadInstances(const int64_t* list, int64_t count, const void* buf, int64_t bytes);
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
 
@@ -111,6 +120,12 @@ private:
         int result = 0;
     };
     int shardOf(int64_t inst) const;
+    // a global list by shard: per shard the local instance numbers and, for each, its index in the caller's list
+    struct ListPart { std::vector<int64_t> list, pos; };
+    std::vector<ListPart> splitList(const int64_t* list, int64_t count) const;
+    static constexpr size_t kStageBytes = (size_t)64 << 20;
+    uint32_t* hStage_ = nullptr;   // pinned (portable) staging of cross-shard copies, allocated on first use and kept
+    size_t stageWords_ = 0;
     // run f(k, batch) on every shard's thread, wait for all; returns the first non-zero result (shard order)
     int fan(const std::function<int(int, Batch&)>& f);
     // run f(batch) on shard k's thread and wait (a single shard: inline, caller's device restored)

@@ -238,6 +238,27 @@ public:
         if (s < 0) throw std::runtime_error(std::string("FX8010Batch::meterSamples: ") + fxb_last_error(h_));
         return s;
     }
+    // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
+    // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
+    // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and
+    // reset are stream-ordered (sync() covers them), save and load synchronous.
+    void copyInstances(const std::vector<int64_t>& src, const std::vector<int64_t>& dst) {
+        if (src.size() != dst.size()) throw std::runtime_error("FX8010Batch::copyInstances: lists of different length");
+        if (fxb_copy_instances(h_, src.data(), dst.data(), (int64_t)src.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::copyInstances: ") + fxb_last_error(h_));
+    }
+    void resetInstances(const std::vector<int64_t>& list) {
+        if (fxb_reset_instances(h_, list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::resetInstances: ") + fxb_last_error(h_));
+    }
+    std::vector<uint8_t> saveInstances(const std::vector<int64_t>& list) {
+        const int64_t bytes = fxb_instance_image_size(h_, (int64_t)list.size());
+        if (bytes < 0) throw std::runtime_error(std::string("FX8010Batch::saveInstances: ") + fxb_last_error(h_));
+        std::vector<uint8_t> image((size_t)bytes);
+        if (fxb_save_instances(h_, list.data(), (int64_t)list.size(), image.data(), bytes) < 0) throw std::runtime_error(std::string("FX8010Batch::saveInstances: ") + fxb_last_error(h_));
+        return image;
+    }
+    void loadInstances(const std::vector<int64_t>& list, const std::vector<uint8_t>& image) {
+        if (fxb_load_instances(h_, list.data(), (int64_t)list.size(), image.data(), (int64_t)image.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::loadInstances: ") + fxb_last_error(h_));
+    }
     // generate the code for blocks of nSamples samples now, not in the first process call (callers with a deadline per block)
     void prepare(int nSamples, bool wait = true) {
         if (fxb_prepare(h_, nSamples, wait ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::prepare: ") + fxb_last_error(h_));

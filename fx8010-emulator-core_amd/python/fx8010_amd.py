@@ -25,6 +25,7 @@ INFO = {
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
+    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -39,6 +40,7 @@ SYMBOLS = [
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
+    "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
@@ -94,6 +96,8 @@ def load():
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
+    sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
+    sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
@@ -388,6 +392,47 @@ class Batch(_Reports):
     def load_state(self, image):
         image = np.ascontiguousarray(image, dtype=np.uint8)
         return self._check(self._lib.fxb_load_state(self._h, image.ctypes.data_as(C.c_void_p), image.size), "load_state")
+
+    # ---- per-instance state (include/fx8010_amd.h "Per-instance state"): lists of global instance numbers
+    @property
+    def instance_words(self):
+        """W: 32-bit words of one instance's record (state rows, then iTRAM slots, then xTRAM slots)"""
+        return self.info("instance_words")
+
+    @staticmethod
+    def _instance_list(v):
+        return np.ascontiguousarray(np.atleast_1d(np.asarray(v)), dtype=np.int64)
+
+    def instance_image_size(self, count):
+        n = int(self._lib.fxb_instance_image_size(self._h, int(count)))
+        if n < 0:
+            raise RuntimeError("instance_image_size failed (%d): %s" % (n, self.last_error()))
+        return n
+
+    def copy_instances(self, src, dst):
+        """instance dst[k] becomes a bit-for-bit copy of src[k] (a source may repeat); stream-ordered, sync() covers it"""
+        src, dst = self._instance_list(src), self._instance_list(dst)
+        if src.size != dst.size:
+            raise ValueError("copy_instances: src and dst must have the same length")
+        return self._check(self._lib.fxb_copy_instances(self._h, C.c_void_p(src.ctypes.data), C.c_void_p(dst.ctypes.data), src.size), "copy_instances")
+
+    def reset_instances(self, instances):
+        """the listed instances take the state of freshly created ones; the delay-line positions are kept; stream-ordered"""
+        v = self._instance_list(instances)
+        return self._check(self._lib.fxb_reset_instances(self._h, C.c_void_p(v.ctypes.data), v.size), "reset_instances")
+
+    def save_instances(self, instances):
+        """an instance image (numpy uint8): a 64-byte header, then one record of instance_words words per listed instance"""
+        v = self._instance_list(instances)
+        buf = np.empty(self.instance_image_size(v.size), dtype=np.uint8)
+        self._check(self._lib.fxb_save_instances(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(buf.ctypes.data), buf.size), "save_instances")
+        return buf
+
+    def load_instances(self, instances, image):
+        """the records of an instance image into the listed instances of this handle (same program and options)"""
+        v = self._instance_list(instances)
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        return self._check(self._lib.fxb_load_instances(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(image.ctypes.data), image.size), "load_instances")
 
     def get_tram_i(self, which, inst, n_slots):
         out = np.empty(n_slots, dtype=np.float32)

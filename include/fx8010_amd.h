@@ -187,6 +187,46 @@ int fxb_prepare(fxb_handle* h, int n_samples, int wait);
 int64_t fxb_state_size(fxb_handle* h);
 int fxb_save_state(fxb_handle* h, void* buf, int64_t cap);
 int fxb_load_state(fxb_handle* h, const void* buf, int64_t bytes);
+/* Per-instance state: copy, reset, save and load by list.  For a host that treats instances as voices or sweep points: restart a
+ * voice, fork a running instance into variants, move a few voices to another handle or GPU, checkpoint the instances it cares
+ * about - without the whole-batch image above.  The state of one instance is a RECORD of W = fxb_info(h, FXB_INFO_INSTANCE_WORDS)
+ * 32-bit words: the state rows in the order of the whole-batch image (registers, output latches, the four delay-line positions,
+ * LFSR words, flags, counter), then the iTRAM slots, then the xTRAM slots - exactly the words fxb_save_state holds for that
+ * instance.  An INSTANCE IMAGE is a 64-byte header (the whole-batch header with a magic of its own and the number of records) and
+ * `count` records back to back: fxb_instance_image_size(h, count) bytes (FX_E_* below 0).  Lists hold global instance numbers
+ * 0..N-1 on any handle, sharded ones included; they are copied before a call returns.  Two HIP kernels move the words as bit
+ * patterns (NaN payloads survive) between the transposed state blocks and packed records; records beyond a 64 MiB scratch go in
+ * pieces.  All four calls are ordered behind every block queued on the handle so far, on whichever stream, and in front of every
+ * later block; they leave meters, armed control tracks and the FXB_INFO_*_BLOCKS counters alone.  FXB_INFO_INSTANCE_GATHERS /
+ * _SCATTERS count the kernels' launches.
+ *
+ * fxb_copy_instances: instance dst[k] becomes a bit-for-bit copy of src[k] - every state row and all delay memory.  A source may
+ *   repeat (fan-out); a destination may neither repeat nor appear among the sources.  Stream-ordered: it may return before it has
+ *   run, fxb_sync covers it.  On a sharded handle a pair that crosses shards goes through pinned host memory and the call blocks.
+ *   What the host knows about the registers does not change (a register it holds as one value is equal in src and dst already).
+ * fxb_reset_instances: every listed instance takes the state of a freshly created one - registers at the value of the last
+ *   broadcast fxb_set_register (the program's initial value if there was none; per-instance writes to that instance are gone),
+ *   latches 0, the LFSR at the reference's seeds, flags 0, counter 0, delay memory 0 - EXCEPT the four delay-line positions, which
+ *   are kept.  Translated code keeps the positions of a program whose delay-line instructions all run unconditionally in scalar
+ *   registers, one set for the wavefront: all instances of such a batch must agree on them.  Kept positions are also what the
+ *   signal needs: where every sample period makes as many reads as writes at offset 0 (every program under programs/) only the
+ *   distance between the positions matters, and a reset instance produces exactly the outputs of a fresh reference object.  For any
+ *   other program the result is "a fresh object whose positions were set to these".  Stream-ordered like the copy.
+ * fxb_save_instances: the records of the listed instances (repeats allowed), in list order, behind the header.  Synchronous.
+ * fxb_load_instances: the inverse, into any handle with the same program and options - instance count, instance numbers and the
+ *   partition into shards may all differ.  Delay-line rule: if the program executes delay-line instructions, the four position
+ *   words of every record must equal those its destination holds now, else FX_E_ARG and nothing changes; handles that have run the
+ *   same number of samples of the same program satisfy it (migration between handles or GPUs, undo before further processing).
+ *   Rotating delay memory to another position is out of scope.  A register the host held as one value and that a record holds
+ *   another value of becomes per-instance, as if fxb_set_register_i had written it.  Synchronous.
+ * 0, FX_E_NOTREADY without a program, or FX_E_ARG with nothing launched and nothing changed: count < 0, a null list with
+ * count > 0, an instance outside 0..N-1, a repeated destination, a destination among the sources, a short buffer, an image of
+ * another program, kind or version.  count == 0 returns 0. */
+int64_t fxb_instance_image_size(fxb_handle* h, int64_t count);
+int fxb_copy_instances(fxb_handle* h, const int64_t* src, const int64_t* dst, int64_t count);
+int fxb_reset_instances(fxb_handle* h, const int64_t* list, int64_t count);
+int fxb_save_instances(fxb_handle* h, const int64_t* list, int64_t count, void* buf, int64_t cap);
+int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes);
 /* one instance's delay memory as the reference holds it (which: 0 = smallDelayBuffer / iTRAM, 1 = largeDelayBuffer / xTRAM; the first
  * n_slots words; words the program cannot reach read 0) and its positions {iTRAM write, iTRAM read, xTRAM write, xTRAM read}
  * (reference smallDelayWritePos ... largeDelayReadPos, include/FX8010.h:214-217) */
@@ -391,7 +431,10 @@ enum {
     FXB_INFO_HOST_INPLACE_BLOCKS = 34, /* host blocks processed on the caller's pinned buffers in place (summed over shards) */
     FXB_INFO_BUS_BLOCKS = 35,          /* bus blocks (fxb_process_block_bus* with a flag set) since creation (summed over shards) */
     FXB_INFO_METER_LAUNCHES = 36,      /* launches of the output-meter kernel (fxb_meter_enable) since creation (summed over shards) */
-    FXB_INFO_IMAJOR_BLOCKS = 37        /* instance-major blocks since creation (summed over shards) */
+    FXB_INFO_IMAJOR_BLOCKS = 37,       /* instance-major blocks since creation (summed over shards) */
+    FXB_INFO_INSTANCE_WORDS = 38,      /* W: 32-bit words of one instance's record (state rows + iTRAM slots + xTRAM slots) */
+    FXB_INFO_INSTANCE_GATHERS = 39,    /* launches of the kernel fx_inst_gather - by fxb_copy_instances and fxb_save_instances - since creation (summed over shards) */
+    FXB_INFO_INSTANCE_SCATTERS = 40    /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
