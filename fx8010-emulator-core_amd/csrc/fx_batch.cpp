@@ -76,6 +76,10 @@ Batch::~Batch() {
     (void)hipFree(dBus_);
     (void)hipFree(dBusStage_);
     (void)hipFree(dMeter_);
+    (void)hipFree(dGain_[0]);
+    (void)hipFree(dGain_[1]);
+    if (hGain_) (void)hipHostFree(hGain_);
+    if (evGain_) (void)hipEventDestroy(evGain_);
     (void)hipFree(dInstList_);
     (void)hipFree(dInstRec_);
     if (hInstList_) (void)hipHostFree(hInstList_);
@@ -838,6 +842,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_HOST_INPLACE_BLOCKS) return hostInplaceBlocks_;
     if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
     if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
+    if (what == FXB_INFO_BUS_GAIN_BLOCKS) return busGainBlocks_;
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;

@@ -78,6 +78,18 @@ public:
     // of 0 becomes the run
     static int checkImajorShape(const float* in, const float* out, int nSamples, int channels, int64_t n, int64_t* inStride, int64_t* outStride, const char** why);
     int sync();
+    // Bus gains (fx_bus.hpp BusGainArgs; include/fx8010_amd.h "Bus gains"): a mode of the handle.  While it is on, the mix of a bus
+    // block with kBusMixOut is launchBusMixGain.  `gains` is [channels][rowPitch] with this batch's instances in columns 0..n-1
+    // (rowPitch 0 = n), copied through pinned memory of the library; null turns the mode off (waits, frees).  busReserveGains is the
+    // allocating half (everything the mode ever needs: FX_E_MEMORY changes nothing), called by busSetGains itself and, for
+    // all-or-nothing over shards, by Sharded in front of it; busReleaseGains frees what a failed attempt left on a handle whose
+    // gains are off.  checked: the caller has found every value finite.  busGetGains is synchronous like meterRead.
+    int busReserveGains();
+    void busReleaseGains();
+    int busSetGains(const float* gains, int64_t rowPitch, int ramp, bool checked = false);
+    int busGetGains(float* gains, int64_t rowPitch = 0);
+    bool busGainsOn() const { return gainsOn_; }
+    static bool gainsFinite(const float* gains, int channels, int64_t n, int64_t rowPitch);
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -444,6 +456,19 @@ private:
     hipEvent_t evBus_ = nullptr;    // behind the last kernel of the most recent bus block
     bool busLaunched_ = false;
     int64_t busBlocks_ = 0;         // FXB_INFO_BUS_BLOCKS
+    // bus gains (fx_batch_bus_gain.cpp): two blocks [channels][n], one of them the target b, the other the current set a.  a is
+    // only meaningful while a ramp is pending: without one a counts as equal to b and its block holds stale words, so consuming
+    // a ramp costs nothing on the device, and the next ramp makes the old target the current set by swapping the two roles.
+    // Every write of a block is a copy on the handle's stream behind evBus_ (a block queued on whatever stream keeps the gains it
+    // was queued with) and in front of evGain_ (a later block on whatever stream waits for it).
+    float* dGain_[2] = {nullptr, nullptr};
+    int gainTarget_ = 0;            // which of the two is b
+    bool gainsOn_ = false, gainRampPending_ = false;
+    float* hGain_ = nullptr;        // pinned staging: the caller's columns, and the 1.0f block of a ramp out of "off"
+    hipEvent_t evGain_ = nullptr;   // behind the most recent copy into a gain block
+    bool gainCopied_ = false;       // ... which may still be running
+    int64_t busGainBlocks_ = 0;     // FXB_INFO_BUS_GAIN_BLOCKS
+    size_t gainFloats() const { return (size_t)prog_.numChannels * (size_t)n_; }
     const float* busCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one
     const float* busCheckedOut_ = nullptr;
     size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;

@@ -576,6 +576,22 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         const hipError_t we = hipStreamWaitEvent(s, evBus_, 0);
         if (we != hipSuccess) return hipFail(we, "bus: waiting for the previous bus block");
     }
+    // ... and with gains on, the most recent copy into a gain block (on the handle's stream) must have landed
+    const bool weighted = (flags & kBusMixOut) && gainsOn_;
+    if (weighted && gainCopied_) {
+        const hipError_t we = hipStreamWaitEvent(s, evGain_, 0);
+        if (we != hipSuccess) return hipFail(we, "bus: waiting for the gains");
+    }
+    BusGainArgs gain{};
+    if (weighted) {
+        gain.target = dGain_[gainTarget_];
+        gain.current = gainRampPending_ ? dGain_[gainTarget_ ^ 1] : nullptr;
+        gain.gainPitch = n_;
+        gain.channels = prog_.numChannels;
+        gain.ramp = gainRampPending_ ? 1 : 0;
+        gain.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
+        gain.samples = nSamples;
+    }
     beginBlock(nSamples, pieces);   // ONE block to the bookkeeping of control changes and to the lowering
     if ((rc = ensureLowered()) != 0) return rc;
     auto lo = [&](int p) { return (int)((int64_t)nSamples * p / pieces); };
@@ -606,7 +622,8 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
             a.narrowIn = nullptr;
             a.narrowOut = narrowOut + first * (size_t)narrowOutPitch;
             a.narrowPitch = narrowOutPitch;
-            e = launchBusMix(a, s);
+            gain.sample0 = lo(p);
+            e = weighted ? launchBusMixGain(a, gain, s) : launchBusMix(a, s);
         } else {
             e = copyRows(out + first * (size_t)shape.outPitch, (size_t)shape.outPitch * 4, dBus_, width, width, (size_t)a.rows, hipMemcpyDefault, s);
         }
@@ -615,6 +632,10 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         busLaunched_ = true;
     }
     ++busBlocks_;   // (blocks whose every piece was queued)
+    if (weighted) {
+        ++busGainBlocks_;
+        gainRampPending_ = false;   // consumed: a counts as b from here on (fx_batch.hpp)
+    }
     return 0;
 }
 

@@ -1,5 +1,5 @@
-// fx_bus.hip — the two kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
-// per-instance scratch, mix the scratch down to one word per group.  gfx950, wave64, one wavefront per workgroup.  The narrow side,
+// fx_bus.hip — the kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
+// per-instance scratch, mix the scratch down to one word per group - plain (fx_bus_mix) or with per-instance gains (fx_bus_mix_gain).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
 // which may be pinned host memory behind PCIe, sees exactly one 256-byte access per wavefront and row.  The wide side: the expand
 // stores 1 KiB per wavefront access; the mix loads 256 contiguous bytes per access for groups of 64 instances and more, and ONE
 // PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
@@ -124,6 +124,98 @@ __global__ __launch_bounds__(64) void fx_bus_mix(BusArgs a) {
     }
 }
 
+// ---- the weighted mix (fx_bus.hpp BusGainArgs): fx_bus_mix with every member multiplied by its weight first --------------------
+//
+// Same geometry, same loads of y, same trees, same one 256-byte store per row; a gain word is loaded beside every y word, with
+// the same lane addressing (gain[c][first + lane]: 256 contiguous bytes per access for K >= 64, one partial access per short
+// group).  The gain words of a wavefront's groups do not depend on the sample, but a workgroup handles ONE row unless a block has
+// more than 65 535 of them (grid.y = rows), so there is nothing to keep in registers across rows: every row re-reads its gains,
+// [C][n] words that 2 * S rows share and the L2 / Infinity Cache hold.  kRamp = false loads the target block only.
+//
+// The weight: (b - a), * t, a + ... and w * y are four roundings (the file is built with -ffp-contract=off); the mute is a
+// select on w in front of the add, so a NaN or Inf of a muted member never reaches the sum.
+template <bool kRamp>
+__device__ __forceinline__ float weightOf(float a, float b, float t, bool atTarget) {
+    if (!kRamp) return b;
+    const float d = b - a;
+    const float m = d * t;
+    const float w = a + m;
+    return atTarget ? b : w;
+}
+
+__device__ __forceinline__ float termOf(float w, float y) {
+    const float prod = w * y;
+    return w == 0.0f ? 0.0f : prod;
+}
+
+template <bool kRamp>
+__global__ __launch_bounds__(64) void fx_bus_mix_gain(BusArgs a, BusGainArgs g) {
+    const unsigned lane = threadIdx.x;
+    const long long K = a.group;
+    const long long g0 = (long long)blockIdx.x * 64;
+    const int here = (int)(a.groups - g0 < 64 ? a.groups - g0 : 64);
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        const float* y = a.wide + row * a.n;
+        const long long s = row / g.channels + g.sample0;              // the sample of the CALL this row belongs to
+        const long long gainRow = (row % g.channels) * g.gainPitch;    // its channel's row of the gain blocks
+        const float t = (float)(s + 1) * g.r;
+        const bool atTarget = s == (long long)g.samples - 1;
+        float res = 0.0f;
+        if (K <= 64) {
+            for (int k0 = 0; k0 < here; k0 += 8) {
+                // (all loads of the eight groups are issued before the first weight is computed)
+                float v[8], ga[8], gb[8];
+                bool have[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const long long first = (g0 + k0 + u) * K;
+                    const long long count = a.n - first < K ? a.n - first : K;
+                    have[u] = k0 + u < here && (long long)lane < count;
+                    v[u] = ga[u] = gb[u] = 0.0f;
+                    if (have[u]) {
+                        v[u] = y[first + lane];
+                        gb[u] = g.target[gainRow + first + lane];
+                        if (kRamp) ga[u] = g.current[gainRow + first + lane];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    float p = 0.0f;
+                    p = have[u] ? p + termOf(weightOf<kRamp>(ga[u], gb[u], t, atTarget), v[u]) : p;
+                    const float sum = treeSum(p);
+                    if ((int)lane == k0 + u) res = sum;
+                }
+            }
+        } else {
+            for (int k = 0; k < here; ++k) {
+                const long long first = (g0 + k) * K;
+                const long long count = a.n - first < K ? a.n - first : K;
+                float p = 0.0f;
+                for (long long m0 = 0; m0 < count; m0 += 256) {
+                    float v[4], ga[4], gb[4];
+                    bool have[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const long long m = m0 + u * 64 + lane;
+                        have[u] = m < count;
+                        v[u] = ga[u] = gb[u] = 0.0f;
+                        if (have[u]) {   // 256 contiguous bytes per load, of y and of each gain block
+                            v[u] = y[first + m];
+                            gb[u] = g.target[gainRow + first + m];
+                            if (kRamp) ga[u] = g.current[gainRow + first + m];
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) p = have[u] ? p + termOf(weightOf<kRamp>(ga[u], gb[u], t, atTarget), v[u]) : p;
+                }
+                const float sum = treeSum(p);
+                if ((int)lane == k) res = sum;
+            }
+        }
+        if ((int)lane < here) a.narrowOut[row * a.narrowPitch + g0 + lane] = res;
+    }
+}
+
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
 }  // namespace
@@ -147,6 +239,20 @@ hipError_t launchBusMix(const BusArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)blocks, (unsigned)(a.rows < 65535 ? a.rows : 65535));
     (void)hipGetLastError();
     hipLaunchKernelGGL(fx_bus_mix, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t stream) {
+    if (badArgs(a) || !a.narrowOut) return hipErrorInvalidValue;
+    if (!g.target || (g.ramp && !g.current) || g.channels < 1 || a.rows % g.channels != 0 || g.gainPitch < a.n || g.samples < 1 || g.sample0 < 0 ||
+        (long long)g.sample0 + a.rows / g.channels > (long long)g.samples)
+        return hipErrorInvalidValue;
+    const long long blocks = (a.groups + 63) / 64;
+    if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks, (unsigned)(a.rows < 65535 ? a.rows : 65535));
+    (void)hipGetLastError();
+    if (g.ramp) hipLaunchKernelGGL(fx_bus_mix_gain<true>, grid, dim3(64), 0, stream, a, g);
+    else hipLaunchKernelGGL(fx_bus_mix_gain<false>, grid, dim3(64), 0, stream, a, g);
     return hipGetLastError();
 }
 

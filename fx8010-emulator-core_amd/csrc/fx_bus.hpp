@@ -1,4 +1,4 @@
-// fx_bus.hpp — launch interface of the two group-bus kernels (device code: fx_bus.hip).
+// fx_bus.hpp — launch interface of the group-bus kernels (device code: fx_bus.hip).
 //
 // A bus block is a sandwich around the unchanged emulation launch: `expand` writes a per-group input [rows][groups] out to the
 // per-instance scratch [rows][n], the emulation runs on the scratch in place, `mix` reduces the scratch to [rows][groups].
@@ -29,5 +29,21 @@ hipError_t launchBusExpand(const BusArgs& a, hipStream_t stream);
 // group's members m = j*64 + l for j ascending, then p[l] += p[l + step] for step = 32 .. 1 (l < step); the result is p[0].
 // fp32, round to nearest, never fused, denormals kept.
 hipError_t launchBusMix(const BusArgs& a, hipStream_t stream);
+
+// The gains of a weighted mix (include/fx8010_amd.h "Bus gains"): two blocks [channels][gainPitch] by instance, device memory.
+struct BusGainArgs {
+    const float* current;    // a: read only while a ramp is pending (may be null otherwise)
+    const float* target;     // b
+    long long gainPitch;     // floats per channel row of both blocks (>= n)
+    int channels;            // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
+    int ramp;                // 1: a ramp is pending, w = a + (b - a) * ((float)(s + 1) * r) and exactly b at s == samples - 1; 0: w = b
+    float r;                 // 1.0f / (float)samples, divided once on the host
+    int samples;             // S of the caller's block, never a piece's
+    int sample0;             // first sample of this piece within the block
+};
+
+// narrowOut[r][g] = the sum of launchBusMix over the terms (w == 0.0f ? +0.0f : w * wide[r][i]) instead of wide[r][i]: a member
+// with a weight of either zero contributes +0.0f whatever it holds.  (b - a), * t, a + and w * y are rounded one by one.
+hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t stream);
 
 }  // namespace fx

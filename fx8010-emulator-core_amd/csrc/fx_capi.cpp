@@ -230,6 +230,8 @@ int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n, int
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t group, unsigned flags, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
 }
+int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGains(gains, ramp); }) : FX_E_ARG; }
+int fxb_bus_get_gains(fxb_handle* h, float* gains) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busGetGains(gains); }) : FX_E_ARG; }
 int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n, int64_t in_stride, int64_t out_stride) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processImajor(in, out, n, in_stride, out_stride, false, nullptr); }) : FX_E_ARG;
 }

@@ -332,6 +332,28 @@ int64_t Sharded::meterSamples() {
     return s;
 }
 
+int Sharded::busSetGains(const float* gains, int ramp) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (ramp != 0 && ramp != 1) { lastError_ = "bus gains: ramp must be 0 or 1"; return FX_E_ARG; }
+    if (!gains) return fan([](int, Batch& b) { return b.busSetGains(nullptr, 0, 0); });
+    if (!Batch::gainsFinite(gains, front().channels(), n_, n_)) { lastError_ = "bus gains: every gain must be finite"; return FX_E_ARG; }
+    int rc = fan([](int, Batch& b) { return b.busReserveGains(); });
+    if (rc != 0) {
+        const std::string why = lastError();
+        fan([](int, Batch& b) { b.busReleaseGains(); return 0; });   // (a no-op on a shard whose gains are on)
+        lastError_ = why;
+        return rc;
+    }
+    return fan([&](int k, Batch& b) { return b.busSetGains(gains + shards_[(size_t)k]->first, n_, ramp, true); });
+}
+int Sharded::busGetGains(float* gains) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (front().busGainsOn() && !gains) { lastError_ = "null buffer"; return FX_E_ARG; }
+    return fan([&](int k, Batch& b) { return b.busGetGains(gains ? gains + shards_[(size_t)k]->first : nullptr, n_); });
+}
+
 int64_t Sharded::instructionCounter() {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
@@ -564,7 +586,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

@@ -80,6 +80,11 @@ public:
     int meterEnable(bool on);
     int meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
     int64_t meterSamples();
+    // bus gains (Batch::busSetGains ...): `gains` is [channels][all instances] by global instance, checked as a whole (every value
+    // finite) before any shard is posted; every shard reserves its blocks first and only when all of them could is any shard's
+    // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.
+    int busSetGains(const float* gains, int ramp);
+    int busGetGains(float* gains);
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

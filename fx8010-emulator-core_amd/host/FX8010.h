@@ -213,6 +213,16 @@ public:
         const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
         if (fxb_process_block_bus(h_, in, out, nSamples, group, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::processBlockBus: ") + fxb_last_error(h_));
     }
+    // per-instance gains of the mixed output (include/fx8010_amd.h "Bus gains"): gains is [channels][instances], every value finite,
+    // or nullptr for gains off (the unweighted sum); with ramp the next mixing block moves every weight linearly from the gains in
+    // force to these and ends exactly on them.  A gain of zero mutes: that instance adds +0.0f whatever it holds.  busGetGains
+    // fills [channels][instances] with the gains in force and throws while gains are off.
+    void busSetGains(const float* gains, bool ramp = false) {
+        if (fxb_bus_set_gains(h_, gains, ramp ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::busSetGains: ") + fxb_last_error(h_));
+    }
+    void busGetGains(float* gains) {
+        if (fxb_bus_get_gains(h_, gains) < 0) throw std::runtime_error(std::string("FX8010Batch::busGetGains: ") + fxb_last_error(h_));
+    }
     // one interleaved stream per instance (include/fx8010_amd.h fxb_process_block_imajor): instance n's nSamples * channels floats,
     // [sample][channel], at in + n * inStride, its output the same way at out + n * outStride (strides in floats, 0 = packed; a
     // larger one walks a whole file or ring per instance in place).  Host buffers, synchronous; in == out with one stride is fine.

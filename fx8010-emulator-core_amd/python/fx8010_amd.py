@@ -25,7 +25,7 @@ INFO = {
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
-    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40,
+    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -38,7 +38,7 @@ SYMBOLS = [
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
-    "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev",
+    "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
@@ -95,6 +95,7 @@ def load():
     sig("fxb_process_block_pitched", i32, vp, vp, vp, i32, i64); sig("fxb_process_block_dev_pitched", i32, vp, vp, vp, i32, i64, vp)
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
+    sig("fxb_bus_set_gains", i32, vp, vp, i32); sig("fxb_bus_get_gains", i32, vp, vp)
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
@@ -534,6 +535,23 @@ class Batch(_Reports):
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
         return self._check(self._lib.fxb_process_block_bus_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(group), flags, C.c_void_p(stream or 0)),
                            "process_block_bus_dev")
+
+    def bus_set_gains(self, gains, ramp=False):
+        """Per-instance gains of the mixed output of bus blocks (include/fx8010_amd.h "Bus gains").  gains: float32 [channels, N] by
+        global instance, every value finite ([N] for mono), or None: gains off, the unweighted sum.  ramp: the next block with
+        mix_out moves every weight linearly from the gains in force to these, reaching them exactly on its last sample."""
+        if gains is None:
+            return self._check(self._lib.fxb_bus_set_gains(self._h, None, 0), "bus_set_gains")
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        assert g.size == self.channels * self.n, "gains must be [channels, N]"
+        return self._check(self._lib.fxb_bus_set_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_gains")
+
+    def bus_get_gains(self):
+        """float32 [channels, N]: the gains in force - while a ramp waits for its block the ones it will start from, after that
+        block its target.  Synchronous; raises while gains are off."""
+        g = np.empty((self.channels, self.n), dtype=np.float32)
+        self._check(self._lib.fxb_bus_get_gains(self._h, C.c_void_p(g.ctypes.data)), "bus_get_gains")
+        return g
 
     def _stream_stride(self, shape, strides):
         """the instance stride (in floats) when an [N, S, channels] array is N interleaved [S][channels] runs at one stride, else None"""

@@ -284,6 +284,51 @@ int fxb_process_block_dev_shards(fxb_handle* h, const float* const* d_in, float*
 int64_t fxb_bus_groups(fxb_handle* h, int64_t group);   /* G, or FX_E_ARG */
 int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n_samples, int64_t group, unsigned flags);
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n_samples, int64_t group, unsigned flags, void* stream);
+/* Bus gains: a weight per (channel, instance) on the way into the sum of FXB_BUS_MIX_OUT - a level per voice, a pan over the
+ * channels of the bus, a mute - with a ramp over one block.  Gains are a mode of the handle like the meters, off by default: no
+ * flag bit of the block calls is taken, and while they are off the mix is the unweighted sum above, by the same kernel as ever.
+ *
+ * The definition.  The handle holds two sets per (channel c, instance n): the CURRENT gains a and the TARGET b.  While gains are
+ * off, a counts as 1.0f everywhere.
+ *   fxb_bus_set_gains(h, gains, 0)   a = b = gains.
+ *   fxb_bus_set_gains(h, gains, 1)   b = gains, a stays: a ramp is now PENDING.
+ *   A second call before a mixing block replaces b; with ramp = 0 it also cancels the pending ramp.
+ *   The next block with FXB_BUS_MIX_OUT consumes a pending ramp: afterwards a = b.  A block without FXB_BUS_MIX_OUT ignores the
+ *   gains and leaves a pending ramp pending.
+ * For one call of S samples (S is the caller's n_samples, never that of a piece the runtime cuts the block into), the member of
+ * channel c and instance n at sample s (0-based) has the output word y and the weight w, everything in fp32, round to nearest,
+ * never fused, denormals kept:
+ *   no ramp pending:  w = b
+ *   ramp pending:     w = b                      if s == S - 1
+ *                     w = a + (b - a) * t        otherwise, with t = (float)(s + 1) * r and r = 1.0f / (float)S - (b - a), the
+ *                                                product and the sum are three roundings, r is one fp32 division
+ *   term = (w == 0.0f) ? +0.0f : w * y           either sign of zero: a muted member contributes +0.0f whatever y is, NaN and Inf
+ *                                                included
+ * The terms then go through exactly the order of the unweighted sum: 64 partial sums start at +0.0f, member m = j*64 + l, where it
+ * exists, is added to p[l] for j ascending, the step = 32 ... 1 tree follows; members that do not exist are not added.
+ * Consequences:
+ *   Gains of 1.0f everywhere give the words of the unweighted sum.  NaNs stay NaNs; their payload is not promised.
+ *   A ramp is per call: two calls of 16 + 17 samples are not one of 33 while a ramp is pending.  Without one they are.
+ *   The last sample of a ramp block carries exactly b.
+ *   The meters read the per-instance block in front of the mix and are therefore pre-fader: a muted NaN voice still counts in
+ *   `nonfinite`.  That is the intended pairing: fxb_meter_read tells which instance to mute.
+ *
+ * fxb_bus_set_gains: gains is [num_channels][N] by global instance, or NULL = gains off.  ramp is 0 or 1.  Every value must be
+ *   finite, else FX_E_ARG and nothing changes (a bad ramp likewise).  The array is copied through pinned memory of the library and
+ *   is the caller's again on return.  Works before a program is loaded; the gains survive program loads; they are not part of the
+ *   state image or of instance records, and fxb_copy_instances / fxb_reset_instances do not touch them: a gain belongs to the mixer
+ *   slot, not to the voice.  All allocation (two blocks of num_channels * N floats per shard, the staging) happens in this call,
+ *   never inside a block; FX_E_MEMORY leaves the gains as they were on every shard.  NULL waits for the queued blocks and frees;
+ *   if that wait reports a device error, the code is returned and the shard it happened on keeps its gains and their memory (on a
+ *   handle of several shards the others have switched theirs off: after a device error call NULL again or destroy the handle).
+ * Ordering: a block queued on whatever stream keeps the gains it was queued with - a set after it does not disturb it - and a
+ *   later block on whatever stream sees the new gains; fxb_sync covers all of it.  (A set does not wait for the queued block on the
+ *   host; a second set behind the same running block does.)
+ * fxb_bus_get_gains: [num_channels][N], the gains in force - a; after a ramp has been consumed that is its target.  Waits as
+ *   fxb_sync does.  FX_E_ARG while gains are off.
+ * FXB_INFO_BUS_GAIN_BLOCKS counts the bus blocks mixed with gains. */
+int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp);
+int fxb_bus_get_gains(fxb_handle* h, float* gains);
 /* Instance-major blocks: one interleaved stream per instance, transposed on the device.  Instance n's input is the
  * n_samples * num_channels floats at in + n * in_stride, ordered [sample][channel] - what n_samples calls of the reference's
  * process() consume and what a WAV file holds - and its output goes to out + n * out_stride the same way.
@@ -434,7 +479,8 @@ enum {
     FXB_INFO_IMAJOR_BLOCKS = 37,       /* instance-major blocks since creation (summed over shards) */
     FXB_INFO_INSTANCE_WORDS = 38,      /* W: 32-bit words of one instance's record (state rows + iTRAM slots + xTRAM slots) */
     FXB_INFO_INSTANCE_GATHERS = 39,    /* launches of the kernel fx_inst_gather - by fxb_copy_instances and fxb_save_instances - since creation (summed over shards) */
-    FXB_INFO_INSTANCE_SCATTERS = 40    /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
+    FXB_INFO_INSTANCE_SCATTERS = 40,   /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
+    FXB_INFO_BUS_GAIN_BLOCKS = 41      /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -19,6 +19,13 @@ of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel a
    With `--trace-run --meter` the traced stretch runs with meters on, and `--kernel-stats` then also reports the meter kernel
    beside the mix kernel, which reads the same per-instance block.
 
+5. `--gains`: what the per-instance mix gains (fxb_bus_set_gains) cost a real-time host.  At every count of --gain-instances three
+   bus handles take turns in stretches in ONE process: gains off (the plain mix kernel), static gains, and a ramp on every block
+   (a set with ramp = 1 in front of every block, inside the timed region: it is what a mixer host with moving faders pays).
+   Median and p99.9 of the three are reported (`--gains-out FILE.txt` keeps the lines).  Before anything is timed, gains of 1.0f
+   must give the words of gains off.  With `--trace-run --gains` the traced run is the same three handles by turns, 200 blocks
+   each, and `--kernel-stats` reports fx_bus_mix_gain (static and ramping) beside fx_bus_mix.
+
 Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
@@ -58,7 +65,7 @@ def mix_model(y, K):
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus, meter=False):
+    def __init__(self, A, progs, n, bus, meter=False, gains=None):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -74,6 +81,13 @@ class Path:
         self.yp = C.c_void_p(self.out.array.ctypes.data)
         if meter:
             self.b.meter_enable()
+        # gains: None = off, "static" = set once, "ramp" = a set with ramp = 1 in front of every block, between two sets of levels
+        self.gains = gains
+        if gains:
+            level = (0.25 + 0.75 * (progs.stimulus(n, 1, seed=99)[0] * np.float32(0.5) + np.float32(0.5))).astype(np.float32)
+            self.levels = [np.ascontiguousarray(level.reshape(1, n)), np.ascontiguousarray((np.float32(1.25) - level).reshape(1, n))]
+            self.lp = [C.c_void_p(g.ctypes.data) for g in self.levels]
+            self.b.bus_set_gains(self.levels[0])
         self.b.prepare(BLOCK, True)
         self.k = 0
         self.times = []
@@ -82,6 +96,8 @@ class Path:
         k, h = self.k, self.b._h
         if k % SLIDER_EVERY == 0:
             assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
+        if self.gains == "ramp" and self.lib.fxb_bus_set_gains(h, self.lp[(k + 1) % 2], 1) != 0:
+            raise RuntimeError("set_gains in front of block %d failed: %s" % (k, self.b.last_error()))
         if self.bus:
             rc = self.lib.fxb_process_block_bus(h, self.xp[k % RING], self.yp, BLOCK, GROUP, 3)
         else:
@@ -221,6 +237,54 @@ def meter_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: No
     return out
 
 
+GAIN_MODES = (("gains off", None), ("static", "static"), ("ramping", "ramp"))
+
+
+def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None):
+    """bus blocks with gains off, static gains and a ramp on every block by turns, in stretches, in one process"""
+    import numpy as np
+    # gains of 1.0f give the words of gains off
+    off, ones = Path(A, progs, n, True), Path(A, progs, n, True, gains="static")
+    ones.b.bus_set_gains(np.ones((1, n), dtype=np.float32))
+    for _ in range(2):
+        off.block()
+        ones.block()
+        want, got = off.out.array, ones.out.array
+        nan = np.isnan(want)
+        if not ((np.isnan(got) == nan).all() and (got.view(np.uint32)[~nan] == want.view(np.uint32)[~nan]).all()):
+            raise RuntimeError("gains of 1.0f differ from gains off at %d instances" % n)
+    off.close()
+    ones.close()
+    paths = [(name, Path(A, progs, n, True, gains=mode)) for name, mode in GAIN_MODES]
+    clocks = {name: [] for name, _ in paths}
+    for _, p in paths:
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in paths:
+                p.stretch(stretch)
+                clocks[name].append(clock())
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "stretch_blocks": stretch}
+    for name, p in paths:
+        r = rt.percentiles(p.times)
+        r.update({"blocks": len(p.times), "bus_gain_blocks": p.b.info("bus_gain_blocks")})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-9s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d blocks mixed with gains  shader clock %s MHz" % (
+            name, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["p999_us"] <= BUDGET_US else "over budget",
+            r["bus_gain_blocks"], r["shader_clock_mhz_behind_a_stretch"]))
+        p.close()
+    return out
+
+
 def bus_row(A, progs, n, blocks, warm, log):
     """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
     block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
@@ -258,12 +322,17 @@ def kernel_shares(path, n):
     rows = list(csv.DictReader(open(path)))
     total = sum(float(r["TotalDurationNs"]) for r in rows)
     groups = -(-n // GROUP)
-    # bytes read + written per launch (the meter: the block, and its 20-byte accumulators in and out)
-    need = {"fx_bus_expand": BLOCK * (groups + n) * 4, "fx_bus_mix": BLOCK * (n + groups) * 4, "fx_meter": BLOCK * n * 4 + 2 * 20 * n}
+    # what to look for in a kernel's demangled name -> bytes read + written per launch (the meter: the block, and its 20-byte
+    # accumulators in and out; the weighted mix: the block, and one or two gain rows of n words that the rows of a block share).
+    # The plain kernels are matched up to their "(" so that fx_bus_mix does not also match fx_bus_mix_gain<...>: this relies on the
+    # full demangled signature that rocprofv3 writes; a table with truncated names ("fx_bus_mix" alone) would match nothing here.
+    mix = BLOCK * (n + groups) * 4
+    need = {"fx_bus_expand": ("fx_bus_expand(", BLOCK * (groups + n) * 4), "fx_bus_mix": ("fx_bus_mix(", mix), "fx_meter": ("fx_meter", BLOCK * n * 4 + 2 * 20 * n),
+            "fx_bus_mix_gain<false>": ("fx_bus_mix_gain<false>", mix + n * 4), "fx_bus_mix_gain<true>": ("fx_bus_mix_gain<true>", mix + 2 * n * 4)}
     out = {"instances": n, "device_time_ns": total, "kernels": {}}
     for r in rows:
-        for key, bytes_ in need.items():
-            if key in r["Name"]:
+        for key, (match, bytes_) in need.items():
+            if match in r["Name"]:
                 avg = float(r["AverageNs"])
                 out["kernels"][key] = {"calls": int(r["Calls"]), "average_ns": round(avg, 1), "share_of_device_time": round(float(r["TotalDurationNs"]) / total, 4),
                                        "bytes_per_launch": bytes_, "achieved_TBps": round(bytes_ / avg / 1e3, 3),
@@ -286,12 +355,42 @@ def main():
     ap.add_argument("--meter", action="store_true", help="bus blocks with output meters off and on by turns (with --trace-run: meters on)")
     ap.add_argument("--meter-instances", default="131072,458752")
     ap.add_argument("--meter-out", default="", help="keep the lines of --meter in this text file")
+    ap.add_argument("--gains", action="store_true", help="bus blocks with gains off, static gains and a ramp on every block by turns (with --trace-run: the same three)")
+    ap.add_argument("--gain-instances", default="131072,458752")
+    ap.add_argument("--gains-out", default="", help="keep the lines of --gains in this text file")
     args = ap.parse_args()
     import torch  # first: its HIP runtime is the one the library binds to
 
     import fx8010_amd as A
     import fx8010_programs as progs
     log = lambda s: print(s, flush=True)
+    if args.trace_run and args.gains:
+        paths = [Path(A, progs, args.trace_instances, True, gains=mode) for _, mode in GAIN_MODES]
+        for _ in range(4):
+            for p in paths:
+                p.stretch(50, timed=False)
+        for p in paths:
+            p.close()
+        return 0
+    if args.gains:
+        lines = []
+
+        def keep(s):
+            lines.append(s)
+            log(s)
+        keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us: gains off, static "
+             "gains, and a ramp on every block (fxb_bus_set_gains with ramp = 1 inside the timed region), by turns in stretches of %d blocks in one "
+             "process, %d blocks per point after %d warm-up blocks; %s" % (GROUP, BUDGET_US, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+        rows = [gains_side_by_side(A, progs, int(v), args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.gain_instances.split(",") if v]
+        if args.kernel_stats:
+            keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances)))
+        if args.gains_out:
+            with open(args.gains_out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump({"gain_rows": rows}, fh, indent=1)
+        return 0
     if args.trace_run:
         p = Path(A, progs, args.trace_instances, True, meter=args.meter)
         p.stretch(200, timed=False)
