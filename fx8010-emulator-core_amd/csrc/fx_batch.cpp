@@ -80,6 +80,10 @@ Batch::~Batch() {
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
     if (evGain_) (void)hipEventDestroy(evGain_);
+    (void)hipFree(dTap_);
+    (void)hipFree(dTapReserved_);
+    (void)hipFree(dTapStage_);
+    if (hTapStage_) (void)hipHostFree(hTapStage_);
     (void)hipFree(dInstList_);
     (void)hipFree(dInstRec_);
     if (hInstList_) (void)hipHostFree(hInstList_);
@@ -843,6 +847,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_BUS_BLOCKS) return busBlocks_;
     if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
     if (what == FXB_INFO_BUS_GAIN_BLOCKS) return busGainBlocks_;
+    if (what == FXB_INFO_BUS_TAP_BLOCKS) return busTapBlocks_;
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;

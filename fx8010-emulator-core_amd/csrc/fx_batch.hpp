@@ -65,7 +65,9 @@ public:
     // place on pinned buffers or staged; kBusDevice: the buffers are checked like processDeviceChecked's, asynchronous on `stream`.
     enum : unsigned { kBusSharedIn = 1u << 0, kBusMixOut = 1u << 1, kBusFlags = 3u };
     enum BusEntry { kBusHost, kBusDevice };
-    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream);
+    // tapOut (null: an untapped block): the caller's [nSamples][channels][T] monitor side of the taps in force, see "Bus taps" below
+    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
+                   float* tapOut = nullptr);
     // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
     static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     // Instance-major blocks (fx_imajor.hpp; include/fx8010_amd.h fxb_process_block_imajor): instance i's input is the run of
@@ -90,6 +92,24 @@ public:
     int busGetGains(float* gains, int64_t rowPitch = 0);
     bool busGainsOn() const { return gainsOn_; }
     static bool gainsFinite(const float* gains, int channels, int64_t n, int64_t rowPitch);
+    // Bus taps (fx_bus.hpp BusTapArgs; include/fx8010_amd.h "Bus taps"): a mode of the handle.  While it is on, a bus block with
+    // kBusMixOut and a tapOut gathers the listed columns of the scratch block, pre-fader, into tapOut beside the mix.  `list` holds
+    // `count` instance numbers of THIS batch, `pos` the column of the caller's [..][total] rows each of them goes to (null: entry k
+    // goes to column k and total == count); total is the T of the whole handle - a shard may own none of the entries (count 0) and
+    // still has taps on.  total == 0 turns the mode off (waits, frees).  busReserveTaps is the allocating half (the device list of
+    // the set to come: FX_E_MEMORY changes nothing), called by Sharded on every shard in front of any busSetTaps, which then waits
+    // for the queued blocks, swaps the lists and cannot run out of memory; busReleaseTaps drops a reservation that is not taken up.
+    // busGetTaps: list[pos[k]] = first + local entry k, for the columns below cap; returns total.
+    static constexpr int64_t kMaxTaps = 65536;
+    int busReserveTaps(int64_t count);
+    void busReleaseTaps();
+    int busSetTaps(const int64_t* list, const int64_t* pos, int64_t count, int64_t total);
+    int64_t busGetTaps(int64_t* list, int64_t cap, int64_t first) const;
+    int64_t busTaps() const { return tapTotal_; }
+    // what a tapped call adds to the refusals of the bus entries that read nothing but the arguments (also asked by Sharded, for
+    // the whole batch): null, or why not.  The footprints of in / out are those of busBuffersApart.
+    static const char* checkTapShape(const float* in, const float* out, const float* tapOut, size_t rows, int64_t total, unsigned flags, int64_t inWidth, int64_t inPitch,
+                                     int64_t outWidth, int64_t outPitch);
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -444,11 +464,14 @@ private:
     // bus blocks: expand -> the ordinary launch in place on the scratch -> mix, piece by piece on one stream
     struct BusShape { int64_t group = 1, groups = 1, inWidth = 0, outWidth = 0, inPitch = 0, outPitch = 0; };
     static constexpr size_t kBusScratchBytes = (size_t)64 << 20;   // 32 samples of 524 288 instances: real-time blocks are never cut
-    int checkBus(const float* in, const float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
+    int checkBus(const float* in, const float* out, const float* tapOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
     int ensureBusScratch(size_t floats);
     int ensureBusStage(size_t floats);
+    // where the tap kernel of a block stores: the caller's rows as the device addresses them (pitch tapTotal_, at the columns of
+    // the device list), or the compact [rows][tapCount_] staging block of a pageable tapOut.  dst null: this batch launches none
+    struct TapRoute { uint32_t* dst = nullptr; int64_t pitch = 0; bool columns = false, staged = false; };
     int runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-               const BusShape& shape, hipStream_t stream);
+               const BusShape& shape, hipStream_t stream, const TapRoute* tap = nullptr);
     float* dBus_ = nullptr;         // the per-instance scratch [samples of a piece][channels][n]
     size_t busCap_ = 0;             // floats
     float* dBusStage_ = nullptr;    // pageable host buffers: the [samples][channels][groups] sides of a block
@@ -469,11 +492,31 @@ private:
     bool gainCopied_ = false;       // ... which may still be running
     int64_t busGainBlocks_ = 0;     // FXB_INFO_BUS_GAIN_BLOCKS
     size_t gainFloats() const { return (size_t)prog_.numChannels * (size_t)n_; }
+    // bus taps (fx_batch_bus_tap.cpp): the list as the host holds it and as the kernel reads it - one device block, tapCount_
+    // instance numbers and, where the entries have columns of their own (a shard), tapCount_ columns behind them.  Only busSetTaps
+    // writes it, behind a wait for everything queued, so a queued block keeps the taps it was queued with.
+    std::vector<int64_t> tapList_, tapPos_;   // this batch's entries (local numbers) and their columns (empty: identity)
+    int64_t tapTotal_ = 0;          // T of the whole handle; 0: taps are off
+    uint32_t* dTap_ = nullptr;      // [tapList_.size()] idx, then [tapPos_.size()] col
+    uint32_t* dTapReserved_ = nullptr;   // busReserveTaps: the block of the set to come
+    size_t tapReservedWords_ = 0;
+    uint32_t* dTapStage_ = nullptr;      // pageable tapOut: [rows][tapCount] on the device, grown on demand
+    size_t tapStageCap_ = 0;             // words
+    uint32_t* hTapStage_ = nullptr;      // ... and, for a shard that places its columns on the host, the same block in pinned memory
+    size_t hTapStageCap_ = 0;
+    int64_t busTapBlocks_ = 0;      // FXB_INFO_BUS_TAP_BLOCKS
+    int64_t tapCount() const { return (int64_t)tapList_.size(); }
+    int planTapRoute(float* tapOut, const void* devTap, size_t rows, TapRoute* route);   // devTap: tapOut as the device addresses it, or null (staged)
+    hipError_t queueTapCopyOut(const TapRoute& route, float* tapOut, size_t rows, hipStream_t stream);
+    void placeTapColumns(const TapRoute& route, float* tapOut, size_t rows);   // behind the wait for that copy
     const float* busCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one
     const float* busCheckedOut_ = nullptr;
     size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;
     const float* busCheckedDevIn_ = nullptr;
     float* busCheckedDevOut_ = nullptr;
+    const float* busCheckedTap_ = nullptr;  // ... and the last d_tap_out
+    size_t busCheckedTapBytes_ = 0;
+    float* busCheckedDevTap_ = nullptr;
     // instance-major blocks: gather -> the ordinary launch in place on the bus scratch -> scatter (the scratch, evBus_ and
     // busLaunched_ are shared with bus blocks: the two kinds may alternate, on different streams)
     int runImajor(const float* in, int64_t inStride, float* out, int64_t outStride, int nSamples, hipStream_t stream);

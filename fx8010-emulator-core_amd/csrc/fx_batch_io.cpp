@@ -507,7 +507,7 @@ bool Batch::busBuffersApart(const float* in, const float* out, size_t rows, int6
 }
 
 // The refusals of the bus entries, in front of everything else: a refused call has launched nothing and changed nothing.
-int Batch::checkBus(const float* in, const float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
+int Batch::checkBus(const float* in, const float* out, const float* tapOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
     if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
     if (group < 1) return fail(FX_E_ARG, "bus: group must be at least 1");
     if (flags & ~(unsigned)kBusFlags) return fail(FX_E_ARG, "bus: unknown flag bits");
@@ -524,6 +524,8 @@ int Batch::checkBus(const float* in, const float* out, int nSamples, int64_t gro
     if (nSamples > 0 && (!in || !out)) return fail(FX_E_ARG, "null buffer");
     if (nSamples > 0 && !busBuffersApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
         return fail(FX_E_ARG, "bus: input and output overlap without being one buffer with one layout");
+    if (const char* why = checkTapShape(in, out, tapOut, (size_t)std::max(nSamples, 0) * (size_t)prog_.numChannels, tapTotal_, flags, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
+        return fail(FX_E_ARG, why);
     *shape = s;
     return 0;
 }
@@ -563,7 +565,7 @@ int Batch::ensureBusStage(size_t floats) {
 // exceed kBusScratchBytes runs in consecutive sample ranges that fit - consecutive blocks to the kernel, like the pieces of
 // processHostPipelined; with control tracks armed the block stays whole (a schedule counts samples from the head of ONE launch).
 int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-                  const BusShape& shape, hipStream_t stream) {
+                  const BusShape& shape, hipStream_t stream, const TapRoute* tap) {
     const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
     const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
     const int pieces = (nSamples + most - 1) / most;
@@ -618,6 +620,22 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
             if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
             return rc;
         }
+        // the taps read the scratch block where the emulation has just written it, like the meter (inside launchBlock): pre-fader
+        if (tap && tap->dst) {
+            BusTapArgs t{};
+            t.wide = reinterpret_cast<const uint32_t*>(dBus_);
+            t.tapOut = tap->dst + first * (size_t)tap->pitch;
+            t.idx = dTap_;
+            t.col = tap->columns ? dTap_ + tapList_.size() : nullptr;
+            t.rows = a.rows;
+            t.n = n_;
+            t.taps = tapCount();
+            t.tapPitch = tap->pitch;
+            if ((e = launchBusTap(t, s)) != hipSuccess) {
+                if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
+                return hipFail(e, "bus: the tap kernel");
+            }
+        }
         if (flags & kBusMixOut) {
             a.narrowIn = nullptr;
             a.narrowOut = narrowOut + first * (size_t)narrowOutPitch;
@@ -632,6 +650,7 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         busLaunched_ = true;
     }
     ++busBlocks_;   // (blocks whose every piece was queued)
+    if (tap) ++busTapBlocks_;   // (counted by every shard that was handed the rows, whether or not an entry falls into it)
     if (weighted) {
         ++busGainBlocks_;
         gainRampPending_ = false;   // consumed: a counts as b from here on (fx_batch.hpp)
@@ -639,15 +658,18 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
     return 0;
 }
 
-int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream) {
+int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
+                      float* tapOut) {
     (void)hipSetDevice(device_);
     BusShape shape;
-    int rc = checkBus(in, out, nSamples, group, flags, inPitch, outPitch, &shape);
+    int rc = checkBus(in, out, tapOut, nSamples, group, flags, inPitch, outPitch, &shape);
     if (rc != 0) return rc;
     if (nSamples == 0) return ensureLowered();
     const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels;
     const size_t inBytes = pcmExtent(rows, shape.inWidth, shape.inPitch), outBytes = pcmExtent(rows, shape.outWidth, shape.outPitch);
-    const void *devIn = nullptr, *devOut = nullptr;
+    const size_t tapBytes = rows * (size_t)tapTotal_ * 4;
+    const void *devIn = nullptr, *devOut = nullptr, *devTap = nullptr;
+    TapRoute route;
     if (entry == kBusDevice) {
         if (in != busCheckedIn_ || out != busCheckedOut_ || inBytes > busCheckedInBytes_ || outBytes > busCheckedOutBytes_) {
             busCheckedIn_ = busCheckedOut_ = nullptr;
@@ -660,19 +682,39 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
             busCheckedDevIn_ = static_cast<const float*>(devIn);
             busCheckedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
         }
-        return runBus(busCheckedDevIn_, busCheckedDevOut_, busCheckedDevIn_, shape.inPitch, busCheckedDevOut_, shape.outPitch, nSamples, flags, shape, stream);
+        if (tapOut && (tapOut != busCheckedTap_ || tapBytes > busCheckedTapBytes_)) {
+            busCheckedTap_ = nullptr;
+            if (!addressable(tapOut, tapBytes, device_, &devTap))
+                return fail(FX_E_ARG, "d_tap_out: not memory of this handle's device or device-visible host memory over the whole block");
+            busCheckedTap_ = tapOut;
+            busCheckedTapBytes_ = tapBytes;
+            busCheckedDevTap_ = static_cast<float*>(const_cast<void*>(devTap));
+        }
+        if (tapOut && (rc = planTapRoute(tapOut, busCheckedDevTap_, rows, &route)) != 0) return rc;
+        return runBus(busCheckedDevIn_, busCheckedDevOut_, busCheckedDevIn_, shape.inPitch, busCheckedDevOut_, shape.outPitch, nSamples, flags, shape, stream,
+                      tapOut ? &route : nullptr);
     }
     // Host entry.  Pinned buffers: the bus kernels read the group words from and store the sums to the caller's memory over PCIe
     // (256 bytes per wavefront access), no copies.  Anything else: the [sample][channel][group] sides are staged.  Whatever
     // happens, nothing of the call may still touch the caller's memory when it returns.
     waitLastLaunch();
+    // The tap rows take their own route, whichever the two sides take: stored in place where tap_out is pinned, else gathered into
+    // a device block and copied out behind the block.  Everything that route needs is allocated here, in front of the first launch.
+    if (tapOut) {
+        if (!(knobs_.hostPipeline && addressable(tapOut, tapBytes, -1, &devTap))) devTap = nullptr;
+        if ((rc = planTapRoute(tapOut, devTap, rows, &route)) != 0) return rc;
+    }
+    const TapRoute* tap = tapOut ? &route : nullptr;
     if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && addressable(out, outBytes, -1, &devOut)) {
         const float* dIn = static_cast<const float*>(devIn);
         float* dOut = static_cast<float*>(const_cast<void*>(devOut));
-        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_);
+        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap);
+        hipError_t te = hipSuccess;
+        if (rc == 0 && tap) te = queueTapCopyOut(route, tapOut, rows, stream_);
         const hipError_t se = hipStreamSynchronize(stream_);
         if (rc != 0) return rc;
-        if (se != hipSuccess) return hipFail(se, "synchronising a bus block on pinned host buffers");
+        if (te != hipSuccess || se != hipSuccess) return hipFail(te != hipSuccess ? te : se, "synchronising a bus block on pinned host buffers");
+        if (tap) placeTapColumns(route, tapOut, rows);
         ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
         return 0;
     }
@@ -688,11 +730,13 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         (void)hipStreamSynchronize(stream_);
         return hipFail(e, "bus H2D");
     }
-    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_);
+    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap);
     if (rc == 0 && mixOut) e = copyRows(out, (size_t)shape.outPitch * 4, stageOut, narrow, narrow, rows, hipMemcpyDefault, stream_);
+    if (rc == 0 && e == hipSuccess && tap) e = queueTapCopyOut(route, tapOut, rows, stream_);
     const hipError_t se = hipStreamSynchronize(stream_);
     if (rc != 0) return rc;
     if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "bus D2H");
+    if (tap) placeTapColumns(route, tapOut, rows);
     ++hostStagedBlocks_;
     return 0;
 }

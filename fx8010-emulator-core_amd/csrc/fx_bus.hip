@@ -1,5 +1,6 @@
 // fx_bus.hip — the kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
-// per-instance scratch, mix the scratch down to one word per group - plain (fx_bus_mix) or with per-instance gains (fx_bus_mix_gain).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
+// per-instance scratch, mix the scratch down to one word per group - plain (fx_bus_mix) or with per-instance gains (fx_bus_mix_gain) -
+// and gather a list of its columns into a narrow monitor side (fx_bus_tap).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
 // which may be pinned host memory behind PCIe, sees exactly one 256-byte access per wavefront and row.  The wide side: the expand
 // stores 1 KiB per wavefront access; the mix loads 256 contiguous bytes per access for groups of 64 instances and more, and ONE
 // PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
@@ -216,6 +217,49 @@ __global__ __launch_bounds__(64) void fx_bus_mix_gain(BusArgs a, BusGainArgs g) 
     }
 }
 
+// ---- the taps (fx_bus.hpp BusTapArgs): columns idx[t] of the scratch block to a narrow side, as bit patterns --------------------
+//
+// One wavefront per workgroup; grid.x = blocks of 64 taps, grid.y = chunks of kTapRows rows (a loop where a block has more chunks
+// than a grid may have).  A lane owns one tap: it reads its instance number (and its column) once and then, per chunk, issues
+// kTapRows independent loads - one per row, a 32-bit byte stride of n * 4 apart - before the first store.  Per row the 64 stores
+// of a wavefront are contiguous (identity columns), which is what the narrow side wants when it is pinned host memory; the loads
+// are a gather - wherever the list points, T words per row out of a block the emulation has just written.  With S * C = 32 rows
+// and T = 64 that is four wavefronts of eight loads each; nothing here scales with n.  No LDS, no floating-point instruction.
+constexpr int kTapRows = 8;   // row loads in flight per lane
+
+__global__ __launch_bounds__(64) void fx_bus_tap(BusTapArgs a) {
+    const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.taps) return;
+    const uint32_t inst = a.idx[t];
+    const uint32_t column = a.col ? a.col[t] : (uint32_t)t;
+    const uint32_t loadStride = (uint32_t)a.n * 4u, storeStride = (uint32_t)a.tapPitch * 4u;   // (both below 2^32: launchBusTap)
+    const long long chunks = (a.rows + kTapRows - 1) / kTapRows;
+    for (long long chunk = blockIdx.y; chunk < chunks; chunk += gridDim.y) {
+        const long long row0 = chunk * kTapRows;
+        const char* p = reinterpret_cast<const char*>(a.wide + row0 * a.n + inst);
+        char* q = reinterpret_cast<char*>(a.tapOut + row0 * a.tapPitch + column);
+        if (row0 + kTapRows <= a.rows) {
+            uint32_t v[kTapRows];
+#pragma unroll
+            for (int u = 0; u < kTapRows; ++u) {
+                v[u] = *reinterpret_cast<const uint32_t*>(p);
+                p += loadStride;
+            }
+#pragma unroll
+            for (int u = 0; u < kTapRows; ++u) {
+                *reinterpret_cast<uint32_t*>(q) = v[u];
+                q += storeStride;
+            }
+        } else {
+            for (long long row = row0; row < a.rows; ++row) {
+                *reinterpret_cast<uint32_t*>(q) = *reinterpret_cast<const uint32_t*>(p);
+                p += loadStride;
+                q += storeStride;
+            }
+        }
+    }
+}
+
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
 }  // namespace
@@ -253,6 +297,18 @@ hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t 
     (void)hipGetLastError();
     if (g.ramp) hipLaunchKernelGGL(fx_bus_mix_gain<true>, grid, dim3(64), 0, stream, a, g);
     else hipLaunchKernelGGL(fx_bus_mix_gain<false>, grid, dim3(64), 0, stream, a, g);
+    return hipGetLastError();
+}
+
+hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream) {
+    constexpr long long kMostTaps = 65536;
+    if (!a.wide || !a.tapOut || !a.idx || a.rows < 1 || a.n < 1 || a.n >= ((long long)1 << 30) || a.taps < 1 || a.taps > kMostTaps ||
+        a.tapPitch < a.taps || a.tapPitch > kMostTaps)
+        return hipErrorInvalidValue;
+    const long long chunks = (a.rows + kTapRows - 1) / kTapRows;
+    const dim3 grid((unsigned)((a.taps + 63) / 64), (unsigned)(chunks < 65535 ? chunks : 65535));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_bus_tap, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

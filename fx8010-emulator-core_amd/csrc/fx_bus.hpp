@@ -46,4 +46,21 @@ struct BusGainArgs {
 // with a weight of either zero contributes +0.0f whatever it holds.  (b - a), * t, a + and w * y are rounded one by one.
 hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t stream);
 
+// Bus taps (include/fx8010_amd.h "Bus taps"): a handful of columns of the scratch block, gathered into a narrow [rows][tapPitch]
+// side beside the mix.  Words move as 32-bit patterns.
+struct BusTapArgs {
+    const uint32_t* wide;    // [rows][n] per-instance scratch, rows packed (device memory)
+    uint32_t* tapOut;        // [rows][tapPitch] (device memory or device-visible host memory)
+    const uint32_t* idx;     // [taps] instance numbers of this batch, each below n (device memory; the caller has checked them)
+    const uint32_t* col;     // [taps] the column of tapOut each tap goes to, each below tapPitch; null: tap t goes to column t
+    long long rows;          // samples * channels
+    long long n;             // instances; n * 4 < 2^32
+    long long taps;          // T of this batch, 1 <= T <= 65 536
+    long long tapPitch;      // words per row of tapOut (>= taps; with `col`, above every column; <= 65 536)
+};
+
+// tapOut[r][col ? col[t] : t] = wide[r][idx[t]]: consecutive lanes own consecutive taps, so a row's store is contiguous where the
+// columns are (256 bytes per wavefront once T >= 64); the load is a gather
+hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream);
+
 }  // namespace fx

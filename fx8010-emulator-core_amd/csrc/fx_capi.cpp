@@ -230,6 +230,16 @@ int fxb_process_block_bus(fxb_handle* h, const float* in, float* out, int n, int
 int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, int n, int64_t group, unsigned flags, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream)); }) : FX_E_ARG;
 }
+int fxb_process_block_bus_tap(fxb_handle* h, const float* in, float* out, float* tap_out, int n, int64_t group, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(in, out, n, group, flags, false, nullptr, tap_out); }) : FX_E_ARG;
+}
+int fxb_process_block_bus_tap_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, int n, int64_t group, unsigned flags, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream), d_tap_out); }) : FX_E_ARG;
+}
+int fxb_bus_set_taps(fxb_handle* h, const int64_t* list, int64_t count) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetTaps(list, count); }) : FX_E_ARG; }
+int64_t fxb_bus_get_taps(fxb_handle* h, int64_t* list, int64_t cap) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.busGetTaps(list, cap); }) : (int64_t)FX_E_ARG;
+}
 int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGains(gains, ramp); }) : FX_E_ARG; }
 int fxb_bus_get_gains(fxb_handle* h, float* gains) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busGetGains(gains); }) : FX_E_ARG; }
 int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n, int64_t in_stride, int64_t out_stride) {

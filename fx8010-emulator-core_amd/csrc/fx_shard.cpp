@@ -258,16 +258,20 @@ int Sharded::processDevicePitched(const float* dIn, float* dOut, int nSamples, i
     if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
     return runOn(0, [&](Batch& b) { return b.processDeviceChecked(dIn, dOut, nSamples, pitch, stream); });
 }
-int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream) {
+int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut) {
     Serial serial(api_);
     lastError_.clear();
     // the refusals that go by the WHOLE batch, before any shard is posted (a refused call launches nothing on any shard)
     if (group < 1) { lastError_ = "bus: group must be at least 1"; return FX_E_ARG; }
     if (flags & ~(unsigned)Batch::kBusFlags) { lastError_ = "bus: unknown flag bits"; return FX_E_ARG; }
     if (device && shards_.size() != 1) { lastError_ = "the device entry of a bus block is for handles of one shard"; return FX_E_ARG; }
+    if (tapOut && (front().busTaps() < 1 || !(flags & Batch::kBusMixOut))) {
+        lastError_ = Batch::checkTapShape(nullptr, nullptr, tapOut, 0, front().busTaps(), flags, 0, 0, 0, 0);
+        return FX_E_ARG;
+    }
     if (flags == 0) return device ? processDevicePitched(in, out, nSamples, n_, stream) : processHost(in, out, nSamples, 0);
     if (shards_.size() == 1)
-        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream); });
+        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream, tapOut); });
     for (auto& w : shards_)
         if (w->first % group != 0) { lastError_ = "bus: a group straddles shards (every shard must begin at a multiple of the group size: fxb_shard_plan)"; return FX_E_ARG; }
     const int64_t groups = (n_ + group - 1) / group;
@@ -276,11 +280,17 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
         lastError_ = "bus: input and output overlap without being one buffer with one layout";
         return FX_E_ARG;
     }
+    // (the tap rows against the footprints of ALL shards' columns; every shard gets the full-width rows and writes its columns)
+    if (nSamples > 0)
+        if (const char* why = Batch::checkTapShape(in, out, tapOut, (size_t)nSamples * (size_t)front().channels(), front().busTaps(), flags, inPitch, inPitch, outPitch, outPitch)) {
+            lastError_ = why;
+            return FX_E_ARG;
+        }
     return fan([&](int k, Batch& b) {
         const int64_t first = shards_[(size_t)k]->first;
         const float* shardIn = in ? in + ((flags & Batch::kBusSharedIn) ? first / group : first) : in;
         float* shardOut = out ? out + ((flags & Batch::kBusMixOut) ? first / group : first) : out;
-        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr);
+        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr, tapOut);
     });
 }
 int Sharded::processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream) {
@@ -352,6 +362,38 @@ int Sharded::busGetGains(float* gains) {
     lastError_.clear();
     if (front().busGainsOn() && !gains) { lastError_ = "null buffer"; return FX_E_ARG; }
     return fan([&](int k, Batch& b) { return b.busGetGains(gains ? gains + shards_[(size_t)k]->first : nullptr, n_); });
+}
+
+int Sharded::busSetTaps(const int64_t* list, int64_t count) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (count < 0 || count > Batch::kMaxTaps) { lastError_ = "bus taps: count must be 0..65536"; return FX_E_ARG; }
+    if (count > 0 && !list) { lastError_ = "bus taps: a null list"; return FX_E_ARG; }
+    for (int64_t k = 0; k < count; ++k)
+        if (list[k] < 0 || list[k] >= n_) { lastError_ = "bus taps: an entry outside 0..N-1"; return FX_E_ARG; }
+    if (count == 0) return fan([](int, Batch& b) { return b.busSetTaps(nullptr, nullptr, 0, 0); });
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.busSetTaps(list, nullptr, count, count); });
+    // every shard reserves the block of its entries first; only when all of them could does any shard's list change
+    const std::vector<ListPart> parts = splitList(list, count);
+    const int rc = fan([&](int k, Batch& b) { return b.busReserveTaps((int64_t)parts[(size_t)k].list.size()); });
+    if (rc != 0) {
+        const std::string why = lastError();
+        fan([](int, Batch& b) { b.busReleaseTaps(); return 0; });
+        lastError_ = why;
+        return rc;
+    }
+    return fan([&](int k, Batch& b) {
+        const ListPart& part = parts[(size_t)k];
+        return b.busSetTaps(part.list.data(), part.pos.data(), (int64_t)part.list.size(), count);
+    });
+}
+int64_t Sharded::busGetTaps(int64_t* list, int64_t cap) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (cap < 0 || (cap > 0 && !list)) { lastError_ = "bus taps: a null list with room asked for"; return FX_E_ARG; }
+    int64_t total = 0;
+    for (auto& w : shards_) total = w->batch->busGetTaps(list, cap, w->first);   // (host state only: no device call)
+    return total;
 }
 
 int64_t Sharded::instructionCounter() {
@@ -586,7 +628,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

@@ -70,7 +70,8 @@ public:
     // group buses (Batch::processBus): `in` / `out` are the caller's full-width buffers, [sample][channel][groups of the whole batch]
     // on a side with its flag.  Every shard must begin at a multiple of `group` (fxb_shard_plan tells the boundaries) and works on
     // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
-    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream);
+    // tapOut (null: none): the caller's full-width [sample][channel][T] rows of the taps in force; a shard writes its entries' columns
+    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut = nullptr);
     // instance-major blocks (Batch::processImajor): shard k works on the runs from in + first_k * inStride on, on its own thread
     // and device.  device: the caller's stream, single-shard handles only.
     int processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream);
@@ -85,6 +86,11 @@ public:
     // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.
     int busSetGains(const float* gains, int ramp);
     int busGetGains(float* gains);
+    // bus taps (Batch::busSetTaps ...): `list` holds GLOBAL instance numbers, checked as a whole before any shard is posted; each
+    // shard gets the entries of its range with their positions in the list (splitList) and reserves its device block first, so
+    // FX_E_MEMORY leaves the old taps in force everywhere.  count 0 turns them off.  get: T, and the first min(T, cap) entries.
+    int busSetTaps(const int64_t* list, int64_t count);
+    int64_t busGetTaps(int64_t* list, int64_t cap);
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

@@ -213,6 +213,25 @@ public:
         const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
         if (fxb_process_block_bus(h_, in, out, nSamples, group, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::processBlockBus: ") + fxb_last_error(h_));
     }
+    // bus taps (include/fx8010_amd.h "Bus taps"): the instances (global numbers, any order, repeats allowed, at most 65 536) whose own
+    // output words, pre-fader, a tapped block delivers beside the mix; an empty list turns taps off.  processBlockBusTap is
+    // processBlockBus with tapOut = [nSamples][channels][busTaps().size()]; it needs mixOut.
+    void busSetTaps(const std::vector<int64_t>& instances) {
+        if (fxb_bus_set_taps(h_, instances.empty() ? nullptr : instances.data(), (int64_t)instances.size()) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::busSetTaps: ") + fxb_last_error(h_));
+    }
+    std::vector<int64_t> busTaps() {
+        const int64_t count = fxb_bus_get_taps(h_, nullptr, 0);
+        if (count < 0) throw std::runtime_error(std::string("FX8010Batch::busTaps: ") + fxb_last_error(h_));
+        std::vector<int64_t> list((size_t)count);
+        if (count > 0) fxb_bus_get_taps(h_, list.data(), count);
+        return list;
+    }
+    void processBlockBusTap(const float* in, float* out, float* tapOut, int nSamples, int64_t group, bool sharedIn = true, bool mixOut = true) {
+        const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
+        if (fxb_process_block_bus_tap(h_, in, out, tapOut, nSamples, group, flags) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::processBlockBusTap: ") + fxb_last_error(h_));
+    }
     // per-instance gains of the mixed output (include/fx8010_amd.h "Bus gains"): gains is [channels][instances], every value finite,
     // or nullptr for gains off (the unweighted sum); with ramp the next mixing block moves every weight linearly from the gains in
     // force to these and ends exactly on them.  A gain of zero mutes: that instance adds +0.0f whatever it holds.  busGetGains

@@ -25,7 +25,7 @@ INFO = {
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
-    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41,
+    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -39,6 +39,7 @@ SYMBOLS = [
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
+    "fxb_bus_set_taps", "fxb_bus_get_taps", "fxb_process_block_bus_tap", "fxb_process_block_bus_tap_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
@@ -96,6 +97,8 @@ def load():
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_bus_set_gains", i32, vp, vp, i32); sig("fxb_bus_get_gains", i32, vp, vp)
+    sig("fxb_bus_set_taps", i32, vp, vp, i64); sig("fxb_bus_get_taps", i64, vp, vp, i64)
+    sig("fxb_process_block_bus_tap", i32, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_tap_dev", i32, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
@@ -504,11 +507,13 @@ class Batch(_Reports):
         """G = ceil(N / group): the columns of a shared input / a mixed output"""
         return self._check(int(self._lib.fxb_bus_groups(self._h, int(group))), "bus_groups")
 
-    def process_block_bus(self, x, group, shared_in=True, mix_out=True, out=None):
+    def process_block_bus(self, x, group, shared_in=True, mix_out=True, out=None, tap_out=None, taps=False):
         """A block with a shared input and / or a mixed output per group of `group` consecutive instances.  x: float32
         [S, channels, G] with shared_in (instance n hears column n // group), else [S, channels, N]; returns [S, channels, G] with
         mix_out (every group's sum, in the order include/fx8010_amd.h fixes), else [S, channels, N] (mono: the channel axis may be
-        left out).  Into `out` when given; x and out in pinned memory (HostBuffer.array) are read and written in place."""
+        left out).  Into `out` when given; x and out in pinned memory (HostBuffer.array) are read and written in place.
+        With taps=True or a tap_out (float32 [S, channels, T], T = len(bus_get_taps()); pinned: stored to in place) the block also
+        delivers the tapped instances' own output words, pre-fader, and returns (out, taps)."""
         G = self.bus_groups(group)
         x = np.ascontiguousarray(x, dtype=np.float32)
         S = x.shape[0]
@@ -518,12 +523,22 @@ class Batch(_Reports):
             out = np.empty(shape, dtype=np.float32)
         assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == int(np.prod(shape))
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        if tap_out is not None or taps:
+            T = int(self._lib.fxb_bus_get_taps(self._h, None, 0))
+            tshape = ((S,) if x.ndim == 2 else (S, self.channels)) + (T,)
+            if tap_out is None:
+                tap_out = np.empty(tshape, dtype=np.float32)
+            assert tap_out.dtype == np.float32 and tap_out.flags["C_CONTIGUOUS"] and tap_out.flags["WRITEABLE"] and tap_out.size == int(np.prod(tshape)), "tap_out must be [S, channels, T]"
+            self._check(self._lib.fxb_process_block_bus_tap(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(tap_out.ctypes.data), S, int(group), flags),
+                        "process_block_bus")
+            return out, tap_out
         self._check(self._lib.fxb_process_block_bus(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), S, int(group), flags), "process_block_bus")
         return out
 
-    def process_block_bus_dev(self, d_in, d_out, n_samples, group, shared_in=True, mix_out=True, stream=None):
+    def process_block_bus_dev(self, d_in, d_out, n_samples, group, shared_in=True, mix_out=True, stream=None, d_tap_out=None):
         """d_in / d_out: device pointers (ints) or contiguous float32 torch tensors, [n_samples, channels, G] on a side with its
-        flag and [n_samples, channels, N] on the other; single-shard handles; asynchronous on `stream` (a hipStream_t as int)."""
+        flag and [n_samples, channels, N] on the other; single-shard handles; asynchronous on `stream` (a hipStream_t as int).
+        d_tap_out: the same for the [n_samples, channels, T] rows of the taps in force (bus_set_taps)."""
         G = self.bus_groups(group)
 
         def ptr(t, width):
@@ -533,6 +548,10 @@ class Batch(_Reports):
             return t.data_ptr()
         a, b = ptr(d_in, G if shared_in else self.n), ptr(d_out, G if mix_out else self.n)
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        if d_tap_out is not None:
+            t = ptr(d_tap_out, int(self._lib.fxb_bus_get_taps(self._h, None, 0)))
+            return self._check(self._lib.fxb_process_block_bus_tap_dev(self._h, C.c_void_p(a), C.c_void_p(b), C.c_void_p(t), int(n_samples), int(group), flags,
+                                                                        C.c_void_p(stream or 0)), "process_block_bus_dev")
         return self._check(self._lib.fxb_process_block_bus_dev(self._h, C.c_void_p(a), C.c_void_p(b), int(n_samples), int(group), flags, C.c_void_p(stream or 0)),
                            "process_block_bus_dev")
 
@@ -552,6 +571,20 @@ class Batch(_Reports):
         g = np.empty((self.channels, self.n), dtype=np.float32)
         self._check(self._lib.fxb_bus_get_gains(self._h, C.c_void_p(g.ctypes.data)), "bus_get_gains")
         return g
+
+    def bus_set_taps(self, instances):
+        """The instances whose own output the next tapped bus blocks deliver beside the mix (include/fx8010_amd.h "Bus taps"): up to
+        65 536 global instance numbers in any order, repeats allowed; None or an empty list turns taps off."""
+        lst = np.ascontiguousarray([] if instances is None else instances, dtype=np.int64).reshape(-1)
+        return self._check(self._lib.fxb_bus_set_taps(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size)), "bus_set_taps")
+
+    def bus_get_taps(self):
+        """int64 [T]: the tap list in force (empty while taps are off)"""
+        T = self._check(int(self._lib.fxb_bus_get_taps(self._h, None, 0)), "bus_get_taps")
+        lst = np.zeros(T, dtype=np.int64)
+        if T:
+            self._check(int(self._lib.fxb_bus_get_taps(self._h, C.c_void_p(lst.ctypes.data), T)), "bus_get_taps")
+        return lst
 
     def _stream_stride(self, shape, strides):
         """the instance stride (in floats) when an [N, S, channels] array is N interleaved [S][channels] runs at one stride, else None"""

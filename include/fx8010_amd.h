@@ -329,6 +329,43 @@ int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, in
  * FXB_INFO_BUS_GAIN_BLOCKS counts the bus blocks mixed with gains. */
 int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp);
 int fxb_bus_get_gains(fxb_handle* h, float* gains);
+/* Bus taps: per-instance monitor outputs by list beside the mixed bus - solo, PFL, a recording of one voice, a look at the voice
+ * whose meter went non-finite - without taking all N columns over PCIe.  Taps are a mode of the handle like the meters and the
+ * gains, off by default: no flag bit is taken and no existing signature or behaviour changes.
+ *
+ * fxb_bus_set_taps: list holds T = count global instance numbers in 0..N-1, in any order; repeats are allowed (one voice may feed
+ *   two monitor columns).  count == 0 (any list) turns taps off and frees their memory.  FX_E_ARG with nothing changed: count < 0,
+ *   count > 65 536 (a tap set is a monitor selection, not a second output path: the cap keeps the device list and every row of
+ *   tap_out small), a null list with count > 0, an entry outside 0..N-1.  The list is copied before the call returns.  All
+ *   allocation for the list happens here, on every shard before any shard's list changes: FX_E_MEMORY leaves the old taps in force
+ *   everywhere.  The call waits for the queued blocks as fxb_meter_enable does, so a queued block keeps the taps it was queued
+ *   with.  Works before a program is loaded; the taps survive program loads; they are not part of the state image or of instance
+ *   records, and fxb_copy_instances / fxb_reset_instances do not touch them: a tap belongs to the mixer slot, not to the voice.
+ * fxb_bus_get_taps: returns T (0 while taps are off) and copies min(T, cap) entries; list may be NULL with cap 0.
+ *
+ * The tapped block.  tap_out is [n_samples][num_channels][T] with a row pitch of exactly T: tap_out[(s*C + c)*T + t] is the 32-bit
+ * word that fxb_process_block on the expanded input writes at out[(s*C + c)*N + list[t]], moved as a bit pattern (NaN payloads
+ * survive).  Taps are pre-fader and pre-mute like the meters: a voice whose gain is 0 is still heard on its tap, which is what PFL
+ * means.  `out` (the mix), instance state, meters, gains with their pending ramp, armed control tracks and every other FXB_INFO_*
+ * counter are exactly what fxb_process_block_bus with the same arguments leaves.  A block cut into sample ranges by the 64 MiB
+ * scratch delivers each range's rows to tap_out + first_row * T.  tap_out == NULL is fxb_process_block_bus / _bus_dev.
+ * n_samples == 0 lowers the program and returns 0.  One small kernel per range gathers the columns from the per-instance block in
+ * device memory, between the program and the mix.
+ * FX_E_ARG (nothing launched, nothing changed): tap_out non-null while taps are off; tap_out non-null without FXB_BUS_MIX_OUT in
+ * flags (without it `out` already holds every column); tap_out sharing a byte with the footprint of `in` or of `out`; every
+ * refusal of fxb_process_block_bus*; the device entry on a handle of several shards or with a d_tap_out the device cannot address
+ * over the whole block (checked and remembered like the other two buffers).
+ * Host entry: synchronous.  A pinned tap_out (fxb_host_alloc ...) is stored to in place over PCIe; any other goes through a device
+ * staging block that grows on demand and is copied out before the call returns (FX_E_MEMORY: nothing launched).  in / out keep
+ * their own in-place / staged decision.  Device entry: asynchronous on `stream`, covered by fxb_sync.
+ * Sharded handles: each shard gets the entries of the list that fall into its range and writes only their columns of the caller's
+ * full-width tap_out; a shard with no entry launches no tap kernel.  The group-alignment condition of bus blocks applies.
+ * FXB_INFO_BUS_TAP_BLOCKS counts the bus blocks that were given a tap_out: once per block and shard, like FXB_INFO_BUS_GAIN_BLOCKS. */
+int     fxb_bus_set_taps(fxb_handle* h, const int64_t* list, int64_t count);
+int64_t fxb_bus_get_taps(fxb_handle* h, int64_t* list, int64_t cap);
+int     fxb_process_block_bus_tap(fxb_handle* h, const float* in, float* out, float* tap_out, int n_samples, int64_t group, unsigned flags);
+int     fxb_process_block_bus_tap_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, int n_samples, int64_t group, unsigned flags,
+                                      void* stream);
 /* Instance-major blocks: one interleaved stream per instance, transposed on the device.  Instance n's input is the
  * n_samples * num_channels floats at in + n * in_stride, ordered [sample][channel] - what n_samples calls of the reference's
  * process() consume and what a WAV file holds - and its output goes to out + n * out_stride the same way.
@@ -480,7 +517,8 @@ enum {
     FXB_INFO_INSTANCE_WORDS = 38,      /* W: 32-bit words of one instance's record (state rows + iTRAM slots + xTRAM slots) */
     FXB_INFO_INSTANCE_GATHERS = 39,    /* launches of the kernel fx_inst_gather - by fxb_copy_instances and fxb_save_instances - since creation (summed over shards) */
     FXB_INFO_INSTANCE_SCATTERS = 40,   /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
-    FXB_INFO_BUS_GAIN_BLOCKS = 41      /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
+    FXB_INFO_BUS_GAIN_BLOCKS = 41,     /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
+    FXB_INFO_BUS_TAP_BLOCKS = 42       /* bus blocks that delivered taps (fxb_process_block_bus_tap* with a tap_out) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -26,6 +26,13 @@ of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel a
    must give the words of gains off.  With `--trace-run --gains` the traced run is the same three handles by turns, 200 blocks
    each, and `--kernel-stats` reports fx_bus_mix_gain (static and ramping) beside fx_bus_mix.
 
+6. `--taps T`: what bus taps (fxb_bus_set_taps, fxb_process_block_bus_tap) cost a real-time host.  At every count of
+   --tap-instances two bus handles, untapped and with T instances tapped into a pinned [32][T] side, take turns in stretches in
+   ONE process; median and p99.9 of both are reported (`--taps-out FILE.txt` keeps the lines).  Before anything is timed the tap
+   words must be the plain path's columns, and the two mixes must stay equal word for word.  With `--trace-run --taps T` the
+   traced stretch runs tapped and with meters on - fx_meter, which reads the whole per-instance block, is the yardstick in the same
+   trace - and `--kernel-stats` then reports fx_bus_tap beside it.
+
 Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
@@ -65,7 +72,7 @@ def mix_model(y, K):
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus, meter=False, gains=None):
+    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -88,6 +95,16 @@ class Path:
             self.levels = [np.ascontiguousarray(level.reshape(1, n)), np.ascontiguousarray((np.float32(1.25) - level).reshape(1, n))]
             self.lp = [C.c_void_p(g.ctypes.data) for g in self.levels]
             self.b.bus_set_gains(self.levels[0])
+        # taps: T instances spread over the batch (the first and the last among them), delivered to a pinned [BLOCK][T] side
+        self.taps, self.tap_list, self.tp = taps, None, None
+        if taps:
+            self.tap_list = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(5).integers(0, n, max(taps - 2, 0))]))[:taps].astype(np.int64)
+            while self.tap_list.size < taps:   # (draws that met: top up with repeats)
+                self.tap_list = np.concatenate([self.tap_list, self.tap_list[:taps - self.tap_list.size]])
+            self.tap_list = np.ascontiguousarray(np.random.default_rng(6).permutation(self.tap_list))
+            self.b.bus_set_taps(self.tap_list)
+            self.tap_out = A.HostBuffer((BLOCK, 1, taps))
+            self.tp = C.c_void_p(self.tap_out.array.ctypes.data)
         self.b.prepare(BLOCK, True)
         self.k = 0
         self.times = []
@@ -98,7 +115,9 @@ class Path:
             assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
         if self.gains == "ramp" and self.lib.fxb_bus_set_gains(h, self.lp[(k + 1) % 2], 1) != 0:
             raise RuntimeError("set_gains in front of block %d failed: %s" % (k, self.b.last_error()))
-        if self.bus:
+        if self.taps:
+            rc = self.lib.fxb_process_block_bus_tap(h, self.xp[k % RING], self.yp, self.tp, BLOCK, GROUP, 3)
+        elif self.bus:
             rc = self.lib.fxb_process_block_bus(h, self.xp[k % RING], self.yp, BLOCK, GROUP, 3)
         else:
             rc = self.lib.fxb_process_block_pitched(h, self.xp[k % RING], self.yp, BLOCK, self.n)
@@ -115,7 +134,7 @@ class Path:
 
     def close(self):
         self.b.close()
-        for h in self.ring + [self.out]:
+        for h in self.ring + [self.out] + ([self.tap_out] if self.taps else []):
             h.close()
 
 
@@ -285,6 +304,54 @@ def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: No
     return out
 
 
+def taps_side_by_side(A, progs, n, taps, blocks, warm, stretch, log, clock=lambda: None):
+    """bus blocks untapped and with `taps` instances tapped by turns, in stretches, in one process"""
+    import numpy as np
+    # the tap words are the plain path's columns, the mix is the untapped one's
+    plain, off, on = Path(A, progs, n, False), Path(A, progs, n, True), Path(A, progs, n, True, taps=taps)
+    for _ in range(2):
+        for p in (plain, off, on):
+            p.block()
+        if not np.array_equal(on.tap_out.array.view(np.uint32), plain.out.array[:, :, on.tap_list].view(np.uint32)):
+            raise RuntimeError("the taps differ from the plain path's columns at %d instances" % n)
+        if not np.array_equal(on.out.array.view(np.uint32), off.out.array.view(np.uint32)):
+            raise RuntimeError("the tapped handle's mix differs from the untapped one's at %d instances" % n)
+    plain.close()
+    paths = [("untapped", off), ("%d taps" % taps, on)]
+    clocks = {name: [] for name, _ in paths}
+    for _, p in paths:
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in paths:
+                p.stretch(stretch)
+                clocks[name].append(clock())
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "taps": taps, "stretch_blocks": stretch}
+    for name, p in paths:
+        r = rt.percentiles(p.times)
+        r.update({"blocks": len(p.times), "bus_tap_blocks": p.b.info("bus_tap_blocks")})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-10s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d tapped blocks  shader clock %s MHz" % (
+            name, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["p999_us"] <= BUDGET_US else "over budget",
+            r["bus_tap_blocks"], r["shader_clock_mhz_behind_a_stretch"]))
+    same = off.k == on.k and np.array_equal(off.out.array.view(np.uint32), on.out.array.view(np.uint32))
+    out["outputs_equal"] = bool(same)
+    out["median_difference_us"] = round(out["%d taps" % taps]["median_us"] - out["untapped"]["median_us"], 1)
+    log("           N=%7d  mixes of the two %s; median with taps - median without: %+.1f us" % (n, "equal" if same else "DIFFER", out["median_difference_us"]))
+    off.close()
+    on.close()
+    return out
+
+
 def bus_row(A, progs, n, blocks, warm, log):
     """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
     block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
@@ -317,7 +384,7 @@ def bus_row(A, progs, n, blocks, warm, log):
     return r
 
 
-def kernel_shares(path, n):
+def kernel_shares(path, n, taps=0):
     """the --stats table of a `--trace-run` under rocprofv3: share of device time and achieved bytes/s of the two bus kernels"""
     rows = list(csv.DictReader(open(path)))
     total = sum(float(r["TotalDurationNs"]) for r in rows)
@@ -329,6 +396,8 @@ def kernel_shares(path, n):
     mix = BLOCK * (n + groups) * 4
     need = {"fx_bus_expand": ("fx_bus_expand(", BLOCK * (groups + n) * 4), "fx_bus_mix": ("fx_bus_mix(", mix), "fx_meter": ("fx_meter", BLOCK * n * 4 + 2 * 20 * n),
             "fx_bus_mix_gain<false>": ("fx_bus_mix_gain<false>", mix + n * 4), "fx_bus_mix_gain<true>": ("fx_bus_mix_gain<true>", mix + 2 * n * 4)}
+    if taps:   # (the tapped words in and out, and the list)
+        need["fx_bus_tap"] = ("fx_bus_tap", 2 * BLOCK * taps * 4 + taps * 4)
     out = {"instances": n, "device_time_ns": total, "kernels": {}}
     for r in rows:
         for key, (match, bytes_) in need.items():
@@ -358,6 +427,9 @@ def main():
     ap.add_argument("--gains", action="store_true", help="bus blocks with gains off, static gains and a ramp on every block by turns (with --trace-run: the same three)")
     ap.add_argument("--gain-instances", default="131072,458752")
     ap.add_argument("--gains-out", default="", help="keep the lines of --gains in this text file")
+    ap.add_argument("--taps", type=int, default=0, help="bus blocks untapped and with this many instances tapped by turns (with --trace-run: tapped, meters on)")
+    ap.add_argument("--tap-instances", default="131072,458752")
+    ap.add_argument("--taps-out", default="", help="keep the lines of --taps in this text file")
     args = ap.parse_args()
     import torch  # first: its HIP runtime is the one the library binds to
 
@@ -391,8 +463,27 @@ def main():
             with open(args.json, "w") as fh:
                 json.dump({"gain_rows": rows}, fh, indent=1)
         return 0
+    if args.taps and not args.trace_run:
+        lines = []
+
+        def keep(s):
+            lines.append(s)
+            log(s)
+        keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us, untapped and with %d "
+             "instances tapped into a pinned side (fxb_process_block_bus_tap) by turns in stretches of %d blocks in one process, %d blocks per point after "
+             "%d warm-up blocks; %s" % (GROUP, BUDGET_US, args.taps, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+        rows = [taps_side_by_side(A, progs, int(v), args.taps, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.tap_instances.split(",") if v]
+        if args.kernel_stats:
+            keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances, args.taps)))
+        if args.taps_out:
+            with open(args.taps_out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump({"tap_rows": rows}, fh, indent=1)
+        return 0 if all(r["outputs_equal"] for r in rows) else 1
     if args.trace_run:
-        p = Path(A, progs, args.trace_instances, True, meter=args.meter)
+        p = Path(A, progs, args.trace_instances, True, meter=args.meter or args.taps > 0, taps=args.taps)
         p.stretch(200, timed=False)
         p.close()
         return 0
