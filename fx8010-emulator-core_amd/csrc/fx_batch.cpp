@@ -84,6 +84,9 @@ Batch::~Batch() {
     (void)hipFree(dTapReserved_);
     (void)hipFree(dTapStage_);
     if (hTapStage_) (void)hipHostFree(hTapStage_);
+    (void)hipFree(dSend_);
+    (void)hipFree(dSendReserved_);
+    freeSendBlocks();
     (void)hipFree(dInstList_);
     (void)hipFree(dInstRec_);
     if (hInstList_) (void)hipHostFree(hInstList_);
@@ -848,6 +851,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_LAUNCHES) return meterLaunches_;
     if (what == FXB_INFO_BUS_GAIN_BLOCKS) return busGainBlocks_;
     if (what == FXB_INFO_BUS_TAP_BLOCKS) return busTapBlocks_;
+    if (what == FXB_INFO_BUS_SEND_BLOCKS) return busSendBlocks_;
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;

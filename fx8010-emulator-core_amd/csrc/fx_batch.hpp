@@ -66,8 +66,9 @@ public:
     enum : unsigned { kBusSharedIn = 1u << 0, kBusMixOut = 1u << 1, kBusFlags = 3u };
     enum BusEntry { kBusHost, kBusDevice };
     // tapOut (null: an untapped block): the caller's [nSamples][channels][T] monitor side of the taps in force, see "Bus taps" below
+    // auxOut (null: no sends delivered): the caller's [nSamples][channels][A] rows of the sends in force, see "Bus sends" below
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
-                   float* tapOut = nullptr);
+                   float* tapOut = nullptr, float* auxOut = nullptr);
     // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
     static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     // Instance-major blocks (fx_imajor.hpp; include/fx8010_amd.h fxb_process_block_imajor): instance i's input is the run of
@@ -110,6 +111,38 @@ public:
     // the whole batch): null, or why not.  The footprints of in / out are those of busBuffersApart.
     static const char* checkTapShape(const float* in, const float* out, const float* tapOut, size_t rows, int64_t total, unsigned flags, int64_t inWidth, int64_t inPitch,
                                      int64_t outWidth, int64_t outPitch);
+    // Bus sends (fx_bus.hpp BusSendArgs; include/fx8010_amd.h "Bus sends"): a mode of the handle.  While it is on, a bus block with
+    // kBusMixOut and an auxOut sums the listed columns of the scratch block, pre-fader and each with a weight of its own, onto the
+    // aux buses of a CSR structure.  A SendSet is what ONE batch holds of the structure of the whole handle: its buses in the
+    // order of their numbers, with local member numbers, the column of the caller's [..][totalBuses] rows each goes to and where
+    // its run begins among the caller's totalEntries entries (what fxb_bus_get_sends and the [C][E] of busSetSendGains go by).
+    // A shard may own no bus and still has sends on; totalBuses == 0 turns the mode off (waits, frees).  busReserveSends is the
+    // allocating half (the device block of the set to come: FX_E_MEMORY changes nothing), called by Sharded on every shard in
+    // front of any busSetSends, which then waits for the queued blocks, takes the block, sets a = b and cancels a pending ramp;
+    // busReleaseSends drops a reservation that is not taken up.  busSetSendGains(gains = the caller's [C][totalEntries], finite)
+    // follows the state machine of busSetGains; the next block with an auxOut consumes a pending ramp.
+    static constexpr int64_t kMaxSendBuses = 65536, kMaxSendEntries = (int64_t)1 << 24;
+    struct SendSet {
+        int64_t totalBuses = 0, totalEntries = 0;
+        std::vector<int64_t> offsets{0};     // [buses + 1] local CSR
+        std::vector<int64_t> members;        // [entries] local instance numbers
+        std::vector<int64_t> column, first;  // [buses]
+        std::vector<float> gain[2];          // [channels][entries]; busSetSends reads gain[0]
+        size_t chunkCount() const;
+    };
+    int busReserveSends(int64_t buses, int64_t entries, int64_t chunks);
+    void busReleaseSends();
+    int busSetSends(SendSet&& set);
+    int busSetSendGains(const float* gains, int ramp);
+    // host state only: this batch's buses into the caller's arrays (offsets[column], members / gains at the bus's global run,
+    // below the caps); returns totalEntries
+    int64_t busGetSends(int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap, int64_t firstInstance) const;
+    int64_t busSendBuses() const { return send_.totalBuses; }
+    int64_t busSendEntries() const { return send_.totalEntries; }
+    // what an auxOut adds to the refusals of the bus entries that read nothing but the arguments (also asked by Sharded, for the
+    // whole batch): null, or why not
+    static const char* checkAuxShape(const float* in, const float* out, const float* tapOut, const float* auxOut, size_t rows, int64_t buses, int64_t taps, unsigned flags,
+                                     int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -464,14 +497,16 @@ private:
     // bus blocks: expand -> the ordinary launch in place on the scratch -> mix, piece by piece on one stream
     struct BusShape { int64_t group = 1, groups = 1, inWidth = 0, outWidth = 0, inPitch = 0, outPitch = 0; };
     static constexpr size_t kBusScratchBytes = (size_t)64 << 20;   // 32 samples of 524 288 instances: real-time blocks are never cut
-    int checkBus(const float* in, const float* out, const float* tapOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
+    int checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
     int ensureBusScratch(size_t floats);
     int ensureBusStage(size_t floats);
     // where the tap kernel of a block stores: the caller's rows as the device addresses them (pitch tapTotal_, at the columns of
     // the device list), or the compact [rows][tapCount_] staging block of a pageable tapOut.  dst null: this batch launches none
+    struct AuxRoute { float* dst = nullptr; int64_t pitch = 0; bool columns = false, staged = false; };   // the same for the fold kernel of the sends
     struct TapRoute { uint32_t* dst = nullptr; int64_t pitch = 0; bool columns = false, staged = false; };
     int runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-               const BusShape& shape, hipStream_t stream, const TapRoute* tap = nullptr);
+               const BusShape& shape, hipStream_t stream, const TapRoute* tap = nullptr, const AuxRoute* aux = nullptr);
+    int busPieceSamples(int nSamples) const;   // the samples of the largest piece runBus cuts a block of nSamples into
     float* dBus_ = nullptr;         // the per-instance scratch [samples of a piece][channels][n]
     size_t busCap_ = 0;             // floats
     float* dBusStage_ = nullptr;    // pageable host buffers: the [samples][channels][groups] sides of a block
@@ -509,6 +544,31 @@ private:
     int planTapRoute(float* tapOut, const void* devTap, size_t rows, TapRoute* route);   // devTap: tapOut as the device addresses it, or null (staged)
     hipError_t queueTapCopyOut(const TapRoute& route, float* tapOut, size_t rows, hipStream_t stream);
     void placeTapColumns(const TapRoute& route, float* tapOut, size_t rows);   // behind the wait for that copy
+    // bus sends (fx_batch_bus_send.cpp): the structure as the host holds it and one device block of 32-bit words - members,
+    // gain block 0, gain block 1, chunk table, bus table, at sendOff_[0..4].  Only busSetSends / busSetSendGains write it, behind a
+    // wait for everything queued.
+    SendSet send_;
+    uint32_t* dSend_ = nullptr;
+    uint32_t* dSendReserved_ = nullptr;  // busReserveSends: the block of the set to come
+    size_t sendReservedWords_ = 0;
+    size_t sendOff_[5] = {0, 0, 0, 0, 0};
+    int64_t sendChunks_ = 0;
+    bool sendIdentity_ = true;           // bus j is column j of the caller's rows (a handle of one shard)
+    int sendTarget_ = 0;                 // which gain block is b
+    bool sendRampPending_ = false;
+    float* dSendPartial_ = nullptr;      // [rows of a piece][sendChunks_] chunk sums, grown on demand in front of a block
+    size_t sendPartialCap_ = 0;          // floats
+    float* dAuxStage_ = nullptr;         // pageable auxOut: [rows][buses of this batch] on the device, grown on demand
+    size_t auxStageCap_ = 0;
+    float* hAuxStage_ = nullptr;         // ... and, for a shard that places its columns on the host, the same block in pinned memory
+    size_t hAuxStageCap_ = 0;
+    int64_t busSendBlocks_ = 0;          // FXB_INFO_BUS_SEND_BLOCKS
+    size_t sendBlockWords(int64_t buses, int64_t entries, size_t chunks) const;
+    void freeSendBlocks();
+    int planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, AuxRoute* route);   // devAux: auxOut as the device addresses it, or null (staged)
+    hipError_t queueAuxCopyOut(const AuxRoute& route, float* auxOut, size_t rows, hipStream_t stream);
+    void placeAuxColumns(const AuxRoute& route, float* auxOut, size_t rows);   // behind the wait for that copy
+    hipError_t launchSends(const AuxRoute& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s);
     const float* busCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one
     const float* busCheckedOut_ = nullptr;
     size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;
@@ -517,6 +577,9 @@ private:
     const float* busCheckedTap_ = nullptr;  // ... and the last d_tap_out
     size_t busCheckedTapBytes_ = 0;
     float* busCheckedDevTap_ = nullptr;
+    const float* busCheckedAux_ = nullptr;  // ... and the last d_aux_out
+    size_t busCheckedAuxBytes_ = 0;
+    float* busCheckedDevAux_ = nullptr;
     // instance-major blocks: gather -> the ordinary launch in place on the bus scratch -> scatter (the scratch, evBus_ and
     // busLaunched_ are shared with bus blocks: the two kinds may alternate, on different streams)
     int runImajor(const float* in, int64_t inStride, float* out, int64_t outStride, int nSamples, hipStream_t stream);

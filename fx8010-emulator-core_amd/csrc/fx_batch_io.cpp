@@ -507,7 +507,7 @@ bool Batch::busBuffersApart(const float* in, const float* out, size_t rows, int6
 }
 
 // The refusals of the bus entries, in front of everything else: a refused call has launched nothing and changed nothing.
-int Batch::checkBus(const float* in, const float* out, const float* tapOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
+int Batch::checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
     if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
     if (group < 1) return fail(FX_E_ARG, "bus: group must be at least 1");
     if (flags & ~(unsigned)kBusFlags) return fail(FX_E_ARG, "bus: unknown flag bits");
@@ -525,6 +525,9 @@ int Batch::checkBus(const float* in, const float* out, const float* tapOut, int 
     if (nSamples > 0 && !busBuffersApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
         return fail(FX_E_ARG, "bus: input and output overlap without being one buffer with one layout");
     if (const char* why = checkTapShape(in, out, tapOut, (size_t)std::max(nSamples, 0) * (size_t)prog_.numChannels, tapTotal_, flags, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
+        return fail(FX_E_ARG, why);
+    if (const char* why = checkAuxShape(nSamples > 0 ? in : nullptr, nSamples > 0 ? out : nullptr, tapOut, auxOut, (size_t)std::max(nSamples, 0) * (size_t)prog_.numChannels,
+                                        send_.totalBuses, tapTotal_, flags, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
         return fail(FX_E_ARG, why);
     *shape = s;
     return 0;
@@ -564,8 +567,15 @@ int Batch::ensureBusStage(size_t floats) {
 // scratch by the runtime), narrowIn / narrowOut: the per-group sides as the device addresses them.  A block whose scratch would
 // exceed kBusScratchBytes runs in consecutive sample ranges that fit - consecutive blocks to the kernel, like the pieces of
 // processHostPipelined; with control tracks armed the block stays whole (a schedule counts samples from the head of ONE launch).
+int Batch::busPieceSamples(int nSamples) const {
+    const size_t perSample = (size_t)prog_.numChannels * (size_t)n_;
+    const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
+    const int pieces = (nSamples + most - 1) / most;
+    return (nSamples + pieces - 1) / pieces;
+}
+
 int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-                  const BusShape& shape, hipStream_t stream, const TapRoute* tap) {
+                  const BusShape& shape, hipStream_t stream, const TapRoute* tap, const AuxRoute* aux) {
     const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
     const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
     const int pieces = (nSamples + most - 1) / most;
@@ -636,6 +646,11 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
                 return hipFail(e, "bus: the tap kernel");
             }
         }
+        // ... and so do the sends, behind the taps and in front of the mix: chunk sums, then the fold to the aux rows
+        if (aux && aux->dst && (e = launchSends(*aux, first, a.rows, nSamples, lo(p), s)) != hipSuccess) {
+            if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
+            return hipFail(e, "bus: the send kernels");
+        }
         if (flags & kBusMixOut) {
             a.narrowIn = nullptr;
             a.narrowOut = narrowOut + first * (size_t)narrowOutPitch;
@@ -651,6 +666,10 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
     }
     ++busBlocks_;   // (blocks whose every piece was queued)
     if (tap) ++busTapBlocks_;   // (counted by every shard that was handed the rows, whether or not an entry falls into it)
+    if (aux) {
+        ++busSendBlocks_;           // (the same)
+        sendRampPending_ = false;   // consumed, as the ramp of the bus gains below
+    }
     if (weighted) {
         ++busGainBlocks_;
         gainRampPending_ = false;   // consumed: a counts as b from here on (fx_batch.hpp)
@@ -659,17 +678,20 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
 }
 
 int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
-                      float* tapOut) {
+                      float* tapOut, float* auxOut) {
     (void)hipSetDevice(device_);
     BusShape shape;
-    int rc = checkBus(in, out, tapOut, nSamples, group, flags, inPitch, outPitch, &shape);
+    int rc = checkBus(in, out, tapOut, auxOut, nSamples, group, flags, inPitch, outPitch, &shape);
     if (rc != 0) return rc;
     if (nSamples == 0) return ensureLowered();
     const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels;
     const size_t inBytes = pcmExtent(rows, shape.inWidth, shape.inPitch), outBytes = pcmExtent(rows, shape.outWidth, shape.outPitch);
     const size_t tapBytes = rows * (size_t)tapTotal_ * 4;
-    const void *devIn = nullptr, *devOut = nullptr, *devTap = nullptr;
+    const size_t auxBytes = rows * (size_t)send_.totalBuses * 4;
+    const size_t pieceRows = (size_t)busPieceSamples(nSamples) * (size_t)prog_.numChannels;
+    const void *devIn = nullptr, *devOut = nullptr, *devTap = nullptr, *devAux = nullptr;
     TapRoute route;
+    AuxRoute auxRoute;
     if (entry == kBusDevice) {
         if (in != busCheckedIn_ || out != busCheckedOut_ || inBytes > busCheckedInBytes_ || outBytes > busCheckedOutBytes_) {
             busCheckedIn_ = busCheckedOut_ = nullptr;
@@ -690,9 +712,18 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
             busCheckedTapBytes_ = tapBytes;
             busCheckedDevTap_ = static_cast<float*>(const_cast<void*>(devTap));
         }
+        if (auxOut && (auxOut != busCheckedAux_ || auxBytes > busCheckedAuxBytes_)) {
+            busCheckedAux_ = nullptr;
+            if (!addressable(auxOut, auxBytes, device_, &devAux))
+                return fail(FX_E_ARG, "d_aux_out: not memory of this handle's device or device-visible host memory over the whole block");
+            busCheckedAux_ = auxOut;
+            busCheckedAuxBytes_ = auxBytes;
+            busCheckedDevAux_ = static_cast<float*>(const_cast<void*>(devAux));
+        }
         if (tapOut && (rc = planTapRoute(tapOut, busCheckedDevTap_, rows, &route)) != 0) return rc;
+        if (auxOut && (rc = planAuxRoute(auxOut, busCheckedDevAux_, rows, pieceRows, &auxRoute)) != 0) return rc;
         return runBus(busCheckedDevIn_, busCheckedDevOut_, busCheckedDevIn_, shape.inPitch, busCheckedDevOut_, shape.outPitch, nSamples, flags, shape, stream,
-                      tapOut ? &route : nullptr);
+                      tapOut ? &route : nullptr, auxOut ? &auxRoute : nullptr);
     }
     // Host entry.  Pinned buffers: the bus kernels read the group words from and store the sums to the caller's memory over PCIe
     // (256 bytes per wavefront access), no copies.  Anything else: the [sample][channel][group] sides are staged.  Whatever
@@ -705,16 +736,24 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         if ((rc = planTapRoute(tapOut, devTap, rows, &route)) != 0) return rc;
     }
     const TapRoute* tap = tapOut ? &route : nullptr;
+    // ... and the aux rows of the sends theirs, in the same way
+    if (auxOut) {
+        if (!(knobs_.hostPipeline && addressable(auxOut, auxBytes, -1, &devAux))) devAux = nullptr;
+        if ((rc = planAuxRoute(auxOut, devAux, rows, pieceRows, &auxRoute)) != 0) return rc;
+    }
+    const AuxRoute* aux = auxOut ? &auxRoute : nullptr;
     if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && addressable(out, outBytes, -1, &devOut)) {
         const float* dIn = static_cast<const float*>(devIn);
         float* dOut = static_cast<float*>(const_cast<void*>(devOut));
-        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap);
+        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap, aux);
         hipError_t te = hipSuccess;
         if (rc == 0 && tap) te = queueTapCopyOut(route, tapOut, rows, stream_);
+        if (rc == 0 && te == hipSuccess && aux) te = queueAuxCopyOut(auxRoute, auxOut, rows, stream_);
         const hipError_t se = hipStreamSynchronize(stream_);
         if (rc != 0) return rc;
         if (te != hipSuccess || se != hipSuccess) return hipFail(te != hipSuccess ? te : se, "synchronising a bus block on pinned host buffers");
         if (tap) placeTapColumns(route, tapOut, rows);
+        if (aux) placeAuxColumns(auxRoute, auxOut, rows);
         ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
         return 0;
     }
@@ -730,13 +769,15 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         (void)hipStreamSynchronize(stream_);
         return hipFail(e, "bus H2D");
     }
-    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap);
+    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap, aux);
     if (rc == 0 && mixOut) e = copyRows(out, (size_t)shape.outPitch * 4, stageOut, narrow, narrow, rows, hipMemcpyDefault, stream_);
     if (rc == 0 && e == hipSuccess && tap) e = queueTapCopyOut(route, tapOut, rows, stream_);
+    if (rc == 0 && e == hipSuccess && aux) e = queueAuxCopyOut(auxRoute, auxOut, rows, stream_);
     const hipError_t se = hipStreamSynchronize(stream_);
     if (rc != 0) return rc;
     if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "bus D2H");
     if (tap) placeTapColumns(route, tapOut, rows);
+    if (aux) placeAuxColumns(auxRoute, auxOut, rows);
     ++hostStagedBlocks_;
     return 0;
 }

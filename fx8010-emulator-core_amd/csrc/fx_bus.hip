@@ -1,6 +1,6 @@
 // fx_bus.hip — the kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
 // per-instance scratch, mix the scratch down to one word per group - plain (fx_bus_mix) or with per-instance gains (fx_bus_mix_gain) -
-// and gather a list of its columns into a narrow monitor side (fx_bus_tap).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
+// gather a list of its columns into a narrow monitor side (fx_bus_tap), and sum member lists of them onto aux buses (fx_bus_send_*).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
 // which may be pinned host memory behind PCIe, sees exactly one 256-byte access per wavefront and row.  The wide side: the expand
 // stores 1 KiB per wavefront access; the mix loads 256 contiguous bytes per access for groups of 64 instances and more, and ONE
 // PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
@@ -260,6 +260,147 @@ __global__ __launch_bounds__(64) void fx_bus_tap(BusTapArgs a) {
     }
 }
 
+// ---- the sends (fx_bus.hpp BusSendArgs): aux buses by member list, summed chunk by chunk --------------------------------------
+//
+// fx_bus_send_chunks: grid.x = the chunks of the host-built table, grid.y = groups of kSendRows rows (a loop where a block has
+// more groups than a grid may have).  A chunk is at most 1 024 consecutive entries of ONE bus: sixteen 64-lane steps.  Per step a
+// lane loads its instance number and its gain words once (256 contiguous bytes per wavefront each) and then issues the eight
+// rows' gathers wide[row][idx] - a 32-bit byte stride of n * 4 apart - before the first add, as fx_bus_tap does; eight partial
+// sums stay in registers.  After the last step come eight trees, and lanes 0..7 store the eight chunk sums to partial[row][chunk].
+// The gain words depend on the row's channel: kCh = 1 and 2 load one and two words per block and step (row groups begin at a
+// multiple of eight rows, so row u of a group is channel u % kCh); kCh = 0 is every other channel count and loads per row.
+// A ragged last group predicates its loads and stores by row: nothing outside the block's rows is read.  The index and the gain
+// words of step j + 1 are requested behind the gathers of step j, so that only a chunk's first step waits for them.
+constexpr int kSendRows = 8;
+
+// one chunk over the eight rows from row0 on; kFull: all eight exist (no predicate anywhere)
+template <bool kRamp, int kCh, bool kFull>
+__device__ __forceinline__ void sendRowGroup(const BusSendArgs& a, const BusSendChunk ck, const long long row0, const unsigned lane) {
+    const uint32_t loadStride = (uint32_t)a.n * 4u;   // (below 2^32: launchBusSend)
+    constexpr int kGains = kCh > 0 ? kCh : kSendRows;
+    float t[kSendRows];
+    bool atTarget[kSendRows], rowOk[kSendRows];
+    long long gainRow[kGains];
+#pragma unroll
+    for (int u = 0; u < kSendRows; ++u) {
+        const long long row = row0 + u;
+        const long long s = row / a.channels + a.sample0;   // the sample of the CALL this row belongs to
+        t[u] = (float)(s + 1) * a.r;
+        atTarget[u] = s == (long long)a.samples - 1;
+        rowOk[u] = kFull || row < a.rows;
+        if (kCh == 0) gainRow[u] = (row % a.channels) * a.gainPitch;
+    }
+    if (kCh > 0) {
+#pragma unroll
+        for (int c = 0; c < kGains; ++c) gainRow[c] = (long long)c * a.gainPitch;
+    }
+    float p[kSendRows];
+#pragma unroll
+    for (int u = 0; u < kSendRows; ++u) p[u] = 0.0f;
+    const char* base = reinterpret_cast<const char*>(a.wide + row0 * a.n);
+    // a step's instance number and gain words (lanes beyond the chunk's end read its first entry and add nothing)
+    auto fetch = [&](uint32_t m0, uint32_t& inst, float (&ga)[kGains], float (&gb)[kGains]) {
+        const uint32_t m = m0 + lane;
+        const uint32_t e = ck.first + (m < ck.count ? m : 0u);
+        inst = a.idx[e];
+#pragma unroll
+        for (int c = 0; c < kGains; ++c) {
+            const bool need = kCh > 0 || rowOk[c];
+            gb[c] = need ? a.target[gainRow[c] + e] : 0.0f;
+            ga[c] = (kRamp && need) ? a.current[gainRow[c] + e] : 0.0f;
+        }
+    };
+    uint32_t inst;
+    float ga[kGains], gb[kGains];
+    fetch(0u, inst, ga, gb);
+    for (uint32_t m0 = 0; m0 < ck.count; m0 += 64u) {
+        const bool have = m0 + lane < ck.count;
+        float y[kSendRows];
+        const char* q = base + (size_t)inst * 4u;
+#pragma unroll
+        for (int u = 0; u < kSendRows; ++u) {
+            y[u] = rowOk[u] ? *reinterpret_cast<const float*>(q) : 0.0f;
+            q += loadStride;
+        }
+        // the next step's index and gains go out behind this step's gathers, so that only the first step waits for them
+        uint32_t instNext = inst;
+        float gaNext[kGains], gbNext[kGains];
+#pragma unroll
+        for (int c = 0; c < kGains; ++c) gaNext[c] = gbNext[c] = 0.0f;
+        if (m0 + 64u < ck.count) fetch(m0 + 64u, instNext, gaNext, gbNext);
+#pragma unroll
+        for (int u = 0; u < kSendRows; ++u) {
+            const int c = kCh > 0 ? u % kGains : u;
+            const float term = termOf(weightOf<kRamp>(ga[c], gb[c], t[u], atTarget[u]), y[u]);
+            p[u] = have ? p[u] + term : p[u];
+        }
+        inst = instNext;
+#pragma unroll
+        for (int c = 0; c < kGains; ++c) {
+            ga[c] = gaNext[c];
+            gb[c] = gbNext[c];
+        }
+    }
+    float mine = 0.0f;
+#pragma unroll
+    for (int u = 0; u < kSendRows; ++u) {
+        const float sum = treeSum(p[u]);
+        if ((int)lane == u) mine = sum;
+    }
+    if (lane < (unsigned)kSendRows && (kFull || row0 + lane < a.rows)) a.partial[(row0 + lane) * a.chunks + blockIdx.x] = mine;
+}
+
+template <bool kRamp, int kCh>
+__global__ __launch_bounds__(64) void fx_bus_send_chunks(BusSendArgs a) {
+    const unsigned lane = threadIdx.x;
+    const BusSendChunk ck = a.chunk[blockIdx.x];
+    const long long groups = (a.rows + kSendRows - 1) / kSendRows;
+    for (long long grp = blockIdx.y; grp < groups; grp += gridDim.y) {
+        const long long row0 = grp * kSendRows;
+        if (row0 + kSendRows <= a.rows) sendRowGroup<kRamp, kCh, true>(a, ck, row0, lane);
+        else sendRowGroup<kRamp, kCh, false>(a, ck, row0, lane);
+    }
+}
+
+// fx_bus_send_fold: the ragged fx_bus_mix over partial.  grid.x = blocks of 64 buses, grid.y strides over the rows.  Lane k takes
+// bus g0 + k: +0.0f for an empty one, a copy of its chunk sum for one chunk (all such lanes in one gather); a bus of more chunks
+// is walked by the whole wavefront, 256 contiguous bytes per load, one tree, and its word lands in lane k.  One 256-byte store per
+// wavefront and row to the narrow side (identity columns), or to the columns of the table.
+__global__ __launch_bounds__(64) void fx_bus_send_fold(BusSendArgs a) {
+    const unsigned lane = threadIdx.x;
+    const long long g0 = (long long)blockIdx.x * 64;
+    const bool mineHere = g0 + lane < a.buses;
+    BusSendBus b{0u, 0u, 0u};
+    if (mineHere) b = a.bus[g0 + lane];
+    const uint32_t column = a.columns ? b.column : (uint32_t)(g0 + lane);
+    const unsigned long long wideBuses = __ballot(mineHere && b.chunks > 1u);
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        const float* c = a.partial + row * a.chunks;
+        float res = 0.0f;
+        if (mineHere && b.chunks == 1u) res = c[b.firstChunk];
+        for (unsigned long long left = wideBuses; left != 0ull; left &= left - 1ull) {
+            const int k = __ffsll((long long)left) - 1;
+            const uint32_t first = laneWord(b.firstChunk, (unsigned)k), count = laneWord(b.chunks, (unsigned)k);
+            float p = 0.0f;
+            for (uint32_t m0 = 0; m0 < count; m0 += 256u) {
+                float v[4];
+                bool have[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const uint32_t m = m0 + (uint32_t)u * 64u + lane;
+                    have[u] = m < count;
+                    v[u] = have[u] ? c[first + m] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) p = have[u] ? p + v[u] : p;
+            }
+            const float sum = treeSum(p);
+            if ((int)lane == k) res = sum;
+        }
+        if (mineHere) a.auxOut[row * a.auxPitch + column] = res;
+    }
+}
+
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
 }  // namespace
@@ -309,6 +450,35 @@ hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.taps + 63) / 64), (unsigned)(chunks < 65535 ? chunks : 65535));
     (void)hipGetLastError();
     hipLaunchKernelGGL(fx_bus_tap, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream) {
+    constexpr long long kMostBuses = 65536, kMostEntries = (long long)1 << 24;
+    if (!a.wide || !a.bus || !a.auxOut || a.rows < 1 || a.n < 1 || a.n >= ((long long)1 << 30) || a.buses < 1 || a.buses > kMostBuses || a.auxPitch < a.buses ||
+        a.auxPitch > kMostBuses || a.entries < 0 || a.entries > kMostEntries || a.chunks < 0 || a.chunks > a.entries || a.chunks > kMostEntries / kSendChunk + kMostBuses ||
+        (a.entries > 0) != (a.chunks > 0) || a.channels < 1 || a.rows % a.channels != 0 || a.samples < 1 || a.sample0 < 0 ||
+        (long long)a.sample0 + a.rows / a.channels > (long long)a.samples)
+        return hipErrorInvalidValue;
+    if (a.chunks > 0 && (!a.idx || !a.target || (a.ramp && !a.current) || !a.chunk || !a.partial || a.gainPitch < a.entries)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    if (a.chunks > 0) {
+        const long long groups = (a.rows + kSendRows - 1) / kSendRows;
+        const dim3 grid((unsigned)a.chunks, (unsigned)(groups < 65535 ? groups : 65535));
+        if (a.ramp) {
+            if (a.channels == 1) hipLaunchKernelGGL((fx_bus_send_chunks<true, 1>), grid, dim3(64), 0, stream, a);
+            else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_send_chunks<true, 2>), grid, dim3(64), 0, stream, a);
+            else hipLaunchKernelGGL((fx_bus_send_chunks<true, 0>), grid, dim3(64), 0, stream, a);
+        } else {
+            if (a.channels == 1) hipLaunchKernelGGL((fx_bus_send_chunks<false, 1>), grid, dim3(64), 0, stream, a);
+            else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_send_chunks<false, 2>), grid, dim3(64), 0, stream, a);
+            else hipLaunchKernelGGL((fx_bus_send_chunks<false, 0>), grid, dim3(64), 0, stream, a);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid((unsigned)((a.buses + 63) / 64), (unsigned)(a.rows < 65535 ? a.rows : 65535));
+    hipLaunchKernelGGL(fx_bus_send_fold, grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -63,4 +63,38 @@ struct BusTapArgs {
 // columns are (256 bytes per wavefront once T >= 64); the load is a gather
 hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream);
 
+// Bus sends (include/fx8010_amd.h "Bus sends"): aux buses by member list.  Bus j owns `entries` of a CSR structure; the entries
+// are cut into chunks of at most kSendChunk positions of ONE bus (the host builds the table), every chunk is summed by one
+// wavefront in the order of launchBusMix, and a bus with more than one chunk is the same sum over its chunk sums.
+constexpr long long kSendChunk = 1024;   // part of the contract, not a tuning knob
+struct BusSendChunk { uint32_t first, count; };          // entries first .. first + count - 1, 1 <= count <= kSendChunk
+struct BusSendBus { uint32_t firstChunk, chunks, column; };   // Q = chunks (0: an empty bus); column of auxOut where `columns` is set
+struct BusSendArgs {
+    const float* wide;            // [rows][n] per-instance scratch, rows packed (device memory)
+    const uint32_t* idx;          // [entries] instance numbers of this batch, each below n (device memory; the caller has checked them)
+    const float* current;         // a: [channels][gainPitch] by entry, read only while a ramp is pending (may be null otherwise)
+    const float* target;          // b
+    const BusSendChunk* chunk;    // [chunks] (device memory); every first + count <= entries
+    const BusSendBus* bus;        // [buses] (device memory); every firstChunk + chunks <= chunks of the launch
+    float* partial;               // [rows][chunks] chunk sums (device memory), written by the first kernel, read by the second
+    float* auxOut;                // [rows][auxPitch] (device memory or device-visible host memory)
+    long long rows;               // samples * channels
+    long long n;                  // instances; n * 4 < 2^32
+    long long entries;            // E of this batch (may be 0: every bus is empty)
+    long long gainPitch;          // floats per channel row of both gain blocks (>= entries)
+    long long chunks;             // of the table (0 iff entries == 0)
+    long long buses;              // of this batch, 1 <= buses <= 65 536
+    long long auxPitch;           // floats per row of auxOut (>= buses; with `columns`, above every column)
+    int columns;                  // 1: bus j goes to column bus[j].column; 0: to column j
+    int channels;                 // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
+    int ramp;                     // as BusGainArgs
+    float r;
+    int samples;
+    int sample0;
+};
+
+// partial[r][q] = the sum of chunk q's terms (w == 0.0f ? +0.0f : w * wide[r][idx[e]]) in the order of launchBusMix, then
+// auxOut[r][column of bus j] = partial[r][firstChunk] for one chunk, that same sum over the bus's chunk sums for more, +0.0f for none
+hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream);
+
 }  // namespace fx

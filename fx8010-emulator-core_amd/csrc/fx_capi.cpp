@@ -240,6 +240,19 @@ int fxb_bus_set_taps(fxb_handle* h, const int64_t* list, int64_t count) { return
 int64_t fxb_bus_get_taps(fxb_handle* h, int64_t* list, int64_t cap) {
     return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.busGetTaps(list, cap); }) : (int64_t)FX_E_ARG;
 }
+int fxb_process_block_bus_aux(fxb_handle* h, const float* in, float* out, float* tap_out, float* aux_out, int n, int64_t group, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(in, out, n, group, flags, false, nullptr, tap_out, aux_out); }) : FX_E_ARG;
+}
+int fxb_process_block_bus_aux_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, float* d_aux_out, int n, int64_t group, unsigned flags, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream), d_tap_out, d_aux_out); }) : FX_E_ARG;
+}
+int fxb_bus_set_sends(fxb_handle* h, int64_t n_aux, const int64_t* offsets, const int64_t* members, const float* gains) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetSends(n_aux, offsets, members, gains); }) : FX_E_ARG;
+}
+int fxb_bus_set_send_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetSendGains(gains, ramp); }) : FX_E_ARG; }
+int64_t fxb_bus_get_sends(fxb_handle* h, int64_t* n_aux, int64_t* offsets, int64_t off_cap, int64_t* members, float* gains, int64_t cap) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.busGetSends(n_aux, offsets, off_cap, members, gains, cap); }) : (int64_t)FX_E_ARG;
+}
 int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGains(gains, ramp); }) : FX_E_ARG; }
 int fxb_bus_get_gains(fxb_handle* h, float* gains) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busGetGains(gains); }) : FX_E_ARG; }
 int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n, int64_t in_stride, int64_t out_stride) {

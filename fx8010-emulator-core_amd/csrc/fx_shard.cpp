@@ -1,6 +1,8 @@
 // fx_shard.cpp — fan-out / fan-in over the shards of a multi-GPU batch (see fx_shard.hpp).
 #include "fx_shard.hpp"
 
+#include <cmath>
+
 #include <cstring>
 
 #include <algorithm>
@@ -258,7 +260,7 @@ int Sharded::processDevicePitched(const float* dIn, float* dOut, int nSamples, i
     if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
     return runOn(0, [&](Batch& b) { return b.processDeviceChecked(dIn, dOut, nSamples, pitch, stream); });
 }
-int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut) {
+int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut, float* auxOut) {
     Serial serial(api_);
     lastError_.clear();
     // the refusals that go by the WHOLE batch, before any shard is posted (a refused call launches nothing on any shard)
@@ -269,9 +271,13 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
         lastError_ = Batch::checkTapShape(nullptr, nullptr, tapOut, 0, front().busTaps(), flags, 0, 0, 0, 0);
         return FX_E_ARG;
     }
+    if (auxOut && (front().busSendBuses() < 1 || !(flags & Batch::kBusMixOut))) {
+        lastError_ = Batch::checkAuxShape(nullptr, nullptr, nullptr, auxOut, 0, front().busSendBuses(), 0, flags, 0, 0, 0, 0);
+        return FX_E_ARG;
+    }
     if (flags == 0) return device ? processDevicePitched(in, out, nSamples, n_, stream) : processHost(in, out, nSamples, 0);
     if (shards_.size() == 1)
-        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream, tapOut); });
+        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream, tapOut, auxOut); });
     for (auto& w : shards_)
         if (w->first % group != 0) { lastError_ = "bus: a group straddles shards (every shard must begin at a multiple of the group size: fxb_shard_plan)"; return FX_E_ARG; }
     const int64_t groups = (n_ + group - 1) / group;
@@ -286,11 +292,18 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
             lastError_ = why;
             return FX_E_ARG;
         }
+    // (... and the aux rows against all of that and the tap rows)
+    if (nSamples > 0)
+        if (const char* why = Batch::checkAuxShape(in, out, tapOut, auxOut, (size_t)nSamples * (size_t)front().channels(), front().busSendBuses(), front().busTaps(), flags, inPitch,
+                                                   inPitch, outPitch, outPitch)) {
+            lastError_ = why;
+            return FX_E_ARG;
+        }
     return fan([&](int k, Batch& b) {
         const int64_t first = shards_[(size_t)k]->first;
         const float* shardIn = in ? in + ((flags & Batch::kBusSharedIn) ? first / group : first) : in;
         float* shardOut = out ? out + ((flags & Batch::kBusMixOut) ? first / group : first) : out;
-        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr, tapOut);
+        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr, tapOut, auxOut);
     });
 }
 int Sharded::processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream) {
@@ -393,6 +406,92 @@ int64_t Sharded::busGetTaps(int64_t* list, int64_t cap) {
     if (cap < 0 || (cap > 0 && !list)) { lastError_ = "bus taps: a null list with room asked for"; return FX_E_ARG; }
     int64_t total = 0;
     for (auto& w : shards_) total = w->batch->busGetTaps(list, cap, w->first);   // (host state only: no device call)
+    return total;
+}
+
+int Sharded::busSetSends(int64_t nAux, const int64_t* offsets, const int64_t* members, const float* gains) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (nAux < 0 || nAux > Batch::kMaxSendBuses) { lastError_ = "bus sends: n_aux must be 0..65536"; return FX_E_ARG; }
+    if (nAux == 0) return fan([](int, Batch& b) { return b.busSetSends(Batch::SendSet{}); });
+    if (!offsets) { lastError_ = "bus sends: null offsets"; return FX_E_ARG; }
+    if (offsets[0] != 0) { lastError_ = "bus sends: offsets[0] must be 0"; return FX_E_ARG; }
+    for (int64_t b = 0; b < nAux; ++b)
+        if (offsets[b + 1] < offsets[b]) { lastError_ = "bus sends: offsets must not decrease"; return FX_E_ARG; }
+    const int64_t entries = offsets[nAux];
+    if (entries > Batch::kMaxSendEntries) { lastError_ = "bus sends: more than 16 777 216 entries"; return FX_E_ARG; }
+    if (entries > 0 && !members) { lastError_ = "bus sends: null members"; return FX_E_ARG; }
+    for (int64_t e = 0; e < entries; ++e)
+        if (members[e] < 0 || members[e] >= n_) { lastError_ = "bus sends: a member outside 0..N-1"; return FX_E_ARG; }
+    const size_t ch = (size_t)front().channels();
+    if (gains)
+        for (size_t i = 0; i < ch * (size_t)entries; ++i)
+            if (!std::isfinite(gains[i])) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
+    // a bus is summed where its members live: no collective on the data path, and no bits that depend on the split
+    std::vector<int> owner((size_t)nAux, 0);
+    for (int64_t b = 0; b < nAux; ++b)
+        for (int64_t e = offsets[b]; e < offsets[b + 1]; ++e) {
+            const int s = shardOf(members[e]);
+            if (e == offsets[b]) owner[(size_t)b] = s;
+            else if (s != owner[(size_t)b]) {
+                lastError_ = "bus sends: the members of aux bus " + std::to_string(b) + " fall into more than one shard (fxb_shard_plan tells the boundaries)";
+                return FX_E_ARG;
+            }
+        }
+    std::vector<Batch::SendSet> parts(shards_.size());
+    for (size_t k = 0; k < parts.size(); ++k) {
+        parts[k].totalBuses = nAux;
+        parts[k].totalEntries = entries;
+    }
+    for (int64_t b = 0; b < nAux; ++b) {
+        Batch::SendSet& part = parts[(size_t)owner[(size_t)b]];
+        const int64_t first = shards_[(size_t)owner[(size_t)b]]->first;
+        for (int64_t e = offsets[b]; e < offsets[b + 1]; ++e) part.members.push_back(members[e] - first);
+        part.offsets.push_back((int64_t)part.members.size());
+        part.column.push_back(b);
+        part.first.push_back(offsets[b]);
+    }
+    for (Batch::SendSet& part : parts) {
+        const size_t mine = part.members.size();
+        part.gain[0].assign(ch * mine, 1.0f);
+        if (gains)
+            for (size_t c = 0; c < ch; ++c)
+                for (size_t j = 0; j < part.column.size(); ++j) {
+                    const size_t lo = (size_t)part.offsets[j], count = (size_t)part.offsets[j + 1] - lo;
+                    if (count > 0) std::memcpy(&part.gain[0][c * mine + lo], gains + c * (size_t)entries + (size_t)part.first[j], count * 4);
+                }
+    }
+    // every shard reserves the block of its buses first; only when all of them could does any shard's structure change
+    const int rc = fan([&](int k, Batch& b) {
+        const Batch::SendSet& part = parts[(size_t)k];
+        return b.busReserveSends((int64_t)part.column.size(), (int64_t)part.members.size(), (int64_t)part.chunkCount());
+    });
+    if (rc != 0) {
+        const std::string why = lastError();
+        fan([](int, Batch& b) { b.busReleaseSends(); return 0; });
+        lastError_ = why;
+        return rc;
+    }
+    return fan([&](int k, Batch& b) { return b.busSetSends(std::move(parts[(size_t)k])); });
+}
+int Sharded::busSetSendGains(const float* gains, int ramp) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (ramp != 0 && ramp != 1) { lastError_ = "bus sends: ramp must be 0 or 1"; return FX_E_ARG; }
+    if (front().busSendBuses() < 1) { lastError_ = "bus sends: sends are off (fxb_bus_set_sends)"; return FX_E_ARG; }
+    const size_t words = (size_t)front().channels() * (size_t)front().busSendEntries();
+    if (words > 0 && !gains) { lastError_ = "null buffer"; return FX_E_ARG; }
+    for (size_t i = 0; i < words; ++i)
+        if (!std::isfinite(gains[i])) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
+    return fan([&](int, Batch& b) { return b.busSetSendGains(gains, ramp); });
+}
+int64_t Sharded::busGetSends(int64_t* nAux, int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (offCap < 0 || cap < 0) { lastError_ = "bus sends: a negative capacity"; return FX_E_ARG; }
+    if (nAux) *nAux = front().busSendBuses();
+    int64_t total = 0;
+    for (auto& w : shards_) total = w->batch->busGetSends(offsets, offCap, members, gains, cap, w->first);   // (host state only: no device call)
     return total;
 }
 
@@ -628,7 +727,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

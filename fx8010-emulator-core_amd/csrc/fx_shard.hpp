@@ -71,7 +71,8 @@ public:
     // on a side with its flag.  Every shard must begin at a multiple of `group` (fxb_shard_plan tells the boundaries) and works on
     // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
     // tapOut (null: none): the caller's full-width [sample][channel][T] rows of the taps in force; a shard writes its entries' columns
-    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut = nullptr);
+    int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut = nullptr,
+                   float* auxOut = nullptr);   // auxOut (null: none): the full-width [sample][channel][A] rows of the sends in force; a shard writes its buses' columns
     // instance-major blocks (Batch::processImajor): shard k works on the runs from in + first_k * inStride on, on its own thread
     // and device.  device: the caller's stream, single-shard handles only.
     int processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream);
@@ -91,6 +92,13 @@ public:
     // FX_E_MEMORY leaves the old taps in force everywhere.  count 0 turns them off.  get: T, and the first min(T, cap) entries.
     int busSetTaps(const int64_t* list, int64_t count);
     int64_t busGetTaps(int64_t* list, int64_t cap);
+    // bus sends (Batch::busSetSends ...): the CSR structure holds GLOBAL instance numbers and is checked as a whole before any
+    // shard is posted; a bus belongs to the shard its members fall into (all into one, else FX_E_ARG naming the bus; an empty bus
+    // to the first shard), every shard reserves its device block first, so FX_E_MEMORY leaves the old sends in force everywhere.
+    // nAux 0 turns them off.  get: E, and what fits under the caps.
+    int busSetSends(int64_t nAux, const int64_t* offsets, const int64_t* members, const float* gains);
+    int busSetSendGains(const float* gains, int ramp);
+    int64_t busGetSends(int64_t* nAux, int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap);
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

@@ -232,6 +232,33 @@ public:
         if (fxb_process_block_bus_tap(h_, in, out, tapOut, nSamples, group, flags) < 0)
             throw std::runtime_error(std::string("FX8010Batch::processBlockBusTap: ") + fxb_last_error(h_));
     }
+    // bus sends (include/fx8010_amd.h "Bus sends"): aux buses by member list, CSR - bus b owns members[offsets[b] .. offsets[b+1]),
+    // global instance numbers in any order, repeats allowed; gains is [channels][E] or empty for 1.0f everywhere; an offsets of
+    // at most one value turns sends off.  busSetSendGains replaces the weights, with ramp over the next block that is given aux
+    // rows.  processBlockBusAux is processBlockBusTap (tapOut may be nullptr) with auxOut = [nSamples][channels][A]: pre-fader
+    // sums in the order the header fixes; it needs mixOut.
+    void busSetSends(const std::vector<int64_t>& offsets, const std::vector<int64_t>& members, const std::vector<float>& gains = {}) {
+        const int64_t buses = offsets.empty() ? 0 : (int64_t)offsets.size() - 1;
+        if (fxb_bus_set_sends(h_, buses, offsets.empty() ? nullptr : offsets.data(), members.empty() ? nullptr : members.data(), gains.empty() ? nullptr : gains.data()) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::busSetSends: ") + fxb_last_error(h_));
+    }
+    void busSetSendGains(const std::vector<float>& gains, bool ramp = false) {
+        if (fxb_bus_set_send_gains(h_, gains.data(), ramp ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::busSetSendGains: ") + fxb_last_error(h_));
+    }
+    struct BusSends { std::vector<int64_t> offsets, members; std::vector<float> gains; };   // gains: the ones in force ([channels][E])
+    BusSends busSends(int channels) {
+        int64_t buses = 0;
+        const int64_t entries = fxb_bus_get_sends(h_, &buses, nullptr, 0, nullptr, nullptr, 0);
+        if (entries < 0) throw std::runtime_error(std::string("FX8010Batch::busSends: ") + fxb_last_error(h_));
+        BusSends s{std::vector<int64_t>((size_t)buses + 1, 0), std::vector<int64_t>((size_t)entries), std::vector<float>((size_t)channels * (size_t)entries)};
+        if (buses > 0) fxb_bus_get_sends(h_, nullptr, s.offsets.data(), buses + 1, s.members.data(), s.gains.data(), entries);
+        return s;
+    }
+    void processBlockBusAux(const float* in, float* out, float* tapOut, float* auxOut, int nSamples, int64_t group, bool sharedIn = true, bool mixOut = true) {
+        const unsigned flags = (sharedIn ? FXB_BUS_SHARED_IN : 0u) | (mixOut ? FXB_BUS_MIX_OUT : 0u);
+        if (fxb_process_block_bus_aux(h_, in, out, tapOut, auxOut, nSamples, group, flags) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::processBlockBusAux: ") + fxb_last_error(h_));
+    }
     // per-instance gains of the mixed output (include/fx8010_amd.h "Bus gains"): gains is [channels][instances], every value finite,
     // or nullptr for gains off (the unweighted sum); with ramp the next mixing block moves every weight linearly from the gains in
     // force to these and ends exactly on them.  A gain of zero mutes: that instance adds +0.0f whatever it holds.  busGetGains

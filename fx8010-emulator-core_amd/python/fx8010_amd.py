@@ -25,7 +25,7 @@ INFO = {
     "num_shadowed": 11, "num_ccr_live": 12, "device": 13, "grid": 14, "inst_per_lane": 15, "kernel": 16, "num_rows": 17,
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
-    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42,
+    "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -40,6 +40,7 @@ SYMBOLS = [
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_bus_set_taps", "fxb_bus_get_taps", "fxb_process_block_bus_tap", "fxb_process_block_bus_tap_dev",
+    "fxb_bus_set_sends", "fxb_bus_set_send_gains", "fxb_bus_get_sends", "fxb_process_block_bus_aux", "fxb_process_block_bus_aux_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
@@ -99,6 +100,8 @@ def load():
     sig("fxb_bus_set_gains", i32, vp, vp, i32); sig("fxb_bus_get_gains", i32, vp, vp)
     sig("fxb_bus_set_taps", i32, vp, vp, i64); sig("fxb_bus_get_taps", i64, vp, vp, i64)
     sig("fxb_process_block_bus_tap", i32, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_tap_dev", i32, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
+    sig("fxb_bus_set_sends", i32, vp, i64, vp, vp, vp); sig("fxb_bus_set_send_gains", i32, vp, vp, i32); sig("fxb_bus_get_sends", i64, vp, vp, vp, i64, vp, vp, i64)
+    sig("fxb_process_block_bus_aux", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_aux_dev", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
@@ -507,13 +510,15 @@ class Batch(_Reports):
         """G = ceil(N / group): the columns of a shared input / a mixed output"""
         return self._check(int(self._lib.fxb_bus_groups(self._h, int(group))), "bus_groups")
 
-    def process_block_bus(self, x, group, shared_in=True, mix_out=True, out=None, tap_out=None, taps=False):
+    def process_block_bus(self, x, group, shared_in=True, mix_out=True, out=None, tap_out=None, taps=False, aux=False, aux_out=None):
         """A block with a shared input and / or a mixed output per group of `group` consecutive instances.  x: float32
         [S, channels, G] with shared_in (instance n hears column n // group), else [S, channels, N]; returns [S, channels, G] with
         mix_out (every group's sum, in the order include/fx8010_amd.h fixes), else [S, channels, N] (mono: the channel axis may be
         left out).  Into `out` when given; x and out in pinned memory (HostBuffer.array) are read and written in place.
         With taps=True or a tap_out (float32 [S, channels, T], T = len(bus_get_taps()); pinned: stored to in place) the block also
-        delivers the tapped instances' own output words, pre-fader, and returns (out, taps)."""
+        delivers the tapped instances' own output words, pre-fader, and returns (out, taps).
+        With aux=True or an aux_out (float32 [S, channels, A], A the aux buses of bus_set_sends; pinned: stored to in place) the
+        block also delivers the sends, pre-fader, and the result gets one more element at its end: (out, aux) or (out, taps, aux)."""
         G = self.bus_groups(group)
         x = np.ascontiguousarray(x, dtype=np.float32)
         S = x.shape[0]
@@ -523,6 +528,21 @@ class Batch(_Reports):
             out = np.empty(shape, dtype=np.float32)
         assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == int(np.prod(shape))
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        if aux_out is not None or aux:
+            lead = (S,) if x.ndim == 2 else (S, self.channels)
+            A = C.c_int64(0)
+            self._check(int(self._lib.fxb_bus_get_sends(self._h, C.byref(A), None, 0, None, None, 0)), "bus_get_sends")
+            if aux_out is None:
+                aux_out = np.empty(lead + (A.value,), dtype=np.float32)
+            assert aux_out.dtype == np.float32 and aux_out.flags["C_CONTIGUOUS"] and aux_out.flags["WRITEABLE"] and aux_out.size == int(np.prod(lead)) * A.value, "aux_out must be [S, channels, A]"
+            if tap_out is not None or taps:
+                T = int(self._lib.fxb_bus_get_taps(self._h, None, 0))
+                if tap_out is None:
+                    tap_out = np.empty(lead + (T,), dtype=np.float32)
+                assert tap_out.dtype == np.float32 and tap_out.flags["C_CONTIGUOUS"] and tap_out.flags["WRITEABLE"] and tap_out.size == int(np.prod(lead)) * T, "tap_out must be [S, channels, T]"
+            self._check(self._lib.fxb_process_block_bus_aux(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(tap_out.ctypes.data) if tap_out is not None else None,
+                                                            C.c_void_p(aux_out.ctypes.data), S, int(group), flags), "process_block_bus")
+            return (out, aux_out) if tap_out is None else (out, tap_out, aux_out)
         if tap_out is not None or taps:
             T = int(self._lib.fxb_bus_get_taps(self._h, None, 0))
             tshape = ((S,) if x.ndim == 2 else (S, self.channels)) + (T,)
@@ -535,10 +555,11 @@ class Batch(_Reports):
         self._check(self._lib.fxb_process_block_bus(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), S, int(group), flags), "process_block_bus")
         return out
 
-    def process_block_bus_dev(self, d_in, d_out, n_samples, group, shared_in=True, mix_out=True, stream=None, d_tap_out=None):
+    def process_block_bus_dev(self, d_in, d_out, n_samples, group, shared_in=True, mix_out=True, stream=None, d_tap_out=None, d_aux_out=None):
         """d_in / d_out: device pointers (ints) or contiguous float32 torch tensors, [n_samples, channels, G] on a side with its
         flag and [n_samples, channels, N] on the other; single-shard handles; asynchronous on `stream` (a hipStream_t as int).
-        d_tap_out: the same for the [n_samples, channels, T] rows of the taps in force (bus_set_taps)."""
+        d_tap_out: the same for the [n_samples, channels, T] rows of the taps in force (bus_set_taps); d_aux_out: for the
+        [n_samples, channels, A] rows of the sends in force (bus_set_sends)."""
         G = self.bus_groups(group)
 
         def ptr(t, width):
@@ -548,6 +569,12 @@ class Batch(_Reports):
             return t.data_ptr()
         a, b = ptr(d_in, G if shared_in else self.n), ptr(d_out, G if mix_out else self.n)
         flags = (BUS_SHARED_IN if shared_in else 0) | (BUS_MIX_OUT if mix_out else 0)
+        if d_aux_out is not None:
+            A = C.c_int64(0)
+            self._check(int(self._lib.fxb_bus_get_sends(self._h, C.byref(A), None, 0, None, None, 0)), "bus_get_sends")
+            t = ptr(d_tap_out, int(self._lib.fxb_bus_get_taps(self._h, None, 0))) if d_tap_out is not None else None
+            return self._check(self._lib.fxb_process_block_bus_aux_dev(self._h, C.c_void_p(a), C.c_void_p(b), C.c_void_p(t) if t is not None else None, C.c_void_p(ptr(d_aux_out, A.value)),
+                                                                        int(n_samples), int(group), flags, C.c_void_p(stream or 0)), "process_block_bus_dev")
         if d_tap_out is not None:
             t = ptr(d_tap_out, int(self._lib.fxb_bus_get_taps(self._h, None, 0)))
             return self._check(self._lib.fxb_process_block_bus_tap_dev(self._h, C.c_void_p(a), C.c_void_p(b), C.c_void_p(t), int(n_samples), int(group), flags,
@@ -585,6 +612,39 @@ class Batch(_Reports):
         if T:
             self._check(int(self._lib.fxb_bus_get_taps(self._h, C.c_void_p(lst.ctypes.data), T)), "bus_get_taps")
         return lst
+
+    def bus_set_sends(self, offsets, members, gains=None):
+        """The aux buses the next bus blocks with aux=True deliver beside the mix (include/fx8010_amd.h "Bus sends"): CSR - bus b
+        owns members[offsets[b]:offsets[b+1]], global instance numbers in any order, repeats allowed; gains float32 [channels, E]
+        (mono: [E]), None for 1.0 everywhere.  offsets None or of one value turns sends off."""
+        off = np.ascontiguousarray([0] if offsets is None else offsets, dtype=np.int64).reshape(-1)
+        mem = np.ascontiguousarray([] if members is None else members, dtype=np.int64).reshape(-1)
+        A = max(int(off.size) - 1, 0)
+        g = None
+        if gains is not None and A > 0:
+            g = np.ascontiguousarray(gains, dtype=np.float32)
+            assert g.size == self.channels * int(off[-1]) and mem.size >= int(off[-1]), "gains must be [channels, E]"
+        assert A == 0 or mem.size >= int(off[-1]), "members must hold offsets[-1] entries"
+        return self._check(self._lib.fxb_bus_set_sends(self._h, A, C.c_void_p(off.ctypes.data), C.c_void_p(mem.ctypes.data) if mem.size else None,
+                                                       C.c_void_p(g.ctypes.data) if g is not None else None), "bus_set_sends")
+
+    def bus_set_send_gains(self, gains, ramp=False):
+        """New weights [channels, E] for the sends in force; with ramp the next block with aux moves every weight linearly from
+        the ones in force to these and ends exactly on them (the state machine of bus_set_gains)."""
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        E = self._check(int(self._lib.fxb_bus_get_sends(self._h, None, None, 0, None, None, 0)), "bus_get_sends")
+        assert g.size == self.channels * E, "gains must be [channels, E]"
+        return self._check(self._lib.fxb_bus_set_send_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_send_gains")
+
+    def bus_get_sends(self):
+        """(offsets int64 [A + 1], members int64 [E], gains float32 [channels, E]) of the sends in force - the gains are a, as
+        bus_get_gains returns them - or (array([0]), empty, empty) while sends are off"""
+        A = C.c_int64(0)
+        E = self._check(int(self._lib.fxb_bus_get_sends(self._h, C.byref(A), None, 0, None, None, 0)), "bus_get_sends")
+        off, mem, g = np.zeros(A.value + 1, dtype=np.int64), np.zeros(E, dtype=np.int64), np.zeros((self.channels, E), dtype=np.float32)
+        if A.value:
+            self._check(int(self._lib.fxb_bus_get_sends(self._h, None, C.c_void_p(off.ctypes.data), off.size, C.c_void_p(mem.ctypes.data), C.c_void_p(g.ctypes.data), E)), "bus_get_sends")
+        return off, mem, g
 
     def _stream_stride(self, shape, strides):
         """the instance stride (in floats) when an [N, S, channels] array is N interleaved [S][channels] runs at one stride, else None"""

@@ -366,6 +366,69 @@ int64_t fxb_bus_get_taps(fxb_handle* h, int64_t* list, int64_t cap);
 int     fxb_process_block_bus_tap(fxb_handle* h, const float* in, float* out, float* tap_out, int n_samples, int64_t group, unsigned flags);
 int     fxb_process_block_bus_tap_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, int n_samples, int64_t group, unsigned flags,
                                       void* stream);
+/* Bus sends: aux buses by member list beside the group mix - an effects bus fed by "a little of every voice", a bus whose members
+ * are not K consecutive slots, a voice on several buses at once - without taking all N columns over PCIe.  Sends are a mode of
+ * the handle like the meters, the gains and the taps, off by default: no flag bit is taken and no existing signature or result
+ * changes.
+ *
+ * The structure.  There are A = n_aux aux buses.  Bus b owns the entries e = offsets[b] .. offsets[b+1] - 1 of `members` (CSR:
+ * offsets has A + 1 values, offsets[0] = 0, non-decreasing, E = offsets[A]); members[e] is a global instance number.  Any order
+ * and repeats are allowed, within a bus and across buses; an empty bus is allowed.  gains is [num_channels][E], one weight per
+ * channel and entry; NULL means 1.0f everywhere.
+ *
+ * fxb_bus_set_sends: n_aux == 0 turns sends off and frees their memory.  FX_E_ARG with nothing changed: A < 0 or A > 65 536,
+ *   E > 16 777 216, a null array that is needed, offsets not as above, a member outside 0..N-1, a non-finite gain.  The arrays are
+ *   copied before the call returns.  All allocation happens here, on every shard before any shard changes: FX_E_MEMORY leaves the
+ *   old sends in force everywhere.  The call waits for the queued blocks as fxb_bus_set_taps does.  It sets a = b = gains and
+ *   cancels a pending ramp.  Works before a program is loaded; the sends survive program loads; they are not part of the state
+ *   image or of instance records, and fxb_copy_instances / fxb_reset_instances do not touch them.
+ * fxb_bus_set_send_gains: replaces the weights of the structure in force ([num_channels][E], finite, else FX_E_ARG; FX_E_ARG
+ *   while sends are off) by the current / target state machine of fxb_bus_set_gains: ramp = 0: a = b = gains; ramp = 1: b = gains
+ *   and a ramp is pending (a is the old b, or stays where a ramp was pending already).  The next block that is given an aux_out
+ *   consumes the ramp; blocks without one leave it pending.  Queued blocks keep the weights they were queued with (the call waits
+ *   for them).
+ * fxb_bus_get_sends: returns E (0 while sends are off), stores A to *n_aux, and copies what fits: offsets[0 .. min(A + 1,
+ *   off_cap) - 1], and the entries below cap of members and of every channel row of gains (row pitch E).  gains is a, as
+ *   fxb_bus_get_gains returns.  Any pointer may be NULL.
+ *
+ * The block.  aux_out is [n_samples][num_channels][A] with a row pitch of exactly A.  aux_out == NULL is
+ * fxb_process_block_bus_tap[_dev] with the remaining arguments.  With it, `out`, tap_out, instance state, meters, the bus gains
+ * with their pending ramp, armed control tracks and every other FXB_INFO_* counter are exactly what that call leaves.
+ * Sends are PRE-FADER: they read the same per-instance block as the meters and the taps, in front of the mix; the bus gains and
+ * their mute do not act on them.  A host that wants a post-fader send multiplies when it sets the send gains; a NaN voice is kept
+ * off an aux bus by a send gain of 0.
+ *
+ * The sum.  Let T(v_0 .. v_{L-1}) be the order of the group mix: 64 partial sums p[0..63] start at +0.0f; for j = 0, 1, ..
+ * every v_{j*64+l} that exists is added to p[l]; then for step = 32 .. 1: p[l] = p[l] + p[l+step] for l < step; T is p[0].
+ * Everything is fp32, round to nearest, never fused, denormals kept.  For bus b, channel c and sample s of a call of S samples,
+ * the entry at position m (e = offsets[b] + m) has the term (w == 0.0f) ? +0.0f : w * y, where y is the word fxb_process_block on
+ * the expanded input writes at out[(s*C + c)*N + members[e]] and w comes from that entry's a / b and the ramp exactly as the
+ * "Bus gains" comment defines it (t = (float)(s+1) * r, r = 1.0f / (float)S with S the caller's block, exactly b on the last
+ * sample).  The positions are cut into chunks of 1 024: c_q = T(the terms of positions q*1024 .. q*1024 + 1023 that exist).
+ * With M_b <= 1 024 entries the bus word is c_0 itself (+0.0f for M_b = 0); otherwise it is T(c_0 .. c_{Q-1}), Q = ceil(M_b /
+ * 1024).  So a bus of at most 1 024 entries that lists the members of a group in ascending order with that group's gains carries
+ * the words of the (weighted) group mix; a larger one does not - the price of many wavefronts per bus.  NaN payloads are not
+ * promised.  1 024 is part of the contract.
+ *
+ * FX_E_ARG (nothing launched, nothing changed): aux_out non-null while sends are off; aux_out non-null without FXB_BUS_MIX_OUT
+ * (the same reason as for taps); aux_out sharing a byte with the footprint of `in`, `out` or tap_out; every refusal of
+ * fxb_process_block_bus_tap*; the device entry on a handle of several shards or with a d_aux_out the device cannot address over
+ * the whole block (checked and remembered like the other buffers).
+ * Routes are those of the tap rows, independently of how in / out / tap_out go: a pinned aux_out is stored to in place; any
+ * other goes through a device staging block that grows on demand in front of the block's first launch (FX_E_MEMORY: nothing
+ * launched) and is copied out before the call returns.  A block cut into sample ranges by the 64 MiB scratch delivers each
+ * range's rows to aux_out + first_row * A.  n_samples == 0 lowers the program and returns 0.
+ * Sharded handles: there is no collective on the data path, and a sum across shards would make the bits depend on the split, so
+ * fxb_bus_set_sends is FX_E_ARG when the members of one aux bus fall into more than one shard (the message names the bus;
+ * fxb_shard_plan tells the boundaries).  Otherwise each shard gets its buses and writes only their columns of the caller's
+ * full-width aux_out; a shard with no bus launches nothing.
+ * FXB_INFO_BUS_SEND_BLOCKS counts the bus blocks that were given an aux_out: once per block and shard. */
+int     fxb_bus_set_sends(fxb_handle* h, int64_t n_aux, const int64_t* offsets, const int64_t* members, const float* gains);
+int     fxb_bus_set_send_gains(fxb_handle* h, const float* gains, int ramp);
+int64_t fxb_bus_get_sends(fxb_handle* h, int64_t* n_aux, int64_t* offsets, int64_t off_cap, int64_t* members, float* gains, int64_t cap); /* returns E */
+int     fxb_process_block_bus_aux(fxb_handle* h, const float* in, float* out, float* tap_out, float* aux_out, int n_samples, int64_t group, unsigned flags);
+int     fxb_process_block_bus_aux_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, float* d_aux_out, int n_samples, int64_t group, unsigned flags,
+                                      void* stream);
 /* Instance-major blocks: one interleaved stream per instance, transposed on the device.  Instance n's input is the
  * n_samples * num_channels floats at in + n * in_stride, ordered [sample][channel] - what n_samples calls of the reference's
  * process() consume and what a WAV file holds - and its output goes to out + n * out_stride the same way.
@@ -518,7 +581,8 @@ enum {
     FXB_INFO_INSTANCE_GATHERS = 39,    /* launches of the kernel fx_inst_gather - by fxb_copy_instances and fxb_save_instances - since creation (summed over shards) */
     FXB_INFO_INSTANCE_SCATTERS = 40,   /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
     FXB_INFO_BUS_GAIN_BLOCKS = 41,     /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
-    FXB_INFO_BUS_TAP_BLOCKS = 42       /* bus blocks that delivered taps (fxb_process_block_bus_tap* with a tap_out) since creation (summed over shards) */
+    FXB_INFO_BUS_TAP_BLOCKS = 42,      /* bus blocks that delivered taps (fxb_process_block_bus_tap* with a tap_out) since creation (summed over shards) */
+    FXB_INFO_BUS_SEND_BLOCKS = 43      /* bus blocks that delivered sends (fxb_process_block_bus_aux* with an aux_out) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

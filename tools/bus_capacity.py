@@ -33,6 +33,15 @@ of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel a
    traced stretch runs tapped and with meters on - fx_meter, which reads the whole per-instance block, is the yardstick in the same
    trace - and `--kernel-stats` then reports fx_bus_tap beside it.
 
+7. `--sends A`: what bus sends (fxb_bus_set_sends, fxb_process_block_bus_aux) cost a real-time host.  Every instance is a member
+   of each of A aux buses (ascending lists, weights of their own), delivered to a pinned [32][A] side.  At every count of
+   --send-instances two bus handles, without sends and with them, take turns in stretches in ONE process; median and p99.9 of
+   both are reported (`--sends-out FILE.txt` keeps the lines).  Before anything is timed the aux words must be the definition of
+   include/fx8010_amd.h applied to the plain path's output, and the two mixes must stay equal word for word.  With `--trace-run
+   --gains --sends A` the traced stretch is 200 blocks of one handle with static bus gains and the sends - fx_bus_mix_gain, which
+   moves 8 bytes per member where the sends move 12, is the yardstick in the same trace - and `--kernel-stats` then reports
+   fx_bus_send_chunks and fx_bus_send_fold beside it.
+
 Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
@@ -69,10 +78,33 @@ def mix_model(y, K):
     return p[..., 0]
 
 
+def tree_model(v):
+    """[..., L] -> [...]: T of include/fx8010_amd.h "Bus sends" (64 partial sums over j ascending, then the shuffle-down tree)"""
+    import numpy as np
+    L = v.shape[-1]
+    p = np.zeros(v.shape[:-1] + (64,), dtype=np.float32)
+    for j in range(-(-L // 64)):
+        w = min(64, L - j * 64)
+        p[..., :w] = p[..., :w] + v[..., j * 64:j * 64 + w]
+    for step in (32, 16, 8, 4, 2, 1):
+        p[..., :step] = p[..., :step] + p[..., step:2 * step]
+    return p[..., 0]
+
+
+def send_all_model(y, w):
+    """y [S, 1, n], w [A, n] (static weights, none of them zero) -> [S, 1, A]: every instance on each bus, ascending"""
+    import numpy as np
+    n = y.shape[-1]
+    assert n % 1024 == 0 and n > 1024
+    term = (w[None, :, :] * y[:, 0, None, :]).astype(np.float32)                       # [S, A, n]
+    chunks = tree_model(term.reshape(term.shape[:2] + (n // 1024, 1024)))             # [S, A, Q]
+    return np.ascontiguousarray(tree_model(chunks)[:, None, :])
+
+
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0):
+    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0, sends=0):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -105,6 +137,14 @@ class Path:
             self.b.bus_set_taps(self.tap_list)
             self.tap_out = A.HostBuffer((BLOCK, 1, taps))
             self.tp = C.c_void_p(self.tap_out.array.ctypes.data)
+        # sends: every instance on each of `sends` aux buses, ascending, bus a with weights of its own; a pinned [BLOCK][sends] side
+        self.sends, self.ap = sends, None
+        if sends:
+            base = (0.25 + 0.75 * (progs.stimulus(n, 1, seed=77)[0] * np.float32(0.5) + np.float32(0.5))).astype(np.float32)
+            self.send_gains = np.ascontiguousarray(np.stack([np.roll(base, 17 * a) for a in range(sends)]))   # [A, n] = [1][E]
+            self.b.bus_set_sends(np.arange(sends + 1, dtype=np.int64) * n, np.tile(np.arange(n, dtype=np.int64), sends), self.send_gains.reshape(1, -1))
+            self.aux_out = A.HostBuffer((BLOCK, 1, sends))
+            self.ap = C.c_void_p(self.aux_out.array.ctypes.data)
         self.b.prepare(BLOCK, True)
         self.k = 0
         self.times = []
@@ -115,7 +155,9 @@ class Path:
             assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
         if self.gains == "ramp" and self.lib.fxb_bus_set_gains(h, self.lp[(k + 1) % 2], 1) != 0:
             raise RuntimeError("set_gains in front of block %d failed: %s" % (k, self.b.last_error()))
-        if self.taps:
+        if self.sends:
+            rc = self.lib.fxb_process_block_bus_aux(h, self.xp[k % RING], self.yp, self.tp, self.ap, BLOCK, GROUP, 3)
+        elif self.taps:
             rc = self.lib.fxb_process_block_bus_tap(h, self.xp[k % RING], self.yp, self.tp, BLOCK, GROUP, 3)
         elif self.bus:
             rc = self.lib.fxb_process_block_bus(h, self.xp[k % RING], self.yp, BLOCK, GROUP, 3)
@@ -134,7 +176,7 @@ class Path:
 
     def close(self):
         self.b.close()
-        for h in self.ring + [self.out] + ([self.tap_out] if self.taps else []):
+        for h in self.ring + [self.out] + ([self.tap_out] if self.taps else []) + ([self.aux_out] if self.sends else []):
             h.close()
 
 
@@ -352,6 +394,54 @@ def taps_side_by_side(A, progs, n, taps, blocks, warm, stretch, log, clock=lambd
     return out
 
 
+def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lambda: None):
+    """bus blocks without sends and with every instance on each of `sends` aux buses by turns, in stretches, in one process"""
+    import numpy as np
+    # the aux words are the definition over the plain path's output, the mix is the one of the handle without sends
+    plain, off, on = Path(A, progs, n, False), Path(A, progs, n, True), Path(A, progs, n, True, sends=sends)
+    for _ in range(2):
+        for p in (plain, off, on):
+            p.block()
+        if not np.array_equal(on.aux_out.array.view(np.uint32), send_all_model(plain.out.array, on.send_gains).view(np.uint32)):
+            raise RuntimeError("the aux buses differ from the definition applied to the plain path's output at %d instances" % n)
+        if not np.array_equal(on.out.array.view(np.uint32), off.out.array.view(np.uint32)):
+            raise RuntimeError("the mix of the handle with sends differs from the one without at %d instances" % n)
+    plain.close()
+    paths = [("no sends", off), ("%d sends" % sends, on)]
+    clocks = {name: [] for name, _ in paths}
+    for _, p in paths:
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in paths:
+                p.stretch(stretch)
+                clocks[name].append(clock())
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "sends": sends, "stretch_blocks": stretch}
+    for name, p in paths:
+        r = rt.percentiles(p.times)
+        r.update({"blocks": len(p.times), "bus_send_blocks": p.b.info("bus_send_blocks")})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-10s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d blocks with sends  shader clock %s MHz" % (
+            name, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["p999_us"] <= BUDGET_US else "over budget",
+            r["bus_send_blocks"], r["shader_clock_mhz_behind_a_stretch"]))
+    same = off.k == on.k and np.array_equal(off.out.array.view(np.uint32), on.out.array.view(np.uint32))
+    out["outputs_equal"] = bool(same)
+    out["median_difference_us"] = round(out["%d sends" % sends]["median_us"] - out["no sends"]["median_us"], 1)
+    log("           N=%7d  mixes of the two %s; median with sends - median without: %+.1f us" % (n, "equal" if same else "DIFFER", out["median_difference_us"]))
+    off.close()
+    on.close()
+    return out
+
+
 def bus_row(A, progs, n, blocks, warm, log):
     """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
     block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
@@ -384,7 +474,7 @@ def bus_row(A, progs, n, blocks, warm, log):
     return r
 
 
-def kernel_shares(path, n, taps=0):
+def kernel_shares(path, n, taps=0, sends=0):
     """the --stats table of a `--trace-run` under rocprofv3: share of device time and achieved bytes/s of the two bus kernels"""
     rows = list(csv.DictReader(open(path)))
     total = sum(float(r["TotalDurationNs"]) for r in rows)
@@ -398,6 +488,10 @@ def kernel_shares(path, n, taps=0):
             "fx_bus_mix_gain<false>": ("fx_bus_mix_gain<false>", mix + n * 4), "fx_bus_mix_gain<true>": ("fx_bus_mix_gain<true>", mix + 2 * n * 4)}
     if taps:   # (the tapped words in and out, and the list)
         need["fx_bus_tap"] = ("fx_bus_tap", 2 * BLOCK * taps * 4 + taps * 4)
+    if sends:   # (per entry: the scratch word, the index and the gain word; the chunk sums out, and in again with the aux words out)
+        chunks = sends * -(-n // 1024)
+        need["fx_bus_send_chunks"] = ("fx_bus_send_chunks", sends * n * (BLOCK * 4 + 8) + BLOCK * chunks * 4)
+        need["fx_bus_send_fold"] = ("fx_bus_send_fold", BLOCK * (chunks + sends) * 4)
     out = {"instances": n, "device_time_ns": total, "kernels": {}}
     for r in rows:
         for key, (match, bytes_) in need.items():
@@ -430,12 +524,40 @@ def main():
     ap.add_argument("--taps", type=int, default=0, help="bus blocks untapped and with this many instances tapped by turns (with --trace-run: tapped, meters on)")
     ap.add_argument("--tap-instances", default="131072,458752")
     ap.add_argument("--taps-out", default="", help="keep the lines of --taps in this text file")
+    ap.add_argument("--sends", type=int, default=0, help="bus blocks without sends and with every instance on each of this many aux buses by turns "
+                    "(with --trace-run --gains: one handle with static bus gains and the sends)")
+    ap.add_argument("--send-instances", default="131072,458752")
+    ap.add_argument("--sends-out", default="", help="keep the lines of --sends in this text file")
     args = ap.parse_args()
     import torch  # first: its HIP runtime is the one the library binds to
 
     import fx8010_amd as A
     import fx8010_programs as progs
     log = lambda s: print(s, flush=True)
+    if args.trace_run and args.sends:
+        p = Path(A, progs, args.trace_instances, True, gains="static" if args.gains else None, sends=args.sends)
+        p.stretch(200, timed=False)
+        p.close()
+        return 0
+    if args.sends:
+        lines = []
+
+        def keep(s):
+            lines.append(s)
+            log(s)
+        keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us, without sends and with "
+             "every instance on each of %d aux buses delivered to a pinned side (fxb_process_block_bus_aux) by turns in stretches of %d blocks in one process, "
+             "%d blocks per point after %d warm-up blocks; %s" % (GROUP, BUDGET_US, args.sends, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+        rows = [sends_side_by_side(A, progs, int(v), args.sends, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.send_instances.split(",") if v]
+        if args.kernel_stats:
+            keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances, sends=args.sends)))
+        if args.sends_out:
+            with open(args.sends_out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump({"send_rows": rows}, fh, indent=1)
+        return 0 if all(r["outputs_equal"] for r in rows) else 1
     if args.trace_run and args.gains:
         paths = [Path(A, progs, args.trace_instances, True, gains=mode) for _, mode in GAIN_MODES]
         for _ in range(4):
