@@ -73,24 +73,23 @@ Batch::~Batch() {
     (void)hipFree(dTracks_);
     (void)hipFree(dIn_);
     (void)hipFree(dOut_);
-    (void)hipFree(dBus_);
-    (void)hipFree(dBusStage_);
+    freeBlock(bus_, false);
+    freeBlock(busStage_, false);
     (void)hipFree(dMeter_);
     (void)hipFree(dGain_[0]);
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
     if (evGain_) (void)hipEventDestroy(evGain_);
-    (void)hipFree(dTap_);
-    (void)hipFree(dTapReserved_);
-    (void)hipFree(dTapStage_);
-    if (hTapStage_) (void)hipHostFree(hTapStage_);
-    (void)hipFree(dSend_);
-    (void)hipFree(dSendReserved_);
+    (void)hipFree(tap_.cur);
+    (void)hipFree(tap_.reserved);
+    freeSideRows(tapRows_);
+    (void)hipFree(sendBlock_.cur);
+    (void)hipFree(sendBlock_.reserved);
     freeSendBlocks();
-    (void)hipFree(dInstList_);
-    (void)hipFree(dInstRec_);
-    if (hInstList_) (void)hipHostFree(hInstList_);
-    if (hInstRec_) (void)hipHostFree(hInstRec_);
+    freeBlock(instList_, false);
+    freeBlock(instRec_, false);
+    freeBlock(hInstList_, true);
+    freeBlock(hInstRec_, true);
     if (evInst_) (void)hipEventDestroy(evInst_);
     if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS

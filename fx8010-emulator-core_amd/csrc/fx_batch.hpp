@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "fx_asm.hpp"
+#include "fx_batch_bus_side.hpp"
 #include "fx_bus.hpp"
 #include "fx_imajor.hpp"
 #include "fx_instances.hpp"
@@ -86,7 +87,8 @@ public:
     // (rowPitch 0 = n), copied through pinned memory of the library; null turns the mode off (waits, frees).  busReserveGains is the
     // allocating half (everything the mode ever needs: FX_E_MEMORY changes nothing), called by busSetGains itself and, for
     // all-or-nothing over shards, by Sharded in front of it; busReleaseGains frees what a failed attempt left on a handle whose
-    // gains are off.  checked: the caller has found every value finite.  busGetGains is synchronous like meterRead.
+    // gains are off.  checked: the caller has found every value finite.  busGetGains is synchronous like meterRead.  Which of the
+    // two gain blocks a set writes and which is in force: RampPair (fx_batch_bus_side.hpp), as for the send gains.
     int busReserveGains();
     void busReleaseGains();
     int busSetGains(const float* gains, int64_t rowPitch, int ramp, bool checked = false);
@@ -99,7 +101,8 @@ public:
     // goes to column k and total == count); total is the T of the whole handle - a shard may own none of the entries (count 0) and
     // still has taps on.  total == 0 turns the mode off (waits, frees).  busReserveTaps is the allocating half (the device list of
     // the set to come: FX_E_MEMORY changes nothing), called by Sharded on every shard in front of any busSetTaps, which then waits
-    // for the queued blocks, swaps the lists and cannot run out of memory; busReleaseTaps drops a reservation that is not taken up.
+    // for the queued blocks, swaps the lists and cannot run out of memory; busReleaseTaps drops a reservation that is not taken up
+    // (ReservedBlock, fx_batch_bus_side.hpp).  The tap rows of a block go the side-row path of fx_batch_bus_side.cpp.
     // busGetTaps: list[pos[k]] = first + local entry k, for the columns below cap; returns total.
     static constexpr int64_t kMaxTaps = 65536;
     int busReserveTaps(int64_t count);
@@ -108,7 +111,8 @@ public:
     int64_t busGetTaps(int64_t* list, int64_t cap, int64_t first) const;
     int64_t busTaps() const { return tapTotal_; }
     // what a tapped call adds to the refusals of the bus entries that read nothing but the arguments (also asked by Sharded, for
-    // the whole batch): null, or why not.  The footprints of in / out are those of busBuffersApart.
+    // the whole batch): null, or why not.  The footprints of in / out are those of busBuffersApart; with either of them null
+    // nothing is compared.  (checkSideShape with the taps' texts.)
     static const char* checkTapShape(const float* in, const float* out, const float* tapOut, size_t rows, int64_t total, unsigned flags, int64_t inWidth, int64_t inPitch,
                                      int64_t outWidth, int64_t outPitch);
     // Bus sends (fx_bus.hpp BusSendArgs; include/fx8010_amd.h "Bus sends"): a mode of the handle.  While it is on, a bus block with
@@ -120,7 +124,8 @@ public:
     // allocating half (the device block of the set to come: FX_E_MEMORY changes nothing), called by Sharded on every shard in
     // front of any busSetSends, which then waits for the queued blocks, takes the block, sets a = b and cancels a pending ramp;
     // busReleaseSends drops a reservation that is not taken up.  busSetSendGains(gains = the caller's [C][totalEntries], finite)
-    // follows the state machine of busSetGains; the next block with an auxOut consumes a pending ramp.
+    // follows the state machine of busSetGains (RampPair); the next block with an auxOut consumes a pending ramp.  The reserved
+    // block and the aux rows of a block are the taps' ReservedBlock and side-row path (fx_batch_bus_side.hpp) over again.
     static constexpr int64_t kMaxSendBuses = 65536, kMaxSendEntries = (int64_t)1 << 24;
     struct SendSet {
         int64_t totalBuses = 0, totalEntries = 0;
@@ -140,9 +145,10 @@ public:
     int64_t busSendBuses() const { return send_.totalBuses; }
     int64_t busSendEntries() const { return send_.totalEntries; }
     // what an auxOut adds to the refusals of the bus entries that read nothing but the arguments (also asked by Sharded, for the
-    // whole batch): null, or why not
+    // whole batch): null, or why not; a null in / out / tapOut is merely not compared.  (checkSideShape with the sends' texts.)
     static const char* checkAuxShape(const float* in, const float* out, const float* tapOut, const float* auxOut, size_t rows, int64_t buses, int64_t taps, unsigned flags,
                                      int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
+    static const char* checkSideShape(const SideTexts& texts, const float* sideOut, size_t rows, int64_t total, unsigned flags, const Footprint* others, int nOthers);
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -489,106 +495,87 @@ private:
     unsigned lastGrid_ = 0;
     int64_t hostStagedBlocks_ = 0, hostInplaceBlocks_ = 0;   // host blocks by route (FXB_INFO_HOST_STAGED_BLOCKS / _INPLACE_BLOCKS)
     // processDeviceChecked: the last buffer pair that passed its checks (a real-time caller pays for the lookups once)
-    const float* checkedIn_ = nullptr;
-    const float* checkedOut_ = nullptr;
-    size_t checkedBytes_ = 0;
-    const float* checkedDevIn_ = nullptr;   // ... and the device addresses of the two
-    float* checkedDevOut_ = nullptr;
+    CheckedAddr checkedIn_, checkedOut_;
+    // `c` holds [p, p + bytes) when this returns 0; else FX_E_ARG with `what`, and c holds nothing
+    int lookup(CheckedAddr& c, const void* p, size_t bytes, const char* what);
+    // an input / output pair, checked together: a miss of either looks both up again, a refusal of either leaves neither cached
+    int lookupPair(CheckedAddr& cIn, const void* in, size_t inBytes, CheckedAddr& cOut, const void* out, size_t outBytes);
     // bus blocks: expand -> the ordinary launch in place on the scratch -> mix, piece by piece on one stream
     struct BusShape { int64_t group = 1, groups = 1, inWidth = 0, outWidth = 0, inPitch = 0, outPitch = 0; };
     static constexpr size_t kBusScratchBytes = (size_t)64 << 20;   // 32 samples of 524 288 instances: real-time blocks are never cut
     int checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
     int ensureBusScratch(size_t floats);
     int ensureBusStage(size_t floats);
-    // where the tap kernel of a block stores: the caller's rows as the device addresses them (pitch tapTotal_, at the columns of
-    // the device list), or the compact [rows][tapCount_] staging block of a pageable tapOut.  dst null: this batch launches none
-    struct AuxRoute { float* dst = nullptr; int64_t pitch = 0; bool columns = false, staged = false; };   // the same for the fold kernel of the sends
-    struct TapRoute { uint32_t* dst = nullptr; int64_t pitch = 0; bool columns = false, staged = false; };
+    // tap / aux: the routes of the two narrow sides beside the mix (fx_batch_bus_side.hpp Route; null: the caller gave no rows)
     int runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-               const BusShape& shape, hipStream_t stream, const TapRoute* tap = nullptr, const AuxRoute* aux = nullptr);
+               const BusShape& shape, hipStream_t stream, const Route* tap = nullptr, const Route* aux = nullptr);
     int busPieceSamples(int nSamples) const;   // the samples of the largest piece runBus cuts a block of nSamples into
-    float* dBus_ = nullptr;         // the per-instance scratch [samples of a piece][channels][n]
-    size_t busCap_ = 0;             // floats
-    float* dBusStage_ = nullptr;    // pageable host buffers: the [samples][channels][groups] sides of a block
-    size_t busStageCap_ = 0;
+    Block<float> bus_;              // the per-instance scratch [samples of a piece][channels][n]
+    Block<float> busStage_;         // pageable host buffers: the [samples][channels][groups] sides of a block
     hipEvent_t evBus_ = nullptr;    // behind the last kernel of the most recent bus block
     bool busLaunched_ = false;
     int64_t busBlocks_ = 0;         // FXB_INFO_BUS_BLOCKS
-    // bus gains (fx_batch_bus_gain.cpp): two blocks [channels][n], one of them the target b, the other the current set a.  a is
-    // only meaningful while a ramp is pending: without one a counts as equal to b and its block holds stale words, so consuming
-    // a ramp costs nothing on the device, and the next ramp makes the old target the current set by swapping the two roles.
+    // bus gains (fx_batch_bus_gain.cpp): two blocks [channels][n] whose roles gainRamp_ keeps (fx_batch_bus_side.hpp RampPair): a
+    // holds stale words unless a ramp is pending, so consuming a ramp costs nothing on the device.
     // Every write of a block is a copy on the handle's stream behind evBus_ (a block queued on whatever stream keeps the gains it
     // was queued with) and in front of evGain_ (a later block on whatever stream waits for it).
     float* dGain_[2] = {nullptr, nullptr};
-    int gainTarget_ = 0;            // which of the two is b
-    bool gainsOn_ = false, gainRampPending_ = false;
+    RampPair gainRamp_;
+    bool gainsOn_ = false;
     float* hGain_ = nullptr;        // pinned staging: the caller's columns, and the 1.0f block of a ramp out of "off"
     hipEvent_t evGain_ = nullptr;   // behind the most recent copy into a gain block
     bool gainCopied_ = false;       // ... which may still be running
     int64_t busGainBlocks_ = 0;     // FXB_INFO_BUS_GAIN_BLOCKS
     size_t gainFloats() const { return (size_t)prog_.numChannels * (size_t)n_; }
-    // bus taps (fx_batch_bus_tap.cpp): the list as the host holds it and as the kernel reads it - one device block, tapCount_
-    // instance numbers and, where the entries have columns of their own (a shard), tapCount_ columns behind them.  Only busSetTaps
-    // writes it, behind a wait for everything queued, so a queued block keeps the taps it was queued with.
+    // the pieces every mode of a bus block is made of (fx_batch_bus_side.cpp)
+    int growBlock(void** p, size_t* cap, size_t want, size_t bytesEach, bool pinned, const char* name);
+    void freeBlock(void** p, size_t* cap, bool pinned);
+    template <class T> int growBlock(Block<T>& b, size_t want, bool pinned, const char* name, size_t bytesEach = sizeof(T)) {
+        return growBlock(reinterpret_cast<void**>(&b.p), &b.cap, want, bytesEach, pinned, name);
+    }
+    template <class T> void freeBlock(Block<T>& b, bool pinned) { freeBlock(reinterpret_cast<void**>(&b.p), &b.cap, pinned); }
+    int reserveBlock(ReservedBlock& b, size_t words, const char* name);
+    void releaseBlock(ReservedBlock& b);
+    void takeUpBlock(ReservedBlock& b, bool any);
+    void freeSideRows(SideRows& side);
+    int planSideRoute(SideRows& side, const SideTexts& texts, float* out, const void* dev, size_t rows, size_t mine, int64_t total, const int64_t* place, Route* route);
+    hipError_t queueSideCopyOut(const SideRows& side, const Route& route, float* out, size_t rows, hipStream_t stream);
+    void placeSideColumns(const SideRows& side, const Route& route, float* out, size_t rows);
+    // bus taps (fx_batch_bus_tap.cpp): the list as the host holds it and as the kernel reads it - one device block (tap_.cur),
+    // tapCount() instance numbers and, where the entries have columns of their own (a shard), as many columns behind them.  Only
+    // busSetTaps writes it, behind a wait for everything queued, so a queued block keeps the taps it was queued with.
     std::vector<int64_t> tapList_, tapPos_;   // this batch's entries (local numbers) and their columns (empty: identity)
     int64_t tapTotal_ = 0;          // T of the whole handle; 0: taps are off
-    uint32_t* dTap_ = nullptr;      // [tapList_.size()] idx, then [tapPos_.size()] col
-    uint32_t* dTapReserved_ = nullptr;   // busReserveTaps: the block of the set to come
-    size_t tapReservedWords_ = 0;
-    uint32_t* dTapStage_ = nullptr;      // pageable tapOut: [rows][tapCount] on the device, grown on demand
-    size_t tapStageCap_ = 0;             // words
-    uint32_t* hTapStage_ = nullptr;      // ... and, for a shard that places its columns on the host, the same block in pinned memory
-    size_t hTapStageCap_ = 0;
+    ReservedBlock tap_;             // cur: [tapList_.size()] idx, then [tapPos_.size()] col; busReserveTaps: the block of the set to come
+    SideRows tapRows_;              // the caller's [S][C][T] side
+    static const SideTexts kTapTexts;
     int64_t busTapBlocks_ = 0;      // FXB_INFO_BUS_TAP_BLOCKS
     int64_t tapCount() const { return (int64_t)tapList_.size(); }
-    int planTapRoute(float* tapOut, const void* devTap, size_t rows, TapRoute* route);   // devTap: tapOut as the device addresses it, or null (staged)
-    hipError_t queueTapCopyOut(const TapRoute& route, float* tapOut, size_t rows, hipStream_t stream);
-    void placeTapColumns(const TapRoute& route, float* tapOut, size_t rows);   // behind the wait for that copy
-    // bus sends (fx_batch_bus_send.cpp): the structure as the host holds it and one device block of 32-bit words - members,
-    // gain block 0, gain block 1, chunk table, bus table, at sendOff_[0..4].  Only busSetSends / busSetSendGains write it, behind a
-    // wait for everything queued.
+    const int64_t* tapPlace() const { return tapPos_.empty() ? nullptr : tapPos_.data(); }
+    hipError_t launchTaps(const Route& route, size_t first, long long rows, hipStream_t s);
+    // bus sends (fx_batch_bus_send.cpp): the structure as the host holds it and one device block of 32-bit words (sendBlock_.cur) -
+    // members, gain block 0, gain block 1, chunk table, bus table, at sendOff_[0..4]; sendRamp_ keeps the roles of the two gain
+    // blocks.  Only busSetSends / busSetSendGains write it, behind a wait for everything queued.
     SendSet send_;
-    uint32_t* dSend_ = nullptr;
-    uint32_t* dSendReserved_ = nullptr;  // busReserveSends: the block of the set to come
-    size_t sendReservedWords_ = 0;
+    ReservedBlock sendBlock_;            // busReserveSends: the block of the set to come
     size_t sendOff_[5] = {0, 0, 0, 0, 0};
     int64_t sendChunks_ = 0;
     bool sendIdentity_ = true;           // bus j is column j of the caller's rows (a handle of one shard)
-    int sendTarget_ = 0;                 // which gain block is b
-    bool sendRampPending_ = false;
-    float* dSendPartial_ = nullptr;      // [rows of a piece][sendChunks_] chunk sums, grown on demand in front of a block
-    size_t sendPartialCap_ = 0;          // floats
-    float* dAuxStage_ = nullptr;         // pageable auxOut: [rows][buses of this batch] on the device, grown on demand
-    size_t auxStageCap_ = 0;
-    float* hAuxStage_ = nullptr;         // ... and, for a shard that places its columns on the host, the same block in pinned memory
-    size_t hAuxStageCap_ = 0;
+    RampPair sendRamp_;
+    Block<float> sendPartial_;           // [rows of a piece][sendChunks_] chunk sums, grown on demand in front of a block
+    SideRows auxRows_;                   // the caller's [S][C][A] side
+    static const SideTexts kAuxTexts;
     int64_t busSendBlocks_ = 0;          // FXB_INFO_BUS_SEND_BLOCKS
     size_t sendBlockWords(int64_t buses, int64_t entries, size_t chunks) const;
     void freeSendBlocks();
-    int planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, AuxRoute* route);   // devAux: auxOut as the device addresses it, or null (staged)
-    hipError_t queueAuxCopyOut(const AuxRoute& route, float* auxOut, size_t rows, hipStream_t stream);
-    void placeAuxColumns(const AuxRoute& route, float* auxOut, size_t rows);   // behind the wait for that copy
-    hipError_t launchSends(const AuxRoute& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s);
-    const float* busCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one
-    const float* busCheckedOut_ = nullptr;
-    size_t busCheckedInBytes_ = 0, busCheckedOutBytes_ = 0;
-    const float* busCheckedDevIn_ = nullptr;
-    float* busCheckedDevOut_ = nullptr;
-    const float* busCheckedTap_ = nullptr;  // ... and the last d_tap_out
-    size_t busCheckedTapBytes_ = 0;
-    float* busCheckedDevTap_ = nullptr;
-    const float* busCheckedAux_ = nullptr;  // ... and the last d_aux_out
-    size_t busCheckedAuxBytes_ = 0;
-    float* busCheckedDevAux_ = nullptr;
+    int planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, Route* route);   // the chunk sums of the largest piece, then planSideRoute
+    hipError_t launchSends(const Route& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s);
+    CheckedAddr busIn_, busOut_;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one (the last d_tap_out / d_aux_out: tapRows_ / auxRows_)
     // instance-major blocks: gather -> the ordinary launch in place on the bus scratch -> scatter (the scratch, evBus_ and
     // busLaunched_ are shared with bus blocks: the two kinds may alternate, on different streams)
     int runImajor(const float* in, int64_t inStride, float* out, int64_t outStride, int nSamples, hipStream_t stream);
     int64_t imajorBlocks_ = 0;      // FXB_INFO_IMAJOR_BLOCKS
-    const float* imajorCheckedIn_ = nullptr;   // kBusDevice: the last pair that passed its checks
-    const float* imajorCheckedOut_ = nullptr;
-    size_t imajorCheckedInBytes_ = 0, imajorCheckedOutBytes_ = 0;
-    const float* imajorCheckedDevIn_ = nullptr;
-    float* imajorCheckedDevOut_ = nullptr;
+    CheckedAddr imajorIn_, imajorOut_;   // kBusDevice: the last pair that passed its checks
     // per-instance state calls (fx_batch_instances.cpp): a device list and a record scratch of their own, allocated on first use,
     // grown on demand and kept - the records up to kInstScratchBytes, the size of the bus scratch (not shared with it: a bus block
     // on a caller's stream and a copy on the handle's stream then never wait for each other's scratch); a call whose records exceed
@@ -598,14 +585,10 @@ private:
     int beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords);   // lower, range check, lists -> device, order behind the blocks
     int endInstanceCall(bool wait);                           // evInst_ behind what was queued
     int64_t recordsPerPiece() const;
-    long long* dInstList_ = nullptr;     // [2][instListCap_]
-    size_t instListCap_ = 0;
-    long long* hInstList_ = nullptr;     // pinned, same shape
-    size_t hInstListCap_ = 0;
-    uint32_t* dInstRec_ = nullptr;
-    size_t instRecCap_ = 0;              // words
-    uint32_t* hInstRec_ = nullptr;       // pinned: the one record of a reset
-    size_t hInstRecCap_ = 0;             // words
+    Block<long long> instList_;          // [2][cap]: cap counts list entries
+    Block<long long> hInstList_;         // pinned, same shape
+    Block<uint32_t> instRec_;            // words
+    Block<uint32_t> hInstRec_;           // pinned: the one record of a reset
     hipEvent_t evInst_ = nullptr;        // behind the last kernel or copy of the most recent instance call
     bool instLaunched_ = false;          // ... which may still be running
     int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS

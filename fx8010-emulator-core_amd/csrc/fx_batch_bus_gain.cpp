@@ -1,8 +1,8 @@
 // fx_batch_bus_gain.cpp — the per-instance mix gains of bus blocks: the state of one batch (fx_batch.hpp "Bus gains", kernel:
 // fx_bus_mix_gain in fx_bus.hip, where it is launched: Batch::runBus).
 //
-// Two device blocks [channels][n]; gainTarget_ names the one that is b, the other one is a and means something only while a ramp
-// is pending.  A set copies the caller's columns into pinned staging on the host (the caller's array is free on return) and from
+// Two device blocks [channels][n]; gainRamp_ (fx_batch_bus_side.hpp RampPair, shared with the send gains) names the one that is
+// b, the other one is a and means something only while a ramp is pending.  A set copies the caller's columns into pinned staging on the host (the caller's array is free on return) and from
 // there, on the handle's stream, into the block that becomes b:
 //   gains off -> on        block 0 = b; with ramp the other block is filled with 1.0f (a while gains are off);
 //   ramp, none pending     a counts as the old b: the two blocks swap roles, the new values go into the block that was a;
@@ -71,7 +71,8 @@ int Batch::busSetGains(const float* gains, int64_t rowPitch, int ramp, bool chec
         if (!gainsOn_) return 0;
         const int rc = sync();   // (blocks queued with the gains still read them)
         if (rc != 0) return rc;  // (a failing call changes nothing: the gains stay on and their blocks stay allocated)
-        gainsOn_ = gainRampPending_ = false;
+        gainsOn_ = false;
+        gainRamp_.consume();
         busReleaseGains();
         return 0;
     }
@@ -87,7 +88,7 @@ int Batch::busSetGains(const float* gains, int64_t rowPitch, int ramp, bool chec
     const size_t block = gainFloats();
     for (int c = 0; c < ch; ++c) std::memcpy(hGain_ + (size_t)c * (size_t)n_, gains + (size_t)c * (size_t)rowPitch, (size_t)n_ * 4);
     const bool fromOff = !gainsOn_;
-    const int target = fromOff ? 0 : ((ramp && !gainRampPending_) ? gainTarget_ ^ 1 : gainTarget_);
+    const int target = fromOff ? 0 : gainRamp_.writeTarget(ramp);
     if (busLaunched_ && (e = hipStreamWaitEvent(stream_, evBus_, 0)) != hipSuccess) return hipFail(e, "bus gains: ordering behind the queued bus blocks");
     if (fromOff && ramp) {
         for (size_t i = 0; i < block; ++i) hGain_[block + i] = 1.0f;
@@ -100,9 +101,8 @@ int Batch::busSetGains(const float* gains, int64_t rowPitch, int ramp, bool chec
         return hipFail(e, "bus gains: copying to the device");
     }
     gainCopied_ = true;
-    gainTarget_ = target;
+    gainRamp_ = RampPair{target, ramp != 0};
     gainsOn_ = true;
-    gainRampPending_ = ramp != 0;
     return 0;
 }
 
@@ -116,7 +116,7 @@ int Batch::busGetGains(float* gains, int64_t rowPitch) {
     if (rc != 0) return rc;
     gainCopied_ = false;   // (the handle's stream has drained)
     // the gains in force: a while a ramp waits for its block, else b (a consumed ramp has left its target in force)
-    const float* from = dGain_[gainRampPending_ ? gainTarget_ ^ 1 : gainTarget_];
+    const float* from = dGain_[gainRamp_.inForce()];
     hipError_t e = hipSuccess;
     for (int c = 0; c < prog_.numChannels && e == hipSuccess; ++c)
         e = hipMemcpy(gains + (size_t)c * (size_t)rowPitch, from + (size_t)c * (size_t)n_, (size_t)n_ * 4, hipMemcpyDeviceToHost);

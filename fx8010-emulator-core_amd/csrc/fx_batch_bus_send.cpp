@@ -1,14 +1,15 @@
 // fx_batch_bus_send.cpp — the sends of bus blocks: the state of one batch (fx_batch.hpp "Bus sends", kernels: fx_bus_send_chunks
-// and fx_bus_send_fold in fx_bus.hip, where they are launched: Batch::runBus).
+// and fx_bus_send_fold in fx_bus.hip, launched by launchSends from Batch::runBus).
 //
 // The structure lives twice: on the host (send_, what busGetSends reads - the weights a and b included) and in ONE device block
-// of 32-bit words: the member numbers [E], the two gain blocks [C][E] whose roles swap from ramp to ramp like the bus gains', the
-// chunk table and the per-bus {first chunk, Q, column} table.  A set is two steps so that several shards can be all-or-nothing:
+// of 32-bit words: the member numbers [E], the two gain blocks [C][E] whose roles swap from ramp to ramp like the bus gains'
+// (sendRamp_, fx_batch_bus_side.hpp RampPair), the chunk table and the per-bus {first chunk, Q, column} table.  A set is two steps so that several shards can be all-or-nothing:
 // busReserveSends allocates the block of the set to come and touches nothing else, busSetSends waits for everything queued on the
 // handle (a queued block keeps the sends it was queued with), takes the reserved block and fills it with a synchronous copy.
 // busSetSendGains waits the same way and copies into the gain block that becomes b: structures and send levels change at human
 // rate, so there is no staging and no event of their own.  The only other allocations are the block of chunk sums and the staging
-// of a pageable aux_out (planAuxRoute), both made in front of a block's first launch.
+// of a pageable aux_out (planAuxRoute), both made in front of a block's first launch; the route, the copy-out and the placement of
+// the columns are the shared side-row path of fx_batch_bus_side.cpp.
 #include "fx_batch.hpp"
 
 #include <algorithm>
@@ -19,22 +20,18 @@
 
 namespace fx {
 
+const SideTexts Batch::kAuxTexts = {"bus sends: aux_out given while sends are off (fxb_bus_set_sends)",
+                                     "bus sends: aux_out needs FXB_BUS_MIX_OUT (without it `out` holds every column)",
+                                     "bus sends: aux_out overlaps the input, the output or the tap rows",
+                                     "d_aux_out: not memory of this handle's device or device-visible host memory over the whole block",
+                                     "hipMalloc bus send staging",
+                                     "pinned staging of the bus sends"};
+
 const char* Batch::checkAuxShape(const float* in, const float* out, const float* tapOut, const float* auxOut, size_t rows, int64_t buses, int64_t taps, unsigned flags,
                                  int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch) {
-    if (!auxOut) return nullptr;
-    if (buses < 1) return "bus sends: aux_out given while sends are off (fxb_bus_set_sends)";
-    if (!(flags & kBusMixOut)) return "bus sends: aux_out needs FXB_BUS_MIX_OUT (without it `out` holds every column)";
-    if (rows == 0) return nullptr;
-    const char* a = reinterpret_cast<const char*>(auxOut);
-    const size_t auxBytes = rows * (size_t)buses * 4;
-    auto meets = [&](const float* other, size_t bytes) {
-        const char* o = reinterpret_cast<const char*>(other);
-        return other && !(a + auxBytes <= o || o + bytes <= a);
-    };
-    if (meets(in, ((rows - 1) * (size_t)inPitch + (size_t)inWidth) * 4) || meets(out, ((rows - 1) * (size_t)outPitch + (size_t)outWidth) * 4) ||
-        meets(tapOut, rows * (size_t)std::max<int64_t>(taps, 0) * 4))
-        return "bus sends: aux_out overlaps the input, the output or the tap rows";
-    return nullptr;
+    const int64_t tapWidth = std::max<int64_t>(taps, 0);
+    const Footprint others[3] = {{in, inWidth, inPitch}, {out, outWidth, outPitch}, {tapOut, tapWidth, tapWidth}};
+    return checkSideShape(kAuxTexts, auxOut, rows, buses, flags, others, 3);
 }
 
 size_t Batch::SendSet::chunkCount() const {
@@ -51,35 +48,14 @@ size_t Batch::sendBlockWords(int64_t buses, int64_t entries, size_t chunks) cons
 int Batch::busReserveSends(int64_t buses, int64_t entries, int64_t chunks) {
     (void)hipSetDevice(device_);
     if (buses < 0 || buses > kMaxSendBuses || entries < 0 || entries > kMaxSendEntries || chunks < 0) return fail(FX_E_ARG, "bus sends: counts out of range");
-    busReleaseSends();
-    if (buses == 0) return 0;
-    const size_t words = sendBlockWords(buses, entries, (size_t)chunks);
-    if (hipMalloc(reinterpret_cast<void**>(&dSendReserved_), words * 4) != hipSuccess) {
-        dSendReserved_ = nullptr;
-        return hipFail(hipErrorOutOfMemory, "hipMalloc bus sends");
-    }
-    sendReservedWords_ = words;
-    return 0;
+    return reserveBlock(sendBlock_, buses == 0 ? 0 : sendBlockWords(buses, entries, (size_t)chunks), "hipMalloc bus sends");
 }
 
-void Batch::busReleaseSends() {
-    if (!dSendReserved_) return;
-    (void)hipSetDevice(device_);
-    (void)hipFree(dSendReserved_);
-    dSendReserved_ = nullptr;
-    sendReservedWords_ = 0;
-}
+void Batch::busReleaseSends() { releaseBlock(sendBlock_); }
 
 void Batch::freeSendBlocks() {
-    (void)hipFree(dSendPartial_);
-    dSendPartial_ = nullptr;
-    sendPartialCap_ = 0;
-    (void)hipFree(dAuxStage_);
-    dAuxStage_ = nullptr;
-    auxStageCap_ = 0;
-    if (hAuxStage_) (void)hipHostFree(hAuxStage_);
-    hAuxStage_ = nullptr;
-    hAuxStageCap_ = 0;
+    freeBlock(sendPartial_, false);
+    freeSideRows(auxRows_);
 }
 
 int Batch::busSetSends(SendSet&& set) {
@@ -97,7 +73,7 @@ int Batch::busSetSends(SendSet&& set) {
         if (m < 0 || m >= n_) return fail(FX_E_ARG, "bus sends: a member outside 0..N-1");
     const size_t chunks = set.chunkCount();
     const size_t words = sendBlockWords(buses, entries, chunks);
-    if (buses > 0 && sendReservedWords_ < words) {
+    if (buses > 0 && sendBlock_.reservedWords < words) {
         const int rc = busReserveSends(buses, entries, (int64_t)chunks);
         if (rc != 0) return rc;
     }
@@ -130,14 +106,10 @@ int Batch::busSetSends(SendSet&& set) {
     const int rc = sync();   // (blocks queued with the old structure still read it)
     if (rc != 0) return rc;
     if (buses > 0) {
-        const hipError_t e = hipMemcpy(dSendReserved_, image.data(), words * 4, hipMemcpyHostToDevice);
+        const hipError_t e = hipMemcpy(sendBlock_.reserved, image.data(), words * 4, hipMemcpyHostToDevice);
         if (e != hipSuccess) return hipFail(e, "bus sends: copying the structure to the device");
     }
-    (void)hipFree(dSend_);
-    dSend_ = buses > 0 ? dSendReserved_ : nullptr;
-    dSendReserved_ = nullptr;
-    sendReservedWords_ = 0;
-    if (buses == 0) busReleaseSends();
+    takeUpBlock(sendBlock_, buses > 0);
     sendOff_[0] = offIdx;
     sendOff_[1] = offGain[0];
     sendOff_[2] = offGain[1];
@@ -147,8 +119,7 @@ int Batch::busSetSends(SendSet&& set) {
     sendIdentity_ = buses == set.totalBuses;
     for (int64_t j = 0; j < buses && sendIdentity_; ++j) sendIdentity_ = set.column[(size_t)j] == j;
     send_ = std::move(set);
-    sendTarget_ = 0;
-    sendRampPending_ = false;   // a = b, and a ramp that was waiting for its block is gone
+    sendRamp_ = RampPair{};   // a = b, and a ramp that was waiting for its block is gone
     if (send_.totalBuses == 0) {
         send_ = SendSet{};
         freeSendBlocks();
@@ -173,23 +144,19 @@ int Batch::busSetSendGains(const float* gains, int ramp) {
         if (!std::isfinite(g)) return fail(FX_E_ARG, "bus sends: every gain must be finite");
     const int rc = sync();   // (blocks queued with the old weights still read them)
     if (rc != 0) return rc;
-    // the state machine of the bus gains: a ramp with none pending makes the old b the new a (the blocks swap roles); anything
-    // else replaces b where it is, and ramp = 0 drops a pending ramp
-    const int target = (ramp && !sendRampPending_) ? sendTarget_ ^ 1 : sendTarget_;
+    const int target = sendRamp_.writeTarget(ramp);   // (the state machine of the bus gains)
     if (mine > 0) {
-        const hipError_t e = hipMemcpy(dSend_ + sendOff_[1 + target], next.data(), next.size() * 4, hipMemcpyHostToDevice);
+        const hipError_t e = hipMemcpy(sendBlock_.cur + sendOff_[1 + target], next.data(), next.size() * 4, hipMemcpyHostToDevice);
         if (e != hipSuccess) return hipFail(e, "bus sends: copying the gains to the device");
     }
     send_.gain[target].swap(next);
-    sendTarget_ = target;
-    sendRampPending_ = ramp != 0;
+    sendRamp_ = RampPair{target, ramp != 0};
     return 0;
 }
 
 int64_t Batch::busGetSends(int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap, int64_t firstInstance) const {
     const size_t ch = (size_t)prog_.numChannels, mine = send_.members.size(), all = (size_t)send_.totalEntries;
-    // the gains in force: a while a ramp waits for its block, else b
-    const std::vector<float>& g = send_.gain[sendRampPending_ ? sendTarget_ ^ 1 : sendTarget_];
+    const std::vector<float>& g = send_.gain[sendRamp_.inForce()];
     for (size_t j = 0; j < send_.column.size(); ++j) {
         const int64_t lo = send_.offsets[j], hi = send_.offsets[j + 1], first = send_.first[j];
         if (offsets && send_.column[j] < offCap) offsets[send_.column[j]] = first;
@@ -204,87 +171,34 @@ int64_t Batch::busGetSends(int64_t* offsets, int64_t offCap, int64_t* members, f
     return send_.totalEntries;
 }
 
-// Where the fold kernel of this block stores, decided - and everything the sends of the block need allocated - before the block's
-// first launch: the chunk sums of the largest piece, and for a pageable aux_out the compact staging rows.
-int Batch::planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, AuxRoute* route) {
-    *route = AuxRoute{};
+// Everything the sends of a block need, allocated before the block's first launch: the chunk sums of the largest piece, then the
+// route of the aux rows (planSideRoute: for a pageable aux_out the compact staging rows).
+int Batch::planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, Route* route) {
+    *route = Route{};
     const size_t mine = send_.column.size();
     if (!auxOut || mine == 0) return 0;   // (a shard that owns none of the buses launches nothing)
     const size_t partial = pieceRows * (size_t)sendChunks_;
-    if (partial > sendPartialCap_) {
+    if (partial > sendPartial_.cap) {
         if (busLaunched_) (void)hipEventSynchronize(evBus_);   // (a block on the caller's stream may still be working on the old one)
         (void)hipStreamSynchronize(stream_);
-        (void)hipFree(dSendPartial_);
-        dSendPartial_ = nullptr;
-        sendPartialCap_ = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&dSendPartial_), partial * 4) != hipSuccess) {
-            dSendPartial_ = nullptr;
-            return hipFail(hipErrorOutOfMemory, "hipMalloc bus send chunk sums");
-        }
-        sendPartialCap_ = partial;
+        const int rc = growBlock(sendPartial_, partial, false, "hipMalloc bus send chunk sums");
+        if (rc != 0) return rc;
     }
-    if (devAux) {
-        route->dst = static_cast<float*>(const_cast<void*>(devAux));
-        route->pitch = send_.totalBuses;
-        route->columns = !sendIdentity_;
-        return 0;
-    }
-    const size_t words = rows * mine;
-    if (words > auxStageCap_) {
-        (void)hipStreamSynchronize(stream_);
-        (void)hipFree(dAuxStage_);
-        dAuxStage_ = nullptr;
-        auxStageCap_ = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&dAuxStage_), words * 4) != hipSuccess) {
-            dAuxStage_ = nullptr;
-            return hipFail(hipErrorOutOfMemory, "hipMalloc bus send staging");
-        }
-        auxStageCap_ = words;
-    }
-    if (!sendIdentity_ && words > hAuxStageCap_) {
-        if (hAuxStage_) (void)hipHostFree(hAuxStage_);
-        hAuxStage_ = nullptr;
-        hAuxStageCap_ = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&hAuxStage_), words * 4, hipHostMallocDefault) != hipSuccess) {
-            hAuxStage_ = nullptr;
-            return hipFail(hipErrorOutOfMemory, "pinned staging of the bus sends");
-        }
-        hAuxStageCap_ = words;
-    }
-    route->dst = dAuxStage_;
-    route->pitch = (int64_t)mine;
-    route->columns = false;
-    route->staged = true;
-    return 0;
-}
-
-// the staged rows on their way out, behind the block on its stream: straight into the caller's rows where bus j is column j,
-// else into the pinned block from which placeAuxColumns puts every column in its place
-hipError_t Batch::queueAuxCopyOut(const AuxRoute& route, float* auxOut, size_t rows, hipStream_t stream) {
-    if (!route.staged) return hipSuccess;
-    const size_t bytes = rows * send_.column.size() * 4;
-    return hipMemcpyAsync(sendIdentity_ ? static_cast<void*>(auxOut) : static_cast<void*>(hAuxStage_), dAuxStage_, bytes, hipMemcpyDeviceToHost, stream);
-}
-
-void Batch::placeAuxColumns(const AuxRoute& route, float* auxOut, size_t rows) {
-    if (!route.staged || sendIdentity_) return;
-    const size_t mine = send_.column.size();
-    for (size_t r = 0; r < rows; ++r)
-        for (size_t j = 0; j < mine; ++j) std::memcpy(auxOut + r * (size_t)send_.totalBuses + (size_t)send_.column[j], hAuxStage_ + r * mine + j, 4);
+    return planSideRoute(auxRows_, kAuxTexts, auxOut, devAux, rows, mine, send_.totalBuses, sendIdentity_ ? nullptr : send_.column.data(), route);
 }
 
 // the launch of one piece (Batch::runBus): rows [first, first + rows) of the block, sample0 the piece's first sample
-hipError_t Batch::launchSends(const AuxRoute& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s) {
+hipError_t Batch::launchSends(const Route& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s) {
     BusSendArgs a{};
-    const uint32_t* words = dSend_;
-    a.wide = dBus_;
+    const uint32_t* words = sendBlock_.cur;
+    a.wide = bus_.p;
     a.idx = words + sendOff_[0];
-    a.target = reinterpret_cast<const float*>(words + sendOff_[1 + sendTarget_]);
-    a.current = sendRampPending_ ? reinterpret_cast<const float*>(words + sendOff_[1 + (sendTarget_ ^ 1)]) : nullptr;
+    a.target = reinterpret_cast<const float*>(words + sendOff_[1 + sendRamp_.target]);
+    a.current = sendRamp_.pending ? reinterpret_cast<const float*>(words + sendOff_[1 + (sendRamp_.target ^ 1)]) : nullptr;
     a.chunk = reinterpret_cast<const BusSendChunk*>(words + sendOff_[3]);
     a.bus = reinterpret_cast<const BusSendBus*>(words + sendOff_[4]);
-    a.partial = dSendPartial_;
-    a.auxOut = route.dst + first * (size_t)route.pitch;
+    a.partial = sendPartial_.p;
+    a.auxOut = reinterpret_cast<float*>(route.dst) + first * (size_t)route.pitch;
     a.rows = rows;
     a.n = n_;
     a.entries = (long long)send_.members.size();
@@ -294,7 +208,7 @@ hipError_t Batch::launchSends(const AuxRoute& route, size_t first, long long row
     a.auxPitch = route.pitch;
     a.columns = route.columns ? 1 : 0;
     a.channels = prog_.numChannels;
-    a.ramp = sendRampPending_ ? 1 : 0;
+    a.ramp = sendRamp_.pending ? 1 : 0;
     a.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
     a.samples = nSamples;
     a.sample0 = sample0;

@@ -101,32 +101,15 @@ int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, 
         instLaunched_ = false;
     }
     const size_t entries = (size_t)count;
-    if (entries > hInstListCap_) {
-        if (hInstList_) (void)hipHostFree(hInstList_);
-        hInstList_ = nullptr;
-        hInstListCap_ = 0;
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&hInstList_), entries * 2 * sizeof(long long), hipHostMallocDefault)) != hipSuccess) { hInstList_ = nullptr; return hipFail(hipErrorOutOfMemory, "pinned instance lists"); }
-        hInstListCap_ = entries;
-    }
-    if (entries > instListCap_) {
-        (void)hipFree(dInstList_);
-        dInstList_ = nullptr;
-        instListCap_ = 0;
-        if ((e = hipMalloc(reinterpret_cast<void**>(&dInstList_), entries * 2 * sizeof(long long))) != hipSuccess) { dInstList_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc instance lists"); }
-        instListCap_ = entries;
-    }
-    if (recordWords > instRecCap_) {
-        (void)hipFree(dInstRec_);
-        dInstRec_ = nullptr;
-        instRecCap_ = 0;
-        if ((e = hipMalloc(reinterpret_cast<void**>(&dInstRec_), recordWords * 4)) != hipSuccess) { dInstRec_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc instance records"); }
-        instRecCap_ = recordWords;
-    }
+    // (two lists of `entries` each; the previous call, the only user of these blocks, has been waited for)
+    if ((rc = growBlock(hInstList_, entries, true, "pinned instance lists", 2 * sizeof(long long))) != 0) return rc;
+    if ((rc = growBlock(instList_, entries, false, "hipMalloc instance lists", 2 * sizeof(long long))) != 0) return rc;
+    if ((rc = growBlock(instRec_, recordWords, false, "hipMalloc instance records")) != 0) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "instance lists");
-    std::memcpy(hInstList_, a, entries * 8);
-    if (b) std::memcpy(hInstList_ + hInstListCap_, b, entries * 8);
-    e = hipMemcpyAsync(dInstList_, hInstList_, entries * 8, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess && b) e = hipMemcpyAsync(dInstList_ + instListCap_, hInstList_ + hInstListCap_, entries * 8, hipMemcpyHostToDevice, stream_);
+    std::memcpy(hInstList_.p, a, entries * 8);
+    if (b) std::memcpy(hInstList_.p + hInstList_.cap, b, entries * 8);
+    e = hipMemcpyAsync(instList_.p, hInstList_.p, entries * 8, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && b) e = hipMemcpyAsync(instList_.p + instList_.cap, hInstList_.p + hInstList_.cap, entries * 8, hipMemcpyHostToDevice, stream_);
     // behind every block queued so far, on whichever stream it was queued
     if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
     if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
@@ -156,14 +139,14 @@ int Batch::copyInstances(const int64_t* src, const int64_t* dst, int64_t count) 
     const int64_t per = recordsPerPiece();
     InstArgs a = instArgs();
     if ((rc = beginInstanceCall(src, dst, count, (size_t)std::min(count, per) * (size_t)a.recStride)) != 0) return rc;
-    a.records = dInstRec_;
+    a.records = instRec_.p;
     hipError_t e = hipSuccess;
     for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
         a.count = std::min(per, count - off);
-        a.list = dInstList_ + off;
+        a.list = instList_.p + off;
         if ((e = launchInstGather(a, stream_)) != hipSuccess) break;
         ++instGathers_;
-        a.list = dInstList_ + instListCap_ + off;
+        a.list = instList_.p + instList_.cap + off;
         if ((e = launchInstScatter(a, stream_)) == hipSuccess) ++instScatters_;
     }
     rc = endInstanceCall(e != hipSuccess);
@@ -178,28 +161,22 @@ int Batch::resetInstances(const int64_t* list, int64_t count) {
     const size_t W = (size_t)a.recStride;
     if ((rc = beginInstanceCall(list, nullptr, count, W)) != 0) return rc;
     hipError_t e = hipSuccess;
-    if (W > hInstRecCap_) {
-        if (hInstRec_) (void)hipHostFree(hInstRec_);
-        hInstRec_ = nullptr;
-        hInstRecCap_ = 0;
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&hInstRec_), W * 4, hipHostMallocDefault)) != hipSuccess) {
-            hInstRec_ = nullptr;
-            (void)endInstanceCall(true);
-            return hipFail(hipErrorOutOfMemory, "pinned reset record");
-        }
-        hInstRecCap_ = W;
+    if ((rc = growBlock(hInstRec_, W, true, "pinned reset record")) != 0) {
+        const std::string why = lastError_;
+        (void)endInstanceCall(true);
+        return fail(rc, why);
     }
     // the record of a freshly created instance (ensureState): registers as the last broadcast write left them, latches 0, the
     // reference's LFSR seeds, flags 0, counter 0, delay memory 0 - the four position words are skipped by the scatter
-    std::memset(hInstRec_, 0, W * 4);
-    for (int r = 0; r < stateLayout_.nRegs; ++r) hInstRec_[r] = bitsOf(hostValue_[(size_t)r]);
-    hInstRec_[stateLayout_.noiseBase + 0] = 0x70f4f854u;   // g_x1, include/FX8010.h:290
-    hInstRec_[stateLayout_.noiseBase + 1] = 0xe1e9f0a7u;   // g_x2, include/FX8010.h:291
-    e = hipMemcpyAsync(dInstRec_, hInstRec_, W * 4, hipMemcpyHostToDevice, stream_);
+    std::memset(hInstRec_.p, 0, W * 4);
+    for (int r = 0; r < stateLayout_.nRegs; ++r) hInstRec_.p[r] = bitsOf(hostValue_[(size_t)r]);
+    hInstRec_.p[stateLayout_.noiseBase + 0] = 0x70f4f854u;   // g_x1, include/FX8010.h:290
+    hInstRec_.p[stateLayout_.noiseBase + 1] = 0xe1e9f0a7u;   // g_x2, include/FX8010.h:291
+    e = hipMemcpyAsync(instRec_.p, hInstRec_.p, W * 4, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess) {
-        a.records = dInstRec_;
+        a.records = instRec_.p;
         a.recStride = 0;
-        a.list = dInstList_;
+        a.list = instList_.p;
         a.count = count;
         a.skipLo = stateLayout_.cursorBase;
         a.skipHi = stateLayout_.cursorBase + 4;
@@ -218,17 +195,17 @@ int Batch::gatherRecords(const int64_t* list, const int64_t* pos, int64_t count,
     InstArgs a = instArgs();
     const size_t W = (size_t)a.recStride;
     if ((rc = beginInstanceCall(list, nullptr, count, (size_t)std::min(count, per) * W)) != 0) return rc;
-    a.records = dInstRec_;
+    a.records = instRec_.p;
     hipError_t e = hipSuccess;
     for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
         a.count = std::min(per, count - off);
-        a.list = dInstList_ + off;
+        a.list = instList_.p + off;
         if ((e = launchInstGather(a, stream_)) != hipSuccess) break;
         ++instGathers_;
         // one copy per piece, straight to where the records belong - with positions, one per run of consecutive positions
         for (int64_t k = 0, run = 0; k < a.count && e == hipSuccess; k += run) {
             run = pos ? recordRun(pos + off + k, a.count - k) : a.count;
-            e = hipMemcpyAsync(buf + (size_t)(pos ? pos[off + k] : off + k) * W, dInstRec_ + (size_t)k * W, (size_t)run * W * 4, hipMemcpyDeviceToHost, stream_);
+            e = hipMemcpyAsync(buf + (size_t)(pos ? pos[off + k] : off + k) * W, instRec_.p + (size_t)k * W, (size_t)run * W * 4, hipMemcpyDeviceToHost, stream_);
         }
     }
     rc = endInstanceCall(true);
@@ -244,14 +221,14 @@ int Batch::scatterRecords(const int64_t* list, const int64_t* pos, int64_t count
     InstArgs a = instArgs();
     const size_t W = (size_t)a.recStride;
     if ((rc = beginInstanceCall(list, nullptr, count, (size_t)std::min(count, per) * W)) != 0) return rc;
-    a.records = dInstRec_;
+    a.records = instRec_.p;
     hipError_t e = hipSuccess;
     for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
         a.count = std::min(per, count - off);
-        a.list = dInstList_ + off;
+        a.list = instList_.p + off;
         for (int64_t k = 0, run = 0; k < a.count && e == hipSuccess; k += run) {
             run = pos ? recordRun(pos + off + k, a.count - k) : a.count;
-            e = hipMemcpyAsync(dInstRec_ + (size_t)k * W, buf + (size_t)(pos ? pos[off + k] : off + k) * W, (size_t)run * W * 4, hipMemcpyHostToDevice, stream_);
+            e = hipMemcpyAsync(instRec_.p + (size_t)k * W, buf + (size_t)(pos ? pos[off + k] : off + k) * W, (size_t)run * W * 4, hipMemcpyHostToDevice, stream_);
         }
         if (e == hipSuccess && (e = launchInstScatter(a, stream_)) == hipSuccess) ++instScatters_;
     }

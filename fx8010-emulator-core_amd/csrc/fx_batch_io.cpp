@@ -308,6 +308,33 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
     return 0;
 }
 
+// The device entries' check of a caller's buffer (fx_batch_bus_side.hpp CheckedAddr): memory of this handle's device, or
+// device-visible host memory, over the whole of [p, p + bytes).  A refusal leaves nothing cached.
+int Batch::lookup(CheckedAddr& c, const void* p, size_t bytes, const char* what) {
+    if (c.holds(p, bytes)) return 0;
+    c.forget();
+    const void* dev = nullptr;
+    if (!addressable(p, bytes, device_, &dev)) return fail(FX_E_ARG, what);
+    c.host = p;
+    c.bytes = bytes;
+    c.dev = const_cast<void*>(dev);
+    return 0;
+}
+
+// ... of an input / output pair, which is checked together: a pair that misses in either half is looked up afresh, one buffer
+// given as both is looked up once, and a refusal of either leaves neither cached
+int Batch::lookupPair(CheckedAddr& cIn, const void* in, size_t inBytes, CheckedAddr& cOut, const void* out, size_t outBytes) {
+    static const char* const what = "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block";
+    if (cIn.holds(in, inBytes) && cOut.holds(out, outBytes)) return 0;
+    cIn.forget();
+    cOut.forget();
+    int rc = lookup(cIn, in, inBytes, what);
+    if (rc != 0) return rc;
+    if (out == in && outBytes == inBytes) cOut = cIn;
+    else if ((rc = lookup(cOut, out, outBytes, what)) != 0) cIn.forget();
+    return rc;
+}
+
 // rows of `width` bytes; one plain copy when neither side has a gap between its rows
 hipError_t Batch::copyRows(void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t stream) {
     if (dstPitch == width && srcPitch == width) return hipMemcpyAsync(dst, src, rows * width, kind, stream);
@@ -320,21 +347,15 @@ int Batch::processDeviceChecked(const float* dIn, float* dOut, int nSamples, int
     if (rc != 0) return rc;
     if (nSamples > 0) {
         const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels, bytes = pcmExtent(rows, n_, pitch);
-        if (dIn != checkedIn_ || dOut != checkedOut_ || bytes > checkedBytes_) {
-            checkedIn_ = checkedOut_ = nullptr;
+        if (!checkedIn_.holds(dIn, bytes) || !checkedOut_.holds(dOut, bytes)) {
+            checkedIn_.forget();
+            checkedOut_.forget();
             if (!pcmDisjointOrSame(dIn, dOut, rows, n_, pitch)) return fail(FX_E_ARG, "input and output overlap without being one buffer");
             // memory of this device, or pinned host memory (its device address goes to the kernel)
-            const void *devIn = nullptr, *devOut = nullptr;
-            if (!addressable(dIn, bytes, device_, &devIn) || (dOut == dIn ? (devOut = devIn, false) : !addressable(dOut, bytes, device_, &devOut)))
-                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
-            checkedIn_ = dIn;
-            checkedOut_ = dOut;
-            checkedBytes_ = bytes;
-            checkedDevIn_ = static_cast<const float*>(devIn);
-            checkedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
+            if (int lrc = lookupPair(checkedIn_, dIn, bytes, checkedOut_, dOut, bytes)) return lrc;
         }
-        dIn = checkedDevIn_;
-        dOut = checkedDevOut_;
+        dIn = static_cast<const float*>(checkedIn_.dev);
+        dOut = static_cast<float*>(checkedOut_.dev);
     }
     beginBlock(nSamples);
     return launchBlock(dIn, dOut, nSamples, stream, pitch, kWholeBlock);
@@ -538,29 +559,17 @@ int Batch::ensureBusScratch(size_t floats) {
         const hipError_t e = hipEventCreateWithFlags(&evBus_, hipEventDisableTiming);
         if (e != hipSuccess) { evBus_ = nullptr; return hipFail(e, "bus event"); }
     }
-    if (floats <= busCap_) return 0;
+    if (floats <= bus_.cap) return 0;
     // (a block on the caller's stream may still be working on the old one)
     if (busLaunched_) (void)hipEventSynchronize(evBus_);
     (void)hipStreamSynchronize(stream_);
-    (void)hipFree(dBus_);
-    dBus_ = nullptr;
-    busCap_ = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBus_), floats * 4);
-    if (e != hipSuccess) { dBus_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc bus scratch"); }
-    busCap_ = floats;
-    return 0;
+    return growBlock(bus_, floats, false, "hipMalloc bus scratch");
 }
 
 int Batch::ensureBusStage(size_t floats) {
-    if (floats <= busStageCap_) return 0;
+    if (floats <= busStage_.cap) return 0;
     (void)hipStreamSynchronize(stream_);
-    (void)hipFree(dBusStage_);
-    dBusStage_ = nullptr;
-    busStageCap_ = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&dBusStage_), floats * 4);
-    if (e != hipSuccess) { dBusStage_ = nullptr; return hipFail(hipErrorOutOfMemory, "hipMalloc bus staging"); }
-    busStageCap_ = floats;
-    return 0;
+    return growBlock(busStage_, floats, false, "hipMalloc bus staging");
 }
 
 // The block itself, asynchronous on `stream`.  in / out: the per-instance sides as the caller gave them (copied to / from the
@@ -575,7 +584,7 @@ int Batch::busPieceSamples(int nSamples) const {
 }
 
 int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-                  const BusShape& shape, hipStream_t stream, const TapRoute* tap, const AuxRoute* aux) {
+                  const BusShape& shape, hipStream_t stream, const Route* tap, const Route* aux) {
     const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
     const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
     const int pieces = (nSamples + most - 1) / most;
@@ -596,23 +605,28 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
     }
     BusGainArgs gain{};
     if (weighted) {
-        gain.target = dGain_[gainTarget_];
-        gain.current = gainRampPending_ ? dGain_[gainTarget_ ^ 1] : nullptr;
+        gain.target = dGain_[gainRamp_.target];
+        gain.current = gainRamp_.pending ? dGain_[gainRamp_.target ^ 1] : nullptr;
         gain.gainPitch = n_;
         gain.channels = prog_.numChannels;
-        gain.ramp = gainRampPending_ ? 1 : 0;
+        gain.ramp = gainRamp_.pending ? 1 : 0;
         gain.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
         gain.samples = nSamples;
     }
     beginBlock(nSamples, pieces);   // ONE block to the bookkeeping of control changes and to the lowering
     if ((rc = ensureLowered()) != 0) return rc;
     auto lo = [&](int p) { return (int)((int64_t)nSamples * p / pieces); };
+    // a failure behind the first launch of a piece: what has been queued still uses the scratch
+    auto failQueued = [&](int rc0, hipError_t e, const char* what) {
+        if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;
+        return e != hipSuccess ? hipFail(e, what) : rc0;
+    };
     const size_t width = (size_t)n_ * 4;
     for (int p = 0; p < pieces; ++p) {
         const int count = lo(p + 1) - lo(p);
         const size_t first = (size_t)lo(p) * ch;
         BusArgs a{};
-        a.wide = dBus_;
+        a.wide = bus_.p;
         a.rows = (long long)count * (long long)ch;
         a.n = n_;
         a.group = shape.group;
@@ -623,34 +637,14 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
             a.narrowPitch = narrowInPitch;
             e = launchBusExpand(a, s);
         } else {
-            e = copyRows(dBus_, width, in + first * (size_t)shape.inPitch, (size_t)shape.inPitch * 4, width, (size_t)a.rows, hipMemcpyDefault, s);
+            e = copyRows(bus_.p, width, in + first * (size_t)shape.inPitch, (size_t)shape.inPitch * 4, width, (size_t)a.rows, hipMemcpyDefault, s);
         }
         if (e != hipSuccess) return hipFail(e, "bus: filling the scratch block");
-        if ((rc = launchBlock(dBus_, dBus_, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) {
-            if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
-            return rc;
-        }
+        if ((rc = launchBlock(bus_.p, bus_.p, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) return failQueued(rc, hipSuccess, nullptr);
         // the taps read the scratch block where the emulation has just written it, like the meter (inside launchBlock): pre-fader
-        if (tap && tap->dst) {
-            BusTapArgs t{};
-            t.wide = reinterpret_cast<const uint32_t*>(dBus_);
-            t.tapOut = tap->dst + first * (size_t)tap->pitch;
-            t.idx = dTap_;
-            t.col = tap->columns ? dTap_ + tapList_.size() : nullptr;
-            t.rows = a.rows;
-            t.n = n_;
-            t.taps = tapCount();
-            t.tapPitch = tap->pitch;
-            if ((e = launchBusTap(t, s)) != hipSuccess) {
-                if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
-                return hipFail(e, "bus: the tap kernel");
-            }
-        }
+        if (tap && tap->dst && (e = launchTaps(*tap, first, a.rows, s)) != hipSuccess) return failQueued(0, e, "bus: the tap kernel");
         // ... and so do the sends, behind the taps and in front of the mix: chunk sums, then the fold to the aux rows
-        if (aux && aux->dst && (e = launchSends(*aux, first, a.rows, nSamples, lo(p), s)) != hipSuccess) {
-            if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
-            return hipFail(e, "bus: the send kernels");
-        }
+        if (aux && aux->dst && (e = launchSends(*aux, first, a.rows, nSamples, lo(p), s)) != hipSuccess) return failQueued(0, e, "bus: the send kernels");
         if (flags & kBusMixOut) {
             a.narrowIn = nullptr;
             a.narrowOut = narrowOut + first * (size_t)narrowOutPitch;
@@ -658,7 +652,7 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
             gain.sample0 = lo(p);
             e = weighted ? launchBusMixGain(a, gain, s) : launchBusMix(a, s);
         } else {
-            e = copyRows(out + first * (size_t)shape.outPitch, (size_t)shape.outPitch * 4, dBus_, width, width, (size_t)a.rows, hipMemcpyDefault, s);
+            e = copyRows(out + first * (size_t)shape.outPitch, (size_t)shape.outPitch * 4, bus_.p, width, width, (size_t)a.rows, hipMemcpyDefault, s);
         }
         if (e == hipSuccess) e = hipEventRecord(evBus_, s);
         if (e != hipSuccess) return hipFail(e, "bus: emptying the scratch block");
@@ -667,12 +661,12 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
     ++busBlocks_;   // (blocks whose every piece was queued)
     if (tap) ++busTapBlocks_;   // (counted by every shard that was handed the rows, whether or not an entry falls into it)
     if (aux) {
-        ++busSendBlocks_;           // (the same)
-        sendRampPending_ = false;   // consumed, as the ramp of the bus gains below
+        ++busSendBlocks_;      // (the same)
+        sendRamp_.consume();   // as the ramp of the bus gains below
     }
     if (weighted) {
         ++busGainBlocks_;
-        gainRampPending_ = false;   // consumed: a counts as b from here on (fx_batch.hpp)
+        gainRamp_.consume();
     }
     return 0;
 }
@@ -690,40 +684,18 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
     const size_t auxBytes = rows * (size_t)send_.totalBuses * 4;
     const size_t pieceRows = (size_t)busPieceSamples(nSamples) * (size_t)prog_.numChannels;
     const void *devIn = nullptr, *devOut = nullptr, *devTap = nullptr, *devAux = nullptr;
-    TapRoute route;
-    AuxRoute auxRoute;
+    Route tapRoute, auxRoute;   // (of a side without rows: empty, and nothing below does anything with it)
+    const Route* tap = tapOut ? &tapRoute : nullptr;
+    const Route* aux = auxOut ? &auxRoute : nullptr;
     if (entry == kBusDevice) {
-        if (in != busCheckedIn_ || out != busCheckedOut_ || inBytes > busCheckedInBytes_ || outBytes > busCheckedOutBytes_) {
-            busCheckedIn_ = busCheckedOut_ = nullptr;
-            if (!addressable(in, inBytes, device_, &devIn) || !addressable(out, outBytes, device_, &devOut))
-                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
-            busCheckedIn_ = in;
-            busCheckedOut_ = out;
-            busCheckedInBytes_ = inBytes;
-            busCheckedOutBytes_ = outBytes;
-            busCheckedDevIn_ = static_cast<const float*>(devIn);
-            busCheckedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
-        }
-        if (tapOut && (tapOut != busCheckedTap_ || tapBytes > busCheckedTapBytes_)) {
-            busCheckedTap_ = nullptr;
-            if (!addressable(tapOut, tapBytes, device_, &devTap))
-                return fail(FX_E_ARG, "d_tap_out: not memory of this handle's device or device-visible host memory over the whole block");
-            busCheckedTap_ = tapOut;
-            busCheckedTapBytes_ = tapBytes;
-            busCheckedDevTap_ = static_cast<float*>(const_cast<void*>(devTap));
-        }
-        if (auxOut && (auxOut != busCheckedAux_ || auxBytes > busCheckedAuxBytes_)) {
-            busCheckedAux_ = nullptr;
-            if (!addressable(auxOut, auxBytes, device_, &devAux))
-                return fail(FX_E_ARG, "d_aux_out: not memory of this handle's device or device-visible host memory over the whole block");
-            busCheckedAux_ = auxOut;
-            busCheckedAuxBytes_ = auxBytes;
-            busCheckedDevAux_ = static_cast<float*>(const_cast<void*>(devAux));
-        }
-        if (tapOut && (rc = planTapRoute(tapOut, busCheckedDevTap_, rows, &route)) != 0) return rc;
-        if (auxOut && (rc = planAuxRoute(auxOut, busCheckedDevAux_, rows, pieceRows, &auxRoute)) != 0) return rc;
-        return runBus(busCheckedDevIn_, busCheckedDevOut_, busCheckedDevIn_, shape.inPitch, busCheckedDevOut_, shape.outPitch, nSamples, flags, shape, stream,
-                      tapOut ? &route : nullptr, auxOut ? &auxRoute : nullptr);
+        if ((rc = lookupPair(busIn_, in, inBytes, busOut_, out, outBytes)) != 0) return rc;
+        if (tapOut && (rc = lookup(tapRows_.checked, tapOut, tapBytes, kTapTexts.notAddressable)) != 0) return rc;
+        if (auxOut && (rc = lookup(auxRows_.checked, auxOut, auxBytes, kAuxTexts.notAddressable)) != 0) return rc;
+        if (tapOut && (rc = planSideRoute(tapRows_, kTapTexts, tapOut, tapRows_.checked.dev, rows, tapList_.size(), tapTotal_, tapPlace(), &tapRoute)) != 0) return rc;
+        if (auxOut && (rc = planAuxRoute(auxOut, auxRows_.checked.dev, rows, pieceRows, &auxRoute)) != 0) return rc;
+        const float* dIn = static_cast<const float*>(busIn_.dev);
+        float* dOut = static_cast<float*>(busOut_.dev);
+        return runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream, tap, aux);
     }
     // Host entry.  Pinned buffers: the bus kernels read the group words from and store the sums to the caller's memory over PCIe
     // (256 bytes per wavefront access), no copies.  Anything else: the [sample][channel][group] sides are staged.  Whatever
@@ -733,35 +705,37 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
     // a device block and copied out behind the block.  Everything that route needs is allocated here, in front of the first launch.
     if (tapOut) {
         if (!(knobs_.hostPipeline && addressable(tapOut, tapBytes, -1, &devTap))) devTap = nullptr;
-        if ((rc = planTapRoute(tapOut, devTap, rows, &route)) != 0) return rc;
+        if ((rc = planSideRoute(tapRows_, kTapTexts, tapOut, devTap, rows, tapList_.size(), tapTotal_, tapPlace(), &tapRoute)) != 0) return rc;
     }
-    const TapRoute* tap = tapOut ? &route : nullptr;
     // ... and the aux rows of the sends theirs, in the same way
     if (auxOut) {
         if (!(knobs_.hostPipeline && addressable(auxOut, auxBytes, -1, &devAux))) devAux = nullptr;
         if ((rc = planAuxRoute(auxOut, devAux, rows, pieceRows, &auxRoute)) != 0) return rc;
     }
-    const AuxRoute* aux = auxOut ? &auxRoute : nullptr;
+    // the tail of both host paths behind runBus and the copies of the two sides (e: their result): the staged side rows on their
+    // way out, the wait - also when the call failed -, the columns of a shard into their places
+    auto finish = [&](int rc0, hipError_t e, const char* what) {
+        if (rc0 == 0 && e == hipSuccess) e = queueSideCopyOut(tapRows_, tapRoute, tapOut, rows, stream_);
+        if (rc0 == 0 && e == hipSuccess) e = queueSideCopyOut(auxRows_, auxRoute, auxOut, rows, stream_);
+        const hipError_t se = hipStreamSynchronize(stream_);
+        if (rc0 != 0) return rc0;
+        if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, what);
+        placeSideColumns(tapRows_, tapRoute, tapOut, rows);
+        placeSideColumns(auxRows_, auxRoute, auxOut, rows);
+        return 0;
+    };
     if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && addressable(out, outBytes, -1, &devOut)) {
         const float* dIn = static_cast<const float*>(devIn);
         float* dOut = static_cast<float*>(const_cast<void*>(devOut));
         rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap, aux);
-        hipError_t te = hipSuccess;
-        if (rc == 0 && tap) te = queueTapCopyOut(route, tapOut, rows, stream_);
-        if (rc == 0 && te == hipSuccess && aux) te = queueAuxCopyOut(auxRoute, auxOut, rows, stream_);
-        const hipError_t se = hipStreamSynchronize(stream_);
-        if (rc != 0) return rc;
-        if (te != hipSuccess || se != hipSuccess) return hipFail(te != hipSuccess ? te : se, "synchronising a bus block on pinned host buffers");
-        if (tap) placeTapColumns(route, tapOut, rows);
-        if (aux) placeAuxColumns(auxRoute, auxOut, rows);
-        ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
-        return 0;
+        if ((rc = finish(rc, hipSuccess, "synchronising a bus block on pinned host buffers")) == 0) ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
+        return rc;
     }
     const size_t side = rows * (size_t)shape.groups;
     const bool sharedIn = (flags & kBusSharedIn) != 0, mixOut = (flags & kBusMixOut) != 0;
     if ((rc = ensureBusStage(side * ((sharedIn ? 1 : 0) + (mixOut ? 1 : 0)))) != 0) return rc;
-    float* stageIn = dBusStage_;
-    float* stageOut = dBusStage_ + (sharedIn ? side : 0);
+    float* stageIn = busStage_.p;
+    float* stageOut = busStage_.p + (sharedIn ? side : 0);
     const size_t narrow = (size_t)shape.groups * 4;
     hipError_t e = hipSuccess;
     if (sharedIn) e = copyRows(stageIn, narrow, in, (size_t)shape.inPitch * 4, narrow, rows, hipMemcpyDefault, stream_);
@@ -771,15 +745,8 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
     }
     rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap, aux);
     if (rc == 0 && mixOut) e = copyRows(out, (size_t)shape.outPitch * 4, stageOut, narrow, narrow, rows, hipMemcpyDefault, stream_);
-    if (rc == 0 && e == hipSuccess && tap) e = queueTapCopyOut(route, tapOut, rows, stream_);
-    if (rc == 0 && e == hipSuccess && aux) e = queueAuxCopyOut(auxRoute, auxOut, rows, stream_);
-    const hipError_t se = hipStreamSynchronize(stream_);
-    if (rc != 0) return rc;
-    if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "bus D2H");
-    if (tap) placeTapColumns(route, tapOut, rows);
-    if (aux) placeAuxColumns(auxRoute, auxOut, rows);
-    ++hostStagedBlocks_;
-    return 0;
+    if ((rc = finish(rc, e, "bus D2H")) == 0) ++hostStagedBlocks_;
+    return rc;
 }
 
 // ---- instance-major blocks: one interleaved [sample][channel] stream per instance (fx_imajor.hpp) ---------------------------------
@@ -852,7 +819,7 @@ int Batch::runImajor(const float* in, int64_t inStride, float* out, int64_t outS
     for (int p = 0; p < pieces; ++p) {
         const int count = lo(p + 1) - lo(p);
         ImajorArgs a{};
-        a.wide = dBus_;
+        a.wide = bus_.p;
         a.first = (long long)lo(p) * (long long)ch;
         a.rows = (long long)count * (long long)ch;
         a.n = n_;
@@ -860,7 +827,7 @@ int Batch::runImajor(const float* in, int64_t inStride, float* out, int64_t outS
         a.stride = inStride;
         hipError_t e = launchImajorGather(a, s);
         if (e != hipSuccess) return hipFail(e, "instance-major block: filling the scratch block");
-        if ((rc = launchBlock(dBus_, dBus_, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) {
+        if ((rc = launchBlock(bus_.p, bus_.p, count, s, n_, pieces > 1 ? kPiece : kWholeBlock)) != 0) {
             if (hipEventRecord(evBus_, s) == hipSuccess) busLaunched_ = true;   // (what has been queued still uses the scratch)
             return rc;
         }
@@ -887,18 +854,8 @@ int Batch::processImajor(const float* in, float* out, int nSamples, int64_t inSt
     const size_t inBytes = ((size_t)(n_ - 1) * (size_t)inStride + run) * 4, outBytes = ((size_t)(n_ - 1) * (size_t)outStride + run) * 4;
     const void *devIn = nullptr, *devOut = nullptr;
     if (entry == kBusDevice) {
-        if (in != imajorCheckedIn_ || out != imajorCheckedOut_ || inBytes > imajorCheckedInBytes_ || outBytes > imajorCheckedOutBytes_) {
-            imajorCheckedIn_ = imajorCheckedOut_ = nullptr;
-            if (!addressable(in, inBytes, device_, &devIn) || !addressable(out, outBytes, device_, &devOut))
-                return fail(FX_E_ARG, "d_in / d_out: not memory of this handle's device or device-visible host memory over the whole block");
-            imajorCheckedIn_ = in;
-            imajorCheckedOut_ = out;
-            imajorCheckedInBytes_ = inBytes;
-            imajorCheckedOutBytes_ = outBytes;
-            imajorCheckedDevIn_ = static_cast<const float*>(devIn);
-            imajorCheckedDevOut_ = static_cast<float*>(const_cast<void*>(devOut));
-        }
-        return runImajor(imajorCheckedDevIn_, inStride, imajorCheckedDevOut_, outStride, nSamples, stream);
+        if ((rc = lookupPair(imajorIn_, in, inBytes, imajorOut_, out, outBytes)) != 0) return rc;
+        return runImajor(static_cast<const float*>(imajorIn_.dev), inStride, static_cast<float*>(imajorOut_.dev), outStride, nSamples, stream);
     }
     // Host entry.  Pinned buffers: the two kernels read the runs from and store them to the caller's memory over PCIe, no copies.
     // Anything else: the n runs are staged as rows of a 2-D copy, [n][run] in device memory, and transposed from there.  Whatever
@@ -914,13 +871,13 @@ int Batch::processImajor(const float* in, float* out, int nSamples, int64_t inSt
     }
     // (one staging block serves both directions: a piece's sub-runs are scattered to where they were gathered from)
     if ((rc = ensureBusStage(run * (size_t)n_)) != 0) return rc;
-    hipError_t e = copyRows(dBusStage_, run * 4, in, (size_t)inStride * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
+    hipError_t e = copyRows(busStage_.p, run * 4, in, (size_t)inStride * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(stream_);
         return hipFail(e, "instance-major H2D");
     }
-    rc = runImajor(dBusStage_, (int64_t)run, dBusStage_, (int64_t)run, nSamples, stream_);
-    if (rc == 0) e = copyRows(out, (size_t)outStride * 4, dBusStage_, run * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
+    rc = runImajor(busStage_.p, (int64_t)run, busStage_.p, (int64_t)run, nSamples, stream_);
+    if (rc == 0) e = copyRows(out, (size_t)outStride * 4, busStage_.p, run * 4, run * 4, (size_t)n_, hipMemcpyDefault, stream_);
     const hipError_t se = hipStreamSynchronize(stream_);
     if (rc != 0) return rc;
     if (e != hipSuccess || se != hipSuccess) return hipFail(e != hipSuccess ? e : se, "instance-major D2H");

@@ -326,17 +326,23 @@ int Sharded::sync() {
     return fan([](int, Batch& b) { return b.sync(); });
 }
 
-int Sharded::meterEnable(bool on) {
-    Serial serial(api_);
-    lastError_.clear();
-    const bool was = front().metering();
-    const int rc = fan([&](int, Batch& b) { return b.meterEnable(on); });
-    if (rc != 0 && on && !was) {
+// The allocating half of an all-or-nothing set: reserve on every shard; if any of them fails, release on all of them and keep the
+// first error - no shard has changed.
+int Sharded::reserveOnAll(const std::function<int(int, Batch&)>& reserve, const std::function<void(Batch&)>& release) {
+    const int rc = fan(reserve);
+    if (rc != 0) {
         const std::string why = lastError();
-        fan([](int, Batch& b) { return b.meterEnable(false); });
+        fan([&](int, Batch& b) { release(b); return 0; });
         lastError_ = why;
     }
     return rc;
+}
+
+int Sharded::meterEnable(bool on) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (!on || front().metering()) return fan([&](int, Batch& b) { return b.meterEnable(on); });
+    return reserveOnAll([](int, Batch& b) { return b.meterEnable(true); }, [](Batch& b) { b.meterEnable(false); });
 }
 int Sharded::meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset) {
     Serial serial(api_);
@@ -361,13 +367,8 @@ int Sharded::busSetGains(const float* gains, int ramp) {
     if (ramp != 0 && ramp != 1) { lastError_ = "bus gains: ramp must be 0 or 1"; return FX_E_ARG; }
     if (!gains) return fan([](int, Batch& b) { return b.busSetGains(nullptr, 0, 0); });
     if (!Batch::gainsFinite(gains, front().channels(), n_, n_)) { lastError_ = "bus gains: every gain must be finite"; return FX_E_ARG; }
-    int rc = fan([](int, Batch& b) { return b.busReserveGains(); });
-    if (rc != 0) {
-        const std::string why = lastError();
-        fan([](int, Batch& b) { b.busReleaseGains(); return 0; });   // (a no-op on a shard whose gains are on)
-        lastError_ = why;
-        return rc;
-    }
+    // (the release: a no-op on a shard whose gains are on)
+    if (const int rc = reserveOnAll([](int, Batch& b) { return b.busReserveGains(); }, [](Batch& b) { b.busReleaseGains(); })) return rc;
     return fan([&](int k, Batch& b) { return b.busSetGains(gains + shards_[(size_t)k]->first, n_, ramp, true); });
 }
 int Sharded::busGetGains(float* gains) {
@@ -388,13 +389,7 @@ int Sharded::busSetTaps(const int64_t* list, int64_t count) {
     if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.busSetTaps(list, nullptr, count, count); });
     // every shard reserves the block of its entries first; only when all of them could does any shard's list change
     const std::vector<ListPart> parts = splitList(list, count);
-    const int rc = fan([&](int k, Batch& b) { return b.busReserveTaps((int64_t)parts[(size_t)k].list.size()); });
-    if (rc != 0) {
-        const std::string why = lastError();
-        fan([](int, Batch& b) { b.busReleaseTaps(); return 0; });
-        lastError_ = why;
-        return rc;
-    }
+    if (const int rc = reserveOnAll([&](int k, Batch& b) { return b.busReserveTaps((int64_t)parts[(size_t)k].list.size()); }, [](Batch& b) { b.busReleaseTaps(); })) return rc;
     return fan([&](int k, Batch& b) {
         const ListPart& part = parts[(size_t)k];
         return b.busSetTaps(part.list.data(), part.pos.data(), (int64_t)part.list.size(), count);
@@ -462,16 +457,11 @@ int Sharded::busSetSends(int64_t nAux, const int64_t* offsets, const int64_t* me
                 }
     }
     // every shard reserves the block of its buses first; only when all of them could does any shard's structure change
-    const int rc = fan([&](int k, Batch& b) {
+    const auto reserve = [&](int k, Batch& b) {
         const Batch::SendSet& part = parts[(size_t)k];
         return b.busReserveSends((int64_t)part.column.size(), (int64_t)part.members.size(), (int64_t)part.chunkCount());
-    });
-    if (rc != 0) {
-        const std::string why = lastError();
-        fan([](int, Batch& b) { b.busReleaseSends(); return 0; });
-        lastError_ = why;
-        return rc;
-    }
+    };
+    if (const int rc = reserveOnAll(reserve, [](Batch& b) { b.busReleaseSends(); })) return rc;
     return fan([&](int k, Batch& b) { return b.busSetSends(std::move(parts[(size_t)k])); });
 }
 int Sharded::busSetSendGains(const float* gains, int ramp) {

@@ -149,6 +149,8 @@ private:
     int fan(const std::function<int(int, Batch&)>& f);
     // run f(batch) on shard k's thread and wait (a single shard: inline, caller's device restored)
     int runOn(int k, const std::function<int(Batch&)>& f);
+    // reserve on every shard; if any fails, release on all of them and keep the first error
+    int reserveOnAll(const std::function<int(int, Batch&)>& reserve, const std::function<void(Batch&)>& release);
     void stopThreads();
     static void loop(Worker* w);
 

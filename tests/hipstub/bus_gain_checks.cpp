@@ -20,6 +20,7 @@
 #include <limits>
 #include <vector>
 
+#include "../../fx8010-emulator-core_amd/csrc/fx_batch_bus_side.hpp"
 #include "../../include/fx8010_amd.h"
 #include "hip_stub.h"
 
@@ -179,9 +180,32 @@ void memory(int devices) {
     fxb_destroy(h);
 }
 
+// the roles of two gain blocks (fx::RampPair, what the bus gains and the send gains both go by): set; ramp; ramp while pending;
+// ramp = 0 while pending; and a block that consumes a ramp
+void rampPair() {
+    fx::RampPair r;
+    CHECK(r.writeTarget(0) == 0 && r.inForce() == 0);   // a set replaces b where it is
+    r = fx::RampPair{r.writeTarget(0), false};
+    CHECK(r.target == 0 && !r.pending && r.inForce() == 0);
+    CHECK(r.writeTarget(1) == 1);                        // a ramp with none pending: the blocks swap roles, the old b is in force as a
+    r = fx::RampPair{r.writeTarget(1), true};
+    CHECK(r.target == 1 && r.pending && r.inForce() == 0);
+    CHECK(r.writeTarget(1) == 1);                        // a ramp while one is pending replaces b in place: a stays
+    r = fx::RampPair{r.writeTarget(1), true};
+    CHECK(r.target == 1 && r.pending && r.inForce() == 0);
+    CHECK(r.writeTarget(0) == 1);                        // ramp = 0 while pending: b in place again, and the ramp is dropped
+    r = fx::RampPair{r.writeTarget(0), false};
+    CHECK(r.target == 1 && !r.pending && r.inForce() == 1);
+    r = fx::RampPair{r.writeTarget(1), true};            // ... and the next ramp swaps back
+    CHECK(r.target == 0 && r.pending && r.inForce() == 1);
+    r.consume();                                         // a block that was fully queued: the target is in force
+    CHECK(r.target == 0 && !r.pending && r.inForce() == 0);
+}
+
 }  // namespace
 
 int main() {
+    rampPair();
     setenv("FXSTUB_DEVICES", "3", 1);   // (read by the stand-in at its first call)
     for (int devices = 1; devices <= 3; devices += 2) {
         indexing(devices);

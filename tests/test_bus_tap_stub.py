@@ -537,6 +537,7 @@ def child_memory():
     G = b.bus_groups(K)
     x = signal(rng, (S, 1, G))
     b.process_block_bus(x, K)   # (code generated, scratch and staging allocated)
+    assert b.prepare(S, True) == 0   # (... and the builder thread is idle: nothing else allocates while allocations are counted)
     old = np.array([807, 0, 400, 0], dtype=np.int64)
     new = tap_list(rng, N, 130)
     new[7] = 400   # (an entry of the middle shard, whatever was drawn)
