@@ -86,6 +86,9 @@ Batch::~Batch() {
     (void)hipFree(sendBlock_.cur);
     (void)hipFree(sendBlock_.reserved);
     freeSendBlocks();
+    (void)hipFree(feedBlock_.cur);
+    (void)hipFree(feedBlock_.reserved);
+    freeBlock(feedSrc_, false);
     freeBlock(instList_, false);
     freeBlock(instRec_, false);
     freeBlock(hInstList_, true);
@@ -851,6 +854,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_BUS_GAIN_BLOCKS) return busGainBlocks_;
     if (what == FXB_INFO_BUS_TAP_BLOCKS) return busTapBlocks_;
     if (what == FXB_INFO_BUS_SEND_BLOCKS) return busSendBlocks_;
+    if (what == FXB_INFO_BUS_FEED_BLOCKS) return busFeedBlocks_;
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;

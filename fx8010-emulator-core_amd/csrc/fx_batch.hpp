@@ -68,9 +68,12 @@ public:
     enum BusEntry { kBusHost, kBusDevice };
     // tapOut (null: an untapped block): the caller's [nSamples][channels][T] monitor side of the taps in force, see "Bus taps" below
     // auxOut (null: no sends delivered): the caller's [nSamples][channels][A] rows of the sends in force, see "Bus sends" below
+    // feed: `in` is the source block [nSamples][channels][M] of the feeds in force (row pitch exactly M), see "Bus feeds" below
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
-                   float* tapOut = nullptr, float* auxOut = nullptr);
+                   float* tapOut = nullptr, float* auxOut = nullptr, bool feed = false);
     // in == out with one layout, or footprints that share no byte (or no element, where both sides have one layout)
+    // a source block of feeds and the output: no shared byte (the layouts differ: there is no in-place form)
+    static bool feedSourceApart(const float* src, const float* out, size_t rows, int64_t sources, int64_t outWidth, int64_t outPitch);
     static bool busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     // Instance-major blocks (fx_imajor.hpp; include/fx8010_amd.h fxb_process_block_imajor): instance i's input is the run of
     // nSamples * channels floats, [sample][channel], at in + i * inStride, its output the same at out + i * outStride (a stride in
@@ -149,6 +152,33 @@ public:
     static const char* checkAuxShape(const float* in, const float* out, const float* tapOut, const float* auxOut, size_t rows, int64_t buses, int64_t taps, unsigned flags,
                                      int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch);
     static const char* checkSideShape(const SideTexts& texts, const float* sideOut, size_t rows, int64_t total, unsigned flags, const Footprint* others, int nOthers);
+    // Bus feeds (fx_bus.hpp BusFeedArgs; include/fx8010_amd.h "Bus feeds"): a mode of the handle, the sends mirrored on the input
+    // side.  While it is on, processBus(..., feed = true) takes `in` as the narrow source block [nSamples][channels][M] and builds
+    // the scratch block from per-instance lists of its columns (launchBusFeed) where kBusSharedIn expands it from n / K.  A FeedSet
+    // is what ONE batch holds of the CSR-by-instance structure of the whole handle: the lists of its own instances - a contiguous
+    // run of the caller's entries that begins at `first` (what fxb_bus_get_feeds and the [C][E] of busSetFeedGains go by).
+    // sources == 0 turns the mode off (waits, frees).  weighted = false is the UNWEIGHTED form (words move as bit patterns); its
+    // gain blocks hold 1.0f, which is what a ramp out of it starts from.  busReserveFeeds / busReleaseFeeds / busSetFeeds are
+    // the two steps of busSetSends over again (ReservedBlock); busSetFeedGains(gains = the caller's [C][totalEntries], finite;
+    // null: back to unweighted) follows the state machine of busSetGains (RampPair); the next feed block consumes a pending ramp.
+    static constexpr int64_t kMaxFeedEntries = (int64_t)1 << 24;
+    struct FeedSet {
+        int64_t sources = 0, totalEntries = 0, first = 0;
+        bool weighted = false;
+        std::vector<int64_t> offsets{0};   // [n + 1] local CSR
+        std::vector<int64_t> columns;      // [entries] source columns
+        std::vector<float> gain[2];        // [channels][entries]; busSetFeeds reads gain[0]
+        bool isMap() const;                // every instance has exactly one entry
+    };
+    int busReserveFeeds(int64_t sources, int64_t entries, bool map);
+    void busReleaseFeeds();
+    int busSetFeeds(FeedSet&& set);
+    int busSetFeedGains(const float* gains, int ramp);
+    // host state only: this batch's lists into the caller's arrays (offsets[firstInstance + i], sources / gains at the global
+    // entries, below the caps)
+    void busGetFeeds(int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap, int64_t firstInstance) const;
+    int64_t busFeedSources() const { return feed_.sources; }
+    int64_t busFeedEntries() const { return feed_.totalEntries; }
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -503,12 +533,13 @@ private:
     // bus blocks: expand -> the ordinary launch in place on the scratch -> mix, piece by piece on one stream
     struct BusShape { int64_t group = 1, groups = 1, inWidth = 0, outWidth = 0, inPitch = 0, outPitch = 0; };
     static constexpr size_t kBusScratchBytes = (size_t)64 << 20;   // 32 samples of 524 288 instances: real-time blocks are never cut
-    int checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape);
+    int checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape,
+                 bool feed = false);
     int ensureBusScratch(size_t floats);
     int ensureBusStage(size_t floats);
     // tap / aux: the routes of the two narrow sides beside the mix (fx_batch_bus_side.hpp Route; null: the caller gave no rows)
     int runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-               const BusShape& shape, hipStream_t stream, const Route* tap = nullptr, const Route* aux = nullptr);
+               const BusShape& shape, hipStream_t stream, const Route* tap = nullptr, const Route* aux = nullptr, const FeedRoute* feed = nullptr);
     int busPieceSamples(int nSamples) const;   // the samples of the largest piece runBus cuts a block of nSamples into
     Block<float> bus_;              // the per-instance scratch [samples of a piece][channels][n]
     Block<float> busStage_;         // pageable host buffers: the [samples][channels][groups] sides of a block
@@ -570,6 +601,22 @@ private:
     void freeSendBlocks();
     int planAuxRoute(float* auxOut, const void* devAux, size_t rows, size_t pieceRows, Route* route);   // the chunk sums of the largest piece, then planSideRoute
     hipError_t launchSends(const Route& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s);
+    // bus feeds (fx_batch_bus_feed.cpp): the structure as the host holds it and one device block of 32-bit words (feedBlock_.cur) -
+    // offsets (CSR form only), source columns, gain block 0, gain block 1, at feedOff_[0..3], every table padded as BusFeedArgs
+    // wants it; feedRamp_ keeps the roles of the two gain blocks.  Only busSetFeeds / busSetFeedGains write it, behind a wait for
+    // everything queued.  feedSrc_: the device copy [rows][M] of a source block that is not device memory, grown on demand in
+    // front of a block's first launch.
+    FeedSet feed_;
+    ReservedBlock feedBlock_;            // busReserveFeeds: the block of the set to come
+    size_t feedOff_[4] = {0, 0, 0, 0};
+    size_t feedGainPitch_ = 0;
+    bool feedMap_ = false;
+    RampPair feedRamp_;
+    Block<uint32_t> feedSrc_;
+    int64_t busFeedBlocks_ = 0;          // FXB_INFO_BUS_FEED_BLOCKS
+    size_t feedBlockWords(int64_t entries, bool map, size_t* off4) const;
+    int planFeedRoute(const float* src, const void* devSrc, size_t rows, FeedRoute* route);
+    hipError_t launchFeed(const FeedRoute& route, size_t first, long long rows, int nSamples, int sample0, hipStream_t s);
     CheckedAddr busIn_, busOut_;   // kBusDevice: the last pair that passed its checks, as processDeviceChecked keeps one (the last d_tap_out / d_aux_out: tapRows_ / auxRows_)
     // instance-major blocks: gather -> the ordinary launch in place on the bus scratch -> scatter (the scratch, evBus_ and
     // busLaunched_ are shared with bus blocks: the two kinds may alternate, on different streams)

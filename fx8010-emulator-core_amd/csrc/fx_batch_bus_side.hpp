@@ -1,4 +1,4 @@
-// fx_batch_bus_side.hpp — the small state holders the modes of a bus block share (taps, sends, gains; fx_batch.hpp), and the ones
+// fx_batch_bus_side.hpp — the small state holders the modes of a bus block share (taps, sends, feeds, gains; fx_batch.hpp), and the ones
 // the other block paths use with them.  Plain structs: what allocates or can fail is a member of Batch (fx_batch_bus_side.cpp).
 #pragma once
 
@@ -49,6 +49,13 @@ struct Route {
 struct Footprint {
     const float* p;
     int64_t width, pitch;
+};
+
+// where the feed kernel of one block gathers from (Batch::planFeedRoute): the caller's source rows [rows][M] where they are
+// memory of the device, else the device copy the runtime makes of them piece by piece
+struct FeedRoute {
+    const uint32_t* dev = nullptr;    // gathered in place; null: staged
+    const float* host = nullptr;      // ... the caller's rows then
 };
 
 // the device block of a set in two steps, so that several shards can be all-or-nothing: Batch::reserveBlock allocates the block

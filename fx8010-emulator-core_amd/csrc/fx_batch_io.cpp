@@ -518,6 +518,7 @@ int Batch::processHostPipelined(const float* in, float* out, int nSamples, int64
 //
 // None of the three kernel tiers knows about groups: a bus block is expand -> the ordinary launch, in place on a per-instance
 // scratch block in device memory -> mix, ordered on one stream.  What crosses PCIe is the [sample][channel][group] side only.
+// A feed block (fx_batch_bus_feed.cpp) fills the scratch from per-instance lists of a source block's columns instead.
 
 bool Batch::busBuffersApart(const float* in, const float* out, size_t rows, int64_t inWidth, int64_t inPitch, int64_t outWidth, int64_t outPitch) {
     const bool oneLayout = inWidth == outWidth && inPitch == outPitch;
@@ -527,23 +528,35 @@ bool Batch::busBuffersApart(const float* in, const float* out, size_t rows, int6
     return oneLayout && pcmDisjointOrSame(in, out, rows, inWidth, inPitch);   // (two column ranges of one buffer)
 }
 
+// the source block [rows][sources] of a feed block and the output: no shared byte
+bool Batch::feedSourceApart(const float* src, const float* out, size_t rows, int64_t sources, int64_t outWidth, int64_t outPitch) {
+    const char *x = reinterpret_cast<const char*>(src), *y = reinterpret_cast<const char*>(out);
+    return x + pcmExtent(rows, sources, sources) <= y || y + pcmExtent(rows, outWidth, outPitch) <= x;
+}
+
 // The refusals of the bus entries, in front of everything else: a refused call has launched nothing and changed nothing.
-int Batch::checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape) {
+int Batch::checkBus(const float* in, const float* out, const float* tapOut, const float* auxOut, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusShape* shape,
+                    bool feed) {
     if (nSamples < 0) return fail(FX_E_ARG, "n_samples < 0");
     if (group < 1) return fail(FX_E_ARG, "bus: group must be at least 1");
     if (flags & ~(unsigned)kBusFlags) return fail(FX_E_ARG, "bus: unknown flag bits");
+    if (feed && feed_.sources < 1) return fail(FX_E_ARG, "bus feeds: feeds are off (fxb_bus_set_feeds)");
+    if (feed && (flags & kBusSharedIn)) return fail(FX_E_ARG, "bus feeds: FXB_BUS_SHARED_IN does not go with a source block");
     BusShape s;
     s.group = std::min(group, n_);   // (a larger group is the one group of everything)
     s.groups = (n_ + s.group - 1) / s.group;
-    s.inWidth = (flags & kBusSharedIn) ? s.groups : n_;
+    s.inWidth = feed ? feed_.sources : (flags & kBusSharedIn) ? s.groups : n_;
     s.outWidth = (flags & kBusMixOut) ? s.groups : n_;
+    if (feed) inPitch = s.inWidth;   // (the source block has a row pitch of exactly M)
     s.inPitch = inPitch > 0 ? inPitch : s.inWidth;
     s.outPitch = outPitch > 0 ? outPitch : s.outWidth;
     if (s.inPitch < s.inWidth || s.outPitch < s.outWidth) return fail(FX_E_ARG, "bus: row pitch below the width of the layout");
     if (pcmStrideTooWide(prog_.numChannels, s.inPitch) || pcmStrideTooWide(prog_.numChannels, s.outPitch) || pcmStrideTooWide(prog_.numChannels, n_))
         return fail(FX_E_ARG, "bus: PCM row too wide: channels * row length * 4 must stay below 2^32 in every layout");
     if (nSamples > 0 && (!in || !out)) return fail(FX_E_ARG, "null buffer");
-    if (nSamples > 0 && !busBuffersApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
+    if (nSamples > 0 && feed && !feedSourceApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.outWidth, s.outPitch))
+        return fail(FX_E_ARG, "bus feeds: src overlaps the output (the layouts differ: there is no in-place form)");
+    if (nSamples > 0 && !feed && !busBuffersApart(in, out, (size_t)nSamples * (size_t)prog_.numChannels, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
         return fail(FX_E_ARG, "bus: input and output overlap without being one buffer with one layout");
     if (const char* why = checkTapShape(in, out, tapOut, (size_t)std::max(nSamples, 0) * (size_t)prog_.numChannels, tapTotal_, flags, s.inWidth, s.inPitch, s.outWidth, s.outPitch))
         return fail(FX_E_ARG, why);
@@ -584,7 +597,7 @@ int Batch::busPieceSamples(int nSamples) const {
 }
 
 int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t narrowInPitch, float* narrowOut, int64_t narrowOutPitch, int nSamples, unsigned flags,
-                  const BusShape& shape, hipStream_t stream, const Route* tap, const Route* aux) {
+                  const BusShape& shape, hipStream_t stream, const Route* tap, const Route* aux, const FeedRoute* feed) {
     const size_t ch = (size_t)prog_.numChannels, perSample = ch * (size_t)n_;
     const int most = tracksArmed() ? nSamples : (int)std::min<size_t>((size_t)nSamples, std::max<size_t>(kBusScratchBytes / (perSample * 4), 1));
     const int pieces = (nSamples + most - 1) / most;
@@ -632,7 +645,10 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         a.group = shape.group;
         a.groups = shape.groups;
         hipError_t e;
-        if (flags & kBusSharedIn) {
+        if (feed) {
+            // the third way to fill the scratch: from the lists of the feeds, out of this piece's source rows
+            e = launchFeed(*feed, first, a.rows, nSamples, lo(p), s);
+        } else if (flags & kBusSharedIn) {
             a.narrowIn = narrowIn + first * (size_t)narrowInPitch;
             a.narrowPitch = narrowInPitch;
             e = launchBusExpand(a, s);
@@ -668,14 +684,18 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         ++busGainBlocks_;
         gainRamp_.consume();
     }
+    if (feed) {
+        ++busFeedBlocks_;
+        feedRamp_.consume();   // (the same)
+    }
     return 0;
 }
 
 int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, int64_t inPitch, int64_t outPitch, BusEntry entry, hipStream_t stream,
-                      float* tapOut, float* auxOut) {
+                      float* tapOut, float* auxOut, bool feed) {
     (void)hipSetDevice(device_);
     BusShape shape;
-    int rc = checkBus(in, out, tapOut, auxOut, nSamples, group, flags, inPitch, outPitch, &shape);
+    int rc = checkBus(in, out, tapOut, auxOut, nSamples, group, flags, inPitch, outPitch, &shape, feed);
     if (rc != 0) return rc;
     if (nSamples == 0) return ensureLowered();
     const size_t rows = (size_t)nSamples * (size_t)prog_.numChannels;
@@ -687,15 +707,25 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
     Route tapRoute, auxRoute;   // (of a side without rows: empty, and nothing below does anything with it)
     const Route* tap = tapOut ? &tapRoute : nullptr;
     const Route* aux = auxOut ? &auxRoute : nullptr;
+    FeedRoute feedRoute;
+    const FeedRoute* fed = feed ? &feedRoute : nullptr;
+    // a source block is gathered where it lies only if the pointer attributes show memory of this device: every word of it is
+    // read many times, and none of those reads may cross PCIe (anything else is copied into the device block of planFeedRoute)
+    auto deviceSource = [&]() -> const void* {
+        hipPointerAttribute_t attr;
+        const void* dev = nullptr;
+        return (pointerAttributes(in, &attr) && attr.type == hipMemoryTypeDevice && addressable(in, inBytes, device_, &dev)) ? dev : nullptr;
+    };
     if (entry == kBusDevice) {
         if ((rc = lookupPair(busIn_, in, inBytes, busOut_, out, outBytes)) != 0) return rc;
         if (tapOut && (rc = lookup(tapRows_.checked, tapOut, tapBytes, kTapTexts.notAddressable)) != 0) return rc;
         if (auxOut && (rc = lookup(auxRows_.checked, auxOut, auxBytes, kAuxTexts.notAddressable)) != 0) return rc;
         if (tapOut && (rc = planSideRoute(tapRows_, kTapTexts, tapOut, tapRows_.checked.dev, rows, tapList_.size(), tapTotal_, tapPlace(), &tapRoute)) != 0) return rc;
         if (auxOut && (rc = planAuxRoute(auxOut, auxRows_.checked.dev, rows, pieceRows, &auxRoute)) != 0) return rc;
+        if (feed && (rc = planFeedRoute(in, deviceSource(), rows, &feedRoute)) != 0) return rc;
         const float* dIn = static_cast<const float*>(busIn_.dev);
         float* dOut = static_cast<float*>(busOut_.dev);
-        return runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream, tap, aux);
+        return runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream, tap, aux, fed);
     }
     // Host entry.  Pinned buffers: the bus kernels read the group words from and store the sums to the caller's memory over PCIe
     // (256 bytes per wavefront access), no copies.  Anything else: the [sample][channel][group] sides are staged.  Whatever
@@ -712,6 +742,8 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         if (!(knobs_.hostPipeline && addressable(auxOut, auxBytes, -1, &devAux))) devAux = nullptr;
         if ((rc = planAuxRoute(auxOut, devAux, rows, pieceRows, &auxRoute)) != 0) return rc;
     }
+    // ... and the source rows of the feeds: in place only where they are memory of this device
+    if (feed && (rc = planFeedRoute(in, deviceSource(), rows, &feedRoute)) != 0) return rc;
     // the tail of both host paths behind runBus and the copies of the two sides (e: their result): the staged side rows on their
     // way out, the wait - also when the call failed -, the columns of a shard into their places
     auto finish = [&](int rc0, hipError_t e, const char* what) {
@@ -724,10 +756,10 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         placeSideColumns(auxRows_, auxRoute, auxOut, rows);
         return 0;
     };
-    if (knobs_.hostPipeline && addressable(in, inBytes, -1, &devIn) && addressable(out, outBytes, -1, &devOut)) {
-        const float* dIn = static_cast<const float*>(devIn);
+    if (knobs_.hostPipeline && (feed || addressable(in, inBytes, -1, &devIn)) && addressable(out, outBytes, -1, &devOut)) {
+        const float* dIn = static_cast<const float*>(devIn);   // (a feed block: the source rows go by feedRoute, not by this)
         float* dOut = static_cast<float*>(const_cast<void*>(devOut));
-        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap, aux);
+        rc = runBus(dIn, dOut, dIn, shape.inPitch, dOut, shape.outPitch, nSamples, flags, shape, stream_, tap, aux, fed);
         if ((rc = finish(rc, hipSuccess, "synchronising a bus block on pinned host buffers")) == 0) ++hostInplaceBlocks_;   // (blocks that were processed: a failed one is not counted)
         return rc;
     }
@@ -743,7 +775,7 @@ int Batch::processBus(const float* in, float* out, int nSamples, int64_t group, 
         (void)hipStreamSynchronize(stream_);
         return hipFail(e, "bus H2D");
     }
-    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap, aux);
+    rc = runBus(in, out, stageIn, shape.groups, stageOut, shape.groups, nSamples, flags, shape, stream_, tap, aux, fed);
     if (rc == 0 && mixOut) e = copyRows(out, (size_t)shape.outPitch * 4, stageOut, narrow, narrow, rows, hipMemcpyDefault, stream_);
     if ((rc = finish(rc, e, "bus D2H")) == 0) ++hostStagedBlocks_;
     return rc;

@@ -1,12 +1,15 @@
 // fx_bus.hip — the kernels around the emulation launch of a bus block (fx_bus.hpp): expand a per-group input to the
 // per-instance scratch, mix the scratch down to one word per group - plain (fx_bus_mix) or with per-instance gains (fx_bus_mix_gain) -
-// gather a list of its columns into a narrow monitor side (fx_bus_tap), and sum member lists of them onto aux buses (fx_bus_send_*).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
+// gather a list of its columns into a narrow monitor side (fx_bus_tap), sum member lists of them onto aux buses (fx_bus_send_*), and
+// build the scratch from per-instance lists of the columns of a narrow source block (fx_bus_feed).  gfx950, wave64, one wavefront per workgroup.  The narrow side,
 // which may be pinned host memory behind PCIe, sees exactly one 256-byte access per wavefront and row.  The wide side: the expand
 // stores 1 KiB per wavefront access; the mix loads 256 contiguous bytes per access for groups of 64 instances and more, and ONE
 // PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
 // 64 trees on 256 bytes; packing several short groups into one load with a segmented tree of the same bits is open).  Groups above
 // 64 are summed by one wavefront, four loads in flight: a group of a whole row (K = N) is one wavefront walking the row.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "fx_bus.hpp"
 
@@ -401,6 +404,213 @@ __global__ __launch_bounds__(64) void fx_bus_send_fold(BusSendArgs a) {
     }
 }
 
+// ---- the feeds (fx_bus.hpp BusFeedArgs): the scratch block built from per-instance lists of source columns -------------------
+//
+// fx_bus_feed: grid.x = spans of kFeedSpan instances, grid.y = groups of kFeedRows rows (a loop where a block has more groups than
+// a grid may have).  A lane owns FOUR consecutive instances of a row, the same four in every row of a group: it loads their
+// offsets, source columns and gain words once per group (one 16-byte access per table, 1 KiB contiguous per wavefront) and issues
+// the gathers src[row][idx] of all eight rows - a 32-bit byte stride of m * 4 apart, out of a block of m * 4 bytes per row that
+// the L2 holds - before the first add.  The wide side is written as fx_bus_expand writes it: one aligned uint4 store per lane and
+// row, 1 KiB per wavefront.  Where a row's span does not begin on a 16-byte boundary (n not a multiple of 4: the boundary moves
+// from row to row) a lane's quad is the tail of its own four words and the head of its neighbour's, fetched by three shuffles;
+// the words in front of the first boundary and at the ragged end go one by one.
+//   kMap:  every instance has exactly one entry, entry i is instance i's: no offsets, no loop.
+//   else:  CSR; a lane walks entry j of its four instances together, up to the longest of their lists.
+//   kMode: 0 unweighted (words move as bit patterns), 1 weighted, 2 weighted with a ramp pending.  kCh as fx_bus_send_chunks.
+// A ragged last group predicates its loads and stores by row: nothing outside the block's rows is read or written.
+constexpr int kFeedRows = 8;
+constexpr unsigned kFeedSpan = 256;   // instances of a row one wavefront writes: one store of 1 KiB
+
+// the words w of instances i .. i + 3 (i = the span's first + lane * 4) to one row; end: behind the span's last instance
+__device__ __forceinline__ void feedStoreRow(uint32_t* dstRow, const unsigned i, const unsigned end, const uint32_t (&w)[4], const unsigned lane) {
+    // the words in front of the lane's 16-byte boundary: the same number in every lane
+    const unsigned h = (unsigned)__builtin_amdgcn_readfirstlane((int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(dstRow + i) >> 2) & 3u)) & 3u));
+    if (h == 0u) {
+        if (i + 4u <= end) {
+            *reinterpret_cast<uint4*>(dstRow + i) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i + (unsigned)e < end) dstRow[i + e] = w[e];
+        }
+        return;
+    }
+    // the aligned quad i + h .. i + h + 3: this lane's last 4 - h words and the next lane's first h
+    const uint32_t n0 = (uint32_t)__shfl_down((int)w[0], 1), n1 = (uint32_t)__shfl_down((int)w[1], 1), n2 = (uint32_t)__shfl_down((int)w[2], 1);
+    uint4 q;
+    if (h == 1u) q = make_uint4(w[1], w[2], w[3], n0);
+    else if (h == 2u) q = make_uint4(w[2], w[3], n0, n1);
+    else q = make_uint4(w[3], n0, n1, n2);
+    // the h words in front belong to the previous lane's quad - which lane 0 has none of, and a lane at the ragged end neither
+    if (lane == 0u || i + h > end) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if ((unsigned)e < h && i + (unsigned)e < end) dstRow[i + e] = w[e];
+    }
+    if (lane < 63u && i + h + 4u <= end) {
+        *reinterpret_cast<uint4*>(dstRow + i + h) = q;
+    } else {
+#pragma unroll
+        for (int e = 1; e < 4; ++e)
+            if ((unsigned)e >= h && i + (unsigned)e < end) dstRow[i + e] = w[e];
+    }
+}
+
+// one span over the eight rows from row0 on; kFull: all eight exist (no row predicate anywhere)
+template <bool kMap, int kMode, int kCh, bool kFull>
+__device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long long row0, const unsigned lane, const unsigned i, const unsigned end) {
+    constexpr bool kWeighted = kMode > 0, kRamp = kMode == 2;
+    constexpr int kGains = kCh > 0 ? kCh : kFeedRows;
+    const uint32_t srcStride = (uint32_t)a.m * 4u;   // (below 2^32: launchBusFeed)
+    float t[kFeedRows];
+    bool atTarget[kFeedRows], rowOk[kFeedRows];
+    long long gainRow[kGains];
+#pragma unroll
+    for (int u = 0; u < kFeedRows; ++u) {
+        const long long row = row0 + u;
+        const long long s = row / a.channels + a.sample0;   // the sample of the CALL this row belongs to
+        t[u] = (float)(s + 1) * a.r;
+        atTarget[u] = s == (long long)a.samples - 1;
+        rowOk[u] = kFull || row < a.rows;
+        if (kCh == 0) gainRow[u] = (row % a.channels) * a.gainPitch;
+    }
+    if (kCh > 0) {
+#pragma unroll
+        for (int c = 0; c < kGains; ++c) gainRow[c] = (long long)c * a.gainPitch;
+    }
+    uint32_t w[kFeedRows][4];
+#pragma unroll
+    for (int u = 0; u < kFeedRows; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[u][k] = 0u;
+    const char* base = reinterpret_cast<const char*>(a.src + row0 * a.m);
+    if (i < end) {
+        if (kMap) {
+            const uint4 ix4 = *reinterpret_cast<const uint4*>(a.idx + i);
+            const uint32_t ix[4] = {ix4.x, ix4.y, ix4.z, ix4.w};
+            float ga[kGains][4], gb[kGains][4];
+#pragma unroll
+            for (int c = 0; c < kGains; ++c) {
+                float4 b4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a4 = b4;
+                if (kWeighted && (kCh > 0 || rowOk[c])) {
+                    b4 = *reinterpret_cast<const float4*>(a.target + gainRow[c] + i);
+                    if (kRamp) a4 = *reinterpret_cast<const float4*>(a.current + gainRow[c] + i);
+                }
+                gb[c][0] = b4.x; gb[c][1] = b4.y; gb[c][2] = b4.z; gb[c][3] = b4.w;
+                ga[c][0] = a4.x; ga[c][1] = a4.y; ga[c][2] = a4.z; ga[c][3] = a4.w;
+            }
+            uint32_t x[kFeedRows][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const char* p = base + (size_t)ix[k] * 4u;
+#pragma unroll
+                for (int u = 0; u < kFeedRows; ++u) {
+                    x[u][k] = rowOk[u] ? *reinterpret_cast<const uint32_t*>(p) : 0u;
+                    p += srcStride;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kFeedRows; ++u) {
+                const int c = kCh > 0 ? u % kGains : u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    w[u][k] = kWeighted ? __builtin_bit_cast(uint32_t, termOf(weightOf<kRamp>(ga[c][k], gb[c][k], t[u], atTarget[u]), __builtin_bit_cast(float, x[u][k])))
+                                        : x[u][k];
+            }
+        } else {
+            const uint4 o4 = *reinterpret_cast<const uint4*>(a.off + i);
+            const uint32_t o[5] = {o4.x, o4.y, o4.z, o4.w, a.off[i + 4u]};
+            uint32_t count[4], longest = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                count[k] = o[k + 1] - o[k];
+                longest = count[k] > longest ? count[k] : longest;
+            }
+            float acc[kFeedRows][4];
+            // entry j of the lane's four instances: index and gain words, the 32 gathers, then the adds - the first term starts the sum
+            auto step = [&](const uint32_t j, auto first) {
+                uint32_t ix[4];
+                bool has[4];
+                float ga[kGains][4], gb[kGains][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    has[k] = j < count[k];
+                    const uint32_t e = o[k] + j;
+                    ix[k] = has[k] ? a.idx[e] : 0u;
+#pragma unroll
+                    for (int c = 0; c < kGains; ++c) {
+                        const bool need = kWeighted && has[k] && (kCh > 0 || rowOk[c]);
+                        gb[c][k] = need ? a.target[gainRow[c] + e] : 0.0f;
+                        ga[c][k] = (kRamp && need) ? a.current[gainRow[c] + e] : 0.0f;
+                    }
+                }
+                uint32_t x[kFeedRows][4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const char* p = base + (size_t)ix[k] * 4u;
+#pragma unroll
+                    for (int u = 0; u < kFeedRows; ++u) {
+                        x[u][k] = (has[k] && rowOk[u]) ? *reinterpret_cast<const uint32_t*>(p) : 0u;
+                        p += srcStride;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kFeedRows; ++u) {
+                    const int c = kCh > 0 ? u % kGains : u;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float xf = __builtin_bit_cast(float, x[u][k]);
+                        const float term = kWeighted ? termOf(weightOf<kRamp>(ga[c][k], gb[c][k], t[u], atTarget[u]), xf) : xf;
+                        if (decltype(first)::value) acc[u][k] = has[k] ? term : 0.0f;
+                        else acc[u][k] = has[k] ? acc[u][k] + term : acc[u][k];
+                    }
+                }
+            };
+            step(0u, std::true_type{});
+            for (uint32_t j = 1u; j < longest; ++j) step(j, std::false_type{});
+#pragma unroll
+            for (int u = 0; u < kFeedRows; ++u)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[u][k] = __builtin_bit_cast(uint32_t, acc[u][k]);
+        }
+    }
+    uint32_t* dst = a.wide + row0 * a.n;
+#pragma unroll
+    for (int u = 0; u < kFeedRows; ++u) {
+        if (rowOk[u]) feedStoreRow(dst, i, end, w[u], lane);   // (the same rows in every lane)
+        dst += a.n;
+    }
+}
+
+template <bool kMap, int kMode, int kCh>
+__global__ __launch_bounds__(64) void fx_bus_feed(BusFeedArgs a) {
+    const unsigned lane = threadIdx.x;
+    const unsigned first = blockIdx.x * kFeedSpan, n = (unsigned)a.n;
+    const unsigned end = n - first < kFeedSpan ? n : first + kFeedSpan;
+    const unsigned i = first + lane * 4u;
+    const long long groups = (a.rows + kFeedRows - 1) / kFeedRows;
+    for (long long grp = blockIdx.y; grp < groups; grp += gridDim.y) {
+        const long long row0 = grp * kFeedRows;
+        if (row0 + kFeedRows <= a.rows) feedRowGroup<kMap, kMode, kCh, true>(a, row0, lane, i, end);
+        else feedRowGroup<kMap, kMode, kCh, false>(a, row0, lane, i, end);
+    }
+}
+
+template <bool kMap>
+void launchFeedVariant(const BusFeedArgs& a, dim3 grid, hipStream_t stream) {
+    if (!a.target) {
+        hipLaunchKernelGGL((fx_bus_feed<kMap, 0, 1>), grid, dim3(64), 0, stream, a);
+    } else if (a.ramp) {
+        if (a.channels == 1) hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 1>), grid, dim3(64), 0, stream, a);
+        else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 2>), grid, dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 0>), grid, dim3(64), 0, stream, a);
+    } else {
+        if (a.channels == 1) hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 1>), grid, dim3(64), 0, stream, a);
+        else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 2>), grid, dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 0>), grid, dim3(64), 0, stream, a);
+    }
+}
+
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
 }  // namespace
@@ -479,6 +689,29 @@ hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream) {
     }
     const dim3 grid((unsigned)((a.buses + 63) / 64), (unsigned)(a.rows < 65535 ? a.rows : 65535));
     hipLaunchKernelGGL(fx_bus_send_fold, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchBusFeed(const BusFeedArgs& a, hipStream_t stream) {
+    constexpr long long kMostEntries = (long long)1 << 24;
+    const auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const bool map = !a.off;
+    const long long n4 = (a.n + 3) / 4 * 4;
+    if (!a.src || !a.wide || a.rows < 1 || a.n < 1 || a.n >= ((long long)1 << 30) || a.m < 1 || a.m >= ((long long)1 << 30) || a.entries < 0 || a.entries > kMostEntries ||
+        (map && a.entries != a.n) || (a.entries > 0 && !a.idx) || !aligned16(a.off) || !aligned16(a.idx) || a.channels < 1 || a.rows % a.channels != 0)
+        return hipErrorInvalidValue;
+    if (a.target) {
+        if ((a.ramp && !a.current) || a.gainPitch < a.entries || a.samples < 1 || a.sample0 < 0 || (long long)a.sample0 + a.rows / a.channels > (long long)a.samples)
+            return hipErrorInvalidValue;
+        if (map && (a.gainPitch < n4 || a.gainPitch % 4 != 0 || !aligned16(a.target) || !aligned16(a.current))) return hipErrorInvalidValue;
+    } else if (a.ramp) {
+        return hipErrorInvalidValue;
+    }
+    const long long groups = (a.rows + kFeedRows - 1) / kFeedRows;
+    const dim3 grid((unsigned)((a.n + kFeedSpan - 1) / kFeedSpan), (unsigned)(groups < 65535 ? groups : 65535));
+    (void)hipGetLastError();
+    if (map) launchFeedVariant<true>(a, grid, stream);
+    else launchFeedVariant<false>(a, grid, stream);
     return hipGetLastError();
 }
 

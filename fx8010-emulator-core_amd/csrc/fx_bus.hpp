@@ -97,4 +97,36 @@ struct BusSendArgs {
 // auxOut[r][column of bus j] = partial[r][firstChunk] for one chunk, that same sum over the bus's chunk sums for more, +0.0f for none
 hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream);
 
+// Bus feeds (include/fx8010_amd.h "Bus feeds"): the scratch block built from per-instance lists of columns of a narrow source
+// block [rows][m].  Instance i owns the entries off[i] .. off[i + 1] - 1 (CSR by instance); the MAP form (off null) is the
+// structure whose every instance has exactly one entry, entry i being instance i's.  Every table is 32-bit words, 16-byte
+// aligned and padded so that a lane reads the words of its four instances with one access whatever n is:
+//   off     [ceil4(n) + 1], the words behind off[n] repeating it (instances that do not exist own nothing); null: the map form
+//   idx     [entries] source columns, each below m (the map form: [ceil4(n)], padded with columns below m)
+//   target  b: [channels][gainPitch] by entry; null: UNWEIGHTED (words move as bit patterns)
+//   current a: read only while a ramp is pending
+// gainPitch >= entries (the map form: >= ceil4(n) and a multiple of 4).
+struct BusFeedArgs {
+    const uint32_t* src;     // [rows][m] source words, rows packed (device memory: every word is gathered many times)
+    uint32_t* wide;          // [rows][n] per-instance scratch, rows packed (device memory)
+    const uint32_t* off;
+    const uint32_t* idx;
+    const float* current;
+    const float* target;
+    long long rows;          // samples * channels
+    long long n;             // instances; n * 4 < 2^32
+    long long m;             // source columns, m >= 1; m * 4 < 2^32
+    long long entries;       // E of this batch, <= 2^24 (the map form: n)
+    long long gainPitch;
+    int channels;            // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
+    int ramp;                // as BusGainArgs
+    float r;
+    int samples;
+    int sample0;
+};
+
+// wide[r][i] = the word of the definition: +0.0f for no entry, term_0 for one, ((term_0 + term_1) + term_2) + ... in entry order
+// for more; term_k = src[r][idx[e]] (unweighted), else (w == 0.0f ? +0.0f : w * src[r][idx[e]]) with w as in launchBusMixGain
+hipError_t launchBusFeed(const BusFeedArgs& a, hipStream_t stream);
+
 }  // namespace fx

@@ -246,6 +246,19 @@ int fxb_process_block_bus_aux(fxb_handle* h, const float* in, float* out, float*
 int fxb_process_block_bus_aux_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, float* d_aux_out, int n, int64_t group, unsigned flags, void* stream) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_in, d_out, n, group, flags, true, static_cast<hipStream_t>(stream), d_tap_out, d_aux_out); }) : FX_E_ARG;
 }
+int fxb_process_block_bus_feed(fxb_handle* h, const float* src, float* out, float* tap_out, float* aux_out, int n, int64_t group, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(src, out, n, group, flags, false, nullptr, tap_out, aux_out, true); }) : FX_E_ARG;
+}
+int fxb_process_block_bus_feed_dev(fxb_handle* h, const float* d_src, float* d_out, float* d_tap_out, float* d_aux_out, int n, int64_t group, unsigned flags, void* stream) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.processBus(d_src, d_out, n, group, flags, true, static_cast<hipStream_t>(stream), d_tap_out, d_aux_out, true); }) : FX_E_ARG;
+}
+int fxb_bus_set_feeds(fxb_handle* h, int64_t n_src, const int64_t* offsets, const int64_t* sources, const float* gains) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetFeeds(n_src, offsets, sources, gains); }) : FX_E_ARG;
+}
+int fxb_bus_set_feed_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetFeedGains(gains, ramp); }) : FX_E_ARG; }
+int64_t fxb_bus_get_feeds(fxb_handle* h, int64_t* n_src, int64_t* offsets, int64_t off_cap, int64_t* sources, float* gains, int64_t cap) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.busGetFeeds(n_src, offsets, off_cap, sources, gains, cap); }) : (int64_t)FX_E_ARG;
+}
 int fxb_bus_set_sends(fxb_handle* h, int64_t n_aux, const int64_t* offsets, const int64_t* members, const float* gains) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetSends(n_aux, offsets, members, gains); }) : FX_E_ARG;
 }

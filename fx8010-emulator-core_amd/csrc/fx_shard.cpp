@@ -260,13 +260,15 @@ int Sharded::processDevicePitched(const float* dIn, float* dOut, int nSamples, i
     if (shards_.size() != 1) { lastError_ = "a batch of several shards takes one buffer pair per shard: fxb_process_block_dev_shards"; return FX_E_ARG; }
     return runOn(0, [&](Batch& b) { return b.processDeviceChecked(dIn, dOut, nSamples, pitch, stream); });
 }
-int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut, float* auxOut) {
+int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut, float* auxOut, bool feed) {
     Serial serial(api_);
     lastError_.clear();
     // the refusals that go by the WHOLE batch, before any shard is posted (a refused call launches nothing on any shard)
     if (group < 1) { lastError_ = "bus: group must be at least 1"; return FX_E_ARG; }
     if (flags & ~(unsigned)Batch::kBusFlags) { lastError_ = "bus: unknown flag bits"; return FX_E_ARG; }
     if (device && shards_.size() != 1) { lastError_ = "the device entry of a bus block is for handles of one shard"; return FX_E_ARG; }
+    if (feed && front().busFeedSources() < 1) { lastError_ = "bus feeds: feeds are off (fxb_bus_set_feeds)"; return FX_E_ARG; }
+    if (feed && (flags & Batch::kBusSharedIn)) { lastError_ = "bus feeds: FXB_BUS_SHARED_IN does not go with a source block"; return FX_E_ARG; }
     if (tapOut && (front().busTaps() < 1 || !(flags & Batch::kBusMixOut))) {
         lastError_ = Batch::checkTapShape(nullptr, nullptr, tapOut, 0, front().busTaps(), flags, 0, 0, 0, 0);
         return FX_E_ARG;
@@ -275,14 +277,19 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
         lastError_ = Batch::checkAuxShape(nullptr, nullptr, nullptr, auxOut, 0, front().busSendBuses(), 0, flags, 0, 0, 0, 0);
         return FX_E_ARG;
     }
-    if (flags == 0) return device ? processDevicePitched(in, out, nSamples, n_, stream) : processHost(in, out, nSamples, 0);
+    if (flags == 0 && !feed) return device ? processDevicePitched(in, out, nSamples, n_, stream) : processHost(in, out, nSamples, 0);
     if (shards_.size() == 1)
-        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream, tapOut, auxOut); });
+        return runOn(0, [&](Batch& b) { return b.processBus(in, out, nSamples, group, flags, 0, 0, device ? Batch::kBusDevice : Batch::kBusHost, stream, tapOut, auxOut, feed); });
+    // (the input side of a feed block has no sum across shards: only the groups of a mixed output must not straddle)
     for (auto& w : shards_)
-        if (w->first % group != 0) { lastError_ = "bus: a group straddles shards (every shard must begin at a multiple of the group size: fxb_shard_plan)"; return FX_E_ARG; }
+        if ((!feed || (flags & Batch::kBusMixOut)) && w->first % group != 0) { lastError_ = "bus: a group straddles shards (every shard must begin at a multiple of the group size: fxb_shard_plan)"; return FX_E_ARG; }
     const int64_t groups = (n_ + group - 1) / group;
-    const int64_t inPitch = (flags & Batch::kBusSharedIn) ? groups : n_, outPitch = (flags & Batch::kBusMixOut) ? groups : n_;
-    if (nSamples > 0 && in && out && !Batch::busBuffersApart(in, out, (size_t)nSamples * (size_t)front().channels(), inPitch, inPitch, outPitch, outPitch)) {
+    const int64_t inPitch = feed ? front().busFeedSources() : (flags & Batch::kBusSharedIn) ? groups : n_, outPitch = (flags & Batch::kBusMixOut) ? groups : n_;
+    if (feed && nSamples > 0 && in && out && !Batch::feedSourceApart(in, out, (size_t)nSamples * (size_t)front().channels(), inPitch, outPitch, outPitch)) {
+        lastError_ = "bus feeds: src overlaps the output (the layouts differ: there is no in-place form)";
+        return FX_E_ARG;
+    }
+    if (!feed && nSamples > 0 && in && out && !Batch::busBuffersApart(in, out, (size_t)nSamples * (size_t)front().channels(), inPitch, inPitch, outPitch, outPitch)) {
         lastError_ = "bus: input and output overlap without being one buffer with one layout";
         return FX_E_ARG;
     }
@@ -301,9 +308,10 @@ int Sharded::processBus(const float* in, float* out, int nSamples, int64_t group
         }
     return fan([&](int k, Batch& b) {
         const int64_t first = shards_[(size_t)k]->first;
-        const float* shardIn = in ? in + ((flags & Batch::kBusSharedIn) ? first / group : first) : in;
+        // (every shard reads the whole source block of a feed block and stages the rows on its own device)
+        const float* shardIn = (in && !feed) ? in + ((flags & Batch::kBusSharedIn) ? first / group : first) : in;
         float* shardOut = out ? out + ((flags & Batch::kBusMixOut) ? first / group : first) : out;
-        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr, tapOut, auxOut);
+        return b.processBus(shardIn, shardOut, nSamples, group, flags, inPitch, outPitch, Batch::kBusHost, nullptr, tapOut, auxOut, feed);
     });
 }
 int Sharded::processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream) {
@@ -483,6 +491,69 @@ int64_t Sharded::busGetSends(int64_t* nAux, int64_t* offsets, int64_t offCap, in
     int64_t total = 0;
     for (auto& w : shards_) total = w->batch->busGetSends(offsets, offCap, members, gains, cap, w->first);   // (host state only: no device call)
     return total;
+}
+
+int Sharded::busSetFeeds(int64_t nSrc, const int64_t* offsets, const int64_t* sources, const float* gains) {
+    Serial serial(api_);
+    lastError_.clear();
+    const size_t ch = (size_t)front().channels();
+    if (nSrc < 0) { lastError_ = "bus feeds: n_src must not be negative"; return FX_E_ARG; }
+    if ((uint64_t)ch * (uint64_t)nSrc * 4u >= ((uint64_t)1 << 32)) { lastError_ = "bus feeds: channels * n_src * 4 must stay below 2^32"; return FX_E_ARG; }
+    if (nSrc == 0) return fan([](int, Batch& b) { return b.busSetFeeds(Batch::FeedSet{}); });
+    if (!offsets) { lastError_ = "bus feeds: null offsets"; return FX_E_ARG; }
+    if (offsets[0] != 0) { lastError_ = "bus feeds: offsets[0] must be 0"; return FX_E_ARG; }
+    for (int64_t i = 0; i < n_; ++i)
+        if (offsets[i + 1] < offsets[i]) { lastError_ = "bus feeds: offsets must not decrease"; return FX_E_ARG; }
+    const int64_t entries = offsets[n_];
+    if (entries > Batch::kMaxFeedEntries) { lastError_ = "bus feeds: more than 16 777 216 entries"; return FX_E_ARG; }
+    if (entries > 0 && !sources) { lastError_ = "bus feeds: null sources"; return FX_E_ARG; }
+    for (int64_t e = 0; e < entries; ++e)
+        if (sources[e] < 0 || sources[e] >= nSrc) { lastError_ = "bus feeds: a source outside 0..M-1"; return FX_E_ARG; }
+    if (gains)
+        for (size_t i = 0; i < ch * (size_t)entries; ++i)
+            if (!std::isfinite(gains[i])) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
+    // a shard's instances own a contiguous run of the entries
+    std::vector<Batch::FeedSet> parts(shards_.size());
+    for (size_t k = 0; k < parts.size(); ++k) {
+        Batch::FeedSet& part = parts[k];
+        const int64_t first = shards_[k]->first, count = shards_[k]->batch->instances();
+        const int64_t lo = offsets[first], mine = offsets[first + count] - lo;
+        part.sources = nSrc;
+        part.totalEntries = entries;
+        part.first = lo;
+        part.weighted = gains != nullptr;
+        part.offsets.resize((size_t)count + 1);
+        for (int64_t i = 0; i <= count; ++i) part.offsets[(size_t)i] = offsets[first + i] - lo;
+        part.columns.assign(sources + lo, sources + lo + mine);
+        part.gain[0].assign(ch * (size_t)mine, 1.0f);
+        if (gains)
+            for (size_t c = 0; c < ch && mine > 0; ++c) std::memcpy(&part.gain[0][c * (size_t)mine], gains + c * (size_t)entries + (size_t)lo, (size_t)mine * 4);
+    }
+    // every shard reserves the block of its lists first; only when all of them could does any shard's structure change
+    const auto reserve = [&](int k, Batch& b) {
+        const Batch::FeedSet& part = parts[(size_t)k];
+        return b.busReserveFeeds(nSrc, (int64_t)part.columns.size(), part.isMap());
+    };
+    if (const int rc = reserveOnAll(reserve, [](Batch& b) { b.busReleaseFeeds(); })) return rc;
+    return fan([&](int k, Batch& b) { return b.busSetFeeds(std::move(parts[(size_t)k])); });
+}
+int Sharded::busSetFeedGains(const float* gains, int ramp) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (ramp != 0 && ramp != 1) { lastError_ = "bus feeds: ramp must be 0 or 1"; return FX_E_ARG; }
+    if (front().busFeedSources() < 1) { lastError_ = "bus feeds: feeds are off (fxb_bus_set_feeds)"; return FX_E_ARG; }
+    const size_t words = gains ? (size_t)front().channels() * (size_t)front().busFeedEntries() : 0;
+    for (size_t i = 0; i < words; ++i)
+        if (!std::isfinite(gains[i])) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
+    return fan([&](int, Batch& b) { return b.busSetFeedGains(gains, ramp); });
+}
+int64_t Sharded::busGetFeeds(int64_t* nSrc, int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (offCap < 0 || cap < 0) { lastError_ = "bus feeds: a negative capacity"; return FX_E_ARG; }
+    if (nSrc) *nSrc = front().busFeedSources();
+    for (auto& w : shards_) w->batch->busGetFeeds(offsets, offCap, sources, gains, cap, w->first);   // (host state only: no device call)
+    return front().busFeedEntries();
 }
 
 int64_t Sharded::instructionCounter() {
@@ -717,7 +788,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

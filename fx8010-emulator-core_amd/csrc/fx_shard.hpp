@@ -72,7 +72,8 @@ public:
     // its own group columns, on its own thread and device.  device: the caller's stream, single-shard handles only.
     // tapOut (null: none): the caller's full-width [sample][channel][T] rows of the taps in force; a shard writes its entries' columns
     int processBus(const float* in, float* out, int nSamples, int64_t group, unsigned flags, bool device, hipStream_t stream, float* tapOut = nullptr,
-                   float* auxOut = nullptr);   // auxOut (null: none): the full-width [sample][channel][A] rows of the sends in force; a shard writes its buses' columns
+                   float* auxOut = nullptr,    // auxOut (null: none): the full-width [sample][channel][A] rows of the sends in force; a shard writes its buses' columns
+                   bool feed = false);         // feed: `in` is the source block [sample][channel][M] of the feeds in force; every shard reads all of it
     // instance-major blocks (Batch::processImajor): shard k works on the runs from in + first_k * inStride on, on its own thread
     // and device.  device: the caller's stream, single-shard handles only.
     int processImajor(const float* in, float* out, int nSamples, int64_t inStride, int64_t outStride, bool device, hipStream_t stream);
@@ -99,6 +100,13 @@ public:
     int busSetSends(int64_t nAux, const int64_t* offsets, const int64_t* members, const float* gains);
     int busSetSendGains(const float* gains, int ramp);
     int64_t busGetSends(int64_t* nAux, int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap);
+    // bus feeds (Batch::busSetFeeds ...): the CSR structure is by GLOBAL instance and is checked as a whole before any shard is
+    // posted; each shard gets the lists of its own instances - a contiguous run of the entries - and reserves its device block
+    // first, so FX_E_MEMORY leaves the old feeds in force everywhere.  The input side has no sum across shards: nothing straddles.
+    // nSrc 0 turns them off.  get: E, and what fits under the caps.
+    int busSetFeeds(int64_t nSrc, const int64_t* offsets, const int64_t* sources, const float* gains);
+    int busSetFeedGains(const float* gains, int ramp);
+    int64_t busGetFeeds(int64_t* nSrc, int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap);
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

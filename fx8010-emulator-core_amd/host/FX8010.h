@@ -259,6 +259,23 @@ public:
         if (fxb_process_block_bus_aux(h_, in, out, tapOut, auxOut, nSamples, group, flags) < 0)
             throw std::runtime_error(std::string("FX8010Batch::processBlockBusAux: ") + fxb_last_error(h_));
     }
+    // bus feeds (include/fx8010_amd.h "Bus feeds"): per-instance input by source list, CSR by instance - instance n hears
+    // sources[offsets[n] .. offsets[n+1]), columns of a source block [nSamples][channels][nSrc], in any order, repeats allowed;
+    // gains is [channels][E] or empty for unweighted (one entry then moves its word as a bit pattern); nSrc == 0 turns feeds off.
+    // setFeedGains replaces the weights, with ramp over the next feed block; an empty vector returns to unweighted.
+    // processBlockBusFeed is processBlockBusAux (tapOut / auxOut may be nullptr) with src in the place of `in`; src may also be
+    // device memory of the handle's device - the aux rows of another handle - and is then gathered where it lies.
+    void setFeeds(int64_t nSrc, const std::vector<int64_t>& offsets, const std::vector<int64_t>& sources, const std::vector<float>& gains = {}) {
+        if (fxb_bus_set_feeds(h_, nSrc, offsets.empty() ? nullptr : offsets.data(), sources.empty() ? nullptr : sources.data(), gains.empty() ? nullptr : gains.data()) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::setFeeds: ") + fxb_last_error(h_));
+    }
+    void setFeedGains(const std::vector<float>& gains, bool ramp = false) {
+        if (fxb_bus_set_feed_gains(h_, gains.empty() ? nullptr : gains.data(), ramp ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::setFeedGains: ") + fxb_last_error(h_));
+    }
+    void processBlockBusFeed(const float* src, float* out, float* tapOut, float* auxOut, int nSamples, int64_t group = 1, bool mixOut = false) {
+        if (fxb_process_block_bus_feed(h_, src, out, tapOut, auxOut, nSamples, group, mixOut ? FXB_BUS_MIX_OUT : 0u) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::processBlockBusFeed: ") + fxb_last_error(h_));
+    }
     // per-instance gains of the mixed output (include/fx8010_amd.h "Bus gains"): gains is [channels][instances], every value finite,
     // or nullptr for gains off (the unweighted sum); with ramp the next mixing block moves every weight linearly from the gains in
     // force to these and ends exactly on them.  A gain of zero mutes: that instance adds +0.0f whatever it holds.  busGetGains

@@ -26,6 +26,7 @@ INFO = {
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
+    "bus_feed_blocks": 44,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -41,6 +42,7 @@ SYMBOLS = [
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_bus_set_taps", "fxb_bus_get_taps", "fxb_process_block_bus_tap", "fxb_process_block_bus_tap_dev",
     "fxb_bus_set_sends", "fxb_bus_set_send_gains", "fxb_bus_get_sends", "fxb_process_block_bus_aux", "fxb_process_block_bus_aux_dev",
+    "fxb_bus_set_feeds", "fxb_bus_set_feed_gains", "fxb_bus_get_feeds", "fxb_process_block_bus_feed", "fxb_process_block_bus_feed_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
@@ -102,6 +104,8 @@ def load():
     sig("fxb_process_block_bus_tap", i32, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_tap_dev", i32, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_bus_set_sends", i32, vp, i64, vp, vp, vp); sig("fxb_bus_set_send_gains", i32, vp, vp, i32); sig("fxb_bus_get_sends", i64, vp, vp, vp, i64, vp, vp, i64)
     sig("fxb_process_block_bus_aux", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_aux_dev", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
+    sig("fxb_bus_set_feeds", i32, vp, i64, vp, vp, vp); sig("fxb_bus_set_feed_gains", i32, vp, vp, i32); sig("fxb_bus_get_feeds", i64, vp, vp, vp, i64, vp, vp, i64)
+    sig("fxb_process_block_bus_feed", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_feed_dev", i32, vp, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
@@ -645,6 +649,79 @@ class Batch(_Reports):
         if A.value:
             self._check(int(self._lib.fxb_bus_get_sends(self._h, None, C.c_void_p(off.ctypes.data), off.size, C.c_void_p(mem.ctypes.data), C.c_void_p(g.ctypes.data), E)), "bus_get_sends")
         return off, mem, g
+
+    def bus_set_feeds(self, n_src, offsets, sources, gains=None):
+        """The lists the next feed blocks build every instance's input from (include/fx8010_amd.h "Bus feeds"): CSR by instance -
+        instance n owns sources[offsets[n]:offsets[n+1]], columns of a source block [S, channels, n_src], in any order, repeats
+        allowed, none allowed; gains float32 [channels, E] (mono: [E]), None for unweighted.  n_src 0 turns feeds off."""
+        n_src = int(n_src)
+        if n_src == 0:
+            return self._check(self._lib.fxb_bus_set_feeds(self._h, 0, None, None, None), "bus_set_feeds")
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        src = np.ascontiguousarray([] if sources is None else sources, dtype=np.int64).reshape(-1)
+        assert off.size == self.n + 1 and src.size >= int(off[-1]), "offsets must hold N + 1 values, sources offsets[-1] entries"
+        g = None
+        if gains is not None:
+            g = np.ascontiguousarray(gains, dtype=np.float32)
+            assert g.size == self.channels * int(off[-1]), "gains must be [channels, E]"
+        return self._check(self._lib.fxb_bus_set_feeds(self._h, n_src, C.c_void_p(off.ctypes.data), C.c_void_p(src.ctypes.data) if src.size else None,
+                                                       C.c_void_p(g.ctypes.data) if g is not None and g.size else None), "bus_set_feeds")
+
+    def bus_set_feed_gains(self, gains, ramp=False):
+        """New weights [channels, E] for the feeds in force, or None: back to unweighted.  With ramp the next feed block moves every
+        weight linearly from the ones in force to these and ends exactly on them (the state machine of bus_set_gains)."""
+        if gains is None:
+            return self._check(self._lib.fxb_bus_set_feed_gains(self._h, None, 0), "bus_set_feed_gains")
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        E = self._check(int(self._lib.fxb_bus_get_feeds(self._h, None, None, 0, None, None, 0)), "bus_get_feeds")
+        assert g.size == self.channels * E, "gains must be [channels, E]"
+        return self._check(self._lib.fxb_bus_set_feed_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_feed_gains")
+
+    def bus_get_feeds(self):
+        """(n_src, offsets int64 [N + 1], sources int64 [E], gains float32 [channels, E]) of the feeds in force - the gains are a,
+        1.0 everywhere while the feeds are unweighted - or (0, array([0]), empty, empty) while feeds are off"""
+        M = C.c_int64(0)
+        E = self._check(int(self._lib.fxb_bus_get_feeds(self._h, C.byref(M), None, 0, None, None, 0)), "bus_get_feeds")
+        if M.value == 0:
+            return 0, np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros((self.channels, 0), dtype=np.float32)
+        off, src, g = np.zeros(self.n + 1, dtype=np.int64), np.zeros(E, dtype=np.int64), np.zeros((self.channels, E), dtype=np.float32)
+        self._check(int(self._lib.fxb_bus_get_feeds(self._h, None, C.c_void_p(off.ctypes.data), off.size, C.c_void_p(src.ctypes.data), C.c_void_p(g.ctypes.data), E)), "bus_get_feeds")
+        return M.value, off, src, g
+
+    def process_block_bus_feed(self, src, group=1, mix_out=False, out=None, tap_out=None, taps=False, aux=False, aux_out=None):
+        """A bus block whose per-instance input is built on the device from the feeds in force (bus_set_feeds).  src: float32
+        [S, channels, M] (mono: [S, M]), pinned, pageable or - through process_block_bus_feed_dev - device memory.  Everything else
+        as process_block_bus without shared_in: returns out, or (out, taps), (out, aux), (out, taps, aux)."""
+        M = C.c_int64(0)
+        self._check(int(self._lib.fxb_bus_get_feeds(self._h, C.byref(M), None, 0, None, None, 0)), "bus_get_feeds")
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        S = src.shape[0]
+        assert M.value == 0 or src.size == S * self.channels * M.value, "src must be [S, channels, M]"
+        lead = (S,) if src.ndim == 2 else (S, self.channels)
+        shape = lead + ((self.bus_groups(group) if mix_out else self.n),)
+        if out is None:
+            out = np.empty(shape, dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size == int(np.prod(shape))
+        if tap_out is None and taps:
+            tap_out = np.empty(lead + (int(self._lib.fxb_bus_get_taps(self._h, None, 0)),), dtype=np.float32)
+        if aux_out is None and aux:
+            A = C.c_int64(0)
+            self._check(int(self._lib.fxb_bus_get_sends(self._h, C.byref(A), None, 0, None, None, 0)), "bus_get_sends")
+            aux_out = np.empty(lead + (A.value,), dtype=np.float32)
+        for side in (tap_out, aux_out):
+            assert side is None or (side.dtype == np.float32 and side.flags["C_CONTIGUOUS"] and side.flags["WRITEABLE"])
+        self._check(self._lib.fxb_process_block_bus_feed(self._h, C.c_void_p(src.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(tap_out.ctypes.data) if tap_out is not None else None,
+                                                         C.c_void_p(aux_out.ctypes.data) if aux_out is not None else None, S, int(group), BUS_MIX_OUT if mix_out else 0), "process_block_bus_feed")
+        res = (out,) + ((tap_out,) if tap_out is not None else ()) + ((aux_out,) if aux_out is not None else ())
+        return res[0] if len(res) == 1 else res
+
+    def process_block_bus_feed_dev(self, d_src, d_out, n_samples, group=1, mix_out=False, stream=None, d_tap_out=None, d_aux_out=None):
+        """The same with pointers the device can address (ints or contiguous float32 torch tensors); single-shard handles;
+        asynchronous on `stream`.  A d_src in device memory is gathered in place, anything else is copied to the device first."""
+        def ptr(t):
+            return None if t is None else C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+        return self._check(self._lib.fxb_process_block_bus_feed_dev(self._h, ptr(d_src), ptr(d_out), ptr(d_tap_out), ptr(d_aux_out), int(n_samples), int(group),
+                                                                     BUS_MIX_OUT if mix_out else 0, C.c_void_p(stream or 0)), "process_block_bus_feed_dev")
 
     def _stream_stride(self, shape, strides):
         """the instance stride (in floats) when an [N, S, channels] array is N interleaved [S][channels] runs at one stride, else None"""

@@ -429,6 +429,74 @@ int64_t fxb_bus_get_sends(fxb_handle* h, int64_t* n_aux, int64_t* offsets, int64
 int     fxb_process_block_bus_aux(fxb_handle* h, const float* in, float* out, float* tap_out, float* aux_out, int n_samples, int64_t group, unsigned flags);
 int     fxb_process_block_bus_aux_dev(fxb_handle* h, const float* d_in, float* d_out, float* d_tap_out, float* d_aux_out, int n_samples, int64_t group, unsigned flags,
                                       void* stream);
+/* Bus feeds: per-instance input by source list, summed on the device - the sends mirrored on the input side.  Every instance owns
+ * a list of columns of a narrow source block [n_samples][num_channels][M], each with a weight per channel; a kernel builds the
+ * per-instance [..][N] block from the lists where FXB_BUS_SHARED_IN builds it from n / group.  With them the aux rows of one
+ * handle feed the effect instances of a second one without leaving the device, a sweep may have members that are not `group`
+ * neighbours, a voice may hear a mix of two sources (a side-chain, a mix-minus), and an input fades in over one block.  Feeds
+ * are a mode of the handle like the meters, the gains, the taps and the sends, off by default: no flag bit is taken and no
+ * existing signature or result changes.
+ *
+ * The structure.  There are M = n_src source columns.  Instance n (a global instance number) owns the entries e = offsets[n] ..
+ * offsets[n+1] - 1 of `sources` (CSR by instance: offsets has N + 1 values, offsets[0] = 0, non-decreasing, E = offsets[N] <=
+ * 16 777 216); sources[e] is a column in 0..M-1.  Any order and repeats are allowed, within a list and across lists; an instance
+ * may have no entry.  gains is [num_channels][E], one weight per channel and entry; NULL means UNWEIGHTED, which is not the same
+ * as 1.0f everywhere (below).
+ *
+ * fxb_bus_set_feeds: n_src == 0 turns feeds off and frees their memory.  FX_E_ARG with nothing changed: M < 0,
+ *   num_channels * M * 4 >= 2^32, E > 16 777 216, a null array that is needed, offsets not as above, a source outside 0..M-1, a
+ *   non-finite gain.  The arrays are copied before the call returns.  All allocation happens here, on every shard before any
+ *   shard changes: FX_E_MEMORY leaves the old feeds in force everywhere.  The call waits for the queued blocks as fxb_bus_set_taps
+ *   does.  It sets a = b = gains and cancels a pending ramp.  Works before a program is loaded; the feeds survive program loads;
+ *   they are not part of the state image or of instance records, and fxb_copy_instances / fxb_reset_instances do not touch them.
+ * fxb_bus_set_feed_gains: replaces the weights of the structure in force ([num_channels][E], finite, else FX_E_ARG; FX_E_ARG
+ *   while feeds are off) by the current / target state machine of fxb_bus_set_gains: ramp = 0: a = b = gains; ramp = 1: b = gains
+ *   and a ramp is pending (a is the old b, or stays where a ramp was pending already; out of unweighted, a is 1.0f everywhere).
+ *   NULL returns to unweighted and drops a pending ramp.  The next FEED block consumes a pending ramp; other blocks leave it
+ *   pending.  Queued blocks keep the weights they were queued with (the call waits for them).
+ * fxb_bus_get_feeds: returns E (0 while feeds are off), stores M to *n_src, and copies what fits: offsets[0 .. min(N + 1,
+ *   off_cap) - 1], and the entries below cap of sources and of every channel row of gains (row pitch E).  gains is a, as
+ *   fxb_bus_get_gains returns; 1.0f everywhere while the feeds are unweighted.  Any pointer may be NULL.
+ *
+ * The block.  src is [n_samples][num_channels][M] with a row pitch of exactly M; it replaces `in`.  flags may carry
+ * FXB_BUS_MIX_OUT only.  group, out, tap_out and aux_out mean what they mean to fxb_process_block_bus_aux[_dev], and so do its
+ * refusals, routes, pieces and event ordering.  n_samples == 0 lowers the program and returns 0.
+ *
+ * The definition.  Everything is fp32, round to nearest, never fused, denormals kept.  For instance n, channel c and sample s of
+ * a call of S samples, the entries are k = 0..F-1 (e = offsets[n] + k) and x_k is the word src[(s*C + c)*M + sources[e]].
+ *   F = 0            the input word is +0.0f.
+ *   unweighted       term_k = x_k.  With F = 1 the word is MOVED AS A 32-BIT PATTERN: a NaN keeps its payload, -0 stays -0.
+ *   weighted         term_k = (w == 0.0f) ? +0.0f : w * x_k, where w comes from that entry's a / b and the ramp exactly as the
+ *                    "Bus gains" comment defines it (t = (float)(s+1) * r, r = 1.0f / (float)S with S the caller's block, never
+ *                    a piece; exactly b on the last sample).
+ *   the word         term_0 for F = 1, else ((term_0 + term_1) + term_2) + ... in entry order: it starts from term_0, not from
+ *                    zero.
+ * NaN payloads are not promised once an addition or a multiplication has happened.  As numpy, over float32 arrays:
+ *   word = zeros(N); for k in range(max F): has = k < F; e = offsets[:-1] + k
+ *       term = x[sources[e]] if unweighted else where(w[e] == 0, +0.0, w[e] * x[sources[e]])
+ *       word = where(has, term if k == 0 else word + term, word)
+ * The instances' state, `out`, meters, taps, sends, bus gains and armed control tracks afterwards are exactly what
+ * fxb_process_block_bus_aux leaves on the [S][C][N] input this defines.
+ * A consequence: unweighted feeds with M = G, one entry per instance and sources[n] = n / K reproduce FXB_BUS_SHARED_IN with
+ * group K, word for word.  A zero gain keeps a NaN source column out of an instance.
+ *
+ * FX_E_ARG (nothing launched, nothing changed), beyond every refusal of fxb_process_block_bus_aux*: feeds off; FXB_BUS_SHARED_IN
+ * in flags; src null with n_samples > 0; src sharing a byte with `out`, tap_out or aux_out (there is no in-place form: the
+ * layouts differ); the device entry on a handle of several shards or with a d_src the device cannot address.
+ * Gathers hit device memory only: every word of src is read many times, so the runtime copies the caller's src rows, pinned or
+ * pageable, into a device block [rows][M] that grows on demand in front of the block's first launch (FX_E_MEMORY: nothing
+ * launched); only a src that the pointer attributes show to be device memory of the handle's device is gathered in place -
+ * through either entry.  out / tap_out / aux_out keep their own in-place / staged decisions.
+ * Sharded handles: each shard gets the lists of its own instances, reads the caller's full-width src and stages the rows on its
+ * own device.  The input side has no sum across shards: no structure is refused for straddling, and shards need not begin at a
+ * multiple of anything for the feed side; FXB_BUS_MIX_OUT keeps its own rule.
+ * FXB_INFO_BUS_FEED_BLOCKS counts the feed blocks: once per block and shard. */
+int     fxb_bus_set_feeds(fxb_handle* h, int64_t n_src, const int64_t* offsets, const int64_t* sources, const float* gains);
+int     fxb_bus_set_feed_gains(fxb_handle* h, const float* gains, int ramp);
+int64_t fxb_bus_get_feeds(fxb_handle* h, int64_t* n_src, int64_t* offsets, int64_t off_cap, int64_t* sources, float* gains, int64_t cap); /* returns E */
+int     fxb_process_block_bus_feed(fxb_handle* h, const float* src, float* out, float* tap_out, float* aux_out, int n_samples, int64_t group, unsigned flags);
+int     fxb_process_block_bus_feed_dev(fxb_handle* h, const float* d_src, float* d_out, float* d_tap_out, float* d_aux_out, int n_samples, int64_t group, unsigned flags,
+                                       void* stream);
 /* Instance-major blocks: one interleaved stream per instance, transposed on the device.  Instance n's input is the
  * n_samples * num_channels floats at in + n * in_stride, ordered [sample][channel] - what n_samples calls of the reference's
  * process() consume and what a WAV file holds - and its output goes to out + n * out_stride the same way.
@@ -582,7 +650,8 @@ enum {
     FXB_INFO_INSTANCE_SCATTERS = 40,   /* launches of the kernel fx_inst_scatter - by copy, reset and load - since creation (summed over shards) */
     FXB_INFO_BUS_GAIN_BLOCKS = 41,     /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
     FXB_INFO_BUS_TAP_BLOCKS = 42,      /* bus blocks that delivered taps (fxb_process_block_bus_tap* with a tap_out) since creation (summed over shards) */
-    FXB_INFO_BUS_SEND_BLOCKS = 43      /* bus blocks that delivered sends (fxb_process_block_bus_aux* with an aux_out) since creation (summed over shards) */
+    FXB_INFO_BUS_SEND_BLOCKS = 43,     /* bus blocks that delivered sends (fxb_process_block_bus_aux* with an aux_out) since creation (summed over shards) */
+    FXB_INFO_BUS_FEED_BLOCKS = 44      /* bus blocks filled by feeds (fxb_process_block_bus_feed*) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -46,6 +46,12 @@ Every path slides the control `decay` like the reference's harness does (realtim
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
     python tools/bus_capacity.py [--blocks 4000] [--json profiles/bus_realtime.json] [--kernel-stats bus_kernel_stats.csv]
+8. `--feeds F`: what bus feeds (fxb_bus_set_feeds, fxb_process_block_bus_feed) cost against the shared input they generalise.
+   F = 1 is the map n / group, unweighted - the words of FXB_BUS_SHARED_IN, checked before anything is timed -, F >= 2 a CSR
+   structure of F weighted entries per instance.  At each of --feed-instances a handle with the shared input and one with feeds
+   take turns in stretches in ONE process; median and p99.9 of both are reported (`--feeds-out FILE.txt` keeps the lines).  With
+   `--trace-run --feeds F` the traced stretch is 200 blocks of each handle: fx_bus_expand, which writes the same bytes, is the
+   yardstick of fx_bus_feed in the same trace.
 """
 import argparse
 import csv
@@ -104,7 +110,7 @@ def send_all_model(y, w):
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0, sends=0):
+    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0, sends=0, feeds=0):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -145,6 +151,19 @@ class Path:
             self.b.bus_set_sends(np.arange(sends + 1, dtype=np.int64) * n, np.tile(np.arange(n, dtype=np.int64), sends), self.send_gains.reshape(1, -1))
             self.aux_out = A.HostBuffer((BLOCK, 1, sends))
             self.ap = C.c_void_p(self.aux_out.array.ctypes.data)
+        # feeds: the input block [BLOCK][G] is the source block.  1: the map n / GROUP, unweighted - the words of the shared input;
+        # F >= 2: CSR, every instance hears F columns (its own group's first) with weights of its own
+        self.feeds = feeds
+        if feeds:
+            G = self.width
+            own = np.arange(n, dtype=np.int64) // GROUP
+            if feeds == 1:
+                self.b.bus_set_feeds(G, np.arange(n + 1, dtype=np.int64), own)
+            else:
+                src = np.ascontiguousarray(np.stack([(own + 7 * k) % G for k in range(feeds)], axis=1).reshape(-1))
+                w = (0.25 + 0.75 * (progs.stimulus(n * feeds, 1, seed=55)[0] * np.float32(0.5) + np.float32(0.5))).astype(np.float32) / np.float32(feeds)
+                self.feed_sources, self.feed_gains = src, np.ascontiguousarray(w.reshape(1, -1))
+                self.b.bus_set_feeds(G, np.arange(n + 1, dtype=np.int64) * feeds, src, self.feed_gains)
         self.b.prepare(BLOCK, True)
         self.k = 0
         self.times = []
@@ -155,7 +174,9 @@ class Path:
             assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
         if self.gains == "ramp" and self.lib.fxb_bus_set_gains(h, self.lp[(k + 1) % 2], 1) != 0:
             raise RuntimeError("set_gains in front of block %d failed: %s" % (k, self.b.last_error()))
-        if self.sends:
+        if self.feeds:
+            rc = self.lib.fxb_process_block_bus_feed(h, self.xp[k % RING], self.yp, None, None, BLOCK, GROUP, 2)
+        elif self.sends:
             rc = self.lib.fxb_process_block_bus_aux(h, self.xp[k % RING], self.yp, self.tp, self.ap, BLOCK, GROUP, 3)
         elif self.taps:
             rc = self.lib.fxb_process_block_bus_tap(h, self.xp[k % RING], self.yp, self.tp, BLOCK, GROUP, 3)
@@ -442,6 +463,53 @@ def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lam
     return out
 
 
+def feeds_side_by_side(A, progs, n, feeds, blocks, warm, stretch, log, clock=lambda: None):
+    """bus blocks with FXB_BUS_SHARED_IN and with feeds (1: the map n / GROUP, unweighted; F >= 2: CSR, F weighted entries per
+    instance) by turns, in stretches, in one process"""
+    import numpy as np
+    shared, fed = Path(A, progs, n, True), Path(A, progs, n, True, feeds=feeds)
+    for _ in range(2):
+        shared.block()
+        fed.block()
+        # the map is the shared input, word for word
+        if feeds == 1 and not np.array_equal(fed.out.array.view(np.uint32), shared.out.array.view(np.uint32)):
+            raise RuntimeError("the mix of the handle with the map n / %d differs from the shared input's at %d instances" % (GROUP, n))
+    paths = [("shared in", shared), ("feeds F=%d" % feeds, fed)]
+    clocks = {name: [] for name, _ in paths}
+    for _, p in paths:
+        p.stretch(warm, timed=False)
+        p.b.prepare(BLOCK, True)
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for name, p in paths:
+                p.stretch(stretch)
+                clocks[name].append(clock())
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "group": GROUP, "feeds": feeds, "stretch_blocks": stretch}
+    for name, p in paths:
+        r = rt.percentiles(p.times)
+        r.update({"blocks": len(p.times), "bus_feed_blocks": p.b.info("bus_feed_blocks")})
+        mhz = [c for c in clocks[name] if c]
+        r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
+        out[name] = r
+        log("%-10s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d feed blocks  shader clock %s MHz" % (
+            name, n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["p999_us"] <= BUDGET_US else "over budget",
+            r["bus_feed_blocks"], r["shader_clock_mhz_behind_a_stretch"]))
+    same = feeds != 1 or (shared.k == fed.k and np.array_equal(shared.out.array.view(np.uint32), fed.out.array.view(np.uint32)))
+    out["outputs_equal"] = bool(same)
+    out["median_difference_us"] = round(out["feeds F=%d" % feeds]["median_us"] - out["shared in"]["median_us"], 1)
+    log("           N=%7d  mixes of the two %s; median with feeds - median with the shared input: %+.1f us" % (
+        n, ("equal" if same else "DIFFER") if feeds == 1 else "not compared (another input)", out["median_difference_us"]))
+    shared.close()
+    fed.close()
+    return out
+
+
 def bus_row(A, progs, n, blocks, warm, log):
     """one count of the sweep.  parity_ok is a comparison: after the timed region a plain handle at the same count replays every
     block of the run (same PCM, same slider schedule, untimed), and the bus path's LAST block must be, word for word, the
@@ -528,12 +596,40 @@ def main():
                     "(with --trace-run --gains: one handle with static bus gains and the sends)")
     ap.add_argument("--send-instances", default="131072,458752")
     ap.add_argument("--sends-out", default="", help="keep the lines of --sends in this text file")
+    ap.add_argument("--feeds", type=int, default=0, help="bus blocks with the shared input and with feeds by turns: 1 = the map n / group, unweighted; F >= 2 = CSR with F "
+                    "weighted entries per instance (with --trace-run: 200 blocks of a handle with the shared input, 200 of one with the map and, for F >= 2, 200 of the CSR one)")
+    ap.add_argument("--feed-instances", default="131072,458752")
+    ap.add_argument("--feeds-out", default="", help="keep the lines of --feeds in this text file")
     args = ap.parse_args()
     import torch  # first: its HIP runtime is the one the library binds to
 
     import fx8010_amd as A
     import fx8010_programs as progs
     log = lambda s: print(s, flush=True)
+    if args.trace_run and args.feeds:
+        # fx_bus_expand of the first handle is the yardstick of fx_bus_feed (map) of the second in the same trace
+        for feeds in (0, 1) + ((args.feeds,) if args.feeds >= 2 else ()):
+            p = Path(A, progs, args.trace_instances, True, feeds=feeds)
+            p.stretch(200, timed=False)
+            p.close()
+        return 0
+    if args.feeds:
+        lines = []
+
+        def keep(s):
+            lines.append(s)
+            log(s)
+        keep("32-sample bus blocks of config5 (mixed output per %d instances, pinned host buffers) against %.3f us, with the shared input (FXB_BUS_SHARED_IN) and with "
+             "feeds (fxb_process_block_bus_feed, F = %d) by turns in stretches of %d blocks in one process, %d blocks per point after %d warm-up blocks; %s" % (
+                 GROUP, BUDGET_US, args.feeds, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+        rows = [feeds_side_by_side(A, progs, int(v), args.feeds, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.feed_instances.split(",") if v]
+        if args.feeds_out:
+            with open(args.feeds_out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump({"feed_rows": rows}, fh, indent=1)
+        return 0 if all(r["outputs_equal"] for r in rows) else 1
     if args.trace_run and args.sends:
         p = Path(A, progs, args.trace_instances, True, gains="static" if args.gains else None, sends=args.sends)
         p.stretch(200, timed=False)
