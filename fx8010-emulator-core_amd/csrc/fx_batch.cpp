@@ -275,6 +275,14 @@ int Batch::ensureTram(const Lowered& low) {
     };
     int rc = grow(dITram_, iSlotsAlloc_, low.iSlots);
     if (rc == 0) rc = grow(dXTram_, xSlotsAlloc_, low.xSlots);
+    // which position kinds the program has an instruction of, per line (ringLine: the rule of fxb_load_instances_rotated)
+    for (int which = 0; which < 2; ++which) tramWrites_[which] = tramReads_[which] = false;
+    for (const Instr& I : prog_.instrs) {
+        if (I.op != IDELAY && I.op != XDELAY) continue;
+        const int which = I.op == XDELAY ? 1 : 0;
+        if (prog_.regs[(size_t)I.r].type == R_WRITE) tramWrites_[which] = true;
+        if (prog_.regs[(size_t)I.r].type == R_READ) tramReads_[which] = true;
+    }
     return rc;
 }
 
@@ -858,11 +866,13 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_IMAJOR_BLOCKS) return imajorBlocks_;
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;
+    if (what == FXB_INFO_INSTANCE_ROTATIONS) return instRotations_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {
         case FXB_INFO_INST_PER_LANE: return instPerLane_;
         case FXB_INFO_INSTANCE_WORDS: return (int64_t)stateRows_ + iSlotsAlloc_ + xSlotsAlloc_;
+        case FXB_INFO_INSTANCE_RINGS: return (ringLine(0).ring() ? 1 : 0) | (ringLine(1).ring() ? 2 : 0);
         case FXB_INFO_KERNEL: return c_.useAsm ? (c_.useXlate ? 8 + (int)c_.variant : 1 + (int)c_.variant) : 0;
         case FXB_INFO_XLATE_CODE_BYTES: return c_.useXlate ? (int64_t)c_.codeBytes : 0;
         case FXB_INFO_XLATE_INLINED: return c_.useXlate ? c_.inlined : 0;

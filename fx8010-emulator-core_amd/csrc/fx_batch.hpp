@@ -235,6 +235,14 @@ public:
     // the delay-line rule of a load: FX_E_ARG unless the program executes no delay-line instruction or the four position words of
     // every record equal those the destination instance holds now.  Changes nothing.
     int checkRecordCursors(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf);
+    // fxb_load_instances_rotated (include/fx8010_amd.h has the definition).  rotationApplies: the program has delay memory and
+    // executes delay-line instructions - otherwise such a load goes the way of the plain one.  recordRotations: the rule of that
+    // call - FX_E_ARG naming the line and the list entry, or rot = [count][2], the rotation of every record on iTRAM and xTRAM
+    // from its position words and those its destination holds now.  Changes nothing.  scatterRecordsRotated: scatterRecords
+    // through fx_inst_scatter_rot; the four position rows keep what they hold.
+    int rotationApplies(bool* applies);
+    int recordRotations(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf, std::vector<int32_t>* rot);
+    int scatterRecordsRotated(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf, const int32_t* rot);
     // what the host knows about the registers follows a load of these `total` records (of all shards: every shard ends up with
     // the same rows): a register with a value other than hostValue_ in any record becomes per-instance, as after setRegisterAt
     void promoteLoaded(const uint32_t* buf, int64_t total);
@@ -629,7 +637,8 @@ private:
     // it runs in pieces.  The lists go through pinned memory of the library, so the caller's arrays are free on return.
     static constexpr size_t kInstScratchBytes = (size_t)64 << 20;
     InstArgs instArgs() const;
-    int beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords);   // lower, range check, lists -> device, order behind the blocks
+    // lower, range check, lists -> device, order behind the blocks; `pairs` (without a list b): [count][2] words that travel in b's place
+    int beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords, const int32_t* pairs = nullptr);
     int endInstanceCall(bool wait);                           // evInst_ behind what was queued
     int64_t recordsPerPiece() const;
     Block<long long> instList_;          // [2][cap]: cap counts list entries
@@ -639,6 +648,13 @@ private:
     hipEvent_t evInst_ = nullptr;        // behind the last kernel or copy of the most recent instance call
     bool instLaunched_ = false;          // ... which may still be running
     int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS
+    int64_t instRotations_ = 0;                    // FXB_INFO_INSTANCE_ROTATIONS
+    // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
+    // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
+    // counts, so such a record is compared - and may be refused - rather than loaded unseen)
+    bool tramWrites_[2] = {false, false}, tramReads_[2] = {false, false};   // set by ensureTram
+    struct RingLine { int size = 0, slots = 0; bool writes = false, reads = false; bool ring() const { return slots > 0 && slots == size; } };
+    RingLine ringLine(int which) const;
 #ifdef FX_DIAGNOSTICS
     int ensureEndStamps();   // the end stamps' buffer (dStamps_), one word per wavefront
 #endif

@@ -8,7 +8,8 @@
 // whatever stream (ev1_, evBus_).  The kernels then run on the handle's stream, in pieces of at most recordsPerPiece() records on
 // the one record scratch - stream order alone keeps a piece's scatter in front of the next piece's gather.  endInstanceCall
 // records evInst_ behind the last of them: a block on another stream waits for it (launchBlock), the host does in waitLastLaunch
-// and sync.
+// and sync.  The rotated load (recordRotations, scatterRecordsRotated) has the frame of the load; its rotation pairs travel with
+// the list, in the place of the second one.
 #include "fx_batch.hpp"
 
 #include <algorithm>
@@ -87,7 +88,7 @@ int64_t Batch::recordsPerPiece() const {
     return (int64_t)std::max<size_t>(kInstScratchBytes / (w * 4), 1);
 }
 
-int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords) {
+int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, size_t recordWords, const int32_t* pairs) {
     (void)hipSetDevice(device_);
     int rc = ensureLowered();
     if (rc != 0) return rc;
@@ -107,9 +108,11 @@ int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, 
     if ((rc = growBlock(instRec_, recordWords, false, "hipMalloc instance records")) != 0) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t), "instance lists");
     std::memcpy(hInstList_.p, a, entries * 8);
-    if (b) std::memcpy(hInstList_.p + hInstList_.cap, b, entries * 8);
+    static_assert(2 * sizeof(int32_t) == sizeof(long long), "a pair of rotations travels in the place of a list entry");
+    const void* second = b ? static_cast<const void*>(b) : static_cast<const void*>(pairs);
+    if (second) std::memcpy(hInstList_.p + hInstList_.cap, second, entries * 8);
     e = hipMemcpyAsync(instList_.p, hInstList_.p, entries * 8, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess && b) e = hipMemcpyAsync(instList_.p + instList_.cap, hInstList_.p + hInstList_.cap, entries * 8, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && second) e = hipMemcpyAsync(instList_.p + instList_.cap, hInstList_.p + hInstList_.cap, entries * 8, hipMemcpyHostToDevice, stream_);
     // behind every block queued so far, on whichever stream it was queued
     if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
     if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
@@ -255,6 +258,99 @@ int Batch::checkRecordCursors(const int64_t* list, const int64_t* pos, int64_t c
                 return fail(FX_E_ARG, "load_instances: a record's delay-line positions differ from those of its destination (the handles have not run the same number of samples)");
     }
     return 0;
+}
+
+Batch::RingLine Batch::ringLine(int which) const {
+    RingLine l;
+    l.size = which ? std::min(prog_.xTramSize, kMaxXTram) : std::min(prog_.iTramSize, kMaxITram);
+    l.slots = which ? xSlotsAlloc_ : iSlotsAlloc_;
+    l.writes = tramWrites_[which];   // (found at the lowering, beside the slots: ensureTram)
+    l.reads = tramReads_[which];
+    return l;
+}
+
+int Batch::rotationApplies(bool* applies) {
+    const int rc = ensureLowered();
+    *applies = rc == 0 && c_.low.tramOpsPerSample > 0 && (iSlotsAlloc_ > 0 || xSlotsAlloc_ > 0);
+    return rc;
+}
+
+int Batch::recordRotations(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf, std::vector<int32_t>* rot) {
+    (void)hipSetDevice(device_);
+    rot->clear();
+    int rc = ensureLowered();
+    if (rc != 0 || count == 0) return rc;
+    const char* why = nullptr;
+    if (!list || !buf || checkInstanceLists(list, nullptr, count, n_, &why) != 0) return fail(FX_E_ARG, why ? why : "instances: a null list or buffer");
+    waitLastLaunch();
+    std::vector<uint32_t> cur((size_t)4 * (size_t)n_);
+    const hipError_t e = hipMemcpy2D(cur.data(), (size_t)n_ * 4, dState_ + (size_t)stateLayout_.cursorBase * nPad_, (size_t)nPad_ * 4, (size_t)n_ * 4, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hipFail(e, "instances: reading the delay-line positions");
+    const size_t W = (size_t)stateRows_ + (size_t)iSlotsAlloc_ + (size_t)xSlotsAlloc_;
+    const bool dane = c_.low.tramDane;
+    rot->assign((size_t)count * 2, 0);
+    for (int which = 0; which < 2; ++which) {
+        const RingLine l = ringLine(which);
+        if (l.slots == 0 || l.size < 1) continue;   // (the program has no memory on this line: nothing to rotate, nothing reads the positions)
+        const char* name = which ? "xTRAM" : "iTRAM";
+        const int64_t Z = l.size;
+        auto refuse = [&](int64_t k, const char* what) {
+            rot->clear();
+            return fail(FX_E_ARG, std::string("load_instances_rotated: ") + name + ", list entry " + std::to_string(pos ? pos[k] : k) + ": " + what);   // (the caller's entry: a shard's pos[k])
+        };
+        for (int64_t k = 0; k < count; ++k) {
+            const uint32_t* rec = buf + (size_t)(pos ? pos[k] : k) * W + (size_t)stateLayout_.cursorBase + (size_t)which * 2;
+            const uint32_t* dst = cur.data() + (size_t)which * 2 * (size_t)n_ + (size_t)list[k];
+            // kind 0: the write position, kind 1: the read position (the DANE model has one counter, in the write word)
+            int64_t d = -1;
+            for (int kind = 0; kind < (dane ? 1 : 2); ++kind) {
+                const int64_t s = rec[kind], t = dst[(size_t)kind * (size_t)n_];
+                if (s >= Z) return refuse(k, "a position word of the record lies outside the line (0 .. size - 1)");
+                if (!dane && !(kind ? l.reads : l.writes)) continue;   // (never moves: does not count)
+                const int64_t dk = (((t - s) % Z) + Z) % Z;
+                if (d >= 0 && dk != d)
+                    return refuse(k, "the record's write and read positions are not at one distance from the destination's (another phase of a program whose reads and writes drift apart, or of a delay instruction in a SKIP shadow)");
+                d = dk;
+            }
+            if (d < 0) d = 0;
+            if (d != 0 && !l.ring())
+                return refuse(k, "the record's delay-line positions differ from the destination's and the line is no ring (a delay write at an offset above 0): it cannot be rotated");
+            (*rot)[(size_t)k * 2 + (size_t)which] = (int32_t)d;
+        }
+    }
+    return 0;
+}
+
+int Batch::scatterRecordsRotated(const int64_t* list, const int64_t* pos, int64_t count, const uint32_t* buf, const int32_t* rot) {
+    if (count == 0) return ensureLowered();
+    if (!buf || !rot) return fail(FX_E_ARG, "instances: a null buffer");
+    int rc = ensureLowered();
+    if (rc != 0) return rc;
+    const int64_t per = recordsPerPiece();
+    InstRotArgs r{};
+    InstArgs& a = r.base;
+    a = instArgs();
+    const size_t W = (size_t)a.recStride;
+    // (lists, rotations and record scratch grow here, in front of the first launch)
+    if ((rc = beginInstanceCall(list, nullptr, count, (size_t)std::min(count, per) * W, rot)) != 0) return rc;
+    a.records = instRec_.p;
+    a.skipLo = stateLayout_.cursorBase;
+    a.skipHi = stateLayout_.cursorBase + 4;
+    r.iSize = ringLine(0).ring() ? iSlotsAlloc_ : 0;
+    r.xSize = ringLine(1).ring() ? xSlotsAlloc_ : 0;
+    hipError_t e = hipSuccess;
+    for (int64_t off = 0; off < count && e == hipSuccess; off += per) {
+        a.count = std::min(per, count - off);
+        a.list = instList_.p + off;
+        r.rot = reinterpret_cast<const int*>(instList_.p + instList_.cap + off);   // (a pair per entry, in the place of the second list)
+        for (int64_t k = 0, run = 0; k < a.count && e == hipSuccess; k += run) {
+            run = pos ? recordRun(pos + off + k, a.count - k) : a.count;
+            e = hipMemcpyAsync(instRec_.p + (size_t)k * W, buf + (size_t)(pos ? pos[off + k] : off + k) * W, (size_t)run * W * 4, hipMemcpyHostToDevice, stream_);
+        }
+        if (e == hipSuccess && (e = launchInstScatterRot(r, stream_)) == hipSuccess) ++instRotations_;
+    }
+    rc = endInstanceCall(true);
+    return e != hipSuccess ? hipFail(e, "instances: records to the device, rotated") : rc;
 }
 
 void Batch::promoteLoaded(const uint32_t* buf, int64_t total) {

@@ -295,6 +295,9 @@ int fxb_save_instances(fxb_handle* h, const int64_t* list, int64_t count, void* 
 int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.loadInstances(list, count, buf, bytes); }) : FX_E_ARG;
 }
+int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.loadInstancesRotated(list, count, buf, bytes); }) : FX_E_ARG;
+}
 int fxb_get_tram_i(fxb_handle* h, int which, int64_t inst, float* out, int n_slots) {
     return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.getTramAt(which, inst, out, n_slots); }) : FX_E_ARG;
 }

@@ -1,5 +1,5 @@
-// fx_instances.hpp — launch interface of the two kernels behind the per-instance state calls (fxb_copy_instances,
-// fxb_reset_instances, fxb_save_instances, fxb_load_instances; device code: fx_instances.hip).
+// fx_instances.hpp — launch interface of the kernels behind the per-instance state calls (fxb_copy_instances,
+// fxb_reset_instances, fxb_save_instances, fxb_load_instances, fxb_load_instances_rotated; device code: fx_instances.hip).
 //
 // The state of one instance is W = stateRows + iSlots + xSlots 32-bit words, scattered over three transposed blocks:
 //   word w < stateRows                    state[w][inst]                          (row pitch nPad)
@@ -39,5 +39,17 @@ hipError_t launchInstGather(const InstArgs& a, hipStream_t stream);
 // words of the listed instances is written: no column >= n, none of the padding up to nPad.  An instance listed twice would be
 // written twice in no defined order - the caller refuses such lists.
 hipError_t launchInstScatter(const InstArgs& a, hipStream_t stream);
+
+// The scatter of fxb_load_instances_rotated: InstArgs as they are, and a rotation per record and delay line.
+struct InstRotArgs {
+    InstArgs base;            // recStride >= W (no broadcast record); skipLo / skipHi as for the scatter
+    const int* rot;           // device memory: [count][2], the rotation of record k on iTRAM (rot[2k]) and xTRAM (rot[2k + 1])
+    int iSize, xSize;         // slots 0 .. size - 1 of a line are a ring (size <= iSlots / xSlots; 0: the line is copied as it is)
+};
+
+// As launchInstScatter, except inside the rings: slot (j + d) mod size of instance list[k] = slot j of records[k], j = 0 .. size - 1,
+// with d = that record's rotation on the line.  A rotation outside 0 .. size - 1 - the runtime computes them in that range - is
+// taken as 0.  Slots from `size` on are copied as they are.
+hipError_t launchInstScatterRot(const InstRotArgs& a, hipStream_t stream);
 
 }  // namespace fx

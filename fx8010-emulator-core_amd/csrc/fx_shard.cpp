@@ -730,7 +730,7 @@ int Sharded::saveInstances(const int64_t* list, int64_t count, void* buf, int64_
     return fan([&](int k, Batch& b) { return b.gatherRecords(parts[(size_t)k].list.data(), parts[(size_t)k].pos.data(), (int64_t)parts[(size_t)k].list.size(), records); });
 }
 
-int Sharded::loadInstances(const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
+int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated) {
     Serial serial(api_);
     lastError_.clear();
     const char* why = nullptr;
@@ -749,10 +749,18 @@ int Sharded::loadInstances(const int64_t* list, int64_t count, const void* buf, 
     auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
     auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
     // the delay-line rule on every shard before any shard changes a word
-    rc = fan([&](int k, Batch& b) { return b.checkRecordCursors(listOf(k), posOf(k), countOf(k), records); });
+    if (rotated) {
+        bool applies = false;
+        if ((rc = runOn(0, [&](Batch& b) { return b.rotationApplies(&applies); })) != 0) return rc;
+        rotated = applies;
+    }
+    std::vector<std::vector<int32_t>> rot(shards_.size());   // rotated: per shard, [its entries][2]
+    rc = fan([&](int k, Batch& b) {
+        return rotated ? b.recordRotations(listOf(k), posOf(k), countOf(k), records, &rot[(size_t)k]) : b.checkRecordCursors(listOf(k), posOf(k), countOf(k), records);
+    });
     if (rc != 0) return rc;
     return fan([&](int k, Batch& b) {
-        const int r = b.scatterRecords(listOf(k), posOf(k), countOf(k), records);
+        const int r = rotated ? b.scatterRecordsRotated(listOf(k), posOf(k), countOf(k), records, rot[(size_t)k].data()) : b.scatterRecords(listOf(k), posOf(k), countOf(k), records);
         if (r == 0) b.promoteLoaded(records, count);
         return r;
     });
@@ -788,7 +796,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS) {
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;
         return sum;

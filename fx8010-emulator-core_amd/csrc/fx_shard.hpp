@@ -122,7 +122,10 @@ public:
     int copyInstances(const int64_t* src, const int64_t* dst, int64_t count);
     int resetInstances(const int64_t* list, int64_t count);
     int saveInstances(const int64_t* list, int64_t count, void* buf, int64_t cap);
-    int loadInstances(const int64_t* list, int64_t count, const void* buf, int64_t bytes);
+    int loadInstances(const int64_t* list, int64_t count, const void* buf, int64_t bytes) { return loadRecords(list, count, buf, bytes, false); }
+    // ... with the delay memory of every record rotated to its destination's positions (Batch::recordRotations); a program that
+    // executes no delay-line instruction or has no delay memory goes the way of loadInstances
+    int loadInstancesRotated(const int64_t* list, int64_t count, const void* buf, int64_t bytes) { return loadRecords(list, count, buf, bytes, true); }
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
 
@@ -135,6 +138,7 @@ public:
     const std::string& lastError();
 
 private:
+    int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
     struct Worker {
         std::unique_ptr<Batch> batch;
         int64_t first = 0, count = 0;

@@ -332,6 +332,10 @@ public:
     void loadInstances(const std::vector<int64_t>& list, const std::vector<uint8_t>& image) {
         if (fxb_load_instances(h_, list.data(), (int64_t)list.size(), image.data(), (int64_t)image.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::loadInstances: ") + fxb_last_error(h_));
     }
+    // ... at any delay-line position: the delay memory of every record is rotated to its destination's positions (fxb_load_instances_rotated)
+    void loadInstancesRotated(const std::vector<int64_t>& list, const std::vector<uint8_t>& image) {
+        if (fxb_load_instances_rotated(h_, list.data(), (int64_t)list.size(), image.data(), (int64_t)image.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::loadInstancesRotated: ") + fxb_last_error(h_));
+    }
     // generate the code for blocks of nSamples samples now, not in the first process call (callers with a deadline per block)
     void prepare(int nSamples, bool wait = true) {
         if (fxb_prepare(h_, nSamples, wait ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::prepare: ") + fxb_last_error(h_));

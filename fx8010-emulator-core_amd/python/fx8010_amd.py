@@ -26,7 +26,7 @@ INFO = {
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
-    "bus_feed_blocks": 44,
+    "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -44,7 +44,7 @@ SYMBOLS = [
     "fxb_bus_set_sends", "fxb_bus_set_send_gains", "fxb_bus_get_sends", "fxb_process_block_bus_aux", "fxb_process_block_bus_aux_dev",
     "fxb_bus_set_feeds", "fxb_bus_set_feed_gains", "fxb_bus_get_feeds", "fxb_process_block_bus_feed", "fxb_process_block_bus_feed_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
-    "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances",
+    "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances", "fxb_load_instances_rotated",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
@@ -109,6 +109,7 @@ def load():
     sig("fxb_process_block_imajor", i32, vp, vp, vp, i32, i64, i64); sig("fxb_process_block_imajor_dev", i32, vp, vp, vp, i32, i64, i64, vp)
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
+    sig("fxb_load_instances_rotated", i32, vp, vp, i64, vp, i64)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
@@ -444,6 +445,13 @@ class Batch(_Reports):
         v = self._instance_list(instances)
         image = np.ascontiguousarray(image, dtype=np.uint8)
         return self._check(self._lib.fxb_load_instances(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(image.ctypes.data), image.size), "load_instances")
+
+    def load_instances_rotated(self, instances, image):
+        """load_instances at any delay-line position: the delay memory of every record is rotated on the GPU to the positions its
+        destination holds (fxb_load_instances_rotated; info("instance_rings") tells which lines can be rotated)"""
+        v = self._instance_list(instances)
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        return self._check(self._lib.fxb_load_instances_rotated(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(image.ctypes.data), image.size), "load_instances_rotated")
 
     def get_tram_i(self, which, inst, n_slots):
         out = np.empty(n_slots, dtype=np.float32)

@@ -217,8 +217,8 @@ int fxb_load_state(fxb_handle* h, const void* buf, int64_t bytes);
  *   partition into shards may all differ.  Delay-line rule: if the program executes delay-line instructions, the four position
  *   words of every record must equal those its destination holds now, else FX_E_ARG and nothing changes; handles that have run the
  *   same number of samples of the same program satisfy it (migration between handles or GPUs, undo before further processing).
- *   Rotating delay memory to another position is out of scope.  A register the host held as one value and that a record holds
- *   another value of becomes per-instance, as if fxb_set_register_i had written it.  Synchronous.
+ *   fxb_load_instances_rotated (below) takes records at any position.  A register the host held as one value and that a record
+ *   holds another value of becomes per-instance, as if fxb_set_register_i had written it.  Synchronous.
  * 0, FX_E_NOTREADY without a program, or FX_E_ARG with nothing launched and nothing changed: count < 0, a null list with
  * count > 0, an instance outside 0..N-1, a repeated destination, a destination among the sources, a short buffer, an image of
  * another program, kind or version.  count == 0 returns 0. */
@@ -227,6 +227,33 @@ int fxb_copy_instances(fxb_handle* h, const int64_t* src, const int64_t* dst, in
 int fxb_reset_instances(fxb_handle* h, const int64_t* list, int64_t count);
 int fxb_save_instances(fxb_handle* h, const int64_t* list, int64_t count, void* buf, int64_t cap);
 int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes);
+/* fxb_load_instances with another delay-line rule: a record loads at ANY position of its destination, its delay memory rotated on
+ * the GPU by the difference of the positions (kernel fx_inst_scatter_rot) - undo after further processing, recall of a sounding
+ * voice, migration between handles of different age.  Images, lists, image checks, the promotion of registers, ordering (behind
+ * every queued block, synchronous) and what is left alone are those of fxb_load_instances.
+ *   For each delay line L (iTRAM, xTRAM) the program uses: Z = its size, A = its allocated slots (FXB_INFO_ITRAM_SLOTS /
+ *   _XTRAM_SLOTS), (w_s, r_s) the record's write and read position words, (w_d, r_d) those the destination holds now.  L is a RING
+ *   when A == Z: in the reference model when every delay write on L has a uniform offset of 0 (every program under programs/), in
+ *   the FX_OPT_TRAM_DANE model always.  FXB_INFO_INSTANCE_RINGS tells.
+ *   The rotation d of a record on L, in 0..Z-1.  Reference model: d_w = (w_d - w_s) mod Z, d_r = (r_d - r_s) mod Z; a position
+ *   kind the program has no instruction of on L (no write, or no read) never moves and does not count (an instruction that is
+ *   there counts even if no instance ever executes it: the conservative side, such records are compared rather than trusted); if both count they must
+ *   agree and d is that value, if one counts d is its value.  DANE model: d = (w_d - w_s) mod Z (the r words are unused there).
+ *   FX_E_ARG, nothing launched, nothing changed, fxb_last_error naming the line and the list entry: a record position word outside
+ *   0..Z-1; d_w != d_r (record and destination are in different phases of a program whose reads and writes drift apart, or of a
+ *   delay instruction in a SKIP shadow); d != 0 on a line that is not a ring (such a line loads with d = 0, as in fxb_load_instances).
+ *   Effect: every state row of the destination takes the record's word - flags included - except the four position rows, which
+ *   keep the destination's values (translated code holds one set of positions per wavefront: the neighbours keep agreeing).  On a
+ *   ring, slot (j + d) mod Z of the destination takes the record's slot j, j = 0..Z-1, as a 32-bit pattern; a line that is not a
+ *   ring is copied as it is.  d may differ between the records of an image and between the two lines of a record.
+ *   From the call on the destination produces the outputs, register bits, instruction counter and LFSR words the saved instance
+ *   would have produced on the same input, bit for bit; its delay memory is the saved instance's, rotated by d.  One caveat:
+ *   out-of-domain flag 1 (FXO_OOD_TRAM_READ_NEG, a read offset beyond the read position) is raised by absolute position, so a
+ *   program with read offsets above 0 may raise it at other samples after a rotation - the data is the same, the library defines
+ *   that read as the wrapped slot.  With d = 0 everywhere the call leaves exactly the state fxb_load_instances leaves.
+ *   A program without delay lines, or one that executes no delay-line instruction, goes the way of fxb_load_instances; otherwise
+ *   FXB_INFO_INSTANCE_ROTATIONS counts the launches and FXB_INFO_INSTANCE_SCATTERS does not.  Returns as fxb_load_instances. */
+int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes);
 /* one instance's delay memory as the reference holds it (which: 0 = smallDelayBuffer / iTRAM, 1 = largeDelayBuffer / xTRAM; the first
  * n_slots words; words the program cannot reach read 0) and its positions {iTRAM write, iTRAM read, xTRAM write, xTRAM read}
  * (reference smallDelayWritePos ... largeDelayReadPos, include/FX8010.h:214-217) */
@@ -651,7 +678,9 @@ enum {
     FXB_INFO_BUS_GAIN_BLOCKS = 41,     /* bus blocks mixed with gains (fxb_bus_set_gains) since creation (summed over shards) */
     FXB_INFO_BUS_TAP_BLOCKS = 42,      /* bus blocks that delivered taps (fxb_process_block_bus_tap* with a tap_out) since creation (summed over shards) */
     FXB_INFO_BUS_SEND_BLOCKS = 43,     /* bus blocks that delivered sends (fxb_process_block_bus_aux* with an aux_out) since creation (summed over shards) */
-    FXB_INFO_BUS_FEED_BLOCKS = 44      /* bus blocks filled by feeds (fxb_process_block_bus_feed*) since creation (summed over shards) */
+    FXB_INFO_BUS_FEED_BLOCKS = 44,     /* bus blocks filled by feeds (fxb_process_block_bus_feed*) since creation (summed over shards) */
+    FXB_INFO_INSTANCE_RINGS = 45,      /* bit 0: iTRAM, bit 1: xTRAM is a ring in which a record can be rotated (fxb_load_instances_rotated); 0 without delay lines */
+    FXB_INFO_INSTANCE_ROTATIONS = 46   /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
