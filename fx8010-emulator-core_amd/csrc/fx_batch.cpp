@@ -71,6 +71,7 @@ Batch::~Batch() {
     clearCodeCache();
     (void)hipFree(dScratch_);
     (void)hipFree(dTracks_);
+    (void)hipFree(dQuietLeft_);
     (void)hipFree(dIn_);
     (void)hipFree(dOut_);
     freeBlock(bus_, false);
@@ -845,9 +846,23 @@ std::string Batch::tierNotePlain() const {
     if (c_.key.empty() && !c_.useAsm && c_.low.steady.empty()) return "not lowered yet (the first block, fxb_prepare or an fxb_info query does it)";
     if (c_.useAsm && c_.useXlate)
         return std::string("translated to gfx950 code (fx_xlate_") + regs[c_.variant] + (c_.stages > 1 ? ", " + std::to_string(c_.stages) + " stages" : "") +
-               (c_.stages <= 1 && c_.prioritySlices ? ", wavefronts of a SIMD by turns" : "") + ")";
+               (c_.stages <= 1 && c_.prioritySlices ? ", wavefronts of a SIMD by turns" : "") + (c_.quiet ? ", quiet loop" : "") + ")";
     if (c_.useAsm) return std::string("interpreter (fx_interp_") + regs[c_.variant] + "): " + (c_.xlateWhyNot.empty() ? "no translation asked for" : c_.xlateWhyNot);
     return "HIP C++ kernel (" + std::to_string(c_.low.instPerLane) + " instance(s) per lane): " + (c_.asmWhyNot.empty() ? "no assembly tier asked for" : c_.asmWhyNot);
+}
+
+// wavefronts of the last launch that left the quiet loop: exit words below the block length (a wavefront that never entered the
+// loop - a block of one sample, state rows outside their class - leaves its word at 0xFFFFFFFF)
+int64_t Batch::quietLeft() {
+    if (!lastLaunchQuiet_ || !dQuietLeft_) return 0;
+    (void)hipSetDevice(device_);
+    waitLastLaunch();
+    const size_t waves = std::min(quietLeftWords_, ((size_t)n_ + 63) / 64);
+    std::vector<uint32_t> words(waves);
+    if (hipMemcpy(words.data(), dQuietLeft_, waves * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    int64_t left = 0;
+    for (uint32_t w : words) left += w < (uint32_t)lastLaunchSamples_;
+    return left;
 }
 
 int64_t Batch::info(int what) {
@@ -887,6 +902,8 @@ int64_t Batch::info(int what) {
         }
         case FXB_INFO_STAGE_TRIALS: { int64_t n = 0; for (const Tuner& t : tune_) n += t.trials; return n; }
         case FXB_INFO_XLATE_CODE_HASH: return c_.useXlate ? (int64_t)c_.codeHash : 0;
+        case FXB_INFO_XLATE_QUIET: return (c_.useXlate && c_.quiet) ? 1 : 0;
+        case FXB_INFO_XLATE_QUIET_LEFT: return quietLeft();
         case FXB_INFO_CODE_CACHE_HITS: return cacheHits_;
         case FXB_INFO_CODE_CACHED: return (int64_t)cache_.size() + (c_.key.empty() ? 0 : 1);
         case FXB_INFO_XLATE_UNSATURATED: return c_.useXlate ? c_.unsaturated : 0;

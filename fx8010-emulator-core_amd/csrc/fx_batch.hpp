@@ -321,6 +321,13 @@ private:
     std::vector<int> trackRegs_;           // register of slot t
     std::vector<PendingTrack> pendingTracks_;  // per slot; steps == 0: not armed
     uint32_t* dTracks_ = nullptr;
+    // the quiet loop's exit words, one per wavefront (fx_xlate.hpp QuietPlan): 0xFFFFFFFF before a launch, then the sample at which
+    // the wavefront left the loop, or the block length
+    uint32_t* dQuietLeft_ = nullptr;
+    size_t quietLeftWords_ = 0;
+    bool lastLaunchQuiet_ = false;
+    int ensureQuietLeft();
+    int64_t quietLeft();             // FXB_INFO_XLATE_QUIET_LEFT
     size_t tracksCap_ = 0;                 // bytes
     bool tracksClear_ = false;             // the device header holds no armed schedule
     std::vector<uint32_t> trackStage_;     // host image of dTracks_ for the block being launched
@@ -378,6 +385,7 @@ private:
         std::vector<uint8_t> wildRow;
         std::string xlateWhyNot;
         bool prioritySlices = false;   // generated code: the wavefronts of a SIMD take turns at the top priority (fx_xlate.hpp)
+        bool quiet = false;            // generated code with a quiet loop (fx_xlate.hpp QuietPlan): wavefronts start there
         bool deferred = false;          // the interpreter runs this one because controls were moving when it was built
         uint32_t* dStream = nullptr;    // records / row table / stage descriptors on the device
         size_t streamCap = 0;

@@ -672,12 +672,14 @@ int Batch::translateInto(Code& c, const BuildInputs& in, bool offline, std::stri
             c.initOff = image.initOff;
             c.ldsBytes = image.ldsBytes;
             c.wildRow = image.wildRow;
-            c.unsaturated = image.steady.unsaturated;
-            c.inlined = image.steady.inlined;
-            c.called = image.steady.called;
-            c.valu = image.steady.valu;
-            c.valuSlow = image.steady.valuSlow;
-            c.valuClocks = image.steady.valuClocks;
+            c.quiet = image.quietOff != 0;
+            const XlateStats& loop = c.quiet ? image.quiet : image.steady;   // the loop that wavefronts start in
+            c.unsaturated = loop.unsaturated;
+            c.inlined = loop.inlined;
+            c.called = loop.called;
+            c.valu = loop.valu;
+            c.valuSlow = loop.valuSlow;
+            c.valuClocks = loop.valuClocks;
             c.vgprConstants = image.vgprConstants;
             if (offline) ++backgroundBuilds_; else ++xlateBuilds_;
             c.stages = image.stages;

@@ -236,6 +236,20 @@ int Batch::ensureEndStamps() {
 }
 #endif
 
+// the quiet loop's exit words ride in the kernarg slot of the stage descriptors, which an unstaged launch leaves unused (nStages
+// stays 0: the template never looks at the pointer)
+int Batch::ensureQuietLeft() {
+    const size_t words = ((size_t)n_ + 63) / 64;
+    if (words <= quietLeftWords_) return 0;
+    waitLastLaunch();
+    (void)hipFree(dQuietLeft_);
+    dQuietLeft_ = nullptr;
+    quietLeftWords_ = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&dQuietLeft_), words * 4) != hipSuccess) return fail(FX_E_MEMORY, "exit words of the quiet loop");
+    quietLeftWords_ = words;
+    return 0;
+}
+
 // Lower if need be and launch: the block has been checked and counted (beginBlock) by the caller.
 int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t stream, int64_t pitch, unsigned mode) {
     int rc = ensureLowered();
@@ -255,6 +269,7 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
     for (;;) {
         const KernelArgs a = kernelArgs(dIn, dOut, nSamples, pitch);
         e = timed ? hipEventRecord(ev0_, s) : hipSuccess;
+        lastLaunchQuiet_ = false;
         if (e == hipSuccess && c_.useAsm) {
             AsmArgs g = asmArgs(a);
 #ifdef FX_DIAGNOSTICS
@@ -263,7 +278,15 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
                 g.stages = dStamps_;
             }
 #endif
-            e = c_.useXlate ? launchAsmFunction(c_.fn, g, (unsigned)((n_ + 63) / 64), c_.ldsBytes, s, (unsigned)c_.stages)
+            const bool quiet = c_.useXlate && c_.quiet && c_.stages <= 1;
+            if (quiet) {
+                if ((rc = ensureQuietLeft()) != 0) return rc;
+                g.stages = dQuietLeft_;
+                e = hipMemsetAsync(dQuietLeft_, 0xff, quietLeftWords_ * 4, s);
+            }
+            lastLaunchQuiet_ = quiet;
+            if (e == hipSuccess)
+                e = c_.useXlate ? launchAsmFunction(c_.fn, g, (unsigned)((n_ + 63) / 64), c_.ldsBytes, s, (unsigned)c_.stages)
                             : launchAsmInterp(g, c_.variant, c_.variant == ASM_LDS ? (size_t)a.nRows * 256 : 0, device_, s);
         } else if (e == hipSuccess) {
             e = launchStepBlock(a, c_.low.multipass, s);

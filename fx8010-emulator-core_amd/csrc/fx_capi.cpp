@@ -399,7 +399,7 @@ int64_t fxp_lower_info(fxp_handle* h, int what) {
     }
 }
 static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, int64_t cap, char* listing, int64_t listing_cap, int stages, int stage,
-                             int* stagesOut, int* info, int infoCap);
+                             int* stagesOut, int* info, int infoCap, std::vector<int32_t>* quietOut = nullptr);
 int fxp_track_register(fxp_handle* h, const char* key) {
     if (!h || !key) return FX_E_ARG;
     const int r = h->prog.findRegister(key);
@@ -421,8 +421,24 @@ int64_t fxp_translate(fxp_handle* h, int vgprs, int stream, void* code, int64_t 
         return FX_E_PROGRAM;
     }
 }
+int64_t fxp_quiet_plan(fxp_handle* h, int vgprs, int32_t* out, int64_t cap) {
+    if (!h) return FX_E_ARG;
+    try {
+        std::vector<int32_t> words;
+        const int64_t rc = translateImpl(h, vgprs, 0, nullptr, 0, nullptr, 0, 1, 0, nullptr, nullptr, 0, &words);
+        if (rc < 0) return rc;
+        if (out && cap > 0) std::memcpy(out, words.data(), (size_t)std::min<int64_t>(cap, (int64_t)words.size()) * 4);
+        return (int64_t)words.size();
+    } catch (const std::exception& e) {
+        h->err = e.what();
+        return codeOf(e);
+    } catch (...) {
+        h->err = "unknown error";
+        return FX_E_PROGRAM;
+    }
+}
 static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, int64_t cap, char* listing, int64_t listing_cap, int stages, int stage,
-                             int* stagesOut, int* info, int infoCap) {
+                             int* stagesOut, int* info, int infoCap, std::vector<int32_t>* quietOut) {
     if (!h->prog.ready) { h->err = "no program loaded"; return FX_E_NOTREADY; }
     if (listing && listing_cap > 0) listing[0] = 0;
     std::vector<float> values(h->prog.regs.size());
@@ -446,7 +462,7 @@ static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, i
     }
     const fx::XlateTemplate* tmpl = fx::xlateTemplate((fx::AsmVariant)v, &h->err);
     if (!tmpl) return FX_E_PROGRAM;
-    if (stream < 0 || stream > 4) { h->err = "stream: 0 steady fast, 1 steady exact, 2 last fast, 3 last exact, 4 run-once"; return FX_E_ARG; }
+    if (stream < 0 || stream > 5 || (stream == 5 && stages >= 2)) { h->err = "stream: 0 steady fast, 1 steady exact, 2 last fast, 3 last exact, 4 run-once, 5 steady quiet (unstaged)"; return FX_E_ARG; }
     std::vector<uint32_t> code4[5];
     std::string text4[5];
     fx::XlateImage plan;
@@ -479,8 +495,33 @@ static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, i
     }
     if (staged && (stage < 0 || stage >= plan.stages)) { h->err = "no such stage"; return FX_E_ARG; }
     if (!staged && !fx::planXlate(steadyRecords, lastRecords, *tmpl, xprog, &plan, code4, text4, &h->err)) return FX_E_PROGRAM;
-    const std::vector<uint32_t>& words = staged ? stagedCode[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : code4[stream];
-    const std::string& text = staged ? stagedText[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : text4[stream];
+    if (quietOut) {
+        // [0] a quiet loop is generated, [1] eligible, [2] saturation sites, [3] dropped by the fast stream, [4] by the quiet loop,
+        // [5] vector instructions of the head check, [6] checked rows, [7] dropped records, [8] records; then per checked row
+        // {register-file row, register index (-1: none), bound bits}, the dropped record indices, the steady records (8 words each)
+        const fx::QuietPlan& q = plan.quietPlan;
+        std::vector<int32_t>& w = *quietOut;
+        w = {q.inForce && plan.quietOff ? 1 : 0, q.eligible ? 1 : 0, q.sites, q.fastDropped, q.quietDropped, q.checkInstructions,
+             (int32_t)q.checkedRows.size(), (int32_t)q.dropped.size(), (int32_t)steadyRecords.size()};
+        for (size_t k = 0; k < q.checkedRows.size(); ++k) {
+            int reg = -1;
+            for (size_t r = 0; r < low.rowOfReg.size(); ++r)
+                if (low.rowOfReg[r] == q.checkedRows[k]) reg = (int)r;
+            int32_t bits;
+            std::memcpy(&bits, &q.checkedBound[k], 4);
+            w.push_back(q.checkedRows[k]);
+            w.push_back(reg);
+            w.push_back(bits);
+        }
+        for (int i : q.dropped) w.push_back(i);
+        for (const fx::MicroOp& r : steadyRecords)
+            for (int k = 0; k < 8; ++k) w.push_back((int32_t)r.w[k]);
+        h->err = q.why;
+        return 0;
+    }
+    if (stream == 5 && staged) { h->err = "a program cut into stages has no quiet loop"; return FX_E_ARG; }
+    const std::vector<uint32_t>& words = stream == 5 ? plan.quietCode : staged ? stagedCode[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : code4[stream];
+    const std::string& text = stream == 5 ? plan.quietListing : staged ? stagedText[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : text4[stream];
     const int64_t bytes = (int64_t)words.size() * 4;
     if (code && cap > 0 && bytes > 0) std::memcpy(code, words.data(), (size_t)std::min<int64_t>(cap, bytes));   // (an empty stream has no data())
     if (listing && listing_cap > 0) {

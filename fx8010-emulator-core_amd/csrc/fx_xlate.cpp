@@ -40,6 +40,74 @@ constexpr LutGuessConstants kLutGuessNarrow{0x437c0000u /* 252.0 */, 0x437b8000u
 constexpr LutGuessConstants kLutGuessWide{0x43fc0000u /* 504.0 */, 0x43fbc000u /* 503.5 */, 0x4b400000u, 0x000003f0u};
 const LutGuessConstants& lutGuess() { return lutLds().wide ? kLutGuessWide : kLutGuessNarrow; }
 
+// Results nobody reads (Translator::run "the program"): per record, 1 = its row is written again, unconditionally, before any
+// instruction of the same sample reads it.  Shared by the translator and the quiet plan (a dead result has no saturation).
+std::vector<uint8_t> deadWritesOf(const std::vector<MicroOp>& records, const std::vector<int>& latchRows) {
+    std::vector<uint8_t> dead(records.size(), 0);
+    {
+        bool shadow = false;
+        std::vector<uint8_t> shadowed(records.size(), 0);
+        for (size_t i = 0; i < records.size(); ++i) {
+            if (records[i].w[0] == AS_PRED) shadow = true;
+            else if (records[i].w[0] == AS_UNPRED) shadow = false;
+            shadowed[i] = shadow;
+        }
+        for (size_t i = 0; i < records.size() && records[i].w[0] != AS_ENDSAMPLE; ++i) {
+            const uint32_t slot = records[i].w[0];
+            if (slot < AS_MACS || slot >= (uint32_t)kAsmSlots || shadowed[i]) continue;
+            const Access a = accessOf(records[i]);
+            if (a.write <= 0) continue;   // (row 0 is the CCR)
+            for (size_t j = i + 1; j < records.size(); ++j) {
+                if (records[j].w[0] == AS_ENDSAMPLE) break;
+                const Access b = accessOf(records[j]);
+                bool reads = false;
+                for (int k = 0; k < b.nReads; ++k) reads = reads || (int)b.reads[k] == a.write;
+                if (reads || ((b.tram || b.noise) && b.write == a.write)) break;
+                if (b.write == a.write && !shadowed[j] && !b.tram && !b.noise) { dead[i] = 1; break; }
+            }
+        }
+        for (int r : latchRows)   // (an output latch is stored as PCM every sample)
+            for (size_t i = 0; i < records.size(); ++i)
+                if (dead[i] && (int)records[i].w[5] == r) dead[i] = 0;
+    }
+    return dead;
+}
+
+// Can the saturation of a record's result be dropped, given an upper bound of |operand| per operand (B(word, uniform))?  Every
+// rounding step is monotone and the bounds are floats, so |exact bound| <= 1 carries through the fp32 (fp64 for INTERP) roundings.
+template <class Bound>
+bool withinUnitRule(uint32_t family, uint32_t kind, const MicroOp& r, const Bound& bound) {
+    const bool uA = kind & 1, uX = kind & 2, uY = kind & 4;
+    if (family <= 1) {  // A +- X*Y: a folded product sits in the X word
+        const double bp = (uX && uY) ? bound(r.w[3], true) : bound(r.w[3], uX) * bound(r.w[4], uY);
+        return bound(r.w[2], uA) + bp <= 1.0;
+    }
+    if (family == 2) {  // (A + X) + Y: a folded A + X sits in the A word
+        const double bs = (uA && uX) ? bound(r.w[2], true) : bound(r.w[2], uA) + bound(r.w[3], uX);
+        return bs + bound(r.w[4], uY) <= 1.0;
+    }
+    // INTERP: a convex combination of A and Y when X is a constant in [2^-20, 1]
+    if (!uX) return false;
+    double omx;
+    const uint64_t bitsOmx = (uint64_t)r.w[6] | ((uint64_t)r.w[7] << 32);
+    std::memcpy(&omx, &bitsOmx, 8);
+    if (!(omx >= 0.0 && omx <= 1.0 - 9.5367431640625e-07)) return false;
+    if (bound(r.w[2], uA) > 1.0) return false;
+    if (uY) {  // folded product X*Y in the X word: |p| <= X = 1 - omx must hold
+        return bound(r.w[3], true) <= 1.0 - omx;
+    }
+    return bound(r.w[4], false) <= 1.0;
+}
+// upper bound of |operand| by class: |c| of a uniform, 1 for a row of the bounded class, +inf for any other row
+double classBound(const std::vector<uint8_t>& wildRow, uint32_t word, bool uniform) {
+    if (uniform) {
+        float f;
+        std::memcpy(&f, &word, 4);
+        return f == f ? std::fabs((double)f) : HUGE_VAL;
+    }
+    return (word < wildRow.size() && !wildRow[word]) ? 1.0 : HUGE_VAL;
+}
+
 class Translator {
   public:
     // exactReturns == nullptr: the exact stream (NaN passes every saturation).  Otherwise the fast stream, which
@@ -49,6 +117,11 @@ class Translator {
                std::string* listing, const std::vector<uint32_t>* exactReturns)
         : tmpl_(t), prog_(prog), base_(codeBase), isLast_(isLast), nextBase_(nextBase), e_(code, listing), fast_(exactReturns != nullptr),
           exactReturns_(exactReturns) { e_.constants(&prog_.vconst); }
+
+    // the quiet loop (fx_xlate.hpp QuietPlan) instead of the steady fast stream: the same code but for the saturations the plan
+    // drops, the check of the plan's rows at the head, and `bailTarget` - the head sync point of the steady FAST loop - where a
+    // wave continues when a lane fails that check
+    void quiet(const QuietPlan* plan, uint32_t bailTarget) { quiet_ = plan; bailTarget_ = bailTarget; }
 
     // Layout of a stream:  head (hot entry) | program | PCM out, advance, loop branch / exit | cold entry stub
     bool run(const std::vector<MicroOp>& records, XlateStats* stats, std::vector<uint32_t>* returns, uint32_t* coldEntry, std::string* err) {
@@ -170,39 +243,14 @@ class Translator {
         // (a later stage of a pipelined program has nothing at its head that could taint it: its flag check sits behind the barriers)
         const bool cleanHead = staged && G.index > 0 && H.leadCount == 0 && !ring && prog_.trackRows.empty();
         if (fast_ && !cleanHead && !leaveIfTainted((*exactReturns_)[syncIndex(0)])) { if (err) *err = err_; return false; }
+        if (quiet_) quietHeadCheck();
 
         // ---- the program
         // Results nobody reads: a row written again, unconditionally, before any instruction of the same sample reads it (the
         // end of the sample counts as a reader: state, packets, the next sample).  The canonical case is the DANE idiom for
         // "test a value": `macs tmp, x, 0, 0` + `skip ccr, ccr, <cond>, n` - tmp is written once per test and never read; the
         // instruction is there for its CCR, which the SKIP's predicate takes straight from x (one()).
-        deadWrite_.assign(records.size(), 0);
-        {
-            bool shadow = false;
-            std::vector<uint8_t> shadowed(records.size(), 0);
-            for (size_t i = 0; i < records.size(); ++i) {
-                if (records[i].w[0] == AS_PRED) shadow = true;
-                else if (records[i].w[0] == AS_UNPRED) shadow = false;
-                shadowed[i] = shadow;
-            }
-            for (size_t i = 0; i < records.size() && records[i].w[0] != AS_ENDSAMPLE; ++i) {
-                const uint32_t slot = records[i].w[0];
-                if (slot < AS_MACS || slot >= (uint32_t)kAsmSlots || shadowed[i]) continue;
-                const Access a = accessOf(records[i]);
-                if (a.write <= 0) continue;   // (row 0 is the CCR)
-                for (size_t j = i + 1; j < records.size(); ++j) {
-                    if (records[j].w[0] == AS_ENDSAMPLE) break;
-                    const Access b = accessOf(records[j]);
-                    bool reads = false;
-                    for (int k = 0; k < b.nReads; ++k) reads = reads || (int)b.reads[k] == a.write;
-                    if (reads || ((b.tram || b.noise) && b.write == a.write)) break;
-                    if (b.write == a.write && !shadowed[j] && !b.tram && !b.noise) { deadWrite_[i] = 1; break; }
-                }
-            }
-            for (int r : prog_.latchRows)   // (an output latch is stored as PCM every sample)
-                for (size_t i = 0; i < records.size(); ++i)
-                    if (deadWrite_[i] && (int)records[i].w[5] == r) deadWrite_[i] = 0;
-        }
+        deadWrite_ = deadWritesOf(records, prog_.latchRows);
         products_.assign((size_t)(fast_ ? prog_.cseEntries : 0), Product());
         for (size_t k = 0; k < products_.size(); ++k) {
             products_[k].vP64 = prog_.cseBase + 2 * (int)k;
@@ -393,6 +441,11 @@ class Translator {
                 e_.sop2(SOP2_ADD_U32, "s_add_u32", sreg(kSTemp), sreg(kSSample), imm32(1));
                 e_.sopc(SOPC_CMP_LT_U32, "s_cmp_lt_u32", sreg(kSTemp), sreg(kSNumSamples));
                 if (!e_.branchBack(SOPP_CBRANCH_SCC1, "s_cbranch_scc1", headWord)) { if (err) *err = "translated loop too long for a branch"; return false; }
+                if (quiet_) {   // the wave stayed to the end of the quiet loop: its exit word is the block length
+                    e_.cold(true);
+                    quietExitWord(sreg(kSNumSamples));
+                    e_.cold(false);
+                }
             }
             const int64_t delta = ((int64_t)nextBase_ - ((int64_t)base_ + (int64_t)e_.bytes() + 4)) / 4;
             if (delta < -32768 || delta > 32767) { if (err) *err = "last-sample stream out of branch range"; return false; }
@@ -767,11 +820,70 @@ class Translator {
     bool leaveIfTainted(uint32_t target) {
         if (target == 0) return fail("internal: fast and exact streams differ in their sync points");
         e_.sopc(SOPC_CMP_LG_U64, "s_cmp_lg_u64", sreg64(kSTaint), imm32(0));
+        if (quiet_) {   // (by way of the exit word, behind the loop)
+            defer(e_.branchForward(SOPP_CBRANCH_SCC1, "s_cbranch_scc1"), [this, target]() { quietLeave(target); });
+            return true;
+        }
         const int64_t delta = ((int64_t)target - ((int64_t)base_ + (int64_t)e_.bytes() + 4)) / 4;
         if (delta < -32768 || delta > 32767) return fail("exact stream out of branch range of the fast stream");
         e_.sopp(SOPP_CBRANCH_SCC1, "s_cbranch_scc1", (uint32_t)delta & 0xffffu, true);
         return true;
     }
+    // ---- the quiet loop (fx_xlate.hpp QuietPlan)
+    // word [wavefront] of the launch's exit words = `value`: lane 0 stores it.  v2 / v3 and s[62:63] are scratch between records.
+    void quietExitWord(const Src& value) {
+        smemLoad(2, kSTemp, 0, kKernargQuietLeft);
+        e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(2), value);
+        e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(3), sreg(kSWave));
+        e_.vop2(VOP2_LSHLREV_B32, "v_lshlrev_b32_e32", 3, imm32(2), 3);
+        e_.waitLgkm0();
+        e_.sop1(SOP1_MOV_B64, "s_mov_b64", named(126, "exec"), imm32(1));
+        e_.global(GLOBAL_STORE_DWORD, false, 2, 3, kSTemp);
+        e_.sop1(SOP1_MOV_B64, "s_mov_b64", named(126, "exec"), named(193, "-1"));
+        e_.waitVmcnt(0);   // (the counted waits of the loops know nothing of this store)
+    }
+    // behind the loop: note the sample at which the wave leaves, then on to `target` in another stream
+    void quietLeave(uint32_t target) {
+        e_.cold(true);
+        quietExitWord(sreg(kSSample));
+        const int64_t delta = ((int64_t)target - ((int64_t)base_ + (int64_t)e_.bytes() + 4)) / 4;
+        if (delta < -32768 || delta > 32767) { err_ = "quiet loop out of branch range of the other streams"; deferredFailed_ = true; }
+        e_.sopp(SOPP_BRANCH, "s_branch", (uint32_t)delta & 0xffffu, true);
+        e_.cold(false);
+    }
+    // Head of a sample, behind the head's own checks: max |row| over the rows the plan checks at kQuietBound and over those it
+    // checks at 1 (v_max3_f32 with |...| on every source), one compare each, OR-ed into s[62:63]; a lane above its bound sends the
+    // wave to the steady FAST loop - same sample, same point: behind that loop's head, in front of record 0 - for good.
+    void quietHeadCheck() {
+        std::vector<int> tight, unit;
+        for (size_t k = 0; k < quiet_->checkedRows.size(); ++k)
+            (quiet_->checkedBound[k] < 1.0f ? tight : unit).push_back(vrow((uint32_t)quiet_->checkedRows[k]));
+        auto group = [this](const std::vector<int>& v, int acc) {
+            const size_t n = v.size();
+            e_.max3Abs(vreg(acc), vreg(v[0]), vreg(v[n > 1 ? 1 : 0]), vreg(v[n > 2 ? 2 : n - 1]));
+            for (size_t i = 3; i < n; i += 2) e_.max3Abs(vreg(acc), vreg(acc), vreg(v[i]), vreg(v[i + 1 < n ? i + 1 : i]));
+        };
+        e_.note("quiet check (a wave that fails it continues at the head sync point of the steady fast loop)");
+        uint32_t tightBits;
+        const float tightBound = kQuietBound;
+        std::memcpy(&tightBits, &tightBound, 4);
+        if (!tight.empty()) {
+            group(tight, 2);
+            e_.vopc(VOPC_CMP_LT_F32, "v_cmp_lt_f32_e32", imm32(tightBits), 2);
+            e_.sop1(SOP1_MOV_B64, "s_mov_b64", sreg64(kSTemp), named(106, "vcc"));
+        }
+        if (!unit.empty()) {
+            group(unit, 3);
+            e_.vopc(VOPC_CMP_LT_F32, "v_cmp_lt_f32_e32", imm32(0x3f800000u), 3);
+            if (tight.empty()) e_.sop1(SOP1_MOV_B64, "s_mov_b64", sreg64(kSTemp), named(106, "vcc"));
+            else e_.sop2(SOP2_OR_B64, "s_or_b64", sreg64(kSTemp), sreg64(kSTemp), named(106, "vcc"));
+        }
+        e_.sop2(SOP2_AND_B64, "s_and_b64", sreg64(kSTemp), sreg64(kSTemp), sreg64(kSValidLanes));   // (lanes without an instance hold anything)
+        e_.sopc(SOPC_CMP_LG_U64, "s_cmp_lg_u64", sreg64(kSTemp), imm32(0));
+        const uint32_t target = bailTarget_;
+        defer(e_.branchForward(SOPP_CBRANCH_SCC1, "s_cbranch_scc1"), [this, target]() { quietLeave(target); });
+    }
+
     // the record is about to read / write these register-file rows: none may still be in flight
     bool touch(const MicroOp& r, bool a, bool x, bool y, bool dst) {
         if (pending_.empty()) return true;
@@ -1305,38 +1417,13 @@ class Translator {
     }
     // upper bound of |operand| that the fast stream may rely on: |c| of a uniform, 1 for a row of the bounded
     // class (the taint checks keep that invariant), +inf for any other row
-    double bound(uint32_t word, bool uniform) const {
-        if (uniform) {
-            float f;
-            std::memcpy(&f, &word, 4);
-            return f == f ? std::fabs((double)f) : HUGE_VAL;
-        }
-        return (word < prog_.wildRow.size() && !prog_.wildRow[word]) ? 1.0 : HUGE_VAL;
-    }
-    // Can the saturation of this instruction's result be dropped in the fast stream?  Every rounding step is
-    // monotone and the bounds are floats, so |exact bound| <= 1 carries through the fp32 (fp64 for INTERP) roundings.
+    double bound(uint32_t word, bool uniform) const { return classBound(prog_.wildRow, word, uniform); }
+    // Can the saturation of this instruction's result be dropped?  The fast stream: by the class bounds (withinUnitRule); the
+    // quiet loop: by its plan, whose running bounds start from the rows the head of the sample has checked.
     bool resultWithinUnit(uint32_t family, uint32_t kind, const MicroOp& r) const {
         if (!fast_ || kind == 7) return false;
-        const bool uA = kind & 1, uX = kind & 2, uY = kind & 4;
-        if (family <= 1) {  // A +- X*Y: a folded product sits in the X word
-            const double bp = (uX && uY) ? bound(r.w[3], true) : bound(r.w[3], uX) * bound(r.w[4], uY);
-            return bound(r.w[2], uA) + bp <= 1.0;
-        }
-        if (family == 2) {  // (A + X) + Y: a folded A + X sits in the A word
-            const double bs = (uA && uX) ? bound(r.w[2], true) : bound(r.w[2], uA) + bound(r.w[3], uX);
-            return bs + bound(r.w[4], uY) <= 1.0;
-        }
-        // INTERP: a convex combination of A and Y when X is a constant in [2^-20, 1]
-        if (!uX) return false;
-        double omx;
-        const uint64_t bitsOmx = (uint64_t)r.w[6] | ((uint64_t)r.w[7] << 32);
-        std::memcpy(&omx, &bitsOmx, 8);
-        if (!(omx >= 0.0 && omx <= 1.0 - 9.5367431640625e-07)) return false;
-        if (bound(r.w[2], uA) > 1.0) return false;
-        if (uY) {  // folded product X*Y in the X word: |p| <= X = 1 - omx must hold
-            return bound(r.w[3], true) <= 1.0 - omx;
-        }
-        return bound(r.w[4], false) <= 1.0;
+        if (quiet_) return index_ < quiet_->idle.size() && quiet_->idle[index_] != 0;
+        return withinUnitRule(family, kind, r, [this](uint32_t word, bool uniform) { return bound(word, uniform); });
     }
 
     // a uniform operand's bit pattern; a NaN or Inf among them rules the fast stream out
@@ -2123,6 +2210,8 @@ class Translator {
     std::string err_;
     bool fast_;
     const std::vector<uint32_t>* exactReturns_;
+    const QuietPlan* quiet_ = nullptr;   // this stream is the quiet loop of that plan
+    uint32_t bailTarget_ = 0;            // ... and leaves for the steady fast loop there
     std::vector<uint32_t> returns_;  // sync points of this stream (see run())
     std::vector<int> pending_;       // VGPRs with a TRAM read in flight
     std::vector<std::pair<uint32_t, int>> pool_;  // uniform constants kept in SGPRs for the whole loop: (bits, SGPR)
@@ -2470,6 +2559,167 @@ XlateProgram xlateProgramOf(const std::vector<MicroOp>& steadyRecords, const std
     return p;
 }
 
+// ---- the quiet plan (fx_xlate.hpp QuietPlan): running bounds over the steady records --------------------------------------
+namespace {
+// fp32 / fp64 operations exactly as the instruction performs them: one rounding each, never contracted into an fma
+float mulF(float a, float b) {
+    if (a == 0.0f || b == 0.0f) return 0.0f;   // (a wild operand is finite while the wave runs this code: 0 * x = 0)
+    volatile float r = a * b;
+    return r;
+}
+float addF(float a, float b) { volatile float r = a + b; return r; }
+double mulD(double a, double b) {
+    if (a == 0.0 || b == 0.0) return 0.0;
+    volatile double r = a * b;
+    return r;
+}
+double addD(double a, double b) { volatile double r = a + b; return r; }
+float absOf(uint32_t bits) {
+    float f;
+    std::memcpy(&f, &bits, 4);
+    return f == f ? std::fabs(f) : HUGE_VALF;
+}
+
+struct QuietPass {
+    std::vector<uint8_t> site, idle, idleByClass;
+    int sites = 0, idleCount = 0, idleByClassCount = 0;
+};
+// One pass over the records with head bounds `rb` (per register-file row; +inf = nothing known): at every record that writes a
+// row the bound becomes min(1, bound of the unsaturated result) - computed with the instruction's own operation sequence in
+// fp32 (fp64 for INTERP's blend): rounding is monotone, so the bound of the rounded result is the rounded bound - and the
+// saturation is idle when that bound is <= 1, or when the fast stream's class rule says so.
+QuietPass quietPass(const std::vector<MicroOp>& records, const XlateProgram& prog, const std::vector<uint8_t>& dead, std::vector<float> rb) {
+    QuietPass out;
+    out.site.assign(records.size(), 0);
+    out.idle.assign(records.size(), 0);
+    out.idleByClass.assign(records.size(), 0);
+    auto classOf = [&](uint32_t row) { return (row < prog.wildRow.size() && !prog.wildRow[row]) ? 1.0f : HUGE_VALF; };
+    auto B = [&](uint32_t word, bool uniform) { return uniform ? absOf(word) : (word < rb.size() ? rb[word] : HUGE_VALF); };
+    auto set = [&](uint32_t row, float b) { if (row < rb.size()) rb[row] = row == 0 ? HUGE_VALF : b; };   // (row 0 is the CCR)
+    for (size_t i = 0; i < records.size(); ++i) {
+        const MicroOp& r = records[i];
+        const uint32_t slot = r.w[0], dst = r.w[5];
+        if (slot == AS_ENDSAMPLE) break;
+        if ((int)i < prog.hoist.leadCount) continue;   // a leading delay-line read: its row holds the loaded value at the head
+        if (slot == AS_NOP || slot == AS_TRAM_IW || slot == AS_TRAM_XW) continue;
+        if (slot == AS_MOV) { set(dst, std::min(classOf(dst), B(r.w[2], r.w[6] & 1u))); continue; }
+        if (slot == AS_LIMIT || slot == AS_LIMITN) {
+            set(dst, std::min(classOf(dst), std::max(B(r.w[3], (r.w[6] & 2u) != 0), B(r.w[4], (r.w[6] & 4u) != 0))));
+            continue;
+        }
+        if (slot < AS_MACS || slot >= (uint32_t)kAsmSlots) { set(dst, classOf(dst)); continue; }   // (a delay-line read: checked against its class)
+        const uint32_t rel = slot - AS_MACS, family = rel / 16, kind = (rel % 16) / 2;
+        const bool uA = kind & 1, uX = kind & 2, uY = kind & 4;
+        if (rel & 1u) set(0, HUGE_VALF);
+        if (kind == 7) { set(dst, std::min(1.0f, absOf(r.w[2]))); continue; }   // folded on the host: the saturated result itself
+        if (dead[i]) continue;                                                  // nothing is computed: the row keeps what it held
+        float ub = HUGE_VALF;
+        if (family <= 1) {
+            const float p = (uX && uY) ? absOf(r.w[3]) : mulF(B(r.w[3], uX), B(r.w[4], uY));
+            ub = addF(B(r.w[2], uA), p);
+        } else if (family == 2) {
+            const float sum = (uA && uX) ? absOf(r.w[2]) : addF(B(r.w[2], uA), B(r.w[3], uX));
+            ub = addF(sum, B(r.w[4], uY));
+        } else if (uX) {   // INTERP with a constant X: (float)((1 - X) * (double)A + (double)(X * Y)), (1 - X) from the record
+            double omx;
+            const uint64_t bitsOmx = (uint64_t)r.w[6] | ((uint64_t)r.w[7] << 32);
+            std::memcpy(&omx, &bitsOmx, 8);
+            const float p = uY ? absOf(r.w[3]) : mulF(absOf(r.w[3]), B(r.w[4], false));
+            if (omx == omx) ub = (float)addD(mulD(std::fabs(omx), (double)B(r.w[2], uA)), (double)p);
+        }
+        const bool byClass = withinUnitRule(family, kind, r, [&](uint32_t word, bool uniform) { return classBound(prog.wildRow, word, uniform); });
+        const bool byBound = ub <= 1.0f;   // (false for a NaN)
+        out.site[i] = 1;
+        ++out.sites;
+        out.idleByClass[i] = byClass;
+        out.idleByClassCount += byClass;
+        out.idle[i] = byClass || byBound;
+        out.idleCount += out.idle[i];
+        set(dst, byBound ? ub : 1.0f);
+    }
+    return out;
+}
+// vector instructions of the head check over n values: the first v_max3_f32 takes three, every further one two; one compare
+int checkCost(size_t n) { return n == 0 ? 0 : 1 + (n > 3 ? (int)((n - 3 + 1) / 2) : 0) + 1; }
+}  // namespace
+
+QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog) {
+    QuietPlan plan;
+    plan.idle.assign(steadyRecords.size(), 0);
+    // eligibility: every condition must hold
+    if (prog.stage.count > 1) plan.why = "the program is cut into stages";
+    else if (!prog.trackRows.empty()) plan.why = "a control track is armed";
+    else if (prog.tramDane) plan.why = "FX_OPT_TRAM_* delay-line model";
+    else if (FX_DIAG_KNOB("FX_XLATE_ENDSTAMP")) plan.why = "end stamps (diagnostics) use the kernarg slot of the exit words";
+    bool anyTram = false;
+    int tramReads = 0;
+    for (size_t i = 0; i < steadyRecords.size() && plan.why.empty(); ++i) {
+        const uint32_t slot = steadyRecords[i].w[0];
+        if (slot == AS_ENDSAMPLE) break;
+        if (slot == AS_PRED || slot == AS_UNPRED || slot == AS_SKIP) plan.why = "SKIP";
+        else if (slot == AS_LUT) plan.why = "LOG / EXP";
+        else if (slot >= AS_TRAM_IR && slot <= AS_TRAM_XW) { anyTram = true; tramReads += slot == AS_TRAM_IR || slot == AS_TRAM_XR; }
+        else if (slot != AS_NOP && slot != AS_MOV && slot != AS_LIMIT && slot != AS_LIMITN && !(slot >= AS_MACS && slot < (uint32_t)kAsmSlots)) plan.why = "a handler call";
+    }
+    if (plan.why.empty() && anyTram && !prog.uniformCursors) plan.why = "per-lane delay-line cursors";
+    // (every delay-line value is in its row at the head of the sample, where the loop checks it - and the head is the only place
+    // where a wave can leave the quiet loop, for either of the other steady streams)
+    if (plan.why.empty() && tramReads != prog.hoist.leadCount) plan.why = "a delay-line read in the middle of the program (not issued a sample ahead)";
+    if (!plan.why.empty()) return plan;
+    plan.eligible = true;
+
+    const size_t nRows = prog.wildRow.size();
+    const std::vector<uint8_t> dead = deadWritesOf(steadyRecords, prog.latchRows);
+    // candidates: every row of the bounded class at kQuietBound, the PCM input rows (wild) at 1
+    std::vector<float> want(nRows, 0.0f);   // 0 = no candidate
+    for (size_t r = 1; r < nRows; ++r)
+        if (!prog.wildRow[r]) want[r] = kQuietBound;
+    for (int r : prog.inRows)
+        if (r > 0 && (size_t)r < nRows && prog.wildRow[(size_t)r]) want[(size_t)r] = 1.0f;
+    std::vector<uint8_t> checked(nRows, 0);
+    for (size_t r = 0; r < nRows; ++r) checked[r] = want[r] > 0.0f;
+    auto headBounds = [&]() {
+        std::vector<float> rb(nRows);
+        for (size_t r = 0; r < nRows; ++r) rb[r] = checked[r] ? want[r] : (prog.wildRow[r] ? HUGE_VALF : 1.0f);
+        return rb;
+    };
+    // start with every candidate checked; in row order, drop a check whenever the number of idle saturations does not fall
+    int best = quietPass(steadyRecords, prog, dead, headBounds()).idleCount;
+    for (size_t r = 0; r < nRows; ++r) {
+        if (!checked[r]) continue;
+        checked[r] = 0;
+        if (quietPass(steadyRecords, prog, dead, headBounds()).idleCount < best) checked[r] = 1;
+    }
+    const QuietPass pass = quietPass(steadyRecords, prog, dead, headBounds());
+    size_t tight = 0, unit = 0;
+    for (size_t r = 0; r < nRows; ++r) {
+        if (!checked[r]) continue;
+        plan.checkedRows.push_back((int)r);
+        plan.checkedBound.push_back(want[r]);
+        ++(want[r] < 1.0f ? tight : unit);
+    }
+    plan.idle = pass.idle;
+    for (size_t i = 0; i < pass.idle.size(); ++i)
+        if (pass.idle[i]) plan.dropped.push_back((int)i);
+    plan.sites = pass.sites;
+    plan.fastDropped = pass.idleByClassCount;
+    plan.quietDropped = pass.idleCount;
+    plan.checkInstructions = checkCost(tight) + checkCost(unit);
+    const int gain = plan.quietDropped - plan.fastDropped;
+    // The loop's premise is a quiet SIGNAL.  A plan that gains nothing from a bound on the PCM input bounds state alone - its
+    // program saturates where the input enters (config3: a = sat(in + rd * fb), and a drives every checked row), and at ordinary
+    // levels that state is above kQuietBound within a few samples: such a program gets no loop.
+    bool inputChecked = unit > 0;
+    for (int r : prog.inRows)
+        if (r > 0 && (size_t)r < nRows && !checked[(size_t)r]) inputChecked = false;
+    if (!inputChecked) plan.why = "the plan gains nothing from a bound on the PCM input: the program saturates where the input enters";
+    else if (plan.checkedRows.empty() || gain < kQuietMinGain || gain < kQuietGainPerCheck * plan.checkInstructions)
+        plan.why = "the plan drops " + std::to_string(gain) + " saturations for " + std::to_string(plan.checkInstructions) + " instructions of checking: not worth a loop";
+    else
+        plan.inForce = true;
+    return plan;
+}
+
 bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<MicroOp>& lastRecords, const XlateTemplate& tmpl,
                const XlateProgram& program, XlateImage* out, std::vector<uint32_t> code[5], std::string listing[5], std::string* err) {
     // hole: [steady fast][last fast][steady exact][last exact][run-once], each on a cache line.  The steady streams
@@ -2531,7 +2781,7 @@ bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<Micr
     out->base[1] = at; at += bytes[1];
     out->base[3] = at; at += bytes[3];
     if (!fastOk) { out->base[0] = out->base[1]; out->base[2] = out->base[3]; }
-    std::vector<uint32_t> exactRet[2];
+    std::vector<uint32_t> exactRet[2], steadyFastRet;
     XlateStats stats[4];
     uint32_t cold[4] = {0, 0, 0, 0};
     for (int k = 1; k >= 0; --k)
@@ -2542,7 +2792,7 @@ bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<Micr
         code[2 * k].clear();  // (a non-finite uniform operand: every wave runs the exact streams)
         if (!fastOk) { cold[2 * k] = cold[2 * k + 1]; stats[2 * k] = stats[2 * k + 1]; continue; }
         if (!translateStream(*recs[k], tmpl, prog[k], out->base[2 * k], k == 1, out->base[2], &exactRet[k], &code[2 * k],
-                             listing ? &listing[2 * k] : nullptr, &stats[2 * k], nullptr, &cold[2 * k], err))
+                             listing ? &listing[2 * k] : nullptr, &stats[2 * k], k == 0 ? &steadyFastRet : nullptr, &cold[2 * k], err))
             return false;
         if (align64((uint32_t)code[2 * k].size() * 4) != bytes[2 * k]) { if (err) *err = "internal: fast stream changed size"; return false; }
     }
@@ -2571,6 +2821,37 @@ bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<Micr
         out->initOff = at;
         out->ldsBytes = program.lutTables.empty() ? 0 : lutLds().bytes(program.lutTables.size());
         at += align64((uint32_t)code[4].size() * 4);
+    }
+    // The quiet loop, behind everything else: the other streams lie - and read, byte for byte - as they do without it.  It is the
+    // steady fast stream translated under the plan; where it does not fit (the hole, a branch range) the program has none.
+    out->quietBase = out->quietOff = 0;
+    out->quietCode.clear();
+    out->quietListing.clear();
+    out->quiet = XlateStats();
+    out->quietPlan = planQuiet(steadyRecords, pooledProgram);
+    if (out->quietPlan.inForce && !fastOk) { out->quietPlan.inForce = false; out->quietPlan.why = "no fast stream (a non-finite uniform operand)"; }
+    if (out->quietPlan.inForce) {
+        const size_t headSync = 4 * steadyRecords.size();
+        std::vector<uint32_t> quietCode;
+        std::string quietText, why;
+        uint32_t quietCold = 0;
+        XlateStats quietStats;
+        Translator t(tmpl, prog[0], at, false, out->base[2], &quietCode, listing ? &quietText : nullptr, &exactRet[0]);
+        t.quiet(&out->quietPlan, headSync < steadyFastRet.size() ? steadyFastRet[headSync] : 0u);
+        bool ok = headSync < steadyFastRet.size() && steadyFastRet[headSync] != 0 && t.run(steadyRecords, &quietStats, nullptr, &quietCold, &why);
+        if (ok && (at - tmpl.holeOff) + align64((uint32_t)quietCode.size() * 4) + 4 > tmpl.holeBytes) { ok = false; why = "no room in the code hole"; }
+        if (ok) {
+            out->quietBase = at;
+            out->quietOff = quietCold;
+            out->quietCode = std::move(quietCode);
+            out->quietListing = std::move(quietText);
+            out->quiet = quietStats;
+            out->steadyFastOff = quietCold;   // waves start in the quiet loop
+            at += align64((uint32_t)out->quietCode.size() * 4);
+        } else {
+            out->quietPlan.inForce = false;
+            out->quietPlan.why = why;
+        }
     }
     out->codeBytes = at - tmpl.holeOff;
     if (out->codeBytes + 4 > tmpl.holeBytes) {

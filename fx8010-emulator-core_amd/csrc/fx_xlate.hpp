@@ -173,6 +173,29 @@ struct XlateStats {
     bool nonFiniteImmediate = false;  // a NaN / Inf among the uniform operands: no fast stream for this program
 };
 
+// The quiet loop: a third steady loop, generated like the fast stream but with RUNNING bounds - an
+// upper bound of |row| per register-file row, carried from record to record - in place of "a bounded row is <= 1".  The
+// bounds start from head bounds that the loop checks at the head of every sample (kQuietBound for a checked row of the
+// bounded class, 1 for a checked wild row such as the PCM input; unchecked rows: 1 / +inf by class); a wave in which any lane
+// fails the check continues in the fast loop, at the same point, for the rest of the launch.  planQuiet is a pure function
+// of the steady records and the program: which rows to check, and at which records the saturation is then idle.
+constexpr float kQuietBound = 0.25f;
+struct QuietPlan {
+    bool eligible = false;             // the program meets the conditions at all (why: which one it misses)
+    bool inForce = false;              // ... and the plan pays: a quiet loop is generated
+    std::string why;
+    std::vector<int> checkedRows;      // ascending
+    std::vector<float> checkedBound;   // per checked row: kQuietBound or 1
+    std::vector<uint8_t> idle;         // per steady record: its saturation is not emitted in the quiet loop
+    std::vector<int> dropped;          // the indices of those records
+    int sites = 0;                     // saturating records of the steady stream whose result is computed
+    int fastDropped = 0;               // ... whose saturation the fast stream drops already
+    int quietDropped = 0;              // ... and the quiet loop (= dropped.size())
+    int checkInstructions = 0;         // vector instructions of the head check
+};
+constexpr int kQuietMinGain = 32, kQuietGainPerCheck = 4;
+QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog);
+
 // Translate one stream of records (encodeAsmStream(ops, nullptr, true): w0 = handler slot) into the code of a
 // whole sample LOOP that starts `codeBase` bytes after the kernel entry: PCM input of the sample (prefetched one
 // sample ahead), the program, PCM output, pointer advance and the branch back.  A steady stream loops while the
@@ -230,6 +253,13 @@ struct XlateImage {
     // COLD entry offsets from the kernel entry; AsmArgs.steady = steadyFastOff | steadyOff << 32, .last likewise
     uint32_t steadyFastOff = 0, steadyOff = 0, lastFastOff = 0, lastOff = 0;
     uint32_t base[4] = {0, 0, 0, 0};  // where the streams start: steady fast, steady exact, last fast, last exact
+    // the quiet loop, behind everything else in the hole (the five other streams lie where they lay without it); quietOff = its
+    // cold entry, which steadyFastOff then names as well: waves start there.  0 = the program has none.
+    uint32_t quietBase = 0, quietOff = 0;
+    std::vector<uint32_t> quietCode;
+    std::string quietListing;          // when listings were asked for
+    QuietPlan quietPlan;
+    XlateStats quiet;
     uint32_t initOff = 0;   // run-once code (AsmArgs.initOff), 0 = none
     uint32_t ldsBytes = 0;  // dynamic LDS per workgroup
     uint32_t codeBytes = 0;
@@ -240,7 +270,7 @@ struct XlateImage {
 // a fingerprint of the code object (template and generated code): what a profile of a launch is a profile OF (bench.py ties the
 // committed hardware-counter passes to it; 63 bits)
 uint64_t imageHash(const XlateImage& image);
-// Lays the four streams out ([steady fast][steady exact][last fast][last exact]) and translates them; code[k] /
+// Lays the four streams out ([steady fast][last fast][steady exact][last exact][run-once][steady quiet]) and translates them; code[k] /
 // listing[k] in that order (listing may be nullptr); code[4] = the run-once code (LDS tables), empty when none.  Without a fast stream (non-finite uniform operand) the
 // fast offsets equal the exact ones.
 bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<MicroOp>& lastRecords, const XlateTemplate& tmpl,

@@ -154,6 +154,7 @@ bool buildXlateImage(const std::vector<MicroOp>& steadyRecords, const std::vecto
     out->elf.assign(tmpl.image, tmpl.image + tmpl.imageBytes);
     const uint32_t offs[5] = {out->base[0], out->base[1], out->base[2], out->base[3], out->initOff};
     for (int k = 0; k < 5; ++k) xl::placeCode(tmpl, &out->elf, offs[k], code[k]);
+    if (out->quietOff) xl::placeCode(tmpl, &out->elf, out->quietBase, out->quietCode);
     return true;
 }
 

@@ -96,7 +96,7 @@ inline Src imm32(uint32_t bits, bool forceLiteral = false) {
 
 // ---- instruction emitter -----------------------------------------------------------------------------------
 class Emitter {
-    static constexpr uint32_t DS_READ2_B32_OP = 0x37, VOP2_ADDC_OP = 0x1c;
+    static constexpr uint32_t DS_READ2_B32_OP = 0x37, VOP2_ADDC_OP = 0x1c, VOP3_MAX3_F32_OP = 0x1d3;
 
   public:
     Emitter(std::vector<uint32_t>* words, std::string* listing) : w_(*words), text_(listing) { tlsWantText = listing != nullptr; }
@@ -190,6 +190,14 @@ class Emitter {
         std::string t = std::string(name) + " " + vdst.text + ", " + ((neg & 1) ? "-" : "") + s0.text + ", " + ((neg & 2) ? "-" : "") + s1.text;
         if (s2) t += std::string(", ") + ((neg & 4) ? "-" : "") + s2->text;
         line(t);
+    }
+    // v_max3_f32 vdst, |s0|, |s1|, |s2| (VOP3A: the abs bits of all three sources)
+    void max3Abs(const Src& vdst, const Src& s0, const Src& s1, const Src& s2) {
+        tally("v_max3_f32");
+        w_.push_back(0xd0000000u | (VOP3_MAX3_F32_OP << 16) | 0x700u | (vdst.code & 0xffu));
+        w_.push_back(s0.code | (s1.code << 9) | (s2.code << 18));
+        ++count_;
+        if (text_) line("v_max3_f32 " + vdst.text + ", |" + s0.text + "|, |" + s1.text + "|, |" + s2.text + "|");
     }
     // VOPC in its VOP3 form, result to VCC, |src0| when abs0
     void vop3cmp(uint32_t op, const char* name, const Src& s0, bool abs0, const Src& s1) {
@@ -392,7 +400,7 @@ private:
         for (const char* f : fast)
             if (startsWith(name, f)) return 205;
         if (startsWith(name, "v_fma_f32")) return 240;
-        if (startsWith(name, "v_med3_f32") || startsWith(name, "v_max_f32") || startsWith(name, "v_min_f32")) return 260;
+        if (startsWith(name, "v_med3_f32") || startsWith(name, "v_max3_f32") || startsWith(name, "v_max_f32") || startsWith(name, "v_min_f32")) return 260;
         if (std::strstr(name, "f64")) return 425;
         return 395;
     }
@@ -470,6 +478,8 @@ constexpr int kSPrefetched = 94;                    // s94 = 1: the leading TRAM
 constexpr int kSEventNext = 28;                         // control tracks: the sample at which the next event of the block's list is due (0xFFFFFFFF: none left)
 constexpr int kSEventPtr = 26;                          // s[26:27]: address of that event's record (fx_xlate.hpp TrackEvent)
 constexpr int kKernargTracks = 0xb8;                    // AsmArgs.tracks (fx_asm.hpp)
+constexpr int kKernargQuietLeft = 0xc0;                 // AsmArgs.stages of an UNSTAGED launch: the quiet loop's exit words, one per wavefront (fx_xlate.hpp QuietPlan)
+constexpr int kSWave = 2;                               // s2 = wavefront of the launch
 constexpr int kSSliceShift = 8;                        // unstaged programs with time-sliced priorities: log2 of a slice in 100 MHz ticks (emitInit)
 constexpr int kSHoistOk = 95;                       // s95 = 1: this launch may issue leading TRAM reads one sample ahead (emitInit)
 constexpr int kVRing = 30;                          // staged programs: lane * 4 + the LDS buffer of this sample's packets (sent and requested, see stageRequest)

@@ -26,7 +26,7 @@ INFO = {
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
-    "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46,
+    "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -52,7 +52,7 @@ SYMBOLS = [
     "fxp_create", "fxp_destroy", "fxp_load_file", "fxp_load_text", "fxp_num_registers", "fxp_register_name",
     "fxp_register_type", "fxp_register_ioindex", "fxp_register_value", "fxp_num_instructions", "fxp_instruction",
     "fxp_itram_size", "fxp_xtram_size", "fxp_error_count", "fxp_error_desc", "fxp_error_row", "fxp_control_count",
-    "fxp_control_at", "fxp_meta_get", "fxp_ready", "fxp_lut", "fxp_lower", "fxp_lower_info", "fxp_translate", "fxp_track_register", "fxp_translate_staged", "fxp_code_hash", "fxp_last_error",
+    "fxp_control_at", "fxp_meta_get", "fxp_ready", "fxp_lut", "fxp_lower", "fxp_lower_info", "fxp_translate", "fxp_quiet_plan", "fxp_track_register", "fxp_translate_staged", "fxp_code_hash", "fxp_last_error",
 ]
 
 
@@ -128,6 +128,7 @@ def load():
     sig("fxp_lut", C.POINTER(C.c_double), i32, i32); sig("fxp_lower", i32, vp); sig("fxp_lower_info", i64, vp, i32)
     sig("fxp_last_error", cp, vp)
     sig("fxp_translate", i64, vp, i32, i32, vp, i64, C.c_char_p, i64)
+    sig("fxp_quiet_plan", i64, vp, i32, C.POINTER(C.c_int32), i64)
     sig("fxp_track_register", i32, vp, cp)
     sig("fxp_translate_staged", i64, vp, i32, i32, i32, i32, vp, i64, C.c_char_p, i64, C.POINTER(C.c_int), C.POINTER(C.c_int), i32)
     sig("fxp_code_hash", i64, vp, i32, i32, C.c_uint)
@@ -244,7 +245,8 @@ class FrontEnd(_Reports):
 
     def translate(self, vgprs=0, stream=0):
         """gfx950 machine code of the program as the batch path generates it: (code bytes, assembler listing).
-        stream: 0 steady fast, 1 steady exact, 2 last-sample fast, 3 last-sample exact."""
+        stream: 0 steady fast, 1 steady exact, 2 last-sample fast, 3 last-sample exact, 4 run-once code, 5 steady quiet
+        (empty when the program has no quiet loop: quiet_plan() says why)."""
         cap, tcap = 1 << 20, 1 << 23
         code = C.create_string_buffer(cap)
         text = C.create_string_buffer(tcap)
@@ -252,6 +254,26 @@ class FrontEnd(_Reports):
         if n < 0:
             raise RuntimeError("fxp_translate: %d %s" % (n, self.last_error()))
         return code.raw[:n], text.value.decode("ascii")
+
+    def quiet_plan(self, vgprs=0):
+        """the plan of the quiet loop (fxp_quiet_plan), read-only: in_force, eligible, why, the counts, checked = [(register-file
+        row, register name or None, bound)], dropped = record indices whose saturation the quiet loop omits, records = the
+        steady stream's records as an (R, 8) uint32 array (w0 handler slot, w2..w4 A / X / Y, w5 R, w6 / w7 flags or INTERP's 1 - X)"""
+        n = int(self._lib.fxp_quiet_plan(self._h, int(vgprs), None, 0))
+        if n < 0:
+            raise RuntimeError("fxp_quiet_plan: %d %s" % (n, self.last_error()))
+        buf = (C.c_int32 * n)()
+        self._lib.fxp_quiet_plan(self._h, int(vgprs), buf, n)
+        why = self.last_error()
+        w = np.frombuffer(buf, dtype=np.int32).copy()
+        c, d, r = int(w[6]), int(w[7]), int(w[8])
+        names = [self._lib.fxp_register_name(self._h, i).decode("latin-1") for i in range(self._lib.fxp_num_registers(self._h))]
+        rows = w[9: 9 + 3 * c].reshape(c, 3)
+        checked = [(int(a), names[b] if 0 <= b < len(names) else None, float(np.array([v], dtype=np.int32).view(np.float32)[0])) for a, b, v in rows]
+        at = 9 + 3 * c
+        return {"in_force": bool(w[0]), "eligible": bool(w[1]), "why": why, "sites": int(w[2]), "fast_dropped": int(w[3]), "quiet_dropped": int(w[4]),
+                "check_instructions": int(w[5]), "checked": checked, "dropped": [int(v) for v in w[at: at + d]],
+                "records": w[at + d: at + d + 8 * r].view(np.uint32).reshape(r, 8)}
 
     def translate_staged(self, stages, stage=0, stream=0, vgprs=0):
         """the program cut into at most `stages` pipeline stages (fx_xlate.hpp StageInfo): (code, listing, actual stages, info)

@@ -647,7 +647,7 @@ enum {
     FXB_INFO_XLATE_INLINED = 19,   /* records of the steady stream turned into straight-line code */
     FXB_INFO_XLATE_CALLED = 20,    /* records of the steady stream that call an interpreter handler */
     FXB_INFO_XLATE_UNSATURATED = 21,/* saturating instructions translated without a saturation (result provably in [-1, 1]) */
-    FXB_INFO_XLATE_VALU = 22,       /* translated program: vector-ALU instructions per wavefront and sample period (steady fast stream) */
+    FXB_INFO_XLATE_VALU = 22,       /* translated program: vector-ALU instructions per wavefront and sample period (the steady loop wavefronts start in) */
     FXB_INFO_XLATE_VALU_SLOW = 23,  /* ... those of the ~4-clock issue class (conversions, min/max/med3, compares, fp64, SGPR sources) */
     FXB_INFO_XLATE_VALU_CLOCKS = 24,/* ... modelled SIMD issue clocks of all of them per wavefront and sample period */
     FXB_INFO_XLATE_VGPR_CONSTANTS = 25, /* uniform constants the translated code keeps in spare VGPRs */
@@ -680,6 +680,10 @@ enum {
     FXB_INFO_BUS_SEND_BLOCKS = 43,     /* bus blocks that delivered sends (fxb_process_block_bus_aux* with an aux_out) since creation (summed over shards) */
     FXB_INFO_BUS_FEED_BLOCKS = 44,     /* bus blocks filled by feeds (fxb_process_block_bus_feed*) since creation (summed over shards) */
     FXB_INFO_INSTANCE_RINGS = 45,      /* bit 0: iTRAM, bit 1: xTRAM is a ring in which a record can be rotated (fxb_load_instances_rotated); 0 without delay lines */
+    FXB_INFO_XLATE_QUIET = 47,      /* 1 when the code in force has a quiet loop (fxp_translate stream 5): its wavefronts start there, and
+                                      FXB_INFO_XLATE_VALU / _VALU_SLOW / _VALU_CLOCKS / _UNSATURATED describe that loop */
+    FXB_INFO_XLATE_QUIET_LEFT = 48, /* wavefronts of the last launch that left the quiet loop - for the steady fast loop (a lane above its bound at
+                                      the head of a sample) or for the exact stream (a non-finite value); waits for that launch (summed over shards) */
     FXB_INFO_INSTANCE_ROTATIONS = 46   /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
@@ -732,6 +736,17 @@ int64_t fxp_lower_info(fxp_handle* h, int what);
  * cannot be translated, see fxp_last_error) and copies at most `cap` bytes of code and at most listing_cap-1
  * characters of the assembler listing (one instruction per line). */
 int64_t fxp_translate(fxp_handle* h, int vgprs, int stream, void* code, int64_t cap, char* listing, int64_t listing_cap);
+/* stream 5 = the steady QUIET loop of an unstaged program that has one (size 0 otherwise): the steady fast stream without the
+ * saturations that cannot fire while the rows checked at the head of each sample stay inside their bounds; wavefronts start
+ * there and leave for the steady fast loop when a lane fails the check (FXB_INFO_XLATE_QUIET, FXB_INFO_XLATE_QUIET_LEFT).
+ * fxp_quiet_plan describes it (read-only): int32 words
+ *   [0] a quiet loop is generated  [1] the program is eligible  [2] saturating records  [3] saturations the fast stream drops
+ *   [4] ... the quiet loop drops  [5] vector instructions of the head check  [6] C = checked rows  [7] D = dropped records
+ *   [8] R = records of the steady stream; then C x {register-file row, register index or -1, bound as float bits},
+ *   D record indices, R x 8 record words.
+ * Copies at most `cap` words, returns the number of words there are (negative FX_E_*); fxp_last_error says why a program has
+ * no quiet loop. */
+int64_t fxp_quiet_plan(fxp_handle* h, int vgprs, int32_t* out, int64_t cap);
 /* ... with `key` among the registers that can have a control track (fxb_set_register_track): the code fxp_translate then
  * returns is what a batch runs after a track has been armed for that register.  0 found, 1 not found, FX_E_ARG beyond 16. */
 int fxp_track_register(fxp_handle* h, const char* key);

@@ -496,13 +496,13 @@ def lint_index_mode(ins, entry_state=UNKNOWN, entries=None, kernel_labels=(), an
 # ------------------------------------------------------------------------------------------------- translated programs
 def image_listing(fe, vgprs=0):
     """The hole image of a translated program as ONE listing, laid out as fx_xlate.cpp planXlate does:
-    [steady fast][last fast][steady exact][last exact][run-once], each on a 64-byte boundary (s_nop filler).
+    [steady fast][last fast][steady exact][last exact][run-once][steady quiet], each on a 64-byte boundary (s_nop filler).
     Returns (listing, bytes): the encoder's byte count, which the re-assembled listing must reproduce."""
     parts, at = [], 0
-    for s in (0, 2, 1, 3, 4):
+    for s in (0, 2, 1, 3, 4, 5):
         code, listing = fe.translate(vgprs, s)
         if not code:
-            continue   # no fast streams (a non-finite uniform operand), no run-once code
+            continue   # no fast streams (a non-finite uniform operand), no run-once code, no quiet loop
         parts.append(listing.strip())
         at += len(code)
         pad = (-at) % 64
@@ -523,7 +523,9 @@ def stream_entries(ins):
             has_pred.add(k + 1)
     out = {}
     for k, i in enumerate(ins):
-        if k > 0 and ins[k - 1].mnem == "s_setpc_b64" and ins[k - 1].ops != ["s[34:35]"]:   # (s[34:35]: the way out, to the template's epilogue)
+        # (s[34:35]: the way out, to the template's epilogue; s[24:25]: the run-once code's way back to the template - what follows
+        # either in the image, filler or the quiet loop's head, is no return point of a call)
+        if k > 0 and ins[k - 1].mnem == "s_setpc_b64" and ins[k - 1].ops not in (["s[34:35]"], ["s[24:25]"]):
             out[i.addr] = UNKNOWN
         elif k not in has_pred:
             out[i.addr] = OFF
