@@ -81,6 +81,9 @@ Batch::~Batch() {
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
     if (evGain_) (void)hipEventDestroy(evGain_);
+    freeBlock(gainList_, false);
+    freeBlock(hGainList_, true);
+    if (evList_) (void)hipEventDestroy(evList_);
     (void)hipFree(tap_.cur);
     (void)hipFree(tap_.reserved);
     freeSideRows(tapRows_);
@@ -882,6 +885,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_INSTANCE_GATHERS) return instGathers_;
     if (what == FXB_INFO_INSTANCE_SCATTERS) return instScatters_;
     if (what == FXB_INFO_INSTANCE_ROTATIONS) return instRotations_;
+    if (what == FXB_INFO_GAIN_LIST_SETS) return gainListSets_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

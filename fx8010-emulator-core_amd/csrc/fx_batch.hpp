@@ -179,6 +179,22 @@ public:
     void busGetFeeds(int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap, int64_t firstInstance) const;
     int64_t busFeedSources() const { return feed_.sources; }
     int64_t busFeedEntries() const { return feed_.totalEntries; }
+    // Gain sets by list (fx_bus.hpp GainScatterArgs; include/fx8010_amd.h "Gain sets by list"; fx_batch_bus_gain_list.cpp): the
+    // moved entries of the bus gains, the send gains or the feed gains, scattered on the device behind evBus_ like the copy of
+    // busSetGains - no wait on the host for the queued blocks.  `list` holds `count` positions of THIS batch (instance numbers;
+    // local entry numbers of send_ / feed_), no two alike, `pos` the column of the caller's [channels][total] values each of them
+    // takes (null: entry k takes column k and total == count).  count == 0 with total > 0 is a shard that owns none of the entries:
+    // it launches nothing and still makes the handle-wide "none pending -> pending" transition.  The caller has checked everything
+    // (checkGainList, the modes) and has called busReserveGainList, the allocating half (device and pinned staging of
+    // count * (channels + 1) words, the event: FX_E_MEMORY changes nothing).  busSendLocalEntry / busFeedLocalEntry: the local
+    // number of a global entry of the structure in force, -1 when it belongs to another shard.
+    static int checkGainList(const int64_t* list, int64_t count, int64_t range, const float* gains, int channels, const char* what, std::string* why);
+    int busReserveGainList(int64_t count);
+    int busSetGainsList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* gains, int ramp);
+    int busSetSendGainsList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* gains, int ramp);
+    int busSetFeedGainsList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* gains, int ramp);
+    int64_t busSendLocalEntry(int64_t entry) const;
+    int64_t busFeedLocalEntry(int64_t entry) const;
     // Output meters (fx_meter.hpp; include/fx8010_amd.h "Output meters"): a mode of the handle.  While it is on every emulation
     // launch is followed, on its stream, by a meter launch over the block it wrote.  meterEnable allocates and zeroes (on) or frees
     // (off) the accumulator rows - the only device allocation of metering; on twice keeps the values.  meterRead is synchronous:
@@ -574,6 +590,26 @@ private:
     bool gainCopied_ = false;       // ... which may still be running
     int64_t busGainBlocks_ = 0;     // FXB_INFO_BUS_GAIN_BLOCKS
     size_t gainFloats() const { return (size_t)prog_.numChannels * (size_t)n_; }
+    // gain sets by list (fx_batch_bus_gain_list.cpp): one staging pair for the three calls - [count] positions, then
+    // [channels][count] values - grown on demand in the call (busReserveGainList), never inside a block, and reused: a set first
+    // waits on the HOST for the previous list set's scatter (evList_, listCopied_).  The bus gains' set is also in front of evGain_
+    // (runBus waits for it as for a full set); runBus waits for evList_ itself in front of a block with sends or feeds while a
+    // list set of theirs is outstanding (sideListCopied_).  sync() clears both flags.
+    struct GainListTarget {
+        uint32_t* block[2];               // the two device gain blocks, [channels][pitch] words each
+        size_t pitch;
+        RampPair* ramp;
+        std::vector<float>* mirror;       // the host copies gain[2] of a structure ([channels][mirrorPitch]); null: none (bus gains)
+        size_t mirrorPitch;
+        bool side;                        // sends / feeds: runBus waits for evList_
+        const char* name;
+    };
+    int setGainList(const GainListTarget& t, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* gains, int ramp);
+    Block<uint32_t> gainList_, hGainList_;
+    hipEvent_t evList_ = nullptr;        // behind the most recent list set
+    bool listCopied_ = false;            // ... which may still be running (the staging is in use)
+    bool sideListCopied_ = false;        // ... and was one of the send or feed gains
+    int64_t gainListSets_ = 0;           // FXB_INFO_GAIN_LIST_SETS
     // the pieces every mode of a bus block is made of (fx_batch_bus_side.cpp)
     int growBlock(void** p, size_t* cap, size_t want, size_t bytesEach, bool pinned, const char* name);
     void freeBlock(void** p, size_t* cap, bool pinned);

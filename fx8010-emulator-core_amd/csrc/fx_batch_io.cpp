@@ -639,6 +639,11 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         const hipError_t we = hipStreamWaitEvent(s, evGain_, 0);
         if (we != hipSuccess) return hipFail(we, "bus: waiting for the gains");
     }
+    // ... and a list set of the send or feed gains (fx_batch_bus_gain_list.cpp), where this block reads those
+    if ((aux || feed) && sideListCopied_) {
+        const hipError_t we = hipStreamWaitEvent(s, evList_, 0);
+        if (we != hipSuccess) return hipFail(we, "bus: waiting for the gains set by list");
+    }
     BusGainArgs gain{};
     if (weighted) {
         gain.target = dGain_[gainRamp_.target];
@@ -970,6 +975,7 @@ int Batch::sync() {
     if (e == hipSuccess && launched_) e = hipEventSynchronize(ev1_);
     if (e == hipSuccess && busLaunched_) e = hipEventSynchronize(evBus_);   // (the last kernel of a bus block on the caller's stream)
     if (e == hipSuccess && instLaunched_ && (e = hipEventSynchronize(evInst_)) == hipSuccess) instLaunched_ = false;
+    if (e == hipSuccess) listCopied_ = sideListCopied_ = false;   // (list sets run on the handle's stream, which has drained)
     return e == hipSuccess ? 0 : hipFail(e, "sync");
 }
 

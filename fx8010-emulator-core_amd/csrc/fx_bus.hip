@@ -611,6 +611,32 @@ void launchFeedVariant(const BusFeedArgs& a, dim3 grid, hipStream_t stream) {
     }
 }
 
+// ---- gain sets by list (fx_bus.hpp GainScatterArgs): the moved faders of a block, scattered into the gain blocks ------------------
+//
+// One wavefront per workgroup, one lane per list entry: grid.x = blocks of 64 entries.  A lane loads its position once, then per
+// channel one word of the staged values - consecutive lanes read consecutive words, 256 bytes per wavefront - and stores it at its
+// position in b, and in a where the set writes both.  The stores go wherever the list points; no two lanes share a word (the host
+// refuses a repeated index), so there is nothing to order.  Plain 32-bit loads and stores: no LDS, no atomics, no floating point.
+__global__ __launch_bounds__(64) void fx_gain_scatter(GainScatterArgs g) {
+    const long long k = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (k >= g.count) return;
+    const uint32_t i = g.idx[k];
+    if ((long long)i >= g.pitch) return;   // (never, behind the host's range check: a word outside the blocks is not written whatever the list holds)
+    const uint32_t* v = g.val + k;
+    uint32_t* b = g.b + i;
+    uint32_t* a = g.a ? g.a + i : nullptr;
+    for (int c = 0; c < g.channels; ++c) {
+        const uint32_t w = *v;
+        *b = w;
+        if (a) {
+            *a = w;
+            a += g.pitch;
+        }
+        v += g.count;
+        b += g.pitch;
+    }
+}
+
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
 }  // namespace
@@ -712,6 +738,15 @@ hipError_t launchBusFeed(const BusFeedArgs& a, hipStream_t stream) {
     (void)hipGetLastError();
     if (map) launchFeedVariant<true>(a, grid, stream);
     else launchFeedVariant<false>(a, grid, stream);
+    return hipGetLastError();
+}
+
+hipError_t launchGainScatter(const GainScatterArgs& a, hipStream_t stream) {
+    if (!a.idx || !a.val || !a.b || a.count < 1 || a.pitch < 1 || a.count > a.pitch || a.pitch >= ((long long)1 << 32) || a.channels < 1) return hipErrorInvalidValue;
+    const long long blocks = (a.count + 63) / 64;
+    if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_gain_scatter, dim3((unsigned)blocks), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

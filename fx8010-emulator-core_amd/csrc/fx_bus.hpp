@@ -129,4 +129,19 @@ struct BusFeedArgs {
 // for more; term_k = src[r][idx[e]] (unweighted), else (w == 0.0f ? +0.0f : w * src[r][idx[e]]) with w as in launchBusMixGain
 hipError_t launchBusFeed(const BusFeedArgs& a, hipStream_t stream);
 
+// A gain set by list (include/fx8010_amd.h "Gain sets by list"): `count` words per channel scattered into one or both of the two
+// gain blocks of the bus gains, the sends or the feeds.  Words move as 32-bit patterns.
+struct GainScatterArgs {
+    const uint32_t* idx;     // [count] positions in a channel row of the blocks, each below pitch and no two alike (device memory; the caller has checked them)
+    const uint32_t* val;     // [channels][count] the new words, row pitch exactly count (device memory)
+    uint32_t* b;             // [channels][pitch] the block that is b
+    uint32_t* a;             // the block that is a, written with the same words (ramp = 0 while a ramp is pending); null: b only
+    long long count;         // K >= 1
+    long long pitch;         // words per channel row of both blocks: n (bus gains), E of this batch (sends), the quad-padded pitch (feeds)
+    int channels;            // C
+};
+
+// b[c][idx[k]] = val[c][k] (and a likewise) for every c and k: one lane per list entry, loads of consecutive words, scattered stores
+hipError_t launchGainScatter(const GainScatterArgs& a, hipStream_t stream);
+
 }  // namespace fx

@@ -266,6 +266,15 @@ int fxb_bus_set_send_gains(fxb_handle* h, const float* gains, int ramp) { return
 int64_t fxb_bus_get_sends(fxb_handle* h, int64_t* n_aux, int64_t* offsets, int64_t off_cap, int64_t* members, float* gains, int64_t cap) {
     return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.busGetSends(n_aux, offsets, off_cap, members, gains, cap); }) : (int64_t)FX_E_ARG;
 }
+int fxb_bus_set_gains_list(fxb_handle* h, const int64_t* list, int64_t count, const float* gains, int ramp) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGainList(fx::Sharded::kGainList, list, count, gains, ramp); }) : FX_E_ARG;
+}
+int fxb_bus_set_send_gains_list(fxb_handle* h, const int64_t* entries, int64_t count, const float* gains, int ramp) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGainList(fx::Sharded::kSendGainList, entries, count, gains, ramp); }) : FX_E_ARG;
+}
+int fxb_bus_set_feed_gains_list(fxb_handle* h, const int64_t* entries, int64_t count, const float* gains, int ramp) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGainList(fx::Sharded::kFeedGainList, entries, count, gains, ramp); }) : FX_E_ARG;
+}
 int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busSetGains(gains, ramp); }) : FX_E_ARG; }
 int fxb_bus_get_gains(fxb_handle* h, float* gains) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.busGetGains(gains); }) : FX_E_ARG; }
 int fxb_process_block_imajor(fxb_handle* h, const float* in, float* out, int n, int64_t in_stride, int64_t out_stride) {

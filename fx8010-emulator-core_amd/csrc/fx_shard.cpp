@@ -556,6 +556,57 @@ int64_t Sharded::busGetFeeds(int64_t* nSrc, int64_t* offsets, int64_t offCap, in
     return front().busFeedEntries();
 }
 
+int Sharded::busSetGainList(GainListKind kind, const int64_t* list, int64_t count, const float* gains, int ramp) {
+    Serial serial(api_);
+    lastError_.clear();
+    static const char* const kNames[3] = {"bus gains by list", "bus send gains by list", "bus feed gains by list"};
+    const char* name = kNames[kind];
+    if (ramp != 0 && ramp != 1) { lastError_ = std::string(name) + ": ramp must be 0 or 1"; return FX_E_ARG; }
+    if (count < 0) { lastError_ = std::string(name) + ": count < 0"; return FX_E_ARG; }
+    int64_t range = 0;
+    if (kind == kGainList) {
+        if (!front().busGainsOn()) { lastError_ = "bus gains by list: gains are off (fxb_bus_set_gains)"; return FX_E_ARG; }
+        range = n_;
+    } else if (kind == kSendGainList) {
+        if (front().busSendBuses() < 1) { lastError_ = "bus send gains by list: sends are off (fxb_bus_set_sends)"; return FX_E_ARG; }
+        range = front().busSendEntries();
+    } else {
+        if (front().busFeedSources() < 1) { lastError_ = "bus feed gains by list: feeds are off (fxb_bus_set_feeds)"; return FX_E_ARG; }
+        range = front().busFeedEntries();
+    }
+    if (count == 0) return 0;
+    if (Batch::checkGainList(list, count, range, gains, front().channels(), name, &lastError_) != 0) return FX_E_ARG;
+    const auto set = [&](Batch& b, const int64_t* l, const int64_t* pos, int64_t mine) {
+        return kind == kGainList ? b.busSetGainsList(l, pos, mine, count, gains, ramp)
+             : kind == kSendGainList ? b.busSetSendGainsList(l, pos, mine, count, gains, ramp)
+                                     : b.busSetFeedGainsList(l, pos, mine, count, gains, ramp);
+    };
+    // (one shard: a global number is a local one - every bus and every list is its own, from entry 0 on)
+    if (shards_.size() == 1)
+        return runOn(0, [&](Batch& b) {
+            const int rc = b.busReserveGainList(count);
+            return rc != 0 ? rc : set(b, list, nullptr, count);
+        });
+    std::vector<ListPart> parts(shards_.size());
+    if (kind == kGainList) parts = splitList(list, count);
+    else
+        for (int64_t k = 0; k < count; ++k) {
+            size_t s = 0;
+            int64_t local = -1;
+            for (; s < shards_.size() && local < 0; ++s) local = kind == kSendGainList ? shards_[s]->batch->busSendLocalEntry(list[k]) : shards_[s]->batch->busFeedLocalEntry(list[k]);
+            if (local < 0) { lastError_ = std::string(name) + ": an entry that no shard holds"; return FX_E_ARG; }   // (host state only; never, behind the range check)
+            parts[s - 1].list.push_back(local);
+            parts[s - 1].pos.push_back(k);
+        }
+    // every shard reserves its staging first; only when all of them could does any shard's state change (staging that has grown
+    // stays: it is no state)
+    if (const int rc = fan([&](int k, Batch& b) { return b.busReserveGainList((int64_t)parts[(size_t)k].list.size()); })) return rc;
+    return fan([&](int k, Batch& b) {
+        const ListPart& part = parts[(size_t)k];
+        return set(b, part.list.data(), part.pos.data(), (int64_t)part.list.size());
+    });
+}
+
 int64_t Sharded::instructionCounter() {
     Serial serial(api_);
     std::vector<int64_t> part(shards_.size(), 0);
@@ -796,7 +847,7 @@ int64_t Sharded::info(int what) {
     std::vector<int64_t> part(shards_.size(), 0);
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
-        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS ||
+        what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
         what == FXB_INFO_XLATE_QUIET_LEFT) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

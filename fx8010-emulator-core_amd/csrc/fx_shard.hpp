@@ -107,6 +107,13 @@ public:
     int busSetFeeds(int64_t nSrc, const int64_t* offsets, const int64_t* sources, const float* gains);
     int busSetFeedGains(const float* gains, int ramp);
     int64_t busGetFeeds(int64_t* nSrc, int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap);
+    // gain sets by list (Batch::busSetGainsList ...): `list` holds GLOBAL instance numbers (bus gains) or GLOBAL entry numbers of the
+    // structure in force (sends, feeds), `gains` is [channels][count].  Everything is checked for the whole handle before any shard
+    // is posted (range, repeats, finiteness, the mode); each shard gets the entries that fall to it with local numbers and their
+    // columns of `gains`, reserves its staging first (FX_E_MEMORY changes nothing anywhere), and a shard without an entry still
+    // makes the handle-wide "none pending -> pending" transition.  count 0: nothing happens.
+    enum GainListKind { kGainList, kSendGainList, kFeedGainList };
+    int busSetGainList(GainListKind kind, const int64_t* list, int64_t count, const float* gains, int ramp);
     int prepare(int nSamples, bool wait);
 
     // state snapshot of the whole batch, laid out by global instance (fx_batch.hpp SnapshotHeader): an image saved from one

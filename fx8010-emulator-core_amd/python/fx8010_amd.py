@@ -26,7 +26,7 @@ INFO = {
     "xlate_code_bytes": 18, "xlate_inlined": 19, "xlate_called": 20, "xlate_unsaturated": 21, "xlate_valu": 22, "xlate_valu_slow": 23, "xlate_valu_clocks": 24, "xlate_vgpr_constants": 25, "xlate_builds": 26, "code_cache_hits": 27, "code_cached": 28, "xlate_background_builds": 29, "xlate_code_hash": 30, "stage_trials": 31, "control_rows": 32,
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
-    "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48,
+    "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -40,6 +40,7 @@ SYMBOLS = [
     "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
+    "fxb_bus_set_gains_list", "fxb_bus_set_send_gains_list", "fxb_bus_set_feed_gains_list",
     "fxb_bus_set_taps", "fxb_bus_get_taps", "fxb_process_block_bus_tap", "fxb_process_block_bus_tap_dev",
     "fxb_bus_set_sends", "fxb_bus_set_send_gains", "fxb_bus_get_sends", "fxb_process_block_bus_aux", "fxb_process_block_bus_aux_dev",
     "fxb_bus_set_feeds", "fxb_bus_set_feed_gains", "fxb_bus_get_feeds", "fxb_process_block_bus_feed", "fxb_process_block_bus_feed_dev",
@@ -100,6 +101,8 @@ def load():
     sig("fxb_bus_groups", i64, vp, i64); sig("fxb_process_block_bus", i32, vp, vp, vp, i32, i64, C.c_uint)
     sig("fxb_process_block_bus_dev", i32, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_bus_set_gains", i32, vp, vp, i32); sig("fxb_bus_get_gains", i32, vp, vp)
+    for name in ("fxb_bus_set_gains_list", "fxb_bus_set_send_gains_list", "fxb_bus_set_feed_gains_list"):
+        sig(name, i32, vp, vp, i64, vp, i32)
     sig("fxb_bus_set_taps", i32, vp, vp, i64); sig("fxb_bus_get_taps", i64, vp, vp, i64)
     sig("fxb_process_block_bus_tap", i32, vp, vp, vp, vp, i32, i64, C.c_uint); sig("fxb_process_block_bus_tap_dev", i32, vp, vp, vp, vp, i32, i64, C.c_uint, vp)
     sig("fxb_bus_set_sends", i32, vp, i64, vp, vp, vp); sig("fxb_bus_set_send_gains", i32, vp, vp, i32); sig("fxb_bus_get_sends", i64, vp, vp, vp, i64, vp, vp, i64)
@@ -626,6 +629,19 @@ class Batch(_Reports):
         assert g.size == self.channels * self.n, "gains must be [channels, N]"
         return self._check(self._lib.fxb_bus_set_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_gains")
 
+    def _set_gains_list(self, fn, what, indices, gains, ramp):
+        lst = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        assert g.size == self.channels * lst.size, "gains must be [channels, len(list)]"
+        return self._check(fn(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size), C.c_void_p(g.ctypes.data) if g.size else None, 1 if ramp else 0), what)
+
+    def bus_set_gains_list(self, instances, gains, ramp=False):
+        """The gains of the listed instances only (include/fx8010_amd.h "Gain sets by list"): instances are global instance numbers,
+        no two alike, gains float32 [channels, len(instances)], column k for instances[k].  ramp: the listed weights move over the
+        next block with mix_out (a ramp already pending keeps its start); without it they are in force at once, and a ramp that is
+        pending for the other instances stays pending.  Does not wait for queued blocks.  Raises while gains are off."""
+        return self._set_gains_list(self._lib.fxb_bus_set_gains_list, "bus_set_gains_list", instances, gains, ramp)
+
     def bus_get_gains(self):
         """float32 [channels, N]: the gains in force - while a ramp waits for its block the ones it will start from, after that
         block its target.  Synchronous; raises while gains are off."""
@@ -670,6 +686,12 @@ class Batch(_Reports):
         assert g.size == self.channels * E, "gains must be [channels, E]"
         return self._check(self._lib.fxb_bus_set_send_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_send_gains")
 
+    def bus_set_send_gains_list(self, entries, gains, ramp=False):
+        """The weights of the listed entries of the sends in force only: entries index the `members` array (what bus_get_sends
+        returns), no two alike, gains float32 [channels, len(entries)].  The rules of bus_set_gains_list; does not wait for queued
+        blocks, where bus_set_send_gains does."""
+        return self._set_gains_list(self._lib.fxb_bus_set_send_gains_list, "bus_set_send_gains_list", entries, gains, ramp)
+
     def bus_get_sends(self):
         """(offsets int64 [A + 1], members int64 [E], gains float32 [channels, E]) of the sends in force - the gains are a, as
         bus_get_gains returns them - or (array([0]), empty, empty) while sends are off"""
@@ -706,6 +728,12 @@ class Batch(_Reports):
         E = self._check(int(self._lib.fxb_bus_get_feeds(self._h, None, None, 0, None, None, 0)), "bus_get_feeds")
         assert g.size == self.channels * E, "gains must be [channels, E]"
         return self._check(self._lib.fxb_bus_set_feed_gains(self._h, C.c_void_p(g.ctypes.data), 1 if ramp else 0), "bus_set_feed_gains")
+
+    def bus_set_feed_gains_list(self, entries, gains, ramp=False):
+        """The weights of the listed entries of the feeds in force only: entries index the `sources` array (what bus_get_feeds
+        returns), no two alike, gains float32 [channels, len(entries)].  Unweighted feeds become weighted first, 1.0 everywhere.
+        The rules of bus_set_gains_list; does not wait for queued blocks, where bus_set_feed_gains does."""
+        return self._set_gains_list(self._lib.fxb_bus_set_feed_gains_list, "bus_set_feed_gains_list", entries, gains, ramp)
 
     def bus_get_feeds(self):
         """(n_src, offsets int64 [N + 1], sources int64 [E], gains float32 [channels, E]) of the feeds in force - the gains are a,

@@ -356,6 +356,46 @@ int fxb_process_block_bus_dev(fxb_handle* h, const float* d_in, float* d_out, in
  * FXB_INFO_BUS_GAIN_BLOCKS counts the bus blocks mixed with gains. */
 int fxb_bus_set_gains(fxb_handle* h, const float* gains, int ramp);
 int fxb_bus_get_gains(fxb_handle* h, float* gains);
+/* Gain sets by list: the faders that moved, and only those.  A mixer moves a few faders per block; the full sets above send every
+ * gain again - 4 * num_channels * N bytes over PCIe for the bus gains, and a wait for every queued block for the send and feed
+ * gains.  These three calls write the listed weights of the structure in force and leave all others alone: the list and the values
+ * go through pinned memory of the library (the arrays are the caller's again on return) and a small kernel scatters them on the
+ * device.  Nothing else changes: not what a block does with a, b and a pending ramp (w, t, r, the w == 0 mute, the summation
+ * orders, which block consumes the ramp), not what fxb_bus_get_gains / _sends / _feeds return (a, for listed and unlisted indices).
+ *
+ * The definition, in the terms of "Bus gains".  The structure - the bus gains, the weights of the sends, the weights of the feeds -
+ * holds a, b and the handle-wide flag PENDING.  `gains` is [num_channels][count] with a row pitch of exactly count; column k
+ * belongs to list[k] - a global instance number in 0..N-1 for the bus gains, a global entry index in 0..E-1 for the sends and the
+ * feeds (the index into the `members` / `sources` array the structure was set with, which is what fxb_bus_get_sends / _feeds
+ * return).  L is the set of listed indices.
+ *   ramp = 1, none pending   a := b everywhere (what "a counts as the old b" already means); b[i] := gains[k] for i in L; a ramp
+ *                            is now pending.
+ *   ramp = 1, one pending    b[i] := gains[k] for i in L; a stays everywhere.
+ *   ramp = 0                 a[i] := b[i] := gains[k] for i in L, and nothing else.  A pending ramp STAYS PENDING for the indices
+ *                            outside L; a listed index has a = b and so carries a constant weight through the ramp block.  This is
+ *                            the one place where a list set is not a full set restricted to L: a full set with ramp = 0 cancels
+ *                            the ramp.
+ *   Indices outside L keep their a and their b in every case.
+ * Feeds that are unweighted: the call makes them weighted first, with a = b = 1.0f everywhere (the rule of fxb_bus_set_feed_gains),
+ *   then applies the above; from then on the entries of an instance with F = 1 go through the multiply - the move of bit patterns
+ *   belongs to unweighted feeds only.
+ * count == 0 returns 0 and changes nothing (unweighted feeds stay unweighted).
+ * FX_E_ARG, with nothing launched and nothing changed: ramp not 0 or 1, count < 0, a null list or null gains with count > 0, an
+ *   index outside its range, a REPEATED index (two lanes would race for one word), a value that is not finite, and the mode being
+ *   off - bus gains off, sends off, feeds off: a list call does not switch a mode on, the full set does that.
+ * FX_E_MEMORY leaves everything as it was on every shard.  The staging - count * (num_channels + 1) words in device memory and as
+ *   many pinned - is grown on demand in the call, never inside a block, and freed with the handle.
+ * Ordering: that of fxb_bus_set_gains, for all three.  The call does not wait on the host for queued blocks; a block queued on
+ *   whatever stream keeps the weights it was queued with, a later block on whatever stream sees the new ones, fxb_sync covers all
+ *   of it.  A second list set behind the same running block does wait on the host for the first one's copy (the staging is
+ *   reused), as a second full gain set does.  The full fxb_bus_set_send_gains / _feed_gains keep their wait for everything queued,
+ *   which includes a list set still in flight.
+ * Sharded handles: every shard gets the entries that fall to it; a shard without one launches nothing and still follows the
+ *   handle-wide "none pending -> pending" step, so that fxb_bus_get_gains and the next ramp block see one state on all shards.
+ * FXB_INFO_GAIN_LIST_SETS counts the launches of the scatter kernel (fx_gain_scatter). */
+int fxb_bus_set_gains_list(fxb_handle* h, const int64_t* list, int64_t count, const float* gains, int ramp);
+int fxb_bus_set_send_gains_list(fxb_handle* h, const int64_t* entries, int64_t count, const float* gains, int ramp);
+int fxb_bus_set_feed_gains_list(fxb_handle* h, const int64_t* entries, int64_t count, const float* gains, int ramp);
 /* Bus taps: per-instance monitor outputs by list beside the mixed bus - solo, PFL, a recording of one voice, a look at the voice
  * whose meter went non-finite - without taking all N columns over PCIe.  Taps are a mode of the handle like the meters and the
  * gains, off by default: no flag bit is taken and no existing signature or behaviour changes.
@@ -684,7 +724,8 @@ enum {
                                       FXB_INFO_XLATE_VALU / _VALU_SLOW / _VALU_CLOCKS / _UNSATURATED describe that loop */
     FXB_INFO_XLATE_QUIET_LEFT = 48, /* wavefronts of the last launch that left the quiet loop - for the steady fast loop (a lane above its bound at
                                       the head of a sample) or for the exact stream (a non-finite value); waits for that launch (summed over shards) */
-    FXB_INFO_INSTANCE_ROTATIONS = 46   /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
+    FXB_INFO_INSTANCE_ROTATIONS = 46,  /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
+    FXB_INFO_GAIN_LIST_SETS = 49       /* launches of the kernel fx_gain_scatter - by fxb_bus_set_gains_list / _send_gains_list / _feed_gains_list - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -42,6 +42,13 @@ of 64 instances ([32][N / 64] in and out over PCIe; an expand and a mix kernel a
    moves 8 bytes per member where the sends move 12, is the yardstick in the same trace - and `--kernel-stats` then reports
    fx_bus_send_chunks and fx_bus_send_fold beside it.
 
+9. `--gains --gains-list K`: a fourth path beside "gains off / static / ramping": a list set of K faders with ramp = 1
+   (fxb_bus_set_gains_list) in front of every block, inside the timed region - the K faders are spread over the instances and
+   alternate between two levels.  It is what a mixer host pays that moves K faders where "ramping" re-sends all N.  With
+   `--trace-run --gains --gains-list K` the traced run is the four handles by turns; fx_gain_scatter then stands beside
+   fx_bus_mix_gain in the table.  `--sends A --send-gains-list K` is the same for the send gains: a third path, sends with a list
+   set of K entries (fxb_bus_set_send_gains_list, ramp = 1) in front of every block.
+
 Every path slides the control `decay` like the reference's harness does (realtime_capacity.py); before anything is timed the bus
 path's output is compared word for word with the summation order include/fx8010_amd.h fixes, applied to the plain path's output.
 
@@ -110,7 +117,7 @@ def send_all_model(y, w):
 class Path:
     """one handle and its pinned buffers; block(k) is one synchronous call on the caller's clock"""
 
-    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0, sends=0, feeds=0):
+    def __init__(self, A, progs, n, bus, meter=False, gains=None, taps=0, sends=0, feeds=0, gains_list=0, send_gains_list=0):
         import numpy as np
         self.A, self.n, self.bus, self.lib = A, n, bus, A.load()
         self.b = A.Batch(n, 1, 0)
@@ -126,13 +133,16 @@ class Path:
         self.yp = C.c_void_p(self.out.array.ctypes.data)
         if meter:
             self.b.meter_enable()
-        # gains: None = off, "static" = set once, "ramp" = a set with ramp = 1 in front of every block, between two sets of levels
+        # gains: None = off, "static" = set once, "ramp" = a set with ramp = 1 in front of every block, between two sets of levels,
+        # "list" = a list set of gains_list faders with ramp = 1 in front of every block, the faders between the same two levels
         self.gains = gains
         if gains:
             level = (0.25 + 0.75 * (progs.stimulus(n, 1, seed=99)[0] * np.float32(0.5) + np.float32(0.5))).astype(np.float32)
             self.levels = [np.ascontiguousarray(level.reshape(1, n)), np.ascontiguousarray((np.float32(1.25) - level).reshape(1, n))]
             self.lp = [C.c_void_p(g.ctypes.data) for g in self.levels]
             self.b.bus_set_gains(self.levels[0])
+            if gains == "list":
+                self.fader, self.fader_levels, self.fp = self.fader_list(n, gains_list, self.levels)
         # taps: T instances spread over the batch (the first and the last among them), delivered to a pinned [BLOCK][T] side
         self.taps, self.tap_list, self.tp = taps, None, None
         if taps:
@@ -151,6 +161,10 @@ class Path:
             self.b.bus_set_sends(np.arange(sends + 1, dtype=np.int64) * n, np.tile(np.arange(n, dtype=np.int64), sends), self.send_gains.reshape(1, -1))
             self.aux_out = A.HostBuffer((BLOCK, 1, sends))
             self.ap = C.c_void_p(self.aux_out.array.ctypes.data)
+            self.send_gains_list = send_gains_list
+            if send_gains_list:
+                flat = np.ascontiguousarray(self.send_gains.reshape(1, -1))
+                self.send_fader, self.send_fader_levels, self.sfp = self.fader_list(flat.shape[1], send_gains_list, [flat, np.ascontiguousarray(np.float32(1.25) - flat)])
         # feeds: the input block [BLOCK][G] is the source block.  1: the map n / GROUP, unweighted - the words of the shared input;
         # F >= 2: CSR, every instance hears F columns (its own group's first) with weights of its own
         self.feeds = feeds
@@ -168,12 +182,26 @@ class Path:
         self.k = 0
         self.times = []
 
+    @staticmethod
+    def fader_list(width, count, levels):
+        """`count` indices spread over 0..width-1, their columns of the two sets of levels, and the pointers of all three"""
+        import numpy as np
+        if not 0 < count <= width:
+            raise RuntimeError("a list of %d faders out of %d" % (count, width))
+        idx = np.ascontiguousarray((np.arange(count, dtype=np.int64) * width) // count)
+        vals = [np.ascontiguousarray(level[:, idx]) for level in levels]
+        return idx, vals, [C.c_void_p(idx.ctypes.data)] + [C.c_void_p(v.ctypes.data) for v in vals]
+
     def block(self):
         k, h = self.k, self.b._h
         if k % SLIDER_EVERY == 0:
             assert self.lib.fxb_set_register(h, b"decay", C.c_float(SLIDER[(k // SLIDER_EVERY) % len(SLIDER)])) == 0
         if self.gains == "ramp" and self.lib.fxb_bus_set_gains(h, self.lp[(k + 1) % 2], 1) != 0:
             raise RuntimeError("set_gains in front of block %d failed: %s" % (k, self.b.last_error()))
+        if self.gains == "list" and self.lib.fxb_bus_set_gains_list(h, self.fp[0], self.fader.size, self.fp[1 + (k + 1) % 2], 1) != 0:
+            raise RuntimeError("set_gains_list in front of block %d failed: %s" % (k, self.b.last_error()))
+        if self.sends and self.send_gains_list and self.lib.fxb_bus_set_send_gains_list(h, self.sfp[0], self.send_fader.size, self.sfp[1 + (k + 1) % 2], 1) != 0:
+            raise RuntimeError("set_send_gains_list in front of block %d failed: %s" % (k, self.b.last_error()))
         if self.feeds:
             rc = self.lib.fxb_process_block_bus_feed(h, self.xp[k % RING], self.yp, None, None, BLOCK, GROUP, 2)
         elif self.sends:
@@ -322,8 +350,13 @@ def meter_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: No
 GAIN_MODES = (("gains off", None), ("static", "static"), ("ramping", "ramp"))
 
 
-def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None):
-    """bus blocks with gains off, static gains and a ramp on every block by turns, in stretches, in one process"""
+def gain_modes(gains_list):
+    return GAIN_MODES + ((("list %d" % gains_list, "list"),) if gains_list else ())
+
+
+def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: None, gains_list=0):
+    """bus blocks with gains off, static gains and a ramp on every block by turns, in stretches, in one process; gains_list: and,
+    as a fourth path, a list set of that many faders with ramp = 1 on every block"""
     import numpy as np
     # gains of 1.0f give the words of gains off
     off, ones = Path(A, progs, n, True), Path(A, progs, n, True, gains="static")
@@ -337,7 +370,7 @@ def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: No
             raise RuntimeError("gains of 1.0f differ from gains off at %d instances" % n)
     off.close()
     ones.close()
-    paths = [(name, Path(A, progs, n, True, gains=mode)) for name, mode in GAIN_MODES]
+    paths = [(name, Path(A, progs, n, True, gains=mode, gains_list=gains_list)) for name, mode in gain_modes(gains_list)]
     clocks = {name: [] for name, _ in paths}
     for _, p in paths:
         p.stretch(warm, timed=False)
@@ -356,7 +389,7 @@ def gains_side_by_side(A, progs, n, blocks, warm, stretch, log, clock=lambda: No
     out = {"instances": n, "group": GROUP, "stretch_blocks": stretch}
     for name, p in paths:
         r = rt.percentiles(p.times)
-        r.update({"blocks": len(p.times), "bus_gain_blocks": p.b.info("bus_gain_blocks")})
+        r.update({"blocks": len(p.times), "bus_gain_blocks": p.b.info("bus_gain_blocks"), "gain_list_sets": p.b.info("gain_list_sets")})
         mhz = [c for c in clocks[name] if c]
         r["shader_clock_mhz_behind_a_stretch"] = round(sum(mhz) / len(mhz), 1) if mhz else None
         out[name] = r
@@ -415,8 +448,9 @@ def taps_side_by_side(A, progs, n, taps, blocks, warm, stretch, log, clock=lambd
     return out
 
 
-def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lambda: None):
-    """bus blocks without sends and with every instance on each of `sends` aux buses by turns, in stretches, in one process"""
+def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lambda: None, send_gains_list=0):
+    """bus blocks without sends and with every instance on each of `sends` aux buses by turns, in stretches, in one process;
+    send_gains_list: and, as a third path, the sends with a list set of that many send gains with ramp = 1 on every block"""
     import numpy as np
     # the aux words are the definition over the plain path's output, the mix is the one of the handle without sends
     plain, off, on = Path(A, progs, n, False), Path(A, progs, n, True), Path(A, progs, n, True, sends=sends)
@@ -429,6 +463,8 @@ def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lam
             raise RuntimeError("the mix of the handle with sends differs from the one without at %d instances" % n)
     plain.close()
     paths = [("no sends", off), ("%d sends" % sends, on)]
+    if send_gains_list:
+        paths.append(("list %d" % send_gains_list, Path(A, progs, n, True, sends=sends, send_gains_list=send_gains_list)))
     clocks = {name: [] for name, _ in paths}
     for _, p in paths:
         p.stretch(warm, timed=False)
@@ -458,8 +494,8 @@ def sends_side_by_side(A, progs, n, sends, blocks, warm, stretch, log, clock=lam
     out["outputs_equal"] = bool(same)
     out["median_difference_us"] = round(out["%d sends" % sends]["median_us"] - out["no sends"]["median_us"], 1)
     log("           N=%7d  mixes of the two %s; median with sends - median without: %+.1f us" % (n, "equal" if same else "DIFFER", out["median_difference_us"]))
-    off.close()
-    on.close()
+    for _, p in paths:
+        p.close()
     return out
 
 
@@ -588,6 +624,7 @@ def main():
     ap.add_argument("--meter-out", default="", help="keep the lines of --meter in this text file")
     ap.add_argument("--gains", action="store_true", help="bus blocks with gains off, static gains and a ramp on every block by turns (with --trace-run: the same three)")
     ap.add_argument("--gain-instances", default="131072,458752")
+    ap.add_argument("--gains-list", type=int, default=0, help="with --gains: a fourth path, a list set of this many faders with ramp = 1 in front of every block")
     ap.add_argument("--gains-out", default="", help="keep the lines of --gains in this text file")
     ap.add_argument("--taps", type=int, default=0, help="bus blocks untapped and with this many instances tapped by turns (with --trace-run: tapped, meters on)")
     ap.add_argument("--tap-instances", default="131072,458752")
@@ -595,6 +632,7 @@ def main():
     ap.add_argument("--sends", type=int, default=0, help="bus blocks without sends and with every instance on each of this many aux buses by turns "
                     "(with --trace-run --gains: one handle with static bus gains and the sends)")
     ap.add_argument("--send-instances", default="131072,458752")
+    ap.add_argument("--send-gains-list", type=int, default=0, help="with --sends: a third path, a list set of this many send gains with ramp = 1 in front of every block")
     ap.add_argument("--sends-out", default="", help="keep the lines of --sends in this text file")
     ap.add_argument("--feeds", type=int, default=0, help="bus blocks with the shared input and with feeds by turns: 1 = the map n / group, unweighted; F >= 2 = CSR with F "
                     "weighted entries per instance (with --trace-run: 200 blocks of a handle with the shared input, 200 of one with the map and, for F >= 2, 200 of the CSR one)")
@@ -631,7 +669,7 @@ def main():
                 json.dump({"feed_rows": rows}, fh, indent=1)
         return 0 if all(r["outputs_equal"] for r in rows) else 1
     if args.trace_run and args.sends:
-        p = Path(A, progs, args.trace_instances, True, gains="static" if args.gains else None, sends=args.sends)
+        p = Path(A, progs, args.trace_instances, True, gains="static" if args.gains else None, sends=args.sends, send_gains_list=args.send_gains_list)
         p.stretch(200, timed=False)
         p.close()
         return 0
@@ -644,7 +682,10 @@ def main():
         keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us, without sends and with "
              "every instance on each of %d aux buses delivered to a pinned side (fxb_process_block_bus_aux) by turns in stretches of %d blocks in one process, "
              "%d blocks per point after %d warm-up blocks; %s" % (GROUP, BUDGET_US, args.sends, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
-        rows = [sends_side_by_side(A, progs, int(v), args.sends, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.send_instances.split(",") if v]
+        if args.send_gains_list:
+            keep("and, as a third path, the sends with a list set of %d send gains with ramp = 1 (fxb_bus_set_send_gains_list) inside the timed region" % args.send_gains_list)
+        rows = [sends_side_by_side(A, progs, int(v), args.sends, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch), args.send_gains_list)
+                for v in args.send_instances.split(",") if v]
         if args.kernel_stats:
             keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances, sends=args.sends)))
         if args.sends_out:
@@ -655,7 +696,7 @@ def main():
                 json.dump({"send_rows": rows}, fh, indent=1)
         return 0 if all(r["outputs_equal"] for r in rows) else 1
     if args.trace_run and args.gains:
-        paths = [Path(A, progs, args.trace_instances, True, gains=mode) for _, mode in GAIN_MODES]
+        paths = [Path(A, progs, args.trace_instances, True, gains=mode, gains_list=args.gains_list) for _, mode in gain_modes(args.gains_list)]
         for _ in range(4):
             for p in paths:
                 p.stretch(50, timed=False)
@@ -671,7 +712,9 @@ def main():
         keep("32-sample bus blocks of config5 (shared input and mixed output per %d instances, pinned host buffers) against %.3f us: gains off, static "
              "gains, and a ramp on every block (fxb_bus_set_gains with ramp = 1 inside the timed region), by turns in stretches of %d blocks in one "
              "process, %d blocks per point after %d warm-up blocks; %s" % (GROUP, BUDGET_US, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
-        rows = [gains_side_by_side(A, progs, int(v), args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for v in args.gain_instances.split(",") if v]
+        if args.gains_list:
+            keep("and, as a fourth path, a list set of %d faders with ramp = 1 (fxb_bus_set_gains_list) in front of every block, inside the timed region" % args.gains_list)
+        rows = [gains_side_by_side(A, progs, int(v), args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch), args.gains_list) for v in args.gain_instances.split(",") if v]
         if args.kernel_stats:
             keep(json.dumps(kernel_shares(args.kernel_stats, args.trace_instances)))
         if args.gains_out:
