@@ -525,6 +525,9 @@ static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, i
         for (int i : q.dropped) w.push_back(i);
         for (const fx::MicroOp& r : steadyRecords)
             for (int k = 0; k < 8; ++k) w.push_back((int32_t)r.w[k]);
+        // ... and behind the records: the number of adds of +0 the quiet loop does not emit, then their record indices
+        w.push_back((int32_t)q.zeroAddsDropped.size());
+        for (int i : q.zeroAddsDropped) w.push_back(i);
         h->err = q.why;
         return 0;
     }

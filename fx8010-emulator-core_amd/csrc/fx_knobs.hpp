@@ -66,4 +66,10 @@ constexpr bool kDiagnosticsBuild = true;
 constexpr bool kDiagnosticsBuild = false;
 #endif
 
+// Translate-time switch of the quiet loop's frame (fx_xlate.cpp zeroAddsOf), for its A/B:
+// FX_XLATE_ZEROADD=0 emits every add of the uniform +0 again.  The loop computes the same words either way; like every diagnostic
+// knob it exists in the diagnostics build only - the release library has the part on.  Read at every translation (not cached: a
+// test translates one program under both settings).
+inline bool knobQuietZeroAdds() { return knobInt(FX_DIAG_KNOB("FX_XLATE_ZEROADD"), 1) != 0; }
+
 }  // namespace fx

@@ -1426,6 +1426,9 @@ class Translator {
         return withinUnitRule(family, kind, r, [this](uint32_t word, bool uniform) { return bound(word, uniform); });
     }
 
+    // the quiet loop: this record's add of the uniform +0 is one the plan found idle (zeroAddsOf)
+    bool zeroAddDropped() const { return quiet_ && index_ < quiet_->zeroAdd.size() && quiet_->zeroAdd[index_] != 0; }
+
     // a uniform operand's bit pattern; a NaN or Inf among them rules the fast stream out
     Src value(uint32_t bits) {
         if ((bits & 0x7f800000u) == 0x7f800000u) nonFinite_ = true;
@@ -1441,10 +1444,10 @@ class Translator {
     }
 
     // v2 -> saturate (NaN passes, FX8010.cpp:275-279) -> row R
-    void satStore(int vR) {
+    void satStore(int vR, int vFrom = 2) {   // (vFrom: fast streams only)
         Src m1 = imm32(0xbf800000u), p1 = imm32(0x3f800000u);
         if (fast_) {  // no NaN can be here (taint discipline): the median is the saturation
-            e_.vop3(VOP3_MED3_F32, "v_med3_f32", vreg(vR), vreg(2), m1, &p1);
+            e_.vop3(VOP3_MED3_F32, "v_med3_f32", vreg(vR), vreg(vFrom), m1, &p1);
             return;
         }
         e_.vopc(VOPC_CMP_U_F32, "v_cmp_u_f32_e32", vreg(2), 2);
@@ -1665,6 +1668,12 @@ class Translator {
             satStore(vR);
             return true;
         }
+        if (zeroAddDropped()) {   // 0 + X * 1.0 with an X that cannot be -0, saturation kept: the median reads row X itself
+            if (within || neg || !inV3 || pv == 3) return fail("internal: the plan drops an add this stream does not have");
+            ++stats_.zeroAddsDropped;
+            satStore(vR, pv);
+            return true;
+        }
         if (inV3) {
             Src a;
             if (!operand(r.w[2], kind & 1, &a)) return false;
@@ -1720,10 +1729,15 @@ class Translator {
             } else {
                 if (!operand(r.w[2], false, &a) || !row(r.w[3], &b)) return false;
             }
-            e_.vop2(VOP2_ADD_F32, "v_add_f32_e32", 2, a, b);
-            Src y;
-            if (!operand(r.w[4], uY, &y)) return false;
-            e_.vop2(VOP2_ADD_F32, "v_add_f32_e32", d, y, 2);
+            if (zeroAddDropped()) {   // (A + X) + 0 with an A + X that cannot be -0: the first sum is the result
+                e_.vop2(VOP2_ADD_F32, "v_add_f32_e32", d, a, b);
+                ++stats_.zeroAddsDropped;
+            } else {
+                e_.vop2(VOP2_ADD_F32, "v_add_f32_e32", 2, a, b);
+                Src y;
+                if (!operand(r.w[4], uY, &y)) return false;
+                e_.vop2(VOP2_ADD_F32, "v_add_f32_e32", d, y, 2);
+            }
         }
         if (within) ++stats_.unsaturated;
         else satStore(vR);
@@ -2641,6 +2655,64 @@ QuietPass quietPass(const std::vector<MicroOp>& records, const XlateProgram& pro
 }
 // vector instructions of the head check over n values: the first v_max3_f32 takes three, every further one two; one compare
 int checkCost(size_t n) { return n == 0 ? 0 : 1 + (n > 3 ? (int)((n - 3 + 1) / 2) : 0) + 1; }
+
+// Adds of the uniform +0 that cannot change a bit.  Every value of the fast and quiet streams is finite, and x + (+0) differs
+// from x in a bit only for x = -0 (which becomes +0).  So one pass over the steady records of an ELIGIBLE program (straight-line
+// code: no SKIP shadow writes a row for some lanes only) carries, per register-file row, "cannot be -0" ("clean").  At the head
+// of a sample no row is clean - PCM input, delay-line reads, state and control rows may hold any bit pattern - and the rows the
+// leading delay-line reads fill are never clean: the next sample's reads land in them in the middle of this one.  The rules
+// (fp32, round to nearest, denormals kept - the mode of every generated stream):
+//   * a sum is clean when one addend is: a + b is -0 only for (-0) + (-0) - an exact cancellation gives +0, and with denormals
+//     kept no other sum of finite values is a zero at all.  The same holds for a - b (-0 only for (-0) - (+0)) with a clean a;
+//   * a uniform is clean unless it is -0 itself - the uniform +0 in particular;
+//   * the saturation hands its operand on unchanged or returns +-1: clean stays clean, whether v_med3_f32 is emitted or the
+//     plan dropped it;
+//   * a product (-0 = 0 * negative), an INTERP result (its fp64 blend can be -0, and so its conversion) and a LIMIT / LIMITN
+//     pick are not clean; a copy is as clean as its source; a host-folded result is a uniform;
+//   * "R = 0 + X * c" emitted as fma(X, c, +0) (zeroPlusScaled) yields the very bits of the mul-then-add it replaces, whose sum
+//     with the uniform +0 is clean by the first two rules - the record is judged as the sum it is.
+// Returns, per record, 1 where the record's add of a uniform +0 has a clean other side: ACC3 (A + X) + 0 with a clean A + X,
+// and MACS 0 + X * (+1.0) - no multiplication is emitted for a unit multiplier, the "product" is row X itself - with a clean X
+// whose saturation stays (the median then reads the row; without one the add is the copy the record needs anyway).
+std::vector<uint8_t> zeroAddsOf(const std::vector<MicroOp>& records, const XlateProgram& prog, const std::vector<uint8_t>& dead,
+                                const std::vector<uint8_t>& idle) {
+    std::vector<uint8_t> out(records.size(), 0), clean(prog.wildRow.size(), 0), never(prog.wildRow.size(), 0);
+    for (const MicroOp& r : records) {
+        if (r.w[0] == AS_ENDSAMPLE) break;
+        if ((r.w[0] == AS_TRAM_IR || r.w[0] == AS_TRAM_XR) && r.w[5] < never.size()) never[r.w[5]] = 1;
+    }
+    never[0] = 1;   // (row 0 is the CCR)
+    auto C = [&](uint32_t word, bool uniform) { return uniform ? word != 0x80000000u : (word < clean.size() && clean[word] != 0); };
+    auto set = [&](uint32_t row, bool c) { if (row < clean.size()) clean[row] = c && !never[row]; };
+    for (size_t i = 0; i < records.size(); ++i) {
+        const MicroOp& r = records[i];
+        const uint32_t slot = r.w[0], dst = r.w[5];
+        if (slot == AS_ENDSAMPLE) break;
+        if ((int)i < prog.hoist.leadCount || slot == AS_NOP || slot == AS_TRAM_IW || slot == AS_TRAM_XW) continue;
+        if (slot == AS_MOV) { set(dst, C(r.w[2], r.w[6] & 1u)); continue; }
+        if (slot < AS_MACS || slot >= (uint32_t)kAsmSlots) { set(dst, false); continue; }   // LIMIT / LIMITN, anything else that writes a row
+        const uint32_t rel = slot - AS_MACS, family = rel / 16, kind = (rel % 16) / 2;
+        const bool uA = kind & 1, uX = kind & 2, uY = kind & 4;
+        if (kind == 7) { set(dst, r.w[2] != 0x80000000u); continue; }
+        if (dead[i]) continue;   // nothing is computed: the row keeps what it held
+        if (family == 0) {
+            const bool unitX = uX && !uY && r.w[3] == 0x3f800000u, unitY = uY && !uX && r.w[4] == 0x3f800000u;
+            const bool saturated = !(i < idle.size() && idle[i]);
+            if (uA && r.w[2] == 0u && (unitX || unitY) && saturated && C(unitX ? r.w[4] : r.w[3], false)) out[i] = 1;
+            // A + p: the folded product of two uniforms is a uniform (in the X word); any other product may be -0
+            set(dst, C(r.w[2], uA) || (uX && uY && r.w[3] != 0x80000000u));
+        } else if (family == 1) {
+            set(dst, C(r.w[2], uA));   // A - p
+        } else if (family == 2) {
+            const bool sum = (uA && uX) ? r.w[2] != 0x80000000u : (C(r.w[2], uA) || C(r.w[3], uX));   // (a folded A + X sits in the A word)
+            if (!(uA && uX) && uY && r.w[4] == 0u && sum) out[i] = 1;
+            set(dst, sum || C(r.w[4], uY));
+        } else {
+            set(dst, false);
+        }
+    }
+    return out;
+}
 }  // namespace
 
 QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog) {
@@ -2705,6 +2777,11 @@ QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgra
     plan.fastDropped = pass.idleByClassCount;
     plan.quietDropped = pass.idleCount;
     plan.checkInstructions = checkCost(tight) + checkCost(unit);
+    // (beside the plan proper: it neither counts as a gain nor changes what is checked)
+    plan.zeroAdd.assign(steadyRecords.size(), 0);
+    if (knobQuietZeroAdds()) plan.zeroAdd = zeroAddsOf(steadyRecords, prog, dead, pass.idle);
+    for (size_t i = 0; i < plan.zeroAdd.size(); ++i)
+        if (plan.zeroAdd[i]) plan.zeroAddsDropped.push_back((int)i);
     const int gain = plan.quietDropped - plan.fastDropped;
     // The loop's premise is a quiet SIGNAL.  A plan that gains nothing from a bound on the PCM input bounds state alone - its
     // program saturates where the input enters (config3: a = sat(in + rd * fb), and a drives every checked row), and at ordinary

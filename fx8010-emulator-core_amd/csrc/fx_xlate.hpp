@@ -170,6 +170,7 @@ struct XlateStats {
     int fusedZeroAdds = 0;    // "R = 0 + X * c", |c| > 0.5, emitted as one fma (bit-identical, see fx_xlate.cpp zeroPlusScaled)
     int deadResults = 0; // instructions whose result nothing reads (only their CCR, if anything, is computed)
     int unsaturated = 0; // saturating instructions whose result provably lies in [-1, 1]: no v_med3 in the fast stream
+    int zeroAddsDropped = 0;  // quiet loop: adds of the uniform +0 to a value that cannot be -0, not emitted (QuietPlan::zeroAdd)
     bool nonFiniteImmediate = false;  // a NaN / Inf among the uniform operands: no fast stream for this program
 };
 
@@ -192,6 +193,10 @@ struct QuietPlan {
     int fastDropped = 0;               // ... whose saturation the fast stream drops already
     int quietDropped = 0;              // ... and the quiet loop (= dropped.size())
     int checkInstructions = 0;         // vector instructions of the head check
+    // adds of the uniform +0 that cannot change a bit (fx_xlate.cpp zeroAddsOf): per steady record, 1 = the quiet loop does not
+    // emit that add; zeroAddsDropped = the indices of those records, ascending.  sites / dropped / checked know nothing of them.
+    std::vector<uint8_t> zeroAdd;
+    std::vector<int> zeroAddsDropped;
 };
 constexpr int kQuietMinGain = 32, kQuietGainPerCheck = 4;
 QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog);

@@ -261,7 +261,8 @@ class FrontEnd(_Reports):
     def quiet_plan(self, vgprs=0):
         """the plan of the quiet loop (fxp_quiet_plan), read-only: in_force, eligible, why, the counts, checked = [(register-file
         row, register name or None, bound)], dropped = record indices whose saturation the quiet loop omits, records = the
-        steady stream's records as an (R, 8) uint32 array (w0 handler slot, w2..w4 A / X / Y, w5 R, w6 / w7 flags or INTERP's 1 - X)"""
+        steady stream's records as an (R, 8) uint32 array (w0 handler slot, w2..w4 A / X / Y, w5 R, w6 / w7 flags or INTERP's 1 - X),
+        zero_adds_dropped = sorted record indices whose add of a uniform +0 the quiet loop does not emit"""
         n = int(self._lib.fxp_quiet_plan(self._h, int(vgprs), None, 0))
         if n < 0:
             raise RuntimeError("fxp_quiet_plan: %d %s" % (n, self.last_error()))
@@ -274,7 +275,8 @@ class FrontEnd(_Reports):
         rows = w[9: 9 + 3 * c].reshape(c, 3)
         checked = [(int(a), names[b] if 0 <= b < len(names) else None, float(np.array([v], dtype=np.int32).view(np.float32)[0])) for a, b, v in rows]
         at = 9 + 3 * c
-        return {"in_force": bool(w[0]), "eligible": bool(w[1]), "why": why, "sites": int(w[2]), "fast_dropped": int(w[3]), "quiet_dropped": int(w[4]),
+        z = at + d + 8 * r
+        return {"zero_adds_dropped": [int(v) for v in w[z + 1: z + 1 + int(w[z])]], "in_force": bool(w[0]), "eligible": bool(w[1]), "why": why, "sites": int(w[2]), "fast_dropped": int(w[3]), "quiet_dropped": int(w[4]),
                 "check_instructions": int(w[5]), "checked": checked, "dropped": [int(v) for v in w[at: at + d]],
                 "records": w[at + d: at + d + 8 * r].view(np.uint32).reshape(r, 8)}
 

@@ -784,7 +784,8 @@ int64_t fxp_translate(fxp_handle* h, int vgprs, int stream, void* code, int64_t 
  *   [0] a quiet loop is generated  [1] the program is eligible  [2] saturating records  [3] saturations the fast stream drops
  *   [4] ... the quiet loop drops  [5] vector instructions of the head check  [6] C = checked rows  [7] D = dropped records
  *   [8] R = records of the steady stream; then C x {register-file row, register index or -1, bound as float bits},
- *   D record indices, R x 8 record words.
+ *   D record indices, R x 8 record words; then Z and Z record indices: the records whose add of a uniform +0 the quiet loop
+ *   does not emit because the other side cannot be -0 (ascending; no part of the counts above).
  * Copies at most `cap` words, returns the number of words there are (negative FX_E_*); fxp_last_error says why a program has
  * no quiet loop. */
 int64_t fxp_quiet_plan(fxp_handle* h, int vgprs, int32_t* out, int64_t cap);
