@@ -2674,6 +2674,9 @@ int checkCost(size_t n) { return n == 0 ? 0 : 1 + (n > 3 ? (int)((n - 3 + 1) / 2
 // Returns, per record, 1 where the record's add of a uniform +0 has a clean other side: ACC3 (A + X) + 0 with a clean A + X,
 // and MACS 0 + X * (+1.0) - no multiplication is emitted for a unit multiplier, the "product" is row X itself - with a clean X
 // whose saturation stays (the median then reads the row; without one the add is the copy the record needs anyway).
+// The MACS form needs a clean row whose running bound is above 1: a sum, a host-folded record and a copy of either carry a bound
+// <= 1, and then quietPass has already found the saturation of 0 + X * 1.0 idle.  What is left is MACMV of a uniform above 1 in
+// magnitude (clean, wild, bound |c|) and copies of it: `macmv w, 4.0, 0, 0 ; macs q, 0, w, 1.0` (tests/quiet_programs.py zero_unit).
 std::vector<uint8_t> zeroAddsOf(const std::vector<MicroOp>& records, const XlateProgram& prog, const std::vector<uint8_t>& dead,
                                 const std::vector<uint8_t>& idle) {
     std::vector<uint8_t> out(records.size(), 0), clean(prog.wildRow.size(), 0), never(prog.wildRow.size(), 0);

@@ -7,8 +7,9 @@ bit on outputs, registers, instruction counters, cursors and delay memory.
 FXB_INFO_XLATE_QUIET_LEFT is predicted from the oracle, never from the code under test (Watch.block): a wavefront leaves when, at
 the head of a sample s in [0, S - 2] of a block of S samples, a lane of it holds |in[s]| above 1 (or not finite) or a checked row
 above its bound; the head value of a row that a leading delay-line read fills is what the oracle shows in that register AFTER
-sample s.  A wavefront that holds a row of the bounded class above 1 or not finite at launch never enters the loop and counts 0;
-so does every wavefront of a block of one sample."""
+sample s (a NaN there - written to the line in an earlier launch - counts as above the bound: test_gpu_zero_signs.py).  A
+wavefront that holds a row of the bounded class above 1 or not finite at launch never enters the loop and counts 0; so does
+every wavefront of a block of one sample."""
 import re
 
 import numpy as np
@@ -124,7 +125,7 @@ class Watch:
                                 any(abs(o.get_register(r)) > b for r, b in self.checked))
                 ref[i][s] = o.process_block(np.ascontiguousarray(x[s:s + 1, :, i]).reshape(1, self.ch) if self.ch > 1 else x[s:s + 1, 0, i].copy())
                 if head and not out:
-                    out = any(abs(o.get_register(r)) > b for r, b in self.reads)
+                    out = any(not abs(o.get_register(r)) <= b for r, b in self.reads)   # (a NaN that comes back out of a delay line leaves too)
                 if out:
                     leaves.add(self.wave[i])
         return ref, len(leaves)

@@ -13,7 +13,7 @@ import numpy as np
 
 import fx8010_programs as P
 
-from quiet_programs import DELAY_EDIT, GENERATED, GENERATED_WIDE, LIMIT_EDIT
+from quiet_programs import DELAY_EDIT, GENERATED, GENERATED_WIDE, LIMIT_EDIT, ZERO_ACC3, ZERO_C, ZERO_PROGRAMS, sweep_program
 from test_xlate import assemble, needs_llvm
 from test_xlate_quiet import ENDSAMPLE, MACS, SLOTS, TRAM_IR, TRAM_XR, f32, front_end, head_states, run_records
 
@@ -213,7 +213,8 @@ def stepped(records, rows, lead, probes):
     return seen
 
 
-def frame_soundness(name, text, cases=400):
+def frame_setup(name, text):
+    """(front end, plan, records, rows of the register file, wild rows, leading delay-line reads) of an eligible program"""
     fe = front_end(text)
     plan = fe.quiet_plan(0)
     assert plan["eligible"], name
@@ -227,6 +228,11 @@ def frame_soundness(name, text, cases=400):
     lead = 0
     while int(records[lead][0]) in (TRAM_IR, TRAM_XR):
         lead += 1
+    return fe, plan, records, n_rows, wild, lead
+
+
+def frame_soundness(name, text, cases=400):
+    fe, plan, records, n_rows, wild, lead = frame_setup(name, text)
     cand = candidates(records)
     dropped = plan["zero_adds_dropped"]
     assert set(dropped) <= set(cand), (name, "only adds of a uniform +0 are dropped")
@@ -271,3 +277,180 @@ def test_an_add_whose_sum_can_be_minus_zero_is_kept():
     clean = text.replace("acc3 c, in, in, 0", "macs c, 0, in, 0.5\nacc3 c, c, in, 0")
     assert len(front_end(clean).quiet_plan(0)["zero_adds_dropped"]) == 1
     assert frame_soundness("kept_add_clean", clean)[0] == 1
+
+
+# ------------------------------------------------------------------------------------------------ the directed family
+# adds of +0 the plan drops, per program: (ACC3 form (A + X) + 0, MACS form 0 + X * 1.0 under a kept saturation)
+ZERO_DROPS = {"zero_pool": (1, 0), "zero_state_read": (0, 0), "zero_sum_product": (2, 0), "zero_interp_limit": (0, 0), "zero_move_const": (0, 0),
+              "zero_acc3": (9, 0), "zero_minus": (0, 0), "zero_unit": (2, 2), "zero_delay": (2, 0)}
+# ... and of the corpus (the programs whose loop drops one run on the device at zero-rich states: test_gpu_zero_signs.py)
+CORPUS_DROPS = {"config5": 24, "gen0": 1, "gen3": 1, "gen5": 1, "gen6": 1, "gen10": 1, "wide3": 1, "gen0_limit": 1, "gen3_delay": 1, "gen2": 2, "gen4": 2,
+                "gen8": 1, "gen9": 1}
+
+
+def reg_file_base():
+    """the VGPR of register-file row 0, from the code's own constant"""
+    header = open(os.path.join(ROOT, "fx8010-emulator-core_amd", "csrc", "fx_xlate_emit.hpp")).read()
+    return int(re.search(r"constexpr int kRegFileBase = (\d+);", header).group(1))
+
+
+def forms(plan):
+    family = [(int(plan["records"][i][0]) - MACS) // 16 for i in plan["zero_adds_dropped"]]
+    assert set(family) <= {0, 2}
+    return family.count(2), family.count(0)
+
+
+def acc3_of_rows(records, a, x):
+    """indices of the records acc3 r, row a, row x, +0"""
+    return [i for i, w in enumerate(records) if MACS + 32 <= int(w[0]) < MACS + 48 and (int(w[0]) - MACS) % 16 // 2 == 4 and
+            (int(w[2]), int(w[3]), int(w[4])) == (a, x, 0)]
+
+
+def test_corpus_counts_of_dropped_adds_are_all_of_the_acc3_form():
+    for name, text in ALL_PROGRAMS:
+        plan = front_end(text).quiet_plan(0)
+        assert forms(plan) == (CORPUS_DROPS.get(name, 0), 0), name
+        assert plan["in_force"] or name in ("gen8", "gen9", "wide0", "wide2", "wide7", "wide8"), name
+
+
+def test_zero_programs_are_in_force_and_drop_what_is_pinned():
+    assert 8 <= len(ZERO_PROGRAMS) <= 12 and sorted(ZERO_DROPS) == sorted(n for n, _ in ZERO_PROGRAMS)
+    minus = 0
+    for name, text in ZERO_PROGRAMS:
+        fe = front_end(text)
+        plan = fe.quiet_plan(0)
+        assert plan["eligible"] and plan["in_force"], (name, plan["why"])
+        assert forms(plan) == ZERO_DROPS[name], (name, forms(plan))
+        assert fe.translate(0, 5)[0]
+        # what the fast loop has and the quiet loop has not is one add of a literal 0 per dropped record, nothing else of that kind
+        quiet, fast = loop_body(fe.translate(0, 5)[1]), loop_body(fe.translate(0, 0)[1])
+        assert zero_adds(fast) - zero_adds(quiet) == sum(ZERO_DROPS[name]), name
+        minus += any(MINUS_ZERO in (int(w[2]), int(w[3]), int(w[4])) for w in plan["records"] if MACS <= int(w[0]) < SLOTS or int(w[0]) in (4, 10, 11))
+    assert minus >= 2, "the literal -0 reaches the records as the uniform 0x80000000"
+
+
+def test_dropped_adds_never_see_minus_zero_zero_programs():
+    with_kept = 0
+    for name, text in ZERO_PROGRAMS:
+        dropped, kept_hit, kept = frame_soundness(name, text)
+        print(name, "adds of +0 dropped %d (ACC3 form %d, MACS form %d), kept %d (of which -0 seen in front: %d)" % ((dropped,) + ZERO_DROPS[name] + (len(kept), len(kept_hit))))
+        assert dropped == sum(ZERO_DROPS[name]), name
+        with_kept += bool(kept_hit)
+    assert with_kept >= 6, "most programs of the family have an add that must stay, and the model sees why"
+
+
+def test_zero_acc3_drops_exactly_the_adds_with_a_clean_side():
+    """the directed ACC3 records of zero_acc3, a0 .. a13 in program order: dropped where A or X is a sum, a non-zero uniform, a
+    folded move (in + the folded product +0: a sum) or a constant record; kept - with -0 seen in front - for (in, in), a product
+    over a row that may be -0, an INTERP result, a LIMIT pick and the leading delay-line read rows beside the input or each other"""
+    name, text = "zero_acc3", dict(ZERO_PROGRAMS)["zero_acc3"]
+    _, plan, records, _, _, _ = frame_setup(name, text)
+    cand = sorted(i for i in candidates(records) if (int(records[i][0]) - MACS) // 16 == 2)
+    directed = cand[-len(ZERO_ACC3):]
+    assert len(directed) == 14 and directed == list(range(directed[0], directed[0] + 14)), "a0 .. a13 are consecutive records"
+    dropped, kept_hit, kept = frame_soundness(name, text, 2000)
+    got = [k for k, i in enumerate(directed) if i in plan["zero_adds_dropped"]]
+    assert got == [1, 2, 3, 4, 8, 11, 12, 13], got
+    assert [k for k, i in enumerate(directed) if i in kept_hit] == [0, 5, 6, 7, 9, 10]
+    # (in, in): both addends the input row
+    in_row = [r for r, n, b in plan["checked"] if n == "in"][0]
+    assert acc3_of_rows(records, in_row, in_row) == [directed[0]] and directed[0] in kept_hit
+
+
+def pool_of(records):
+    """the multipliers of "R = 0 + X * c", |c| > 0.5 finite and not +-1, of the MACS family: the six most frequent, first seen first"""
+    count = {}
+    for w in records:
+        slot = int(w[0])
+        if slot == ENDSAMPLE:
+            break
+        if not MACS <= slot < MACS + 16:
+            continue
+        kind = (slot - MACS) // 2
+        if not kind & 1 or int(w[2]) != 0 or kind & 6 not in (2, 4):
+            continue
+        c = int(w[3] if kind & 6 == 2 else w[4])
+        if 0x3f000000 < c & 0x7fffffff < 0x7f800000 and c & 0x7fffffff != 0x3f800000:
+            count[c] = count.get(c, 0) + 1
+    order = sorted(count, key=lambda c: -count[c])    # (stable: ties stay in the order of first appearance)
+    return order[:6], order[6:]
+
+
+LITERAL = {0x3f000000: "0.5", 0x3f800000: "1.0", 0xbf800000: "-1.0", 0x40800000: "4.0", 0x40000000: "2.0", 0xbf000000: "-0.5", 0xc0000000: "-2.0", 0xc0800000: "-4.0"}
+
+
+def literal(c):
+    return LITERAL.get(c, "0x%08x" % c)
+
+
+def test_pooled_constants_are_fused_and_the_others_multiplied_and_added():
+    """zero_pool has more than six multipliers above 0.5 in magnitude: in streams 0 and 5 alike v_fma_f32 appears for exactly the
+    six that sit in s88 .. s93, the others are v_mul_f32 then v_add_f32 with a literal 0, and 0.5 and +-1.0 are never fused"""
+    text = dict(ZERO_PROGRAMS)["zero_pool"]
+    fe = front_end(text)
+    records = fe.quiet_plan(0)["records"]
+    pooled, others = pool_of(records)
+    f = lambda v: int(np.float32(v).view(np.uint32))   # noqa: E731
+    assert len(pooled) == 6 and others and set(pooled) | set(others) >= {f(v) for v in (0.50000006, 0.75, -0.6, 0.999, 1.5, 4.0, 0.7)}
+    base = reg_file_base()
+    in_reg = "v%d" % (base + 1)
+    for stream in (0, 5):
+        listing = fe.translate(0, stream)[1]
+        sgpr = {int(m.group(1)): int(m.group(2), 16) for m in re.finditer(r"^s_mov_b32 s(8[89]|9[0-3]), (0x[0-9a-f]+)$", listing, re.M)}
+        inline = {int(m.group(1)): int(np.float32(float(m.group(2))).view(np.uint32)) for m in re.finditer(r"^s_mov_b32 s(8[89]|9[0-3]), (-?\d\.\d)$", listing, re.M)}
+        sgpr.update(inline)
+        assert sorted(sgpr.values()) == sorted(pooled), (stream, sgpr, pooled)
+        body = loop_body(listing)
+        fused = set()
+        for l in body:
+            if l.startswith("v_fma_f32"):
+                m = re.match(r"v_fma_f32 v\d+, v\d+, s(\d+), 0$", l)
+                assert m, (stream, l)
+                fused.add(sgpr[int(m.group(1))])
+        assert fused == set(pooled), (stream, fused)
+        assert not fused & {f(0.5), f(1.0), f(-1.0)}
+        for c in others + [f(0.5), f(0.25), f(0.001)]:
+            at = [k for k, l in enumerate(body) if re.match(r"v_mul_f32_e32 v\d+, %s, %s$" % (re.escape(literal(c)), in_reg), l)]
+            assert at, (stream, literal(c), "the multiplication of the input by an unpooled constant")
+            product = lambda k: re.match(r"v_mul_f32_e32 (v\d+),", body[k]).group(1)   # noqa: E731
+            assert any(re.match(r"v_add_f32_e32 v\d+, 0, %s$" % product(k), body[k + 1]) for k in at), (stream, literal(c), [body[k:k + 2] for k in at])
+        # +-1.0 is never multiplied: 0 + in and 0 - in on the input's own row
+        assert any(re.match(r"v_add_f32_e32 v\d+, 0, %s$" % in_reg, l) for l in body) and any(re.match(r"v_sub_f32_e32 v\d+, 0, %s$" % in_reg, l) for l in body)
+        assert not any(re.match(r"v_mul_f32_e32 v\d+, -?1\.0, ", l) for l in body), stream
+
+
+def test_the_macs_form_is_emitted_and_its_median_reads_row_x():
+    """zero_unit: `macmv w0, 4.0` makes w0 a clean row OUTSIDE [-1, 1] - the copy of a uniform above 1 is the one way to such a row,
+    every sum, constant record and copy of those carries a running bound <= 1 and its 0 + X * 1.0 loses the saturation instead -
+    so `macs u0, 0, w0, 1.0` keeps its saturation and the plan drops its add: family 0 in zero_adds_dropped, the quiet loop's
+    v_med3_f32 reads row X itself where the fast loop adds the literal 0 into v2 first.  The same with the multiplier in X."""
+    text = dict(ZERO_PROGRAMS)["zero_unit"]
+    fe = front_end(text)
+    plan = fe.quiet_plan(0)
+    records = plan["records"]
+    marked = [i for i in plan["zero_adds_dropped"] if (int(records[i][0]) - MACS) // 16 == 0]
+    assert len(marked) == 2
+    base = reg_file_base()
+    quiet, fast = loop_body(fe.translate(0, 5)[1]), loop_body(fe.translate(0, 0)[1])
+    for i in marked:
+        w = records[i]
+        kind = (int(w[0]) - MACS) % 16 // 2
+        assert kind in (3, 5) and int(w[2]) == 0 and int(w[3] if kind == 3 else w[4]) == 0x3f800000 and i not in plan["dropped"]
+        x, r = base + int(w[4] if kind == 3 else w[3]), base + int(w[5])
+        assert "v_med3_f32 v%d, v%d, -1.0, 1.0" % (r, x) in quiet
+        assert "v_med3_f32 v%d, v%d, -1.0, 1.0" % (r, x) not in fast
+        k = fast.index("v_med3_f32 v%d, v2, -1.0, 1.0" % r)
+        assert fast[k - 1] == "v_add_f32_e32 v2, 0, v%d" % x
+    dropped, kept_hit, kept = frame_soundness("zero_unit", text, 2000)
+    assert dropped == 4
+
+
+def test_the_sweep_program_fuses_exactly_where_the_rule_says():
+    """macs r, 0, in, c of the denormal sweep: one v_fma_f32 each (c in either position) in the fast stream for |c| > 0.5 but +-1.0,
+    none otherwise - and never one in the exact stream"""
+    for c in ZERO_C:
+        fe = front_end(sweep_program(c))
+        fast, exact = ops_of(fe.translate(0, 0)[1]), ops_of(fe.translate(0, 1)[1])
+        fused = sum(l.startswith("v_fma_f32") for l in fast)
+        assert fused == (2 if abs(float(c)) > 0.5 and abs(float(c)) != 1.0 else 0), (c, fused)
+        assert not any(l.startswith("v_fma_f32") for l in exact), c
