@@ -18,9 +18,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "fx8010-emulator-core_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fx8010_programs as progs  # noqa: E402
-from pyoracle import Reference  # noqa: E402
+import multichannel_programs as mc  # noqa: E402
+from pyoracle import Oracle, Reference  # noqa: E402
 
 HDR = "static a\nstatic b\ninput in 0\noutput out 0\nstatic noise\nstatic rd\ncontrol vol = 0.5\n"
 
@@ -123,6 +125,11 @@ PARSER_CORPUS = [
     "static a\r\nend\r\n", "static a\n\tmacs\ta,\ta,\ta,\ta\nend", "static a_b9\nstatic _x\nmacs a_b9, _x, 0, 0\nend", "static a.b\nend",
     "static a\nmacs a, a.b, 0, 0\nend", "static a\nmacs a, -a, 0, 0\nend", "static a\nmacs a, 0, 0, 0 end",
 ]
+
+
+# the harness's slider schedule on two channels: both controls move, each input is heard through the other's channel as well
+STEREO_SLIDER = ("input l 0\ninput r 1\noutput ol 0\noutput or 1\ncontrol vol = 0.5\ncontrol pan = 0.25\nstatic t\n"
+                 "macs t, r, l, vol\nmacs ol, l, r, pan\nmacs or, t, vol, r\nmacs ol, ol, t, pan\nend")
 
 
 def main():
@@ -251,6 +258,30 @@ def main():
             c["sets_bits"] = {"0": [(r, PAY[r]) for r in who]}
             coll.append(c)
     out["nan_collisions.json"] = coll
+
+    # 6d. two to four channels (tests/multichannel_programs.py): the directed programs of the input-refresh rule, 16 generated
+    # programs that the restatement reports inside the parity domain, the slider schedule on a stereo program, and the loader's
+    # answer to an input index beyond the last channel.  96 samples, one stimulus stream per channel.
+    multi = []
+    for name, (ch, text, regs) in sorted(mc.DIRECTED.items()):
+        multi.append(run_case(name, text, mc.stimulus(progs, 1, 96, ch)[:, :, 0], regs=regs, channels=ch))
+    seed = 0
+    while sum(c["name"].startswith("generated") for c in multi) < 16:
+        ch, text, regs = mc.generated(seed)
+        x = mc.stimulus(progs, 1, 96, ch, seed=seed)[:, :, 0].copy()
+        o = Oracle(ch)
+        assert o.load_text(text)
+        o.process_block(x)
+        if o.ood_flags() == 0:
+            multi.append(run_case("generated%d" % seed, text, x, regs=regs, channels=ch))
+        seed += 1
+    sets = {0: [("vol", 0.1), ("pan", 0.75)], 24: [("vol", 0.25)], 48: [("vol", 0.5), ("pan", -0.5)], 72: [("vol", 1.0)]}
+    multi.append(run_case("slider_stereo", STEREO_SLIDER, mc.stimulus(progs, 1, 96, 2, seed=77)[:, :, 0], channels=2, sets=sets,
+                          regs=("vol", "pan", "l", "r", "t", "ol", "or", "ccr")))
+    for ch in (2, 4):
+        multi.append(run_case("input_index_beyond_%d_channels" % ch, "input a 0\ninput b %d\noutput o 0\nmacs o, a, b, 0.5\nend" % ch,
+                              np.zeros((4, ch), np.float32), channels=ch))
+    out["multichannel.json"] = multi
 
     # 7. loader corpus
     corpus = []

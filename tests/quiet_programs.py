@@ -49,16 +49,19 @@ def generated(seed):
 GENERATED = [("gen%d" % s, generated(s)) for s in range(12)]
 
 
-def generated_wide(seed):
+def generated_wide(seed, channels=None):
     """generated() and what else a quiet plan admits: LIMIT / LIMITN with rows and constants in every operand position (the PCM
     input as X or Y among them), folded moves (macs r, x, 0, 0), fully constant records, both delay lines with leading reads whose
-    rows nothing writes again - and, for every third seed, two channels (two input and two output rows)."""
+    rows nothing writes again - and, for every third seed, two channels (two input and two output rows).  `channels` asks for
+    that many (in0 .. / out0 ..: every input in every operand position, so under the A of any channel) instead."""
     rng = np.random.default_rng(515100 + seed)
     stereo = seed % 3 == 1
     n_regs, n_instr = int(rng.integers(4, 20)), int(rng.integers(120, 320))
     regs = ["r%d" % i for i in range(n_regs)]
     ins = ["inl", "inr"] if stereo else ["in"]
     outs = ["outl", "outr"] if stereo else ["out"]
+    if channels is not None:
+        ins, outs = ["in%d" % c for c in range(channels)], ["out%d" % c for c in range(channels)]
     coef = ["0.3", "0.5", "-0.25", "0.125", "0.7", "-0.6", "0.05", "k", "0.999", "1.0", "0"]
     lines = ["input %s %d" % (n, i) for i, n in enumerate(ins)] + ["output %s %d" % (n, i) for i, n in enumerate(outs)]
     lines += ["control k = 0.4"] + ["static %s" % r for r in regs]

@@ -53,12 +53,36 @@ def run_oracle(case, text=None):
     return o
 
 
-@pytest.mark.parametrize("fixture", ["opcodes.json", "known_answers.json", "slider.json", "feedback_delay.json", "nonfinite.json", "nan_collisions.json"])
+@pytest.mark.parametrize("fixture", ["opcodes.json", "known_answers.json", "slider.json", "feedback_delay.json", "nonfinite.json", "nan_collisions.json",
+                                     "multichannel.json"])
 def test_oracle_matches_reference_vectors(fixture):
     for case in load(fixture):
         o = run_oracle(case)
         if case["name"] != "skip_over_end":
             assert o.ood_flags() == 0, case["name"]
+
+
+def test_multichannel_fixture_holds_what_it_is_for():
+    """multichannel.json (guards the fixture generator): every directed program of tests/multichannel_programs.py with the text
+    the device tests run, 16 generated programs, all of 2 .. 4 channels; in sparse4 the channels nothing writes are +0 words; the
+    SKIPs of the shadow programs fire in some samples and not in others; both loader cases fail on the input index"""
+    import multichannel_programs as mc
+    cases = {c["name"]: c for c in load("multichannel.json")}
+    for name, (ch, text, regs) in mc.DIRECTED.items():
+        assert cases[name]["program"] == text and cases[name]["channels"] == ch and sorted(cases[name]["registers"]) == sorted(regs), name
+        assert cases[name]["shape"] == [96, ch]
+    gen = [c for n, c in cases.items() if n.startswith("generated")]
+    assert len(gen) == 16 and {c["channels"] for c in gen} == {2, 3, 4}
+    for c in gen:
+        assert (c["channels"], c["program"]) == mc.generated(int(c["name"][9:]))[:2], c["name"]
+    y = f32(cases["sparse4"]["output"], (96, 4)).view(np.uint32)
+    assert not y[:, (0, 2)].any() and y[:, 1].any() and y[:, 3].any()
+    for name, records, shadow in (("shadow_only", 8, 2), ("delay_into_input", 9, 1), ("stale_register", 8, 1), ("two_outputs_one_channel", 7, 1)):
+        fired = (96 * records - cases[name]["counter"]) // shadow   # (a skipped record is not counted)
+        assert 96 * records - cases[name]["counter"] == fired * shadow and 20 <= fired <= 76, (name, fired)
+    for ch in (2, 4):
+        c = cases["input_index_beyond_%d_channels" % ch]
+        assert not c["load_ok"] and c["channels"] == ch and len(c["errors"]) > 1
 
 
 def test_known_answers_are_the_surveyed_bits():
