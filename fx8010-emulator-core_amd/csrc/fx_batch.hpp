@@ -19,6 +19,7 @@
 #include "fx_bus.hpp"
 #include "fx_imajor.hpp"
 #include "fx_instances.hpp"
+#include "fx_registers.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -262,6 +263,24 @@ public:
     // what the host knows about the registers follows a load of these `total` records (of all shards: every shard ends up with
     // the same rows): a register with a value other than hostValue_ in any record becomes per-instance, as after setRegisterAt
     void promoteLoaded(const uint32_t* buf, int64_t total);
+    // Register calls by list (fx_registers.hpp; include/fx8010_amd.h "Register sets by list"; fx_batch_registers.cpp).  `regs` holds
+    // nKeys register numbers of the program (resolveRegisters), `list` holds `count` instance numbers of THIS batch, `pos` the column
+    // of the caller's [nKeys][total] values each of them has (null: entry i has column i and total == count).  The caller has checked
+    // everything (checkRegisterList) and, for a set, has called reserveRegisterList - the allocating half (device and pinned staging,
+    // the event: FX_E_MEMORY changes nothing).  count == 0 is a shard that owns none of the entries: nothing is launched and nothing
+    // changes.  setRegistersList leaves the batch as count * nKeys calls of setRegisterAt would, without their wait: the words are
+    // scattered on the handle's stream behind every block queued so far on whatever stream (ev1_, evBus_) and in front of evInst_,
+    // the event of the instance calls - every later block, state access and sync is ordered behind it as behind a copy of
+    // instances.  getRegistersList is synchronous and equals getRegisterAt word for word: a register that lives on the host only is
+    // answered from hostValue_, the others by one gather.
+    bool stateReady() const { return dState_ != nullptr; }
+    int resolveRegisters(const char* const* keys, int nKeys, std::vector<int>* regs);   // 0, or 1 and lastError names the key
+    // the refusals that read nothing but the arguments (Sharded asks for the whole handle): every instance in 0..n-1 and, unique
+    // (a set), no instance and no register twice
+    static int checkRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const void* values, bool unique, std::string* why);
+    int reserveRegisterList(int nKeys, int64_t count);
+    int setRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* values);
+    int getRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, float* values);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -693,6 +712,13 @@ private:
     bool instLaunched_ = false;          // ... which may still be running
     int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS
     int64_t instRotations_ = 0;                    // FXB_INFO_INSTANCE_ROTATIONS
+    // register calls by list (fx_batch_registers.cpp): one staging pair of 32-bit words, [count] instance numbers (64-bit), then
+    // [nKeys][count] values, then [nKeys] rows - grown by reserveRegisterList and reused: a call first waits on the HOST for the
+    // previous instance call or list set (evInst_, instLaunched_)
+    Block<uint32_t> regList_, hRegList_;
+    static size_t regListWords(int nKeys, int64_t count) { return (size_t)count * 2 + (size_t)nKeys * (size_t)count + (size_t)nKeys; }
+    int stageRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, RegListArgs* a);
+    int64_t regListSets_ = 0, regListGets_ = 0;    // FXB_INFO_REGISTER_LIST_SETS / _GETS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

@@ -307,6 +307,12 @@ int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const 
 int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.loadInstancesRotated(list, count, buf, bytes); }) : FX_E_ARG;
 }
+int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.setRegistersList(keys, n_keys, list, count, values); }) : FX_E_ARG;
+}
+int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.getRegistersList(keys, n_keys, list, count, values); }) : FX_E_ARG;
+}
 int fxb_get_tram_i(fxb_handle* h, int which, int64_t inst, float* out, int n_slots) {
     return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.getTramAt(which, inst, out, n_slots); }) : FX_E_ARG;
 }

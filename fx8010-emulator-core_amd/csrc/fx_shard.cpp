@@ -817,6 +817,31 @@ int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, in
     });
 }
 
+int Sharded::registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* name = set ? "set_registers_list" : "get_registers_list";
+    if (nKeys < 0 || count < 0) { lastError_ = std::string(name) + ": a negative n_keys or count"; return FX_E_ARG; }
+    if (nKeys > 0 && !keys) { lastError_ = std::string(name) + ": null keys"; return FX_E_ARG; }
+    if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
+    // (the program is replicated: the front shard's register numbers are every shard's)
+    std::vector<int> regs;
+    if (const int rc = front().resolveRegisters(keys, nKeys, &regs)) { lastError_ = front().lastError(); return rc; }
+    if (count == 0 || nKeys == 0) return 0;
+    const void* values = set ? static_cast<const void*>(in) : static_cast<const void*>(out);
+    if (Batch::checkRegisterList(regs, list, count, n_, values, set, &lastError_) != 0) return FX_E_ARG;
+    const bool one = shards_.size() == 1;
+    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    if (!set) return fan([&](int k, Batch& b) { return b.getRegistersList(regs, listOf(k), posOf(k), countOf(k), count, out); });
+    // every shard reserves its staging first; only when all of them could is anything queued or noted anywhere (staging that has
+    // grown stays: it is no state)
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveRegisterList(nKeys, countOf(k)); })) return rc;
+    return fan([&](int k, Batch& b) { return b.setRegistersList(regs, listOf(k), posOf(k), countOf(k), count, in); });
+}
+
 int Sharded::getTramAt(int which, int64_t inst, float* out, int nSlots) {
     Serial serial(api_);
     lastError_.clear();
@@ -848,6 +873,7 @@ int64_t Sharded::info(int what) {
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
         what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
+        what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS ||
         what == FXB_INFO_XLATE_QUIET_LEFT) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

@@ -133,6 +133,16 @@ public:
     // ... with the delay memory of every record rotated to its destination's positions (Batch::recordRotations); a program that
     // executes no delay-line instruction or has no delay memory goes the way of loadInstances
     int loadInstancesRotated(const int64_t* list, int64_t count, const void* buf, int64_t bytes) { return loadRecords(list, count, buf, bytes, true); }
+    // register calls by list (Batch "Register calls by list"): `list` holds GLOBAL instance numbers, `values` is [nKeys][count].
+    // The keys are resolved and everything is checked for the whole handle before any shard is posted; each shard gets the
+    // entries that fall to it with local numbers and their columns of `values` and, for a set, reserves its staging first
+    // (FX_E_MEMORY changes nothing anywhere).  A shard without an entry launches nothing and changes nothing.
+    int setRegistersList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* values) {
+        return registersList(true, keys, nKeys, list, count, values, nullptr);
+    }
+    int getRegistersList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, float* values) {
+        return registersList(false, keys, nKeys, list, count, nullptr, values);
+    }
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
 
@@ -146,6 +156,7 @@ public:
 
 private:
     int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
+    int registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out);
     struct Worker {
         std::unique_ptr<Batch> batch;
         int64_t first = 0, count = 0;

@@ -319,6 +319,24 @@ public:
         if (src.size() != dst.size()) throw std::runtime_error("FX8010Batch::copyInstances: lists of different length");
         if (fxb_copy_instances(h_, src.data(), dst.data(), (int64_t)src.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::copyInstances: ") + fxb_last_error(h_));
     }
+    // Registers by list (include/fx8010_amd.h "Register sets by list"): values[k * list.size() + i] is register keys[k] of instance
+    // list[i].  The set leaves the batch as one setRegisterValue per word would and is stream-ordered behind the queued blocks
+    // (sync() covers it); the get is synchronous.  Both throw when a key is no register.
+    void setRegistersList(const std::vector<std::string>& keys, const std::vector<int64_t>& list, const std::vector<float>& values) {
+        if (values.size() != keys.size() * list.size()) throw std::runtime_error("FX8010Batch::setRegistersList: values must hold keys x list words");
+        std::vector<const char*> names;
+        for (const std::string& k : keys) names.push_back(k.c_str());
+        if (fxb_set_registers_list(h_, names.data(), (int)names.size(), list.data(), (int64_t)list.size(), values.data()) != 0)
+            throw std::runtime_error(std::string("FX8010Batch::setRegistersList: ") + fxb_last_error(h_));
+    }
+    std::vector<float> getRegistersList(const std::vector<std::string>& keys, const std::vector<int64_t>& list) {
+        std::vector<const char*> names;
+        for (const std::string& k : keys) names.push_back(k.c_str());
+        std::vector<float> values(keys.size() * list.size());
+        if (fxb_get_registers_list(h_, names.data(), (int)names.size(), list.data(), (int64_t)list.size(), values.data()) != 0)
+            throw std::runtime_error(std::string("FX8010Batch::getRegistersList: ") + fxb_last_error(h_));
+        return values;
+    }
     void resetInstances(const std::vector<int64_t>& list) {
         if (fxb_reset_instances(h_, list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::resetInstances: ") + fxb_last_error(h_));
     }

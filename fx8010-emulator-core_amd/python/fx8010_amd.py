@@ -27,6 +27,7 @@ INFO = {
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
     "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
+    "register_list_sets": 50, "register_list_gets": 51,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -37,7 +38,7 @@ SYMBOLS = [
     "fx_instruction_counter", "fx_error_count", "fx_error_desc", "fx_error_row", "fx_control_count", "fx_control_at",
     "fx_meta_get", "fx_set_option", "fxb_set_option", "fxp_set_option", "fx_set_channels", "fx_get_channels", "fx_ready", "fx_last_error", "fx_last_create_error",
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
-    "fxb_get_register_i", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
+    "fxb_get_register_i", "fxb_set_registers_list", "fxb_get_registers_list", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_bus_set_gains_list", "fxb_bus_set_send_gains_list", "fxb_bus_set_feed_gains_list",
@@ -113,6 +114,7 @@ def load():
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
     sig("fxb_load_instances_rotated", i32, vp, vp, i64, vp, i64)
+    sig("fxb_set_registers_list", i32, vp, vp, i32, vp, i64, vp); sig("fxb_get_registers_list", i32, vp, vp, i32, vp, i64, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
@@ -411,6 +413,37 @@ class Batch(_Reports):
 
     def get_register_bits_i(self, key, inst):
         return int(np.float32(self.get_register_i(key, inst)).view(np.uint32))
+
+    @staticmethod
+    def _key_table(keys):
+        names = [keys] if isinstance(keys, (str, bytes)) else list(keys)
+        table = (C.c_char_p * max(len(names), 1))(*[k.encode() if isinstance(k, str) else k for k in names])
+        return table, len(names)
+
+    def set_registers_list(self, keys, instances, values):
+        """Registers `keys` of the listed instances only (include/fx8010_amd.h "Register sets by list"): instances are global
+        instance numbers, no two alike, values float32 [len(keys), len(instances)], row k for keys[k], as bit patterns.  Leaves the
+        handle as one set_register_i per word would; stream-ordered behind the queued blocks - it does not wait for them, sync()
+        covers it.  Returns 0, or 1 when a key is no register."""
+        table, n_keys = self._key_table(keys)
+        lst = self._instance_list(instances)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.size != n_keys * lst.size:
+            raise ValueError("set_registers_list: values must be [len(keys), len(instances)]")
+        return self._check(self._lib.fxb_set_registers_list(self._h, table, n_keys, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
+                                                            C.c_void_p(v.ctypes.data) if v.size else None), "set_registers_list")
+
+    def get_registers_list(self, keys, instances):
+        """float32 [len(keys), len(instances)]: what get_register_i returns for every (key, instance), bit for bit, with one
+        gather on the device.  Synchronous; repeats are allowed.  Raises KeyError when a key is no register."""
+        table, n_keys = self._key_table(keys)
+        lst = self._instance_list(instances)
+        out = np.zeros((n_keys, lst.size), dtype=np.float32)
+        rc = self._check(self._lib.fxb_get_registers_list(self._h, table, n_keys, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
+                                                          C.c_void_p(out.ctypes.data) if out.size else None), "get_registers_list")
+        if rc != 0:
+            raise KeyError(self.last_error())
+        return out
 
     def seed_noise_i(self, inst, x1, x2):
         return self._check(self._lib.fxb_seed_noise_i(self._h, inst, x1, x2), "seed_noise_i")

@@ -254,6 +254,38 @@ int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const 
  *   A program without delay lines, or one that executes no delay-line instruction, goes the way of fxb_load_instances; otherwise
  *   FXB_INFO_INSTANCE_ROTATIONS counts the launches and FXB_INFO_INSTANCE_SCATTERS does not.  Returns as fxb_load_instances. */
 int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes);
+/* Register sets by list: the parameters of the program itself - a cutoff, a decay, a pitch per voice - for the instances a host
+ * moves, scattered on the GPU behind the queued blocks.  fxb_set_register_i waits on the host for every queued block and copies
+ * four bytes; fxb_set_register_array moves all N values of a register.  These two move n_keys * count words with one launch.
+ *
+ * values[k * count + i] belongs to register keys[k] of global instance list[i]: the [key][entry] order, as the gain lists use
+ * [channel][entry].
+ * fxb_set_registers_list: afterwards the handle is in exactly the state that n_keys * count calls of
+ *   fxb_set_register_i(h, keys[k], list[i], values[k * count + i]) would have left - the words on the device, what the library
+ *   knows about the registers, what every get call then returns.  Values are 32-bit patterns: NaN payloads, -0 and denormals
+ *   arrive as given and nothing is checked for finiteness (fxb_set_register_i checks nothing either).
+ *   Ordering: the call is STREAM-ORDERED.  It runs behind every block queued on the handle so far, on whichever stream - such a
+ *   block keeps the values it was queued with - and in front of every block queued later, on whichever stream.  It may return
+ *   before it has run; fxb_sync covers it, and so does every call that waits for the queued blocks: fxb_set_register, _i, _array,
+ *   the get calls, fxb_save_state, the calls by instance list.  The caller's arrays are free on return.  A second list set behind
+ *   the same running block does wait on the host for the first one's scatter (the staging is reused).
+ *   Code: as with fxb_set_register_i, the FIRST per-instance write to a register whose value the code in force has folded in asks
+ *   for other code, which the next block generates (or finds cached); every later write to that register is a plain scatter.  A
+ *   real-time host therefore makes its first list set of every register it will move BEFORE fxb_prepare.
+ * fxb_get_registers_list: values[k * count + i] = what fxb_get_register_i(h, keys[k], list[i]) returns, bit for bit.  Synchronous
+ *   (it waits for everything queued, a list set included).  A register whose value the library holds once for all instances is
+ *   answered without a launch.  Repeated instances and repeated keys are allowed.
+ * Returns 0 - also for count == 0 or n_keys == 0, once the keys have been looked up - or, with nothing launched and nothing
+ *   changed: FX_E_ARG for a negative count or n_keys, a null keys / list / values with something to do, an instance outside
+ *   0..N-1, n_keys * count >= 2^31 and, for the set only, an instance listed twice or two keys that name one register (the order
+ *   of two scattered words is undefined); FX_E_NOTREADY without a program; 1 for a key that is no register (fxb_last_error names
+ *   it); FX_E_MEMORY when the staging - 2 * count + n_keys * (count + 1) words in device memory and as many pinned, grown on
+ *   demand in the call, never inside a block, freed with the handle - could not be allocated, on any shard.
+ * Sharded handles: every shard gets the entries that fall to it with their columns of `values`; a shard without one launches
+ *   nothing and changes nothing, as with fxb_set_register_i.
+ * FXB_INFO_REGISTER_LIST_SETS / _GETS count the launches of the two kernels (fx_reg_scatter, fx_reg_gather). */
+int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values);
+int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values);
 /* one instance's delay memory as the reference holds it (which: 0 = smallDelayBuffer / iTRAM, 1 = largeDelayBuffer / xTRAM; the first
  * n_slots words; words the program cannot reach read 0) and its positions {iTRAM write, iTRAM read, xTRAM write, xTRAM read}
  * (reference smallDelayWritePos ... largeDelayReadPos, include/FX8010.h:214-217) */
@@ -725,7 +757,9 @@ enum {
     FXB_INFO_XLATE_QUIET_LEFT = 48, /* wavefronts of the last launch that left the quiet loop - for the steady fast loop (a lane above its bound at
                                       the head of a sample) or for the exact stream (a non-finite value); waits for that launch (summed over shards) */
     FXB_INFO_INSTANCE_ROTATIONS = 46,  /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
-    FXB_INFO_GAIN_LIST_SETS = 49       /* launches of the kernel fx_gain_scatter - by fxb_bus_set_gains_list / _send_gains_list / _feed_gains_list - since creation (summed over shards) */
+    FXB_INFO_GAIN_LIST_SETS = 49,      /* launches of the kernel fx_gain_scatter - by fxb_bus_set_gains_list / _send_gains_list / _feed_gains_list - since creation (summed over shards) */
+    FXB_INFO_REGISTER_LIST_SETS = 50,  /* launches of the kernel fx_reg_scatter - by fxb_set_registers_list - since creation (summed over shards) */
+    FXB_INFO_REGISTER_LIST_GETS = 51   /* launches of the kernel fx_reg_gather - by fxb_get_registers_list - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

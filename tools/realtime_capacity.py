@@ -13,6 +13,12 @@ its audio on the GPU pays).  After the timed region the device's LAST block is c
 replays every block of the run for sampled instances (same PCM, same slider schedule).
 
     python tools/realtime_capacity.py [--blocks 5000] [--instances 4096,...] [--json profiles/r05_realtime.json]
+
+--register-list: instead of the sweep, what per-instance register writes in front of every block cost - no writes,
+fxb_set_registers_list, fxb_set_register_array and fxb_set_register_i by turns in one process (register_paths;
+profiles/register_list_realtime.txt).
+
+    python tools/realtime_capacity.py --register-list [--blocks 3000] [--register-instances 131072,458752] [--register-out FILE]
 """
 import argparse
 import ctypes as C
@@ -180,8 +186,141 @@ def run(torch, A, progs, instances, blocks, warm, modes=("host", "device"), log=
     return out
 
 
+REGISTER_KEYS = ("damp", "decay", "diff", "u")   # config5: its three declared controls and a state register
+REGISTER_LIST, REGISTER_SINGLES = 1024, 64
+
+
+def register_paths(torch, A, progs, n, blocks, warm, stretch, log, clock=lambda: None, only=None):
+    """--register-list: 32-sample blocks of config5 from pinned host buffers, four handles by turns in stretches in one process:
+    no register writes; fxb_set_registers_list of 1 024 instances x 4 registers in front of every block; fxb_set_register_array of
+    the same 4 registers; fxb_set_register_i for 64 x 4 values (the smaller count: a call waits for the queued blocks and copies
+    four bytes).  The writes are inside the block's time.  All four handles hold per-instance values of the four registers from
+    the start, so all four run the same code (a handle whose controls are folded into the code runs faster code: that would be
+    another comparison).  only: the one path of a profiler run."""
+    import numpy as np
+
+    text = progs.config5()
+    lib = A.load()
+    names = ("none", "list %d" % REGISTER_LIST, "array", "single %d" % REGISTER_SINGLES)
+    paths = []
+    rng = np.random.default_rng(5)
+    keys = (C.c_char_p * len(REGISTER_KEYS))(*[k.encode() for k in REGISTER_KEYS])
+    ring = [progs.stimulus(n, BLOCK, first_sample=k * BLOCK) for k in range(RING)]
+    xin = [torch.empty((BLOCK, n), dtype=torch.float32).pin_memory() for _ in range(RING)]
+    for t, r in zip(xin, ring):
+        t.numpy()[...] = r
+    xp = [C.cast(t.data_ptr(), C.POINTER(C.c_float)) for t in xin]
+    for name in names:
+        if only and name.split()[0] != only:
+            continue
+        b = A.Batch(n, 1, 0)
+        if not b.load_text(text):
+            raise RuntimeError("load failed: %s" % b.errors())
+        rows = rng.uniform(0.1, 0.4, (len(REGISTER_KEYS), n)).astype(np.float32)
+        rows[3] *= np.float32(0.01)
+        for k, key in enumerate(REGISTER_KEYS):
+            assert b.set_register_array(key, rows[k]) == 0
+        b.prepare(BLOCK, True)
+        yout = torch.empty((BLOCK, n), dtype=torch.float32).pin_memory()
+        # the moved voices: spread over the instances, other ones in every block of a ring of lists
+        lists = [np.ascontiguousarray(rng.permutation(n)[:REGISTER_LIST].astype(np.int64)) for _ in range(RING)]
+        values = [np.ascontiguousarray(rows[:, L]) for L in lists]
+        paths.append({"name": name, "b": b, "rows": rows, "yout": yout, "yp": C.cast(yout.data_ptr(), C.POINTER(C.c_float)), "lists": lists, "values": values, "times": [], "clocks": [], "k": 0})
+
+    def block(p, timed):
+        b, k, h = p["b"], p["k"], p["b"]._h
+        p["k"] += 1
+        L, v = p["lists"][k % RING], p["values"][k % RING]
+        t0 = time.perf_counter_ns()
+        kind = p["name"].split()[0]
+        if kind == "list":
+            rc = lib.fxb_set_registers_list(h, keys, len(REGISTER_KEYS), C.c_void_p(L.ctypes.data), REGISTER_LIST, C.c_void_p(v.ctypes.data))
+            assert rc == 0, (rc, b.last_error())
+        elif kind == "array":
+            for j, key in enumerate(REGISTER_KEYS):
+                rc = lib.fxb_set_register_array(h, key.encode(), C.c_void_p(p["rows"][j].ctypes.data))
+                assert rc == 0, rc
+        elif kind == "single":
+            for j, key in enumerate(REGISTER_KEYS):
+                name = key.encode()
+                for i in range(REGISTER_SINGLES):
+                    lib.fxb_set_register_i(h, name, int(L[i]), C.c_float(float(v[j, i])))
+        rc = lib.fxb_process_block(h, xp[k % RING], p["yp"], BLOCK)
+        if rc != 0:
+            raise RuntimeError("block %d failed (%d): %s" % (k, rc, b.last_error()))
+        if timed:
+            p["times"].append((time.perf_counter_ns() - t0) * 1e-3)
+
+    for p in paths:
+        for _ in range(warm):
+            block(p, False)
+        p["b"].prepare(BLOCK, True)
+        p["builds"] = (p["b"].info("xlate_builds"), p["b"].info("xlate_background_builds"))
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for p in paths:   # by turns: what else happens on the host and the device meets all of them
+                for _ in range(stretch):
+                    block(p, True)
+                p["clocks"].append(clock())   # (one reading right behind the stretch's last block, outside every timed block)
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "rows": []}
+    for p in paths:
+        b = p["b"]
+        r = percentiles(p["times"])
+        mhz = [c for c in p["clocks"] if c]
+        r.update({"path": p["name"], "instances": n, "within_budget_p999": r["p999_us"] <= BUDGET_US, "shader_clock_mhz_behind_a_stretch": round(sum(mhz) / len(mhz), 1) if mhz else None,
+                  "register_list_sets": b.info("register_list_sets"), "tier": b.tier_note(),
+                  "translations_in_timed_region": [b.info("xlate_builds") - p["builds"][0], b.info("xlate_background_builds") - p["builds"][1]]})
+        out["rows"].append(r)
+        log("%-11s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d list sets  translations in the timed region %s  shader clock %s MHz" % (
+            p["name"], n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["within_budget_p999"] else "over budget", r["register_list_sets"],
+            r["translations_in_timed_region"], r["shader_clock_mhz_behind_a_stretch"]))
+        b.close()
+    return out
+
+
+def register_main(args, torch, A, progs):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bus_capacity import shader_clock_reader
+    lines = []
+
+    def keep(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    if args.trace_run:   # under rocprofv3 --kernel-trace --stats: the list path alone, a run of its own
+        register_paths(torch, A, progs, args.trace_instances, 200, 50, 200, keep, only="list")
+        return
+    keep("32-sample blocks of config5 (pinned host buffers, fxb_process_block) against %.3f us: no register writes; fxb_set_registers_list of %d instances x %d registers "
+         "(%s); fxb_set_register_array of the same registers; fxb_set_register_i for %d x %d values - in front of every block, inside the timed region, by turns in stretches "
+         "of %d blocks in one process, %d blocks per point after %d warm-up blocks; %s" % (
+             BUDGET_US, REGISTER_LIST, len(REGISTER_KEYS), ", ".join(REGISTER_KEYS), REGISTER_SINGLES, len(REGISTER_KEYS), args.stretch, args.blocks, args.warmup,
+             torch.cuda.get_device_name(0)))
+    out = [register_paths(torch, A, progs, n, args.blocks, args.warmup, args.stretch, keep, shader_clock_reader(torch)) for n in [int(v) for v in args.register_instances.split(",") if v]]
+    for point in out:
+        med = {r["path"].split()[0]: r["median_us"] for r in point["rows"]}
+        keep("            N=%7d  median over no writes: list %+.1f us, array %+.1f us, single %+.1f us" % (point["instances"], med["list"] - med["none"], med["array"] - med["none"], med["single"] - med["none"]))
+    if args.register_out:
+        with open(args.register_out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--register-list", action="store_true", help="the four register-write paths by turns (register_paths) instead of the capacity sweep")
+    ap.add_argument("--register-instances", default="131072,458752")
+    ap.add_argument("--register-out", default="", help="keep the lines of --register-list in this text file")
+    ap.add_argument("--stretch", type=int, default=250, help="--register-list: blocks of one path before the next takes its turn")
+    ap.add_argument("--trace-run", action="store_true", help="--register-list: 200 blocks of the list path alone, for a profiler run of its own")
+    ap.add_argument("--trace-instances", type=int, default=458752)
     ap.add_argument("--blocks", type=int, default=5000)
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--instances", default="4096,16384,65536,98304,131072,147456,163840,180224,196608")
@@ -194,6 +333,8 @@ def main():
 
     import fx8010_amd as A
     import fx8010_programs as progs
+    if args.register_list:
+        return register_main(args, torch, A, progs)
     inst = [int(v) for v in args.instances.split(",") if v]
     dev_inst = [int(v) for v in args.device_instances.split(",") if v] or [4096, 65536, 131072, 262144, 393216, 458752, 524288, 557056, 589824]
     log = lambda s: print(s, flush=True)
