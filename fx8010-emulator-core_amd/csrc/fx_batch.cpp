@@ -862,12 +862,26 @@ int64_t Batch::quietLeft() {
     if (!lastLaunchQuiet_ || !dQuietLeft_) return 0;
     (void)hipSetDevice(device_);
     waitLastLaunch();
-    const size_t waves = std::min(quietLeftWords_, ((size_t)n_ + 63) / 64);
-    std::vector<uint32_t> words(waves);
-    if (hipMemcpy(words.data(), dQuietLeft_, waves * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const size_t stride = lastLaunchSums_ ? 2 : 1;
+    const size_t waves = std::min(quietLeftWords_ / 2, ((size_t)n_ + 63) / 64);
+    std::vector<uint32_t> words(waves * stride);
+    if (hipMemcpy(words.data(), dQuietLeft_, words.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     int64_t left = 0;
-    for (uint32_t w : words) left += w < (uint32_t)lastLaunchSamples_;
+    for (size_t k = 0; k < waves; ++k) left += words[k * stride] < (uint32_t)lastLaunchSamples_;
     return left;
+}
+// repairs of the last launch's sum groups, summed over its wavefronts: the second word of each pair (a wavefront that never
+// entered the loop leaves it at 0xFFFFFFFF: no repair)
+int64_t Batch::quietRepairs() {
+    if (!lastLaunchSums_ || !dQuietLeft_) return 0;
+    (void)hipSetDevice(device_);
+    waitLastLaunch();
+    const size_t waves = std::min(quietLeftWords_ / 2, ((size_t)n_ + 63) / 64);
+    std::vector<uint32_t> words(waves * 2);
+    if (hipMemcpy(words.data(), dQuietLeft_, words.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    int64_t repairs = 0;
+    for (size_t k = 0; k < waves; ++k) repairs += words[2 * k + 1] == 0xffffffffu ? 0 : words[2 * k + 1];
+    return repairs;
 }
 
 int64_t Batch::info(int what) {
@@ -912,6 +926,9 @@ int64_t Batch::info(int what) {
         case FXB_INFO_XLATE_CODE_HASH: return c_.useXlate ? (int64_t)c_.codeHash : 0;
         case FXB_INFO_XLATE_QUIET: return (c_.useXlate && c_.quiet) ? 1 : 0;
         case FXB_INFO_XLATE_QUIET_LEFT: return quietLeft();
+        case FXB_INFO_XLATE_QUIET_REPAIRS: return quietRepairs();
+        case FXB_INFO_XLATE_SUM_GROUPS: return (c_.useXlate && c_.sumGroups) ? c_.sumGroupCount : 0;
+        case FXB_INFO_XLATE_SUM_LINKS: return (c_.useXlate && c_.sumGroups) ? c_.sumLinkCount : 0;
         case FXB_INFO_CODE_CACHE_HITS: return cacheHits_;
         case FXB_INFO_CODE_CACHED: return (int64_t)cache_.size() + (c_.key.empty() ? 0 : 1);
         case FXB_INFO_XLATE_UNSATURATED: return c_.useXlate ? c_.unsaturated : 0;

@@ -361,6 +361,8 @@ private:
     uint32_t* dQuietLeft_ = nullptr;
     size_t quietLeftWords_ = 0;
     bool lastLaunchQuiet_ = false;
+    bool lastLaunchSums_ = false;    // ... in a loop with sum groups: the words are pairs {exit sample, repairs}
+    int64_t quietRepairs();          // FXB_INFO_XLATE_QUIET_REPAIRS
     int ensureQuietLeft();
     int64_t quietLeft();             // FXB_INFO_XLATE_QUIET_LEFT
     size_t tracksCap_ = 0;                 // bytes
@@ -421,6 +423,8 @@ private:
         std::string xlateWhyNot;
         bool prioritySlices = false;   // generated code: the wavefronts of a SIMD take turns at the top priority (fx_xlate.hpp)
         bool quiet = false;            // generated code with a quiet loop (fx_xlate.hpp QuietPlan): wavefronts start there
+        bool sumGroups = false;        // ... with sum groups (fx_xlate.hpp SumGroup)
+        int sumGroupCount = 0, sumLinkCount = 0;
         bool deferred = false;          // the interpreter runs this one because controls were moving when it was built
         uint32_t* dStream = nullptr;    // records / row table / stage descriptors on the device
         size_t streamCap = 0;

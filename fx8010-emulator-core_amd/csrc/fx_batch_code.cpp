@@ -673,6 +673,9 @@ int Batch::translateInto(Code& c, const BuildInputs& in, bool offline, std::stri
             c.ldsBytes = image.ldsBytes;
             c.wildRow = image.wildRow;
             c.quiet = image.quietOff != 0;
+            c.sumGroups = c.quiet && image.sumGroups;
+            c.sumGroupCount = c.sumGroups ? (int)image.quietPlan.sumGroups.size() : 0;
+            c.sumLinkCount = c.sumGroups ? image.quietPlan.sumLinks : 0;
             const XlateStats& loop = c.quiet ? image.quiet : image.steady;   // the loop that wavefronts start in
             c.unsaturated = loop.unsaturated;
             c.inlined = loop.inlined;

@@ -238,8 +238,9 @@ int Batch::ensureEndStamps() {
 
 // the quiet loop's exit words ride in the kernarg slot of the stage descriptors, which an unstaged launch leaves unused (nStages
 // stays 0: the template never looks at the pointer)
+// (two words per wavefront: a loop with sum groups writes pairs {exit sample, repairs}, one without them the first half only)
 int Batch::ensureQuietLeft() {
-    const size_t words = ((size_t)n_ + 63) / 64;
+    const size_t words = 2 * (((size_t)n_ + 63) / 64);
     if (words <= quietLeftWords_) return 0;
     waitLastLaunch();
     (void)hipFree(dQuietLeft_);
@@ -269,7 +270,7 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
     for (;;) {
         const KernelArgs a = kernelArgs(dIn, dOut, nSamples, pitch);
         e = timed ? hipEventRecord(ev0_, s) : hipSuccess;
-        lastLaunchQuiet_ = false;
+        lastLaunchQuiet_ = lastLaunchSums_ = false;
         if (e == hipSuccess && c_.useAsm) {
             AsmArgs g = asmArgs(a);
 #ifdef FX_DIAGNOSTICS
@@ -285,6 +286,7 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
                 e = hipMemsetAsync(dQuietLeft_, 0xff, quietLeftWords_ * 4, s);
             }
             lastLaunchQuiet_ = quiet;
+            lastLaunchSums_ = quiet && c_.sumGroups;
             if (e == hipSuccess)
                 e = c_.useXlate ? launchAsmFunction(c_.fn, g, (unsigned)((n_ + 63) / 64), c_.ldsBytes, s, (unsigned)c_.stages)
                             : launchAsmInterp(g, c_.variant, c_.variant == ASM_LDS ? (size_t)a.nRows * 256 : 0, device_, s);

@@ -477,7 +477,7 @@ static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, i
     }
     const fx::XlateTemplate* tmpl = fx::xlateTemplate((fx::AsmVariant)v, &h->err);
     if (!tmpl) return FX_E_PROGRAM;
-    if (stream < 0 || stream > 5 || (stream == 5 && stages >= 2)) { h->err = "stream: 0 steady fast, 1 steady exact, 2 last fast, 3 last exact, 4 run-once, 5 steady quiet (unstaged)"; return FX_E_ARG; }
+    if (stream < 0 || stream > 6 || (stream >= 5 && stages >= 2)) { h->err = "stream: 0 steady fast, 1 steady exact, 2 last fast, 3 last exact, 4 run-once, 5 steady quiet, 6 steady quiet with sum groups (5, 6: unstaged)"; return FX_E_ARG; }
     std::vector<uint32_t> code4[5];
     std::string text4[5];
     fx::XlateImage plan;
@@ -534,12 +534,31 @@ static int64_t translateImpl(fxp_handle* h, int vgprs, int stream, void* code, i
         // ... and behind the records: the number of adds of +0 the quiet loop does not emit, then their record indices
         w.push_back((int32_t)q.zeroAddsDropped.size());
         for (int i : q.zeroAddsDropped) w.push_back(i);
+        // ... then the sum groups (fx_xlate.hpp SumGroup): their number, the links in them; per group {row, T bits, links, flags
+        // (1 first, 2 last of its chain, 4 the start is watched), start VGPR, bits of the running bound of the value in front of
+        // the group's chain} and per link {record, watched, negate, addend row (-1: a product), addend VGPR (-1: the row itself),
+        // sum VGPR, bits of the addend's running bound}
+        w.push_back((int32_t)q.sumGroups.size());
+        w.push_back(q.sumLinks);
+        for (const fx::SumGroup& g : q.sumGroups) {
+            int32_t bits;
+            std::memcpy(&bits, &g.threshold, 4);
+            auto bitsOf = [](float f) { int32_t b; std::memcpy(&b, &f, 4); return b; };
+            w.insert(w.end(), {g.row, bits, (int32_t)g.links.size(), (g.first ? 1 : 0) | (g.last ? 2 : 0) | (g.watchStart ? 4 : 0), g.startReg, bitsOf(g.startBound)});
+            for (size_t k = 0; k < g.links.size(); ++k)
+                w.insert(w.end(), {g.links[k], g.watched[k], g.negate[k], g.addendRow[k], g.addendReg[k], g.dstReg[k], bitsOf(q.addendBound[(size_t)g.links[k]])});
+        }
         h->err = q.why;
         return 0;
     }
-    if (stream == 5 && staged) { h->err = "a program cut into stages has no quiet loop"; return FX_E_ARG; }
-    const std::vector<uint32_t>& words = stream == 5 ? plan.quietCode : staged ? stagedCode[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : code4[stream];
-    const std::string& text = stream == 5 ? plan.quietListing : staged ? stagedText[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : text4[stream];
+    if (stream >= 5 && staged) { h->err = "a program cut into stages has no quiet loop"; return FX_E_ARG; }
+    // (stream 5 = the quiet loop without sum groups whatever the image carries; stream 6 = the loop with them, empty where the plan has none)
+    static const std::vector<uint32_t> noWords;
+    static const std::string noText;
+    const std::vector<uint32_t>& quietWords = stream == 6 ? (plan.sumGroups ? plan.quietCode : noWords) : (plan.sumGroups ? plan.plainQuietCode : plan.quietCode);
+    const std::string& quietText = stream == 6 ? (plan.sumGroups ? plan.quietListing : noText) : (plan.sumGroups ? plan.plainQuietListing : plan.quietListing);
+    const std::vector<uint32_t>& words = stream >= 5 ? quietWords : staged ? stagedCode[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : code4[stream];
+    const std::string& text = stream >= 5 ? quietText : staged ? stagedText[stream == 4 ? (size_t)plan.stages * 4 : (size_t)stage * 4 + (size_t)stream] : text4[stream];
     const int64_t bytes = (int64_t)words.size() * 4;
     if (code && cap > 0 && bytes > 0) std::memcpy(code, words.data(), (size_t)std::min<int64_t>(cap, bytes));   // (an empty stream has no data())
     if (listing && listing_cap > 0) {

@@ -71,5 +71,9 @@ constexpr bool kDiagnosticsBuild = false;
 // knob it exists in the diagnostics build only - the release library has the part on.  Read at every translation (not cached: a
 // test translates one program under both settings).
 inline bool knobQuietZeroAdds() { return knobInt(FX_DIAG_KNOB("FX_XLATE_ZEROADD"), 1) != 0; }
+// The same for the quiet loop's sum groups (fx_xlate.hpp SumGroup): FX_XLATE_SUMGROUPS=0 makes the device run the loop without
+// them (stream 5); FX_XLATE_SUMGROUP_MAX=n caps a group at n links instead of kSumGroupMax (the A/B of the cap).
+inline bool knobQuietSumGroups() { return knobInt(FX_DIAG_KNOB("FX_XLATE_SUMGROUPS"), 1) != 0; }
+inline int knobQuietSumGroupMax(int otherwise) { const int n = knobInt(FX_DIAG_KNOB("FX_XLATE_SUMGROUP_MAX"), otherwise); return n < 2 ? otherwise : n; }
 
 }  // namespace fx

@@ -122,6 +122,8 @@ class Translator {
     // drops, the check of the plan's rows at the head, and `bailTarget` - the head sync point of the steady FAST loop - where a
     // wave continues when a lane fails that check
     void quiet(const QuietPlan* plan, uint32_t bailTarget) { quiet_ = plan; bailTarget_ = bailTarget; }
+    // ... with the plan's sum groups (fx_xlate.hpp SumGroup): stream 6
+    void sumGroups(bool on) { sums_ = on; }
 
     // Layout of a stream:  head (hot entry) | program | PCM out, advance, loop branch / exit | cold entry stub
     bool run(const std::vector<MicroOp>& records, XlateStats* stats, std::vector<uint32_t>* returns, uint32_t* coldEntry, std::string* err) {
@@ -508,6 +510,10 @@ class Translator {
             if (ring) inputBurst(0, true);
         }
         if (!prog_.trackRows.empty()) trackInit();
+        if (sums_) {
+            e_.sop1(SOP1_MOV_B64, "s_mov_b64", sreg64(kSSumForce), imm32(0));
+            e_.sop1(SOP1_MOV_B32, "s_mov_b32", sreg(kSSumRepairs), imm32(0));
+        }
         // (inline constants where the bit pattern has one, as the assembler would choose: the listing must re-assemble to the same bytes)
         for (const auto& c : pool_) e_.sop1(SOP1_MOV_B32, "s_mov_b32", sreg(c.second), imm32(c.first));
         for (const auto& c : prog_.vconst) e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(c.second), imm32(c.first));
@@ -831,14 +837,20 @@ class Translator {
     }
     // ---- the quiet loop (fx_xlate.hpp QuietPlan)
     // word [wavefront] of the launch's exit words = `value`: lane 0 stores it.  v2 / v3 and s[62:63] are scratch between records.
+    // With sum groups the words are pairs per wavefront: {value, repairs of the wavefront}.
     void quietExitWord(const Src& value) {
         smemLoad(2, kSTemp, 0, kKernargQuietLeft);
         e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(2), value);
         e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(3), sreg(kSWave));
-        e_.vop2(VOP2_LSHLREV_B32, "v_lshlrev_b32_e32", 3, imm32(2), 3);
+        e_.vop2(VOP2_LSHLREV_B32, "v_lshlrev_b32_e32", 3, imm32(sums_ ? 3 : 2), 3);
         e_.waitLgkm0();
         e_.sop1(SOP1_MOV_B64, "s_mov_b64", named(126, "exec"), imm32(1));
         e_.global(GLOBAL_STORE_DWORD, false, 2, 3, kSTemp);
+        if (sums_) {
+            e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(2), sreg(kSSumRepairs));
+            e_.vop2(VOP2_ADD_U32, "v_add_u32_e32", 3, imm32(4), 3);
+            e_.global(GLOBAL_STORE_DWORD, false, 2, 3, kSTemp);
+        }
         e_.sop1(SOP1_MOV_B64, "s_mov_b64", named(126, "exec"), named(193, "-1"));
         e_.waitVmcnt(0);   // (the counted waits of the loops know nothing of this store)
     }
@@ -882,6 +894,82 @@ class Translator {
         e_.sopc(SOPC_CMP_LG_U64, "s_cmp_lg_u64", sreg64(kSTemp), imm32(0));
         const uint32_t target = bailTarget_;
         defer(e_.branchForward(SOPP_CBRANCH_SCC1, "s_cbranch_scc1"), [this, target]() { quietLeave(target); });
+    }
+
+    // ---- sum groups (fx_xlate.hpp SumGroup)
+    // A link of group g: its addend into the group's register (a product) or copied there (a row that is rewritten before the
+    // test), the unsaturated sum into the register the plan names; behind the last link, the test.
+    bool sumLink(const MicroOp& r, size_t gi) {
+        const SumGroup& g = quiet_->sumGroups[gi];
+        size_t k = 0;
+        while (k < g.links.size() && (size_t)g.links[k] != index_) ++k;
+        if (k == g.links.size()) return fail("internal: a record outside its sum group");
+        const uint32_t rel = r.w[0] - AS_MACS, family = rel / 16, kind = (rel % 16) / 2;
+        plainMode();
+        int addend;
+        if (g.addendRow[k] < 0) {
+            bool inV3;
+            productDst_ = g.addendReg[k];
+            const bool ok = family <= 1 && g.addendReg[k] >= 0 && product(r, kind, &inV3) && inV3;
+            productDst_ = -1;
+            if (!ok) return err_.empty() ? fail("internal: a link whose addend is no product") : false;
+            addend = g.addendReg[k];
+        } else {
+            if (!row((uint32_t)g.addendRow[k], &addend)) return false;
+            if (g.addendReg[k] >= 0) e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(g.addendReg[k]), vreg(addend));
+            if (family == 2) ++stats_.zeroAddsDropped; else ++stats_.unitMultipliers;
+        }
+        const int cur = k == 0 ? g.startReg : g.dstReg[k - 1];
+        e_.vop2(g.negate[k] ? VOP2_SUB_F32 : VOP2_ADD_F32, g.negate[k] ? "v_sub_f32_e32" : "v_add_f32_e32", g.dstReg[k], vreg(cur), addend);
+        if (k + 1 < g.links.size()) return true;
+        // the test: max |watched sums| against T, valid lanes only; a lane above it sends the wave through the repair stub
+        std::vector<int> v;
+        if (g.watchStart) v.push_back(g.startReg);
+        for (size_t i = 0; i < g.links.size(); ++i)
+            if (g.watched[i]) v.push_back(g.dstReg[i]);
+        const size_t n = v.size();
+        e_.note("sum group test");
+        e_.max3Abs(vreg(2), vreg(v[0]), vreg(v[n > 1 ? 1 : 0]), vreg(v[n > 2 ? 2 : n - 1]));
+        for (size_t i = 3; i < n; i += 2) e_.max3Abs(vreg(2), vreg(2), vreg(v[i]), vreg(v[i + 1 < n ? i + 1 : i]));
+        uint32_t tBits;
+        std::memcpy(&tBits, &g.threshold, 4);
+        e_.vopc(VOPC_CMP_LT_F32, "v_cmp_lt_f32_e32", imm32(tBits), 2);
+        e_.sop2(SOP2_AND_B64, "s_and_b64", sreg64(kSTemp), named(106, "vcc"), sreg64(kSValidLanes));   // (lanes without an instance hold anything)
+        if (!g.first) e_.sop2(SOP2_OR_B64, "s_or_b64", sreg64(kSTemp), sreg64(kSTemp), sreg64(kSSumForce));
+        e_.sopc(SOPC_CMP_LG_U64, "s_cmp_lg_u64", sreg64(kSTemp), imm32(0));
+        defer(e_.branchForward(SOPP_CBRANCH_SCC1, "s_cbranch_scc1"), [this, gi]() { sumRepair(gi); });
+        // (a chain of one group computes beside its row - the stub needs the start value - and moves the end in)
+        const int vR = vrow((uint32_t)g.row);
+        if (g.last && g.dstReg[k] != vR) e_.vop1(VOP1_MOV, "v_mov_b32_e32", vreg(vR), vreg(g.dstReg[k]));
+        return true;
+    }
+    // Behind the loop: the group again from its start, every link as the fast stream has it - add, v_med3_f32 (all values are
+    // finite) - for ALL lanes: a lane that did not fire gets the bits it had.  Writes the watched sums and the group's end, which
+    // is all the loop reads behind the test; tells the next group when the end is above T; counts the repair.
+    void sumRepair(size_t gi) {
+        const SumGroup& g = quiet_->sumGroups[gi];
+        Src m1 = imm32(0xbf800000u), p1 = imm32(0x3f800000u);
+        e_.cold(true);
+        e_.note("sum group repair");
+        int cur = g.startReg;
+        for (size_t k = 0; k < g.links.size(); ++k) {
+            const int addend = g.addendReg[k] >= 0 ? g.addendReg[k] : vrow((uint32_t)g.addendRow[k]);
+            e_.vop2(g.negate[k] ? VOP2_SUB_F32 : VOP2_ADD_F32, g.negate[k] ? "v_sub_f32_e32" : "v_add_f32_e32", 2, vreg(cur), addend);
+            const int dst = (g.watched[k] || k + 1 == g.links.size()) ? g.dstReg[k] : 3;
+            e_.vop3(VOP3_MED3_F32, "v_med3_f32", vreg(dst), vreg(2), m1, &p1);
+            cur = dst;
+        }
+        if (!g.last) {
+            uint32_t tBits;
+            std::memcpy(&tBits, &g.threshold, 4);
+            e_.max3Abs(vreg(2), vreg(cur), vreg(cur), vreg(cur));
+            e_.vopc(VOPC_CMP_LT_F32, "v_cmp_lt_f32_e32", imm32(tBits), 2);
+            e_.sop2(SOP2_AND_B64, "s_and_b64", sreg64(kSSumForce), named(106, "vcc"), sreg64(kSValidLanes));
+        } else if (!g.first) {
+            e_.sop1(SOP1_MOV_B64, "s_mov_b64", sreg64(kSSumForce), imm32(0));
+        }
+        e_.sop2(SOP2_ADD_U32, "s_add_u32", sreg(kSSumRepairs), sreg(kSSumRepairs), imm32(1));
+        e_.cold(false);
     }
 
     // the record is about to read / write these register-file rows: none may still be in flight
@@ -1529,7 +1617,7 @@ class Translator {
         if (entry) *entry = -1;
         if (uX && uY) return true;
         Src a;
-        int b, dst = 3;
+        int b, dst = productDst_ >= 0 ? productDst_ : 3;   // (productDst_: a link of a sum group keeps its product, sumLink)
         if (!uX && !uY) {
             if (!operand(r.w[3], false, &a) || !row(r.w[4], &b)) return false;
         } else if (uX) {
@@ -2164,6 +2252,7 @@ class Translator {
             if (!ccr) {
                 if (!touch(r, !(kind & 1u), !(kind & 2u), !(kind & 4u), true)) return false;
                 ++stats_.inlined;
+                if (sums_ && quiet_ && index_ < quiet_->groupOf.size() && quiet_->groupOf[index_] >= 0) return sumLink(r, (size_t)quiet_->groupOf[index_]);
                 switch (family) {
                     case 0: return macs(r, kind, false);
                     case 1: return macs(r, kind, true);
@@ -2226,6 +2315,8 @@ class Translator {
     const std::vector<uint32_t>* exactReturns_;
     const QuietPlan* quiet_ = nullptr;   // this stream is the quiet loop of that plan
     uint32_t bailTarget_ = 0;            // ... and leaves for the steady fast loop there
+    bool sums_ = false;                  // ... with the plan's sum groups
+    int productDst_ = -1;                // product(): the VGPR the next product goes to instead of v3
     std::vector<uint32_t> returns_;  // sync points of this stream (see run())
     std::vector<int> pending_;       // VGPRs with a TRAM read in flight
     std::vector<std::pair<uint32_t, int>> pool_;  // uniform constants kept in SGPRs for the whole loop: (bits, SGPR)
@@ -2596,6 +2687,7 @@ float absOf(uint32_t bits) {
 
 struct QuietPass {
     std::vector<uint8_t> site, idle, idleByClass;
+    std::vector<float> aBound, addendBound;   // per saturating record: bound of the A operand / of what is added to it (QuietPlan)
     int sites = 0, idleCount = 0, idleByClassCount = 0;
 };
 // One pass over the records with head bounds `rb` (per register-file row; +inf = nothing known): at every record that writes a
@@ -2607,6 +2699,8 @@ QuietPass quietPass(const std::vector<MicroOp>& records, const XlateProgram& pro
     out.site.assign(records.size(), 0);
     out.idle.assign(records.size(), 0);
     out.idleByClass.assign(records.size(), 0);
+    out.aBound.assign(records.size(), HUGE_VALF);
+    out.addendBound.assign(records.size(), HUGE_VALF);
     auto classOf = [&](uint32_t row) { return (row < prog.wildRow.size() && !prog.wildRow[row]) ? 1.0f : HUGE_VALF; };
     auto B = [&](uint32_t word, bool uniform) { return uniform ? absOf(word) : (word < rb.size() ? rb[word] : HUGE_VALF); };
     auto set = [&](uint32_t row, float b) { if (row < rb.size()) rb[row] = row == 0 ? HUGE_VALF : b; };   // (row 0 is the CCR)
@@ -2628,11 +2722,14 @@ QuietPass quietPass(const std::vector<MicroOp>& records, const XlateProgram& pro
         if (kind == 7) { set(dst, std::min(1.0f, absOf(r.w[2]))); continue; }   // folded on the host: the saturated result itself
         if (dead[i]) continue;                                                  // nothing is computed: the row keeps what it held
         float ub = HUGE_VALF;
+        out.aBound[i] = B(r.w[2], uA);
         if (family <= 1) {
             const float p = (uX && uY) ? absOf(r.w[3]) : mulF(B(r.w[3], uX), B(r.w[4], uY));
+            out.addendBound[i] = p;
             ub = addF(B(r.w[2], uA), p);
         } else if (family == 2) {
             const float sum = (uA && uX) ? absOf(r.w[2]) : addF(B(r.w[2], uA), B(r.w[3], uX));
+            if (!uA) out.addendBound[i] = B(r.w[3], uX);
             ub = addF(sum, B(r.w[4], uY));
         } else if (uX) {   // INTERP with a constant X: (float)((1 - X) * (double)A + (double)(X * Y)), (1 - X) from the record
             double omx;
@@ -2774,6 +2871,9 @@ QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgra
         ++(want[r] < 1.0f ? tight : unit);
     }
     plan.idle = pass.idle;
+    plan.aBound = pass.aBound;
+    plan.addendBound = pass.addendBound;
+    plan.groupOf.assign(steadyRecords.size(), -1);
     for (size_t i = 0; i < pass.idle.size(); ++i)
         if (pass.idle[i]) plan.dropped.push_back((int)i);
     plan.sites = pass.sites;
@@ -2798,6 +2898,211 @@ QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgra
     else
         plan.inForce = true;
     return plan;
+}
+
+// ---- sum groups (fx_xlate.hpp SumGroup) -------------------------------------------------------------------------------------
+namespace {
+// the coverage pass of one chain: from T at every point where the value is known to be <= T (the start of each group: a
+// watched sum or a start bounded by T; every watched sum), add the addends' bounds as the instruction adds - no covered sum above 1
+bool sumsCovered(float T, const std::vector<float>& addend, const std::vector<uint8_t>& watched, const std::vector<uint8_t>& groupStart) {
+    float s = T;
+    for (size_t k = 0; k < addend.size(); ++k) {
+        if (groupStart[k]) s = T;
+        if (watched[k]) { s = T; continue; }
+        s = addF(s, addend[k]);
+        if (!(s <= 1.0f)) return false;
+    }
+    return true;
+}
+// the largest float T in [0, 1] for which the pass succeeds (the pass is monotone in T: bisection over the bit patterns);
+// negative: not even T = 0 does
+float sumThreshold(const std::vector<float>& addend, const std::vector<uint8_t>& watched, const std::vector<uint8_t>& groupStart) {
+    if (!sumsCovered(0.0f, addend, watched, groupStart)) return -1.0f;
+    uint32_t lo = 0u, hi = 0x3f800000u;   // lo succeeds
+    if (sumsCovered(1.0f, addend, watched, groupStart)) return 1.0f;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        float t;
+        std::memcpy(&t, &mid, 4);
+        if (sumsCovered(t, addend, watched, groupStart)) lo = mid; else hi = mid;
+    }
+    float t;
+    std::memcpy(&t, &lo, 4);
+    return t;
+}
+// the links of a plan (fx_xlate.hpp SumGroup), per steady record: row = R (-1: the record is no link), addendRow = the row that is
+// added as it stands (-1: a product), negate = it is subtracted
+struct SumLink { int row, addendRow; bool negate; };
+std::vector<SumLink> sumLinksOf(const QuietPlan& plan, const std::vector<MicroOp>& records, const XlateProgram& prog, const std::vector<uint8_t>& dead, size_t end) {
+    std::vector<SumLink> link(records.size(), SumLink{-1, -1, false});
+    for (size_t i = (size_t)std::max(0, prog.hoist.leadCount); i < end; ++i) {
+        const MicroOp& r = records[i];
+        const uint32_t slot = r.w[0], R = r.w[5];
+        if (slot < AS_MACS || slot >= (uint32_t)kAsmSlots || dead[i]) continue;
+        const uint32_t rel = slot - AS_MACS, family = rel / 16, kind = (rel % 16) / 2;
+        const bool uA = kind & 1, uX = kind & 2, uY = kind & 4;
+        if ((rel & 1u) || family > 2 || kind == 7 || uA || R == 0 || r.w[2] != R || R >= prog.wildRow.size()) continue;   // (row 0 is the CCR)
+        if (plan.idle[i] || !(plan.addendBound[i] < HUGE_VALF)) continue;
+        if ((!uX && r.w[3] == R) || (!uY && r.w[4] == R)) continue;
+        SumLink l{(int)R, -1, family == 1};
+        if (family <= 1) {
+            if (uX && uY) continue;
+            const uint32_t unit = (uX && !uY) ? r.w[3] : (uY && !uX) ? r.w[4] : 0u;
+            if ((unit & 0x7fffffffu) == 0x3f800000u) {   // no multiplication is emitted: the addend is the row itself
+                l.addendRow = (int)(uX ? r.w[4] : r.w[3]);
+                if (unit >> 31) l.negate = !l.negate;
+            }
+        } else {
+            if (uX || !uY || r.w[4] != 0u || i >= plan.zeroAdd.size() || !plan.zeroAdd[i]) continue;
+            l.addendRow = (int)r.w[3];
+        }
+        link[i] = l;
+    }
+    return link;
+}
+}  // namespace
+
+void planSumGroups(QuietPlan* plan, const std::vector<MicroOp>& records, const XlateProgram& prog, int spareFirst, int spareEnd, int groupMax) {
+    plan->sumGroups.clear();
+    plan->groupOf.assign(records.size(), -1);
+    plan->sumLinks = 0;
+    if (!plan->inForce || plan->addendBound.size() != records.size() || spareEnd - spareFirst < 5 || groupMax < 2) return;
+    const std::vector<uint8_t> dead = deadWritesOf(records, prog.latchRows);
+    size_t end = 0;
+    while (end < records.size() && records[end].w[0] != AS_ENDSAMPLE) ++end;
+    // rows the next sample's delay-line reads land in, in the middle of this one: never read later than where they stand
+    std::vector<uint8_t> landing(prog.wildRow.size(), 0);
+    for (int k = 0; k < prog.hoist.leadCount && (size_t)k < end; ++k)
+        if (records[(size_t)k].w[5] < landing.size()) landing[records[(size_t)k].w[5]] = 1;
+    using Link = SumLink;
+    const std::vector<Link> link = sumLinksOf(*plan, records, prog, dead, end);
+    const int costMed3 = Emitter::issueCostOf("v_med3_f32"), costMax3 = Emitter::issueCostOf("v_max3_f32"),
+              costCmp = Emitter::issueCostOf("v_cmp_lt_f32"), costMov = Emitter::issueCostOf("v_mov_b32");
+    // chains, in the order of their first links; a chain that overlaps one already grouped stays as it is (one set of registers)
+    std::vector<uint8_t> seen(records.size(), 0);
+    size_t busyUntil = 0;
+    for (size_t i = 0; i < end; ++i) {
+        if (link[i].row < 0 || seen[i]) continue;
+        const int R = link[i].row;
+        std::vector<int> chain;
+        for (size_t j = i; j < end; ++j) {
+            if (link[j].row == R) { chain.push_back((int)j); seen[j] = 1; continue; }
+            const Access a = accessOf(records[j]);
+            bool touches = a.write == R;
+            for (int q = 0; q < a.nReads; ++q) touches = touches || (int)a.reads[q] == R;
+            if (touches) break;
+        }
+        if (chain.size() < 2 || (size_t)chain.front() < busyUntil) continue;
+        const size_t n = chain.size();
+        std::vector<float> addend(n);
+        std::vector<uint8_t> watched(n, 0), groupStart(n, 0);
+        float slack = 0.0f;
+        for (size_t k = 0; k < n; ++k) {
+            addend[k] = plan->addendBound[(size_t)chain[k]];
+            slack += addend[k];
+            if (addend[k] > kSumSmallAddend || slack > kSumSlack) { watched[k] = 1; slack = 0.0f; }
+        }
+        // an addend row is copied where something writes it between its link and the group's test
+        auto rewritten = [&](int row, int from, int to) {
+            if (row >= 0 && (size_t)row < landing.size() && landing[(size_t)row]) return true;
+            for (int j = from + 1; j <= to; ++j)
+                if (accessOf(records[(size_t)j]).write == row) return true;
+            return false;
+        };
+        // groups, greedily: as many links as the cap and the spare registers allow - two that carry the chain's value from
+        // group to group by turns, one for the covered sums, one per watched sum inside the group and one per kept addend
+        const int carry[2] = {spareFirst, spareFirst + 1}, running = spareFirst + 2, pool = spareFirst + 3;
+        std::vector<std::pair<size_t, size_t>> cut;   // [first, last] link of each group
+        for (size_t first = 0; first < n;) {
+            size_t last = first;
+            for (size_t cand = first + 1; cand < n && cand - first + 1 <= (size_t)groupMax; ++cand) {
+                int regs = 0;
+                for (size_t k = first; k <= cand; ++k) {
+                    regs += k < cand && watched[k];
+                    regs += link[(size_t)chain[k]].addendRow < 0 || rewritten(link[(size_t)chain[k]].addendRow, chain[k], chain[cand]);
+                }
+                if (pool + regs > spareEnd) break;
+                last = cand;
+            }
+            // (inside a chain a group ends where a sum is watched anyway, when it can: the forced watch at its end then costs no operand)
+            if (last + 1 < n && !watched[last])
+                for (size_t j = last; j > first; --j)
+                    if (watched[j]) { last = j; break; }
+            cut.emplace_back(first, last);
+            first = last + 1;
+        }
+        // (a trailing single link joins nothing: it runs as it does without groups, on the canonical row; one left over by
+        // the cap takes a link from the group in front of it when that has three or more)
+        if (cut.size() >= 2 && cut.back().first == cut.back().second && cut[cut.size() - 2].second - cut[cut.size() - 2].first >= 2) {
+            --cut[cut.size() - 2].second;
+            --cut.back().first;
+        }
+        while (!cut.empty() && cut.back().first == cut.back().second) cut.pop_back();
+        bool whole = !cut.empty();
+        for (const auto& c : cut) whole = whole && c.second > c.first;   // (no room for two links somewhere: the chain stays as it is)
+        if (!whole) continue;
+        // T, registers and the price of every group; a group at the END of the chain that does not pay is left out (its links run
+        // as they do without groups, on the canonical row) and the rest is planned again; one anywhere else: no groups at all
+        const std::vector<float> allAddends = addend;
+        const std::vector<uint8_t> natural = watched;
+        std::vector<SumGroup> groups;
+        size_t grouped = 0;
+        for (bool settled = false; !settled && !cut.empty();) {
+            addend = allAddends;
+            watched = natural;
+            groupStart.assign(n, 0);
+            for (const auto& c : cut) { groupStart[c.first] = 1; watched[c.second] = 1; }
+            grouped = cut.back().second + 1;
+            addend.resize(grouped);
+            watched.resize(grouped);
+            groupStart.resize(grouped);
+            const float T = sumThreshold(addend, watched, groupStart);
+            groups.clear();
+            if (T < 0.0f) { cut.clear(); break; }
+            std::vector<uint8_t> pays(cut.size(), 0);
+            for (size_t q = 0; q < cut.size(); ++q) {
+                SumGroup g;
+                g.row = R;
+                g.first = q == 0;
+                g.last = q + 1 == cut.size();
+                g.threshold = T;
+                g.startBound = plan->aBound[(size_t)chain[0]];
+                g.watchStart = g.first && !(g.startBound <= T);
+                g.startReg = g.first ? kRegFileBase + R : carry[(q - 1) & 1];
+                int next = pool, operands = g.watchStart ? 1 : 0, copies = 0;
+                for (size_t k = cut[q].first; k <= cut[q].second; ++k) {
+                    const Link& l = link[(size_t)chain[k]];
+                    const bool isLast = k == cut[q].second;
+                    g.links.push_back(chain[k]);
+                    g.watched.push_back(watched[k]);
+                    g.negate.push_back(l.negate);
+                    g.addendRow.push_back(l.addendRow);
+                    const bool keep = l.addendRow < 0 || rewritten(l.addendRow, chain[k], chain[cut[q].second]);
+                    g.addendReg.push_back(keep ? next++ : -1);
+                    copies += keep && l.addendRow >= 0;
+                    operands += watched[k];
+                    // the end of a group: the other carry register - or row R itself at the end of a chain of several groups
+                    g.dstReg.push_back(isLast ? ((g.last && !g.first) ? kRegFileBase + R : carry[q & 1]) : (watched[k] ? next++ : running));
+                }
+                copies += g.last && g.first;   // (a chain of one group moves its end into the row)
+                const int tests = 1 + (operands > 3 ? (operands - 3 + 1) / 2 : 0);
+                const int removed = (int)g.links.size() * costMed3, added = tests * costMax3 + costCmp + copies * costMov;
+                pays[q] = removed > added && next <= spareEnd;
+                groups.push_back(std::move(g));
+            }
+            settled = true;
+            for (size_t q = 0; q + 1 < cut.size(); ++q)
+                if (!pays[q]) cut.clear();
+            if (!cut.empty() && !pays.back()) { cut.pop_back(); settled = false; }
+        }
+        if (cut.empty()) continue;
+        for (SumGroup& g : groups) {
+            for (int idx : g.links) plan->groupOf[(size_t)idx] = (int)plan->sumGroups.size();
+            plan->sumLinks += (int)g.links.size();
+            plan->sumGroups.push_back(std::move(g));
+        }
+        busyUntil = (size_t)chain[grouped - 1] + 1;
+    }
 }
 
 bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<MicroOp>& lastRecords, const XlateTemplate& tmpl,
@@ -2908,6 +3213,9 @@ bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<Micr
     out->quietCode.clear();
     out->quietListing.clear();
     out->quiet = XlateStats();
+    out->sumGroups = false;
+    out->plainQuietCode.clear();
+    out->plainQuietListing.clear();
     out->quietPlan = planQuiet(steadyRecords, pooledProgram);
     if (out->quietPlan.inForce && !fastOk) { out->quietPlan.inForce = false; out->quietPlan.why = "no fast stream (a non-finite uniform operand)"; }
     if (out->quietPlan.inForce) {
@@ -2927,6 +3235,39 @@ bool planXlate(const std::vector<MicroOp>& steadyRecords, const std::vector<Micr
             out->quietListing = std::move(quietText);
             out->quiet = quietStats;
             out->steadyFastOff = quietCold;   // waves start in the quiet loop
+            // ... with sum groups where the plan has any: the same loop at the same place, the groups' saturations in stubs
+            // behind it.  The loop without them stays available (plainQuiet*: stream 5 reads as it always did).
+            out->sumGroups = false;
+            out->plainQuietCode.clear();
+            out->plainQuietListing.clear();
+            out->plainQuiet = XlateStats();
+            if (knobQuietSumGroups())
+                planSumGroups(&out->quietPlan, steadyRecords, pooledProgram, pooledProgram.cseBase + 3 * pooledProgram.cseEntries,
+                              tmpl.vgprs - (int)pooledProgram.vconst.size(), knobQuietSumGroupMax(kSumGroupMax));
+            if (!out->quietPlan.sumGroups.empty()) {
+                std::vector<uint32_t> groupCode;
+                std::string groupText, groupWhy;
+                uint32_t groupCold = 0;
+                XlateStats groupStats;
+                Translator tg(tmpl, prog[0], at, false, out->base[2], &groupCode, listing ? &groupText : nullptr, &exactRet[0]);
+                tg.quiet(&out->quietPlan, steadyFastRet[headSync]);
+                tg.sumGroups(true);
+                if (tg.run(steadyRecords, &groupStats, nullptr, &groupCold, &groupWhy) &&
+                    (at - tmpl.holeOff) + align64((uint32_t)groupCode.size() * 4) + 4 <= tmpl.holeBytes) {
+                    out->plainQuietCode = std::move(out->quietCode);
+                    out->plainQuietListing = std::move(out->quietListing);
+                    out->plainQuiet = out->quiet;
+                    out->quietCode = std::move(groupCode);
+                    out->quietListing = std::move(groupText);
+                    out->quiet = groupStats;
+                    out->quietOff = out->steadyFastOff = groupCold;
+                    out->sumGroups = true;
+                } else {   // (the hole, a branch range: the loop without groups runs)
+                    out->quietPlan.sumGroups.clear();
+                    out->quietPlan.groupOf.assign(steadyRecords.size(), -1);
+                    out->quietPlan.sumLinks = 0;
+                }
+            }
             at += align64((uint32_t)out->quietCode.size() * 4);
         } else {
             out->quietPlan.inForce = false;

@@ -181,6 +181,36 @@ struct XlateStats {
 // fails the check continues in the fast loop, at the same point, for the rest of the launch.  planQuiet is a pure function
 // of the steady records and the program: which rows to check, and at which records the saturation is then idle.
 constexpr float kQuietBound = 0.25f;
+// Sum groups: the saturations the quiet plan must KEEP are mostly the links of one accumulator chain -
+// `macs m, m, u, 0.05`, `acc3 m, m, u, 0`: R = sat(R +- addend), nothing else touching R in between - whose running bound
+// passes 1 after a few links although the values rarely do.  A LINK is such a record: MACS / MACSN, or an ACC3 whose add of +0
+// the plan drops; saturation kept; A = its own result row R (not the CCR, which is not live at it either); X and Y are not R and
+// not both uniform; the addend's running bound is finite.  A CHAIN is a maximal run of links on one row with no other reader or
+// writer of R between them; a GROUP is >= 2 consecutive links of a chain under ONE test.  Inside a group the loop with sum groups
+// (stream 6) writes unsaturated sums into spare VGPRs and keeps every addend; behind the last link it tests max |watched sums|
+// against the chain's threshold T <= 1, and only where a valid lane is above T a stub behind the loop recomputes the group with
+// its saturations (add, v_med3_f32 per link - the fast stream's form), counts one repair and returns behind the test.
+//   * a partial sum is WATCHED (an operand of the test) or COVERED: the bound pass - fp32, monotone rounding - starts at T where
+//     the last value known to be <= T was (a watched sum; the chain's start when its bound is <= T) and adds the addends'
+//     running bounds; every covered sum's bound is <= 1.  T is the largest float for which that holds (bisection over the pass).
+//   * the sum after a large addend (bound above kSumSmallAddend) is watched, and so is the one at which the small addends
+//     since the last watched sum would pass kSumSlack, and the last of every group (it is the next group's start).
+//   * test passed: every watched |sum| <= T <= 1 and every covered |sum| <= 1, so each skipped median would have returned its
+//     operand; test failed: the stub computes what the loop without groups computes.  After a repair the group's end may lie
+//     above T: the stub then raises s[4:5], which the next group's test ORs in.
+struct SumGroup {
+    int row = 0;                       // R
+    bool first = false, last = false;  // of its chain: starts from row R itself / leaves row R canonical
+    bool watchStart = false;           // the chain's start is not bounded by T: the start value is an operand of the test too
+    float threshold = 1.0f;            // T (one per chain)
+    float startBound = 0.0f;           // running bound of the value in front of the CHAIN (watchStart = it is above T)
+    int startReg = 0;                  // VGPR that holds the value in front of the group
+    std::vector<int> links;            // record indices
+    std::vector<uint8_t> watched, negate;      // per link: in the test / the addend is subtracted
+    std::vector<int> addendRow;        // per link: the register-file row that is the addend, -1 = a product
+    std::vector<int> addendReg;        // per link: spare VGPR of the product / of the copy of a row rewritten before the test; -1 = the row itself
+    std::vector<int> dstReg;           // per link: VGPR its sum goes to
+};
 struct QuietPlan {
     bool eligible = false;             // the program meets the conditions at all (why: which one it misses)
     bool inForce = false;              // ... and the plan pays: a quiet loop is generated
@@ -197,9 +227,22 @@ struct QuietPlan {
     // emit that add; zeroAddsDropped = the indices of those records, ascending.  sites / dropped / checked know nothing of them.
     std::vector<uint8_t> zeroAdd;
     std::vector<int> zeroAddsDropped;
+    // what the final bound pass knew at every saturating record: the bound of its A operand and of what is added to it (the
+    // product, or ACC3's X row; +inf = nothing known).  planSumGroups reads them.
+    std::vector<float> aBound, addendBound;
+    // sum groups (planSumGroups): chains of kept saturations on one accumulator row, checked by the group
+    std::vector<SumGroup> sumGroups;
+    std::vector<int> groupOf;          // per steady record: index into sumGroups, -1 = the record is no link of a group
+    int sumLinks = 0;                  // links inside groups (= saturations the grouped loop leaves to its repair stubs)
 };
 constexpr int kQuietMinGain = 32, kQuietGainPerCheck = 4;
 QuietPlan planQuiet(const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog);
+// Finds the chains of `plan` (an in-force plan of these records), cuts them into groups of at most `groupMax` links that fit the
+// spare VGPRs [spareFirst, spareEnd) and fills plan->sumGroups / groupOf / sumLinks.  A pure function of its arguments.
+constexpr int kSumGroupMax = 12;
+constexpr float kSumSmallAddend = 0.0625f, kSumSlack = 0.25f;
+void planSumGroups(QuietPlan* plan, const std::vector<MicroOp>& steadyRecords, const XlateProgram& prog, int spareFirst, int spareEnd,
+                   int groupMax = kSumGroupMax);
 
 // Translate one stream of records (encodeAsmStream(ops, nullptr, true): w0 = handler slot) into the code of a
 // whole sample LOOP that starts `codeBase` bytes after the kernel entry: PCM input of the sample (prefetched one
@@ -265,6 +308,13 @@ struct XlateImage {
     std::string quietListing;          // when listings were asked for
     QuietPlan quietPlan;
     XlateStats quiet;
+    // Where the plan has sum groups, quietCode / quietListing / quiet are the loop WITH them (stream 6): that is what the image
+    // carries and what waves run.  plainQuietCode / plainQuietListing = the same loop without groups (stream 5: byte for byte
+    // what it is for a plan without groups), kept for inspection; sumGroups = the image carries stream 6.
+    bool sumGroups = false;
+    std::vector<uint32_t> plainQuietCode;
+    std::string plainQuietListing;
+    XlateStats plainQuiet;
     uint32_t initOff = 0;   // run-once code (AsmArgs.initOff), 0 = none
     uint32_t ldsBytes = 0;  // dynamic LDS per workgroup
     uint32_t codeBytes = 0;

@@ -376,6 +376,8 @@ public:
     void note(const char* what) {
         if (text_) lines_.push_back(std::string("; ") + what);
     }
+    // issue clocks x 100 of an instruction by its mnemonic (the table below): what a plan weighs its instructions with
+    static int issueCostOf(const char* name) { return issueCost(name); }
 
 private:
     bool listing() const { return text_ != nullptr; }
@@ -478,8 +480,12 @@ constexpr int kSPrefetched = 94;                    // s94 = 1: the leading TRAM
 constexpr int kSEventNext = 28;                         // control tracks: the sample at which the next event of the block's list is due (0xFFFFFFFF: none left)
 constexpr int kSEventPtr = 26;                          // s[26:27]: address of that event's record (fx_xlate.hpp TrackEvent)
 constexpr int kKernargTracks = 0xb8;                    // AsmArgs.tracks (fx_asm.hpp)
-constexpr int kKernargQuietLeft = 0xc0;                 // AsmArgs.stages of an UNSTAGED launch: the quiet loop's exit words, one per wavefront (fx_xlate.hpp QuietPlan)
-constexpr int kSWave = 2;                               // s2 = wavefront of the launch
+constexpr int kKernargQuietLeft = 0xc0;                 // AsmArgs.stages of an UNSTAGED launch: the quiet loop's exit words, one per wavefront - pairs {exit sample, repairs} for a loop with sum groups (fx_xlate.hpp QuietPlan, SumGroup)
+// the quiet loop with sum groups (fx_xlate.hpp SumGroup; s4..s7 are free in unstaged generated code): s[4:5] = lanes whose chain
+// value a repair left above the threshold (the next group's test ORs them in), s6 = repairs of this wavefront in this launch.
+// Its exit words are PAIRS per wavefront: {sample at which it left, repairs}.
+constexpr int kSSumForce = 4, kSSumRepairs = 6;
+constexpr int kSWave = 2;                             // s2 = wavefront of the launch
 constexpr int kSSliceShift = 8;                        // unstaged programs with time-sliced priorities: log2 of a slice in 100 MHz ticks (emitInit)
 constexpr int kSHoistOk = 95;                       // s95 = 1: this launch may issue leading TRAM reads one sample ahead (emitInit)
 constexpr int kVRing = 30;                          // staged programs: lane * 4 + the LDS buffer of this sample's packets (sent and requested, see stageRequest)

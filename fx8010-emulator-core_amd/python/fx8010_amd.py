@@ -27,7 +27,7 @@ INFO = {
     "host_staged_blocks": 33, "host_inplace_blocks": 34, "bus_blocks": 35, "meter_launches": 36, "imajor_blocks": 37,
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
     "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
-    "register_list_sets": 50, "register_list_gets": 51,
+    "register_list_sets": 50, "register_list_gets": 51, "xlate_sum_groups": 52, "xlate_sum_links": 53, "xlate_quiet_repairs": 54,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -251,7 +251,8 @@ class FrontEnd(_Reports):
     def translate(self, vgprs=0, stream=0):
         """gfx950 machine code of the program as the batch path generates it: (code bytes, assembler listing).
         stream: 0 steady fast, 1 steady exact, 2 last-sample fast, 3 last-sample exact, 4 run-once code, 5 steady quiet
-        (empty when the program has no quiet loop: quiet_plan() says why)."""
+        (empty when the program has no quiet loop: quiet_plan() says why), 6 steady quiet with sum groups - what the device runs
+        in place of stream 5 where the plan has groups (empty where it has none)."""
         cap, tcap = 1 << 20, 1 << 23
         code = C.create_string_buffer(cap)
         text = C.create_string_buffer(tcap)
@@ -264,7 +265,10 @@ class FrontEnd(_Reports):
         """the plan of the quiet loop (fxp_quiet_plan), read-only: in_force, eligible, why, the counts, checked = [(register-file
         row, register name or None, bound)], dropped = record indices whose saturation the quiet loop omits, records = the
         steady stream's records as an (R, 8) uint32 array (w0 handler slot, w2..w4 A / X / Y, w5 R, w6 / w7 flags or INTERP's 1 - X),
-        zero_adds_dropped = sorted record indices whose add of a uniform +0 the quiet loop does not emit"""
+        zero_adds_dropped = sorted record indices whose add of a uniform +0 the quiet loop does not emit,
+        sum_groups = [{row, threshold, first, last, watch_start, start_reg, start_bound, links, watched, negate, addend_row,
+        addend_reg, dst_reg, addend_bound}] (fx_xlate.hpp SumGroup: per-link lists; links = record indices; the bounds are the
+        plan's running bounds of the chain's start and of every addend), sum_links = the links in them"""
         n = int(self._lib.fxp_quiet_plan(self._h, int(vgprs), None, 0))
         if n < 0:
             raise RuntimeError("fxp_quiet_plan: %d %s" % (n, self.last_error()))
@@ -278,7 +282,18 @@ class FrontEnd(_Reports):
         checked = [(int(a), names[b] if 0 <= b < len(names) else None, float(np.array([v], dtype=np.int32).view(np.float32)[0])) for a, b, v in rows]
         at = 9 + 3 * c
         z = at + d + 8 * r
-        return {"zero_adds_dropped": [int(v) for v in w[z + 1: z + 1 + int(w[z])]], "in_force": bool(w[0]), "eligible": bool(w[1]), "why": why, "sites": int(w[2]), "fast_dropped": int(w[3]), "quiet_dropped": int(w[4]),
+        g = z + 1 + int(w[z])
+        groups, q = [], g + 2
+        for _ in range(int(w[g])):
+            row, bits, n, flags, start, sbits = (int(v) for v in w[q: q + 6])
+            per = w[q + 6: q + 6 + 7 * n].reshape(n, 7)
+            f32 = lambda v: float(np.array([v], dtype=np.int32).view(np.float32)[0])   # noqa: E731
+            groups.append({"row": row, "threshold": float(np.array([bits], dtype=np.int32).view(np.float32)[0]), "first": bool(flags & 1), "last": bool(flags & 2),
+                           "watch_start": bool(flags & 4), "start_reg": start, "links": [int(v) for v in per[:, 0]], "watched": [bool(v) for v in per[:, 1]],
+                           "negate": [bool(v) for v in per[:, 2]], "addend_row": [int(v) for v in per[:, 3]], "addend_reg": [int(v) for v in per[:, 4]],
+                           "dst_reg": [int(v) for v in per[:, 5]], "addend_bound": [f32(v) for v in per[:, 6]], "start_bound": f32(sbits)})
+            q += 6 + 7 * n
+        return {"sum_groups": groups, "sum_links": int(w[g + 1]), "zero_adds_dropped": [int(v) for v in w[z + 1: z + 1 + int(w[z])]], "in_force": bool(w[0]), "eligible": bool(w[1]), "why": why, "sites": int(w[2]), "fast_dropped": int(w[3]), "quiet_dropped": int(w[4]),
                 "check_instructions": int(w[5]), "checked": checked, "dropped": [int(v) for v in w[at: at + d]],
                 "records": w[at + d: at + d + 8 * r].view(np.uint32).reshape(r, 8)}
 

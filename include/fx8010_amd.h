@@ -759,7 +759,12 @@ enum {
     FXB_INFO_INSTANCE_ROTATIONS = 46,  /* launches of the kernel fx_inst_scatter_rot - by fxb_load_instances_rotated - since creation (summed over shards) */
     FXB_INFO_GAIN_LIST_SETS = 49,      /* launches of the kernel fx_gain_scatter - by fxb_bus_set_gains_list / _send_gains_list / _feed_gains_list - since creation (summed over shards) */
     FXB_INFO_REGISTER_LIST_SETS = 50,  /* launches of the kernel fx_reg_scatter - by fxb_set_registers_list - since creation (summed over shards) */
-    FXB_INFO_REGISTER_LIST_GETS = 51   /* launches of the kernel fx_reg_gather - by fxb_get_registers_list - since creation (summed over shards) */
+    FXB_INFO_REGISTER_LIST_GETS = 51,  /* launches of the kernel fx_reg_gather - by fxb_get_registers_list - since creation (summed over shards) */
+    FXB_INFO_XLATE_SUM_GROUPS = 52,    /* sum groups of the quiet loop in force (fxp_translate stream 6; 0: the loop has none, or there is no loop): chains of
+                                          saturating sums on one accumulator that the loop tests once per group instead of saturating every link */
+    FXB_INFO_XLATE_SUM_LINKS = 53,     /* ... and the saturating instructions inside those groups */
+    FXB_INFO_XLATE_QUIET_REPAIRS = 54  /* how often the last launch re-did a sum group with its saturations (a lane's partial sum above the group's
+                                          threshold), summed over wavefronts; a repair does not leave the loop; waits for that launch (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
@@ -819,7 +824,17 @@ int64_t fxp_translate(fxp_handle* h, int vgprs, int stream, void* code, int64_t 
  *   [4] ... the quiet loop drops  [5] vector instructions of the head check  [6] C = checked rows  [7] D = dropped records
  *   [8] R = records of the steady stream; then C x {register-file row, register index or -1, bound as float bits},
  *   D record indices, R x 8 record words; then Z and Z record indices: the records whose add of a uniform +0 the quiet loop
- *   does not emit because the other side cannot be -0 (ascending; no part of the counts above).
+ *   does not emit because the other side cannot be -0 (ascending; no part of the counts above); then G and L: the sum groups of
+ *   the loop and the links in them (below), and G x {register-file row R of the chain, threshold T as float bits, N = links of
+ *   the group, flags (1 first, 2 last group of its chain, 4 the chain's start is an operand of the test), VGPR that holds the
+ *   value in front of the group, running bound of the chain's start as float bits, N x {record index, 1 = its sum is an
+ *   operand of the test (watched), 1 = the addend is subtracted, register-file row that is the addend or -1 for a product,
+ *   VGPR the addend is kept in or -1 for the row itself, VGPR of its sum, running bound of the addend as float bits}}.
+ * stream 6 = the quiet loop WITH sum groups (size 0 where the plan has none - no chain, or a VGPR build without spare registers):
+ * the loop of stream 5 in which the kept saturations of an accumulator chain - R = sat(R +- addend), link after link - are
+ * tested once per group of links (max |watched sums| against T) and re-done, in a stub behind the loop, only when a lane with an
+ * instance is above T.  Where stream 6 exists it is what the device runs in place of stream 5 (FXB_INFO_XLATE_SUM_GROUPS,
+ * _SUM_LINKS, _QUIET_REPAIRS); stream 5 reads the same either way.
  * Copies at most `cap` words, returns the number of words there are (negative FX_E_*); fxp_last_error says why a program has
  * no quiet loop. */
 int64_t fxp_quiet_plan(fxp_handle* h, int vgprs, int32_t* out, int64_t cap);

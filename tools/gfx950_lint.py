@@ -494,12 +494,13 @@ def lint_index_mode(ins, entry_state=UNKNOWN, entries=None, kernel_labels=(), an
 
 
 # ------------------------------------------------------------------------------------------------- translated programs
-def image_listing(fe, vgprs=0):
+def image_listing(fe, vgprs=0, quiet_stream=5):
     """The hole image of a translated program as ONE listing, laid out as fx_xlate.cpp planXlate does:
     [steady fast][last fast][steady exact][last exact][run-once][steady quiet], each on a 64-byte boundary (s_nop filler).
-    Returns (listing, bytes): the encoder's byte count, which the re-assembled listing must reproduce."""
+    quiet_stream=6 lays it out with the quiet loop that has sum groups (what the device runs where the plan has groups), repair
+    stubs included.  Returns (listing, bytes): the encoder's byte count, which the re-assembled listing must reproduce."""
     parts, at = [], 0
-    for s in (0, 2, 1, 3, 4, 5):
+    for s in (0, 2, 1, 3, 4, quiet_stream):
         code, listing = fe.translate(vgprs, s)
         if not code:
             continue   # no fast streams (a non-finite uniform operand), no run-once code, no quiet loop
