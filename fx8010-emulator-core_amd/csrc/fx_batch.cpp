@@ -99,6 +99,8 @@ Batch::~Batch() {
     freeBlock(hInstRec_, true);
     freeBlock(regList_, false);
     freeBlock(hRegList_, true);
+    freeBlock(tramStage_, false);
+    freeBlock(hTramStage_, true);
     if (evInst_) (void)hipEventDestroy(evInst_);
     if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS
@@ -904,6 +906,8 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_GAIN_LIST_SETS) return gainListSets_;
     if (what == FXB_INFO_REGISTER_LIST_SETS) return regListSets_;
     if (what == FXB_INFO_REGISTER_LIST_GETS) return regListGets_;
+    if (what == FXB_INFO_TRAM_LIST_SETS) return tramListSets_;
+    if (what == FXB_INFO_TRAM_LIST_GETS) return tramListGets_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

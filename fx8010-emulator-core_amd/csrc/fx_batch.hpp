@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
@@ -20,6 +21,7 @@
 #include "fx_imajor.hpp"
 #include "fx_instances.hpp"
 #include "fx_registers.hpp"
+#include "fx_tram.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -281,6 +283,19 @@ public:
     int reserveRegisterList(int nKeys, int64_t count);
     int setRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* values);
     int getRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, float* values);
+    // Delay-line windows by list (fx_tram.hpp; include/fx8010_amd.h "Delay-line windows by list"; fx_batch_tram.cpp).  `list` holds
+    // `count` instance numbers of THIS batch, `pos` the window of the caller's values each of them has (null: entry i has window
+    // i); `in` is a set (stride 0: one window for all, FXB_TRAM_BROADCAST), `out` a get.  checkTramList holds the refusals that read
+    // nothing but the arguments (Sharded asks for the whole handle); reserveTramList lowers the program, refuses a window the line
+    // does not have, and is the allocating half (staging, the event: FX_E_MEMORY changes nothing) - count == 0 there still checks
+    // the window, so that every shard is asked before any shard changes a word.  tramList with count == 0 is a shard that owns
+    // none of the entries: nothing is launched and nothing changes.  A set is queued on the handle's stream behind every block
+    // queued so far on whatever stream (ev1_, evBus_) and in front of evInst_, as a register list set is; it waits on the HOST for
+    // the previous list or instance call (the staging is reused), so a call of several pieces blocks between them.  A get is
+    // synchronous.  There is no host mirror of delay memory: nothing else changes.
+    static int checkTramList(bool set, int which, const int64_t* list, int64_t count, int64_t n, int first, int nWords, const void* values, unsigned flags, std::string* why);
+    int reserveTramList(bool set, int which, int64_t count, int first, int nWords, unsigned flags);
+    int tramList(int which, const int64_t* list, const int64_t* pos, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -723,6 +738,12 @@ private:
     static size_t regListWords(int nKeys, int64_t count) { return (size_t)count * 2 + (size_t)nKeys * (size_t)count + (size_t)nKeys; }
     int stageRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, RegListArgs* a);
     int64_t regListSets_ = 0, regListGets_ = 0;    // FXB_INFO_REGISTER_LIST_SETS / _GETS
+    // delay-line windows by list (fx_batch_tram.cpp): a staging pair of 32-bit words of its own - [entries] instance numbers
+    // (64-bit), then the windows of a piece, at most kInstScratchBytes of them - grown by reserveTramList and reused: a piece first
+    // waits on the HOST for the previous instance call or list set (evInst_, instLaunched_)
+    Block<uint32_t> tramStage_, hTramStage_;
+    int64_t tramEntriesPerPiece(int nWords) const { return (int64_t)std::max<size_t>(kInstScratchBytes / ((size_t)nWords * 4), 1); }
+    int64_t tramListSets_ = 0, tramListGets_ = 0;  // FXB_INFO_TRAM_LIST_SETS / _GETS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

@@ -313,6 +313,12 @@ int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, c
 int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.getRegistersList(keys, n_keys, list, count, values); }) : FX_E_ARG;
 }
+int fxb_set_tram_list(fxb_handle* h, int which, const int64_t* list, int64_t count, int first, int n_words, const float* values, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.setTramList(which, list, count, first, n_words, values, flags); }) : FX_E_ARG;
+}
+int fxb_get_tram_list(fxb_handle* h, int which, const int64_t* list, int64_t count, int first, int n_words, float* values, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.getTramList(which, list, count, first, n_words, values, flags); }) : FX_E_ARG;
+}
 int fxb_get_tram_i(fxb_handle* h, int which, int64_t inst, float* out, int n_slots) {
     return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.getTramAt(which, inst, out, n_slots); }) : FX_E_ARG;
 }

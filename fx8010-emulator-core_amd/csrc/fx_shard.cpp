@@ -842,6 +842,25 @@ int Sharded::registersList(bool set, const char* const* keys, int nKeys, const i
     return fan([&](int k, Batch& b) { return b.setRegistersList(regs, listOf(k), posOf(k), countOf(k), count, in); });
 }
 
+int Sharded::tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set) {
+    Serial serial(api_);
+    lastError_.clear();
+    const void* values = set ? static_cast<const void*>(in) : static_cast<const void*>(out);
+    // everything that reads nothing but the arguments, for the whole handle and with the caller's indices
+    if (Batch::checkTramList(set, which, list, count, n_, first, nWords, values, flags, &lastError_) != 0) return FX_E_ARG;
+    if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
+    const bool one = shards_.size() == 1;
+    const std::vector<ListPart> parts = (one || count == 0) ? std::vector<ListPart>(shards_.size()) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto posOf = [&](int k) { return (one || (flags & FXB_TRAM_BROADCAST)) ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    // every shard is asked first - the window against its line, its staging; only when all of them could is anything queued
+    // anywhere (staging that has grown stays: it is no state)
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveTramList(set, which, countOf(k), first, nWords, flags); })) return rc;
+    if (count == 0 || nWords == 0) return 0;
+    return fan([&](int k, Batch& b) { return b.tramList(which, listOf(k), posOf(k), countOf(k), first, nWords, set ? in : nullptr, set ? nullptr : out, flags); });
+}
+
 int Sharded::getTramAt(int which, int64_t inst, float* out, int nSlots) {
     Serial serial(api_);
     lastError_.clear();
@@ -873,7 +892,7 @@ int64_t Sharded::info(int what) {
     fan([&](int k, Batch& b) { part[(size_t)k] = b.info(what); return 0; });
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
         what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
-        what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS ||
+        what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS || what == FXB_INFO_TRAM_LIST_SETS || what == FXB_INFO_TRAM_LIST_GETS ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

@@ -143,6 +143,16 @@ public:
     int getRegistersList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, float* values) {
         return registersList(false, keys, nKeys, list, count, nullptr, values);
     }
+    // delay-line windows by list (Batch "Delay-line windows by list"): `list` holds GLOBAL instance numbers, window i of `values`
+    // belongs to list[i].  The whole list is checked first; then every shard is asked for the window and its staging
+    // (reserveTramList) before any shard is posted a word; each shard gets the entries that fall to it with local numbers and
+    // their windows of `values`.  A shard without an entry launches nothing and changes nothing.
+    int setTramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* values, unsigned flags) {
+        return tramList(which, list, count, first, nWords, values, nullptr, flags, true);
+    }
+    int getTramList(int which, const int64_t* list, int64_t count, int first, int nWords, float* values, unsigned flags) {
+        return tramList(which, list, count, first, nWords, nullptr, values, flags, false);
+    }
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
 
@@ -157,6 +167,7 @@ public:
 private:
     int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
     int registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out);
+    int tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set);
     struct Worker {
         std::unique_ptr<Batch> batch;
         int64_t first = 0, count = 0;

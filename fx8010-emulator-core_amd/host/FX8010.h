@@ -337,6 +337,22 @@ public:
             throw std::runtime_error(std::string("FX8010Batch::getRegistersList: ") + fxb_last_error(h_));
         return values;
     }
+    // Delay-line windows by list (include/fx8010_amd.h "Delay-line windows by list"): values[i * nWords + j] is word first + j of
+    // delay line `which` (0 iTRAM, 1 xTRAM) of instance list[i]; flags: FXB_TRAM_LOGICAL (the index is the age in the ring),
+    // FXB_TRAM_BROADCAST (set only: values is one window of nWords for every listed instance).  The set is stream-ordered behind
+    // the queued blocks (sync() covers it); the get is synchronous.
+    void setTramList(int which, const std::vector<int64_t>& list, int first, int nWords, const std::vector<float>& values, unsigned flags = 0) {
+        const size_t windows = (flags & FXB_TRAM_BROADCAST) ? 1 : list.size();
+        if (nWords < 0 || values.size() != windows * (size_t)nWords) throw std::runtime_error("FX8010Batch::setTramList: values must hold one window of nWords per listed instance (one in all with FXB_TRAM_BROADCAST)");
+        if (fxb_set_tram_list(h_, which, list.data(), (int64_t)list.size(), first, nWords, values.data(), flags) != 0)
+            throw std::runtime_error(std::string("FX8010Batch::setTramList: ") + fxb_last_error(h_));
+    }
+    std::vector<float> getTramList(int which, const std::vector<int64_t>& list, int first, int nWords, unsigned flags = 0) {
+        std::vector<float> values(list.size() * (size_t)(nWords > 0 ? nWords : 0));
+        if (fxb_get_tram_list(h_, which, list.data(), (int64_t)list.size(), first, nWords, values.data(), flags) != 0)
+            throw std::runtime_error(std::string("FX8010Batch::getTramList: ") + fxb_last_error(h_));
+        return values;
+    }
     void resetInstances(const std::vector<int64_t>& list) {
         if (fxb_reset_instances(h_, list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::resetInstances: ") + fxb_last_error(h_));
     }

@@ -28,9 +28,11 @@ INFO = {
     "instance_words": 38, "instance_gathers": 39, "instance_scatters": 40, "bus_gain_blocks": 41, "bus_tap_blocks": 42, "bus_send_blocks": 43,
     "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
     "register_list_sets": 50, "register_list_gets": 51, "xlate_sum_groups": 52, "xlate_sum_links": 53, "xlate_quiet_repairs": 54,
+    "tram_list_sets": 55, "tram_list_gets": 56,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
+TRAM_LOGICAL, TRAM_BROADCAST = 1, 2  # FXB_TRAM_* of include/fx8010_amd.h
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -38,7 +40,7 @@ SYMBOLS = [
     "fx_instruction_counter", "fx_error_count", "fx_error_desc", "fx_error_row", "fx_control_count", "fx_control_at",
     "fx_meta_get", "fx_set_option", "fxb_set_option", "fxp_set_option", "fx_set_channels", "fx_get_channels", "fx_ready", "fx_last_error", "fx_last_create_error",
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
-    "fxb_get_register_i", "fxb_set_registers_list", "fxb_get_registers_list", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
+    "fxb_get_register_i", "fxb_set_registers_list", "fxb_get_registers_list", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_set_tram_list", "fxb_get_tram_list", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_bus_set_gains_list", "fxb_bus_set_send_gains_list", "fxb_bus_set_feed_gains_list",
@@ -89,6 +91,7 @@ def load():
     sig("fxb_shard_plan", i32, i64, i32, C.POINTER(i64), C.POINTER(i64))
     sig("fxb_shard_kernel_ms", f32, vp, i32)
     sig("fxb_prepare", i32, vp, i32, i32); sig("fxb_state_size", i64, vp); sig("fxb_save_state", i32, vp, vp, i64); sig("fxb_load_state", i32, vp, vp, i64)
+    sig("fxb_set_tram_list", i32, vp, i32, vp, i64, i32, i32, vp, C.c_uint); sig("fxb_get_tram_list", i32, vp, i32, vp, i64, i32, i32, vp, C.c_uint)
     sig("fxb_get_tram_i", i32, vp, i32, i64, vp, i32); sig("fxb_get_cursors_i", i32, vp, i64, C.POINTER(C.c_int32))
     sig("fxb_process_block_dev_shards", i32, vp, C.POINTER(vp), C.POINTER(vp), i32)
     sig("fxb_load_file", i32, vp, cp); sig("fxb_load_text", i32, vp, cp)
@@ -527,6 +530,33 @@ class Batch(_Reports):
         v = self._instance_list(instances)
         image = np.ascontiguousarray(image, dtype=np.uint8)
         return self._check(self._lib.fxb_load_instances_rotated(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(image.ctypes.data), image.size), "load_instances_rotated")
+
+    def set_tram_list(self, which, instances, first, values, logical=False):
+        """A window of delay line `which` (0 iTRAM, 1 xTRAM) of the listed instances only (include/fx8010_amd.h "Delay-line windows
+        by list"): instances are global instance numbers, no two alike; values float32 [len(instances), n_words] - row i is the
+        window of instances[i], words first .. first + n_words - 1 - or 1-D [n_words], ONE window written to every listed instance.
+        logical: the index is the age in the ring (0 = the newest word), resolved per instance on the device; else it is the slot.
+        Bit patterns.  Stream-ordered behind the queued blocks - it does not wait for them, sync() covers it."""
+        lst = self._instance_list(instances)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.ndim == 1:
+            flags, n_words = TRAM_BROADCAST, int(v.size)
+        elif v.ndim == 2 and v.shape[0] == lst.size:
+            flags, n_words = 0, int(v.shape[1])
+        else:
+            raise ValueError("set_tram_list: values must be [n_words] or [len(instances), n_words]")
+        flags |= TRAM_LOGICAL if logical else 0
+        return self._check(self._lib.fxb_set_tram_list(self._h, int(which), C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size), int(first), n_words,
+                                                       C.c_void_p(v.ctypes.data) if v.size else None, flags), "set_tram_list")
+
+    def get_tram_list(self, which, instances, first, n_words, logical=False):
+        """float32 [len(instances), n_words]: the same windows read back, bit for bit, with one gather on the device.  Synchronous;
+        repeats are allowed.  Without `logical` row i equals get_tram_i(which, instances[i], ...)[first : first + n_words]."""
+        lst = self._instance_list(instances)
+        out = np.zeros((lst.size, int(n_words)), dtype=np.float32)
+        self._check(self._lib.fxb_get_tram_list(self._h, int(which), C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size), int(first), int(n_words),
+                                                C.c_void_p(out.ctypes.data) if out.size else None, TRAM_LOGICAL if logical else 0), "get_tram_list")
+        return out
 
     def get_tram_i(self, which, inst, n_slots):
         out = np.empty(n_slots, dtype=np.float32)

@@ -286,6 +286,46 @@ int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count
  * FXB_INFO_REGISTER_LIST_SETS / _GETS count the launches of the two kernels (fx_reg_scatter, fx_reg_gather). */
 int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values);
 int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values);
+/* Delay-line windows by list: a window of ONE delay line of the instances a host names, written or read on the GPU - the burst
+ * that excites a string or comb voice at note-on, the zeros that cut a reverb tail without touching the filter registers, an
+ * impulse response or loop to pre-fill, a look at what a loop holds now.  fxb_get_tram_i handles one instance per call behind a
+ * host wait and there is no setter; the save / edit / load round trip of records moves every word of every record both ways.
+ *
+ * which: 0 = iTRAM, 1 = xTRAM, as in fxb_get_tram_i.  values[i * n_words + j] is word first + j of global instance list[i] - one
+ * voice's window is contiguous; with FXB_TRAM_BROADCAST (set only) `values` is ONE window, values[j], written to every listed
+ * instance.  Words are 32-bit patterns: nothing is checked for finiteness, signalling NaNs and payloads survive.
+ * What "word k" is depends on the flags.  A = the allocated slots of the line (FXB_INFO_ITRAM_SLOTS / _XTRAM_SLOTS), Z = its size.
+ *   without FXB_TRAM_LOGICAL: word k is slot k - the words fxb_get_tram_i shows and a record holds at stateRows (+ iSlots) + k.
+ *     Any line, ring or not; 0 <= first, 0 <= n_words, first + n_words <= A.
+ *   FXB_TRAM_LOGICAL: word a is the word that a delay write at position 0 stored a + 1 writes ago (a = 0: the newest).  Only a
+ *     line that is a ring (FXB_INFO_INSTANCE_RINGS bit `which`: A == Z); 0 <= first < Z, 1 <= n_words <= Z; the window may wrap
+ *     the end of the ring.  With p the instance's write position word of that line (fxb_get_cursors_i [2 * which]) it is slot
+ *     (p - 1 - a) mod Z, and under FX_OPT_TRAM_DANE slot (p + 1 + a) mod Z.  p is read on the device, per instance, by the kernel
+ *     that moves the window: behind every queued block, whatever position each voice stands at.
+ * fxb_set_tram_list: STREAM-ORDERED, in the frame of fxb_set_registers_list: it runs behind every block queued on the handle so
+ *   far, on whichever stream, and in front of every block queued later; fxb_sync and every call that waits for the queued blocks
+ *   cover it.  It returns when the words are staged: the caller's arrays are free on return.  A second list or instance call
+ *   behind the same running block waits on the host for the first one (the staging is reused).  The program is lowered first, so
+ *   that the delay memory exists.  Nothing but the words changes: no code is generated again, registers, meters, tracks and the
+ *   counters are as they were.
+ * fxb_get_tram_list: synchronous (it waits for everything queued).  Without FXB_TRAM_LOGICAL it equals fxb_get_tram_i word for
+ *   word on every listed instance.  Repeated instances are allowed.
+ * Size: the windows are staged in a block of the library's own of at most 64 MiB (device, and as much pinned), grown on demand
+ *   in the call.  A call whose windows exceed it runs in pieces along the list; a SET of several pieces blocks on the host between
+ *   them.  The calls are made for tens to thousands of voices times a few thousand words.
+ * Returns 0 - also for count == 0, or n_words == 0 without FXB_TRAM_LOGICAL, once the other arguments have been checked - or, with
+ *   nothing launched and nothing changed on any shard: FX_E_ARG (fxb_last_error names the argument, and for a list entry the
+ *   caller's index) for a null list or values with something to do, a negative count, count >= 2^31, `which` outside 0..1, an
+ *   unknown flag bit, FXB_TRAM_BROADCAST on a get, an instance outside 0..N-1, an instance listed twice in a set (two lanes
+ *   would race), a window outside the bounds above, FXB_TRAM_LOGICAL on a line that is no ring or that the program does not
+ *   have; FX_E_NOTREADY without a program; FX_E_MEMORY when the staging could not be allocated, on any shard.
+ * Sharded handles: every shard is asked (window, staging) before any shard changes a word; then every shard gets the entries
+ *   that fall to it with their windows of `values`.  A shard without an entry launches nothing.
+ * FXB_INFO_TRAM_LIST_SETS / _GETS count the launches of the two kernels (fx_tram_scatter, fx_tram_gather). */
+#define FXB_TRAM_LOGICAL   (1u << 0)   /* index = age in the ring, resolved per instance on the device */
+#define FXB_TRAM_BROADCAST (1u << 1)   /* set only: `values` is ONE window, written to every listed instance */
+int fxb_set_tram_list(fxb_handle* h, int which, const int64_t* list, int64_t count, int first, int n_words, const float* values, unsigned flags);
+int fxb_get_tram_list(fxb_handle* h, int which, const int64_t* list, int64_t count, int first, int n_words, float* values, unsigned flags);
 /* one instance's delay memory as the reference holds it (which: 0 = smallDelayBuffer / iTRAM, 1 = largeDelayBuffer / xTRAM; the first
  * n_slots words; words the program cannot reach read 0) and its positions {iTRAM write, iTRAM read, xTRAM write, xTRAM read}
  * (reference smallDelayWritePos ... largeDelayReadPos, include/FX8010.h:214-217) */
@@ -763,8 +803,10 @@ enum {
     FXB_INFO_XLATE_SUM_GROUPS = 52,    /* sum groups of the quiet loop in force (fxp_translate stream 6; 0: the loop has none, or there is no loop): chains of
                                           saturating sums on one accumulator that the loop tests once per group instead of saturating every link */
     FXB_INFO_XLATE_SUM_LINKS = 53,     /* ... and the saturating instructions inside those groups */
-    FXB_INFO_XLATE_QUIET_REPAIRS = 54  /* how often the last launch re-did a sum group with its saturations (a lane's partial sum above the group's
+    FXB_INFO_XLATE_QUIET_REPAIRS = 54, /* how often the last launch re-did a sum group with its saturations (a lane's partial sum above the group's
                                           threshold), summed over wavefronts; a repair does not leave the loop; waits for that launch (summed over shards) */
+    FXB_INFO_TRAM_LIST_SETS = 55,      /* launches of the kernel fx_tram_scatter - by fxb_set_tram_list - since creation (summed over shards) */
+    FXB_INFO_TRAM_LIST_GETS = 56       /* launches of the kernel fx_tram_gather - by fxb_get_tram_list - since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
