@@ -101,6 +101,8 @@ Batch::~Batch() {
     freeBlock(hRegList_, true);
     freeBlock(tramStage_, false);
     freeBlock(hTramStage_, true);
+    freeBlock(meterStage_, false);
+    freeBlock(hMeterStage_, true);
     if (evInst_) (void)hipEventDestroy(evInst_);
     if (evBus_) (void)hipEventDestroy(evBus_);
 #ifdef FX_DIAGNOSTICS
@@ -908,6 +910,9 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_REGISTER_LIST_GETS) return regListGets_;
     if (what == FXB_INFO_TRAM_LIST_SETS) return tramListSets_;
     if (what == FXB_INFO_TRAM_LIST_GETS) return tramListGets_;
+    if (what == FXB_INFO_METER_SELECTS) return meterSelects_;
+    if (what == FXB_INFO_METER_LIST_READS) return meterListReads_;
+    if (what == FXB_INFO_METER_LIST_RESETS) return meterListResets_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

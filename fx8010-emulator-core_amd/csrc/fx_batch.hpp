@@ -26,6 +26,7 @@
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
 #include "fx_meter.hpp"
+#include "fx_meter_list.hpp"
 #include "fx_knobs.hpp"
 #include "fx_model.hpp"
 
@@ -296,6 +297,23 @@ public:
     static int checkTramList(bool set, int which, const int64_t* list, int64_t count, int64_t n, int first, int nWords, const void* values, unsigned flags, std::string* why);
     int reserveTramList(bool set, int which, int64_t count, int first, int nWords, unsigned flags);
     int tramList(int which, const int64_t* list, const int64_t* pos, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags);
+    // Meter queries by list (fx_meter_list.hpp; include/fx8010_amd.h "Meter queries by list"; fx_batch_meter_list.cpp).  The
+    // check... functions hold the refusals that read nothing but the arguments (Sharded asks for the whole handle); the reserve...
+    // functions are the allocating half (staging, the event: FX_E_MEMORY changes nothing; FX_E_ARG while metering is off) and take
+    // what falls to THIS batch - nothing to do there reserves nothing.  meterSelect looks at the local columns first .. first +
+    // nRange - 1, writes the min(M, cap) smallest matching numbers firstGlobal + (column - first) to `list`, ascending, and returns
+    // M; nothing beyond min(M, cap) is touched.  meterReadList writes column pos[i] (null: i) of the caller's [channels][total]
+    // arrays for list[i].  Both are synchronous.  meterResetList is queued on the handle's stream behind every block queued so
+    // far on whatever stream (ev1_, evBus_) and in front of evInst_, as a register list set is; it waits on the HOST only for the
+    // previous list or instance call.  With count == 0 (a shard that owns no entry) nothing is launched and nothing changes.
+    // None of them touches meterSamples_.
+    static int checkMeterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
+    static int checkMeterList(const char* name, const int64_t* list, int64_t count, int64_t n, bool unique, std::string* why);
+    int reserveMeterSelect(int64_t nRange, int64_t cap);
+    int reserveMeterList(int64_t count, bool gather);
+    int64_t meterSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
+    int meterReadList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
+    int meterResetList(const int64_t* list, int64_t count);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -744,6 +762,12 @@ private:
     Block<uint32_t> tramStage_, hTramStage_;
     int64_t tramEntriesPerPiece(int nWords) const { return (int64_t)std::max<size_t>(kInstScratchBytes / ((size_t)nWords * 4), 1); }
     int64_t tramListSets_ = 0, tramListGets_ = 0;  // FXB_INFO_TRAM_LIST_SETS / _GETS
+    // meter queries by list (fx_batch_meter_list.cpp): one staging pair of 64-bit words for the three calls - a select's chunk
+    // offsets, total and list; a list call's list and packed rows - grown by the reserve... functions and reused: the synchronous
+    // calls have drained everything, a reset first waits on the HOST for the previous instance call or list set (evInst_)
+    Block<unsigned long long> meterStage_, hMeterStage_;
+    int reserveMeterStage(size_t words, bool needEvent);
+    int64_t meterSelects_ = 0, meterListReads_ = 0, meterListResets_ = 0;   // FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

@@ -1,0 +1,215 @@
+// fx_batch_meter_list.cpp — the meter queries by list of one batch: the instances whose meter passes a threshold, compacted on
+// the device into an ascending list; the accumulators of listed instances gathered, and zeroed (include/fx8010_amd.h "Meter
+// queries by list", fx_batch.hpp "Meter queries by list", kernels: fx_meter_list.hip).
+//
+// The select and the list read are synchronous: they wait as sync() does - which covers a list reset still in flight - launch on
+// the handle's stream and wait for it.  The list reset rides the frame of the register list set (fx_batch_registers.cpp): it
+// waits on the HOST for the previous instance call or list set only, copies the list into pinned staging (the caller's list is
+// free on return) and from there to the device, makes the handle's stream wait for every block queued so far on whatever stream
+// (ev1_, evBus_ - a block's meter launch sits in front of its ev1_ record), launches fx_meter_zero there and records evInst_ behind
+// it: every later block, on whichever stream, is ordered behind it as behind a copy of instances.
+//
+// One staging pair of 64-bit words serves the three calls - none of them can find it in use: the synchronous two have drained
+// everything, the reset waits for evInst_ first.  A select lays it out as [chunk counts / offsets][the total][the list], so that
+// the total and the head of the list come back in one copy; a list call as [the list][the packed rows].  meterSamples_ and the
+// host's view of everything else stay as they are: the list calls touch accumulator words only.
+#include "fx_batch.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "../../include/fx8010_amd.h"
+
+namespace fx {
+
+namespace {
+// entries of a select's list that travel with the total in the first copy
+constexpr int64_t kSelectHead = 4096;
+size_t selectWords(int64_t nRange, int64_t cap) { return (size_t)meterSelectChunks(nRange) + 1 + (size_t)std::min(cap, nRange); }
+size_t listWords(int channels, int64_t count, bool gather) { return (size_t)count + (gather ? (meterPackedBytes(channels, count) + 7) / 8 : 0); }
+}  // namespace
+
+int Batch::checkMeterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why) {
+    if (stat < FXB_METER_ENERGY || stat > FXB_METER_NONFINITE) { *why = "meter_select: stat must be 0..3 (FXB_METER_ENERGY .. FXB_METER_NONFINITE)"; return FX_E_ARG; }
+    if (flags & ~(unsigned)FXB_METER_BELOW) { *why = "meter_select: flags has an unknown bit"; return FX_E_ARG; }
+    if (std::isnan(threshold)) { *why = "meter_select: the threshold is NaN"; return FX_E_ARG; }
+    if (first < 0 || nRange < 0 || first > n || nRange > n - first) { *why = "meter_select: first .. first + n_range - 1 must lie in 0.." + std::to_string(n - 1); return FX_E_ARG; }
+    if (cap < 0) { *why = "meter_select: cap < 0"; return FX_E_ARG; }
+    if (cap > 0 && !list) { *why = "meter_select: a null list with cap > 0"; return FX_E_ARG; }
+    return 0;
+}
+
+int Batch::checkMeterList(const char* name, const int64_t* list, int64_t count, int64_t n, bool unique, std::string* why) {
+    const std::string who(name);
+    if (count < 0) { *why = who + ": count < 0"; return FX_E_ARG; }
+    if (count == 0) return 0;
+    if (!list) { *why = who + ": a null list"; return FX_E_ARG; }
+    if (count >= ((int64_t)1 << 31)) { *why = who + ": count must stay below 2^31"; return FX_E_ARG; }
+    for (int64_t i = 0; i < count; ++i)
+        if (list[i] < 0 || list[i] >= n) { *why = who + ": entry " + std::to_string(i) + " of the list is outside 0.." + std::to_string(n - 1); return FX_E_ARG; }
+    if (!unique) return 0;
+    // repeats: a bitmap over the instances where that is the cheaper one to clear, else a sorted copy (checkRegisterList)
+    int64_t twice = -1;
+    if ((n + 63) / 64 <= 16 * count) {
+        std::vector<uint64_t> seen((size_t)((n + 63) / 64), 0);
+        for (int64_t i = 0; i < count && twice < 0; ++i) {
+            uint64_t& word = seen[(size_t)(list[i] >> 6)];
+            const uint64_t bit = (uint64_t)1 << (list[i] & 63);
+            if (word & bit) twice = list[i];
+            word |= bit;
+        }
+    } else {
+        std::vector<int64_t> sorted(list, list + count);
+        std::sort(sorted.begin(), sorted.end());
+        const auto at = std::adjacent_find(sorted.begin(), sorted.end());
+        if (at != sorted.end()) twice = *at;
+    }
+    if (twice >= 0) { *why = who + ": instance " + std::to_string(twice) + " is listed more than once (reset)"; return FX_E_ARG; }
+    return 0;
+}
+
+int Batch::reserveMeterStage(size_t words, bool needEvent) {
+    (void)hipSetDevice(device_);
+    if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (words == 0) return 0;
+    if (needEvent && !evInst_) {
+        const hipError_t e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming);
+        if (e != hipSuccess) { evInst_ = nullptr; return hipFail(hipErrorOutOfMemory, "meter list event"); }
+    }
+    if (words <= meterStage_.cap && words <= hMeterStage_.cap) return 0;
+    // (the previous list reset may still be reading the block that goes)
+    if (instLaunched_ && hipEventSynchronize(evInst_) == hipSuccess) instLaunched_ = false;
+    int rc = growBlock(meterStage_, words, false, "hipMalloc meter list staging");
+    if (rc == 0) rc = growBlock(hMeterStage_, words, true, "pinned staging of the meter list");
+    return rc;
+}
+
+int Batch::reserveMeterSelect(int64_t nRange, int64_t cap) { return reserveMeterStage(nRange > 0 ? selectWords(nRange, cap) : 0, false); }
+int Batch::reserveMeterList(int64_t count, bool gather) { return reserveMeterStage(count > 0 ? listWords(prog_.numChannels, count, gather) : 0, !gather); }
+
+int64_t Batch::meterSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
+    (void)hipSetDevice(device_);
+    if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (nRange == 0) return 0;
+    if (selectWords(nRange, cap) > meterStage_.cap || selectWords(nRange, cap) > hMeterStage_.cap) return fail(FX_E_ARG, "meter_select: no staging reserved (reserveMeterSelect)");
+    const int rc = sync();
+    if (rc != 0) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == 8, "meter list staging");
+    const size_t chunks = (size_t)meterSelectChunks(nRange);
+    const int64_t room = std::min(cap, nRange);
+    MeterSelectArgs a{};
+    a.rows = dMeter_;
+    a.offsets = meterStage_.p;
+    a.list = room > 0 ? reinterpret_cast<long long*>(meterStage_.p + chunks + 1) : nullptr;
+    a.n = n_;
+    a.nPad = nPad_;
+    a.first = first;
+    a.nRange = nRange;
+    a.firstGlobal = firstGlobal;
+    a.cap = room;
+    a.threshold = threshold;
+    a.channels = prog_.numChannels;
+    a.stat = stat;
+    a.below = below ? 1 : 0;
+    hipError_t e = launchMeterSelect(a, stream_);
+    if (e == hipSuccess) ++meterSelects_;
+    // the total and the head of the list in one copy; the rest of a long list once the total says how long it is
+    const int64_t head = std::min(room, kSelectHead);
+    unsigned long long* const hTotal = hMeterStage_.p + chunks;
+    if (e == hipSuccess) e = hipMemcpyAsync(hTotal, meterStage_.p + chunks, (size_t)(1 + head) * 8, hipMemcpyDeviceToHost, stream_);
+    hipError_t se = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return hipFail(e, "meter_select");
+    const int64_t m = (int64_t)*hTotal, take = std::min(m, room);
+    if (take > head) {
+        e = hipMemcpyAsync(hTotal + 1 + head, meterStage_.p + chunks + 1 + head, (size_t)(take - head) * 8, hipMemcpyDeviceToHost, stream_);
+        se = hipStreamSynchronize(stream_);
+        if (e == hipSuccess) e = se;
+        if (e != hipSuccess) return hipFail(e, "meter_select: the list");
+    }
+    if (take > 0) std::memcpy(list, hTotal + 1, (size_t)take * 8);
+    return m;
+}
+
+int Batch::meterReadList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset) {
+    (void)hipSetDevice(device_);
+    if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (count == 0) return 0;
+    const int channels = prog_.numChannels;
+    const size_t k = (size_t)count, words = listWords(channels, count, true);
+    if (words > meterStage_.cap || words > hMeterStage_.cap) return fail(FX_E_ARG, "meter_read_list: no staging reserved (reserveMeterList)");
+    const int rc = sync();
+    if (rc != 0) return rc;
+    std::memcpy(hMeterStage_.p, list, k * 8);
+    MeterListArgs a{};
+    a.rows = dMeter_;
+    a.list = reinterpret_cast<const long long*>(meterStage_.p);
+    a.packed = meterStage_.p + k;
+    a.count = count;
+    a.n = n_;
+    a.nPad = nPad_;
+    a.channels = channels;
+    a.reset = reset ? 1 : 0;
+    hipError_t e = hipMemcpyAsync(meterStage_.p, hMeterStage_.p, k * 8, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) e = launchMeterGather(a, stream_);
+    if (e == hipSuccess) {
+        ++meterListReads_;
+        e = hipMemcpyAsync(hMeterStage_.p + k, meterStage_.p + k, meterPackedBytes(channels, count), hipMemcpyDeviceToHost, stream_);
+    }
+    const hipError_t se = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return hipFail(e, "meter_read_list: the gather");
+    // the packed side: energy [channels][count], then peak, full_scale, nonfinite (fx_meter_list.hpp)
+    const size_t rowWords = (size_t)channels * k;
+    const char* packed = reinterpret_cast<const char*>(hMeterStage_.p + k);
+    const char* part[4] = {packed, packed + rowWords * 8, packed + rowWords * 12, packed + rowWords * 16};
+    char* out[4] = {reinterpret_cast<char*>(energy), reinterpret_cast<char*>(peak), reinterpret_cast<char*>(fullScale), reinterpret_cast<char*>(nonfinite)};
+    for (int r = 0; r < 4; ++r) {
+        if (!out[r]) continue;
+        const size_t bytes = r == 0 ? 8 : 4;
+        for (int c = 0; c < channels; ++c) {
+            const char* from = part[r] + (size_t)c * k * bytes;
+            char* to = out[r] + (size_t)c * (size_t)total * bytes;
+            if (!pos) std::memcpy(to, from, k * bytes);
+            else for (size_t i = 0; i < k; ++i) std::memcpy(to + (size_t)pos[i] * bytes, from + i * bytes, bytes);
+        }
+    }
+    return 0;
+}
+
+int Batch::meterResetList(const int64_t* list, int64_t count) {
+    (void)hipSetDevice(device_);
+    if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (count == 0) return 0;
+    const size_t k = (size_t)count;
+    if (k > meterStage_.cap || k > hMeterStage_.cap || !evInst_) return fail(FX_E_ARG, "meter_reset_list: no staging reserved (reserveMeterList)");
+    if (instLaunched_) {
+        const hipError_t e = hipEventSynchronize(evInst_);
+        if (e != hipSuccess) return hipFail(e, "meter_reset_list: waiting for the previous call");
+        instLaunched_ = false;
+    }
+    std::memcpy(hMeterStage_.p, list, k * 8);
+    MeterListArgs a{};
+    a.rows = dMeter_;
+    a.list = reinterpret_cast<const long long*>(meterStage_.p);
+    a.count = count;
+    a.n = n_;
+    a.nPad = nPad_;
+    a.channels = prog_.numChannels;
+    hipError_t e = hipMemcpyAsync(meterStage_.p, hMeterStage_.p, k * 8, hipMemcpyHostToDevice, stream_);
+    // behind every block queued so far, on whichever stream it was queued - its meter launch included
+    if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
+    if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+    if (e == hipSuccess) e = launchMeterZero(a, stream_);
+    if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);   // (nothing may still read the staging)
+        return hipFail(e, "meter_reset_list: queueing the zeroing");
+    }
+    instLaunched_ = true;
+    ++meterListResets_;
+    return 0;
+}
+
+}  // namespace fx

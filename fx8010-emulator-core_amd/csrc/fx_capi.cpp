@@ -287,6 +287,15 @@ int fxb_meter_enable(fxb_handle* h, int on) { return h ? guardCode(&h->batch.fro
 int fxb_meter_read(fxb_handle* h, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterRead(energy, peak, full_scale, nonfinite, reset != 0); }) : FX_E_ARG;
 }
+int64_t fxb_meter_select(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelect(stat, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
+}
+int fxb_meter_read_list(fxb_handle* h, const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadList(list, count, energy, peak, full_scale, nonfinite, reset != 0); }) : FX_E_ARG;
+}
+int fxb_meter_reset_list(fxb_handle* h, const int64_t* list, int64_t count) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterResetList(list, count); }) : FX_E_ARG;
+}
 int64_t fxb_meter_samples(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSamples(); }) : FX_E_ARG; }
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }

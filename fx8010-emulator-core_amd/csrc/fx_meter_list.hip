@@ -1,0 +1,195 @@
+// fx_meter_list.hip — the kernels behind the meter queries by list (fx_meter_list.hpp): an ordered stream compaction of the
+// instances whose meter passes a threshold, a gather of the accumulators of listed instances (with their zeroing), and a kernel
+// that only zeroes them.  gfx950, wave64, workgroups of 256 lanes.  Plain HIP C++, vector loads and stores only.
+//
+// The select.  A lane owns one instance of the range.  It reads the one accumulator row the query names for each of the up to
+// four channels - a wavefront access is 512 contiguous bytes of an energy row, 256 of the others - and takes the maximum.  The
+// compare is done in fp64: the energy is an fp64 word already, a peak (the bits of a non-negative finite float) and a counter (a
+// uint32) convert to fp64 without rounding, the maximum of fp64 values is one of them, and the threshold is the caller's double
+// as it came.  No accumulator is ever NaN (fx_meter.hip never writes one) and the runtime refuses a NaN threshold, so V >= t and
+// V < t are each other's complement and equal the compare of the real numbers.  That was preferred over turning the threshold into
+// a bit-pattern bound on the host: one rule for four formats, and nothing to get wrong at the ends of a format's range.
+//
+// The compaction is three launches and no workgroup ever waits for another one:
+//   fx_meter_count  a ballot and a popcount give each wavefront its count, LDS adds the four of a workgroup: offsets[chunk];
+//   fx_meter_scan   ONE workgroup of kMeterScanWidth lanes: a lane sums the ceil(chunks / 256) consecutive counts it owns, an
+//                   inclusive scan of the 256 lane sums in LDS, then the lane rewrites its counts as their exclusive scan; the
+//                   total M goes behind them.  Up to 256 chunks (65 536 instances) a lane has at most one count; above, it loops;
+//   fx_meter_emit   recomputes the predicate (the rows cannot have changed: the call is synchronous) and writes the instance number
+//                   firstGlobal + i at offsets[chunk] + rank, the rank being the matches in the wavefronts in front plus those in
+//                   the lanes below, where that is below cap.  A chunk whose offset has reached cap returns at once.
+// The position of a number depends on counts only, never on the order of atomics - there are none: ascending, and the same bits
+// run to run.  Columns at and beyond n never match, whatever the padding of the rows holds; first and nRange need no alignment
+// (a chunk is 256 instances FROM `first`).
+//
+// The gather and the zero: one lane per list entry, which walks the channels.  The instance's words are one segment per lane and
+// row - the list decides; the packed side is written 256 (energy: 512) contiguous bytes per wavefront.  With `reset` the lane that
+// has read a column stores its zeros: the read and the zeroing are one lane's program order.  An entry outside [0, n) is skipped.
+//
+// Resource usage (-O3, gfx950, from -Rpass-analysis=kernel-resource-usage), VGPRs / scratch bytes per lane / LDS bytes per
+// workgroup: fx_meter_count 14 / 0 / 16, fx_meter_scan 16 / 0 / 2 048, fx_meter_emit 16 / 0 / 16, fx_meter_gather 33 / 0 / 0,
+// fx_meter_zero 18 / 0 / 0; eight wavefronts per SIMD each.
+#include <hip/hip_runtime.h>
+
+#include "fx_meter.hpp"
+#include "fx_meter_list.hpp"
+
+namespace fx {
+
+namespace {
+
+constexpr int kLanes = kMeterSelectChunk;
+constexpr int kWaves = kLanes / 64;
+static_assert(kMeterScanWidth == kLanes, "the scan is one workgroup of that many lanes");
+
+// whether instance first + i of the range matches; i is the lane's index in the range
+__device__ __forceinline__ bool meterMatches(const MeterSelectArgs& a, long long i) {
+    if (i >= a.nRange) return false;
+    const long long col = a.first + i;
+    if (col >= a.n) return false;   // (cannot be: first + nRange <= n.  The padding never matches.)
+    const char* ch = static_cast<const char*>(a.rows);
+    double best = 0.0;
+    for (int c = 0; c < a.channels; ++c, ch += meterChannelBytes(a.nPad)) {
+        double v;
+        if (a.stat == 0) v = reinterpret_cast<const double*>(ch + meterEnergyOff(a.nPad))[col];
+        else if (a.stat == 1) v = (double)reinterpret_cast<const float*>(ch + meterPeakOff(a.nPad))[col];
+        else if (a.stat == 2) v = (double)reinterpret_cast<const uint32_t*>(ch + meterFullScaleOff(a.nPad))[col];
+        else v = (double)reinterpret_cast<const uint32_t*>(ch + meterNonfiniteOff(a.nPad))[col];
+        best = (c == 0 || v > best) ? v : best;
+    }
+    return a.below ? best < a.threshold : best >= a.threshold;
+}
+
+__global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) {
+    __shared__ unsigned waveCount[kWaves];
+    const unsigned t = threadIdx.x;
+    const bool match = meterMatches(a, (long long)blockIdx.x * kLanes + t);
+    const unsigned long long mask = __ballot(match);
+    if ((t & 63u) == 0) waveCount[t >> 6] = (unsigned)__popcll(mask);
+    __syncthreads();
+    if (t == 0) {
+        unsigned sum = 0;
+        for (int w = 0; w < kWaves; ++w) sum += waveCount[w];
+        a.offsets[blockIdx.x] = sum;
+    }
+}
+
+// one workgroup: offsets[0 .. chunks - 1] counts -> their exclusive scan, offsets[chunks] = the total.  Lane t owns the `per`
+// consecutive counts from t * per on: the loads of one lane are independent, so their latencies overlap
+__global__ __launch_bounds__(kLanes) void fx_meter_scan(unsigned long long* offsets, long long chunks) {
+    __shared__ unsigned long long s[kLanes];
+    const unsigned t = threadIdx.x;
+    const long long per = (chunks + kLanes - 1) / kLanes;
+    const long long lo = (long long)t * per < chunks ? (long long)t * per : chunks, hi = lo + per < chunks ? lo + per : chunks;
+    unsigned long long mine = 0;
+    for (long long k = lo; k < hi; ++k) mine += offsets[k];
+    s[t] = mine;
+    __syncthreads();
+    // Hillis-Steele over the lane sums, inclusive: after the step of width d, s[t] is the sum of the 2d sums ending at t
+    for (unsigned d = 1; d < (unsigned)kLanes; d <<= 1) {
+        const unsigned long long add = t >= d ? s[t - d] : 0;
+        __syncthreads();
+        s[t] += add;
+        __syncthreads();
+    }
+    unsigned long long run = s[t] - mine;   // the matches in front of this lane's counts
+    for (long long k = lo; k < hi; ++k) {
+        const unsigned long long c = offsets[k];
+        offsets[k] = run;
+        run += c;
+    }
+    if (t == kLanes - 1) offsets[chunks] = s[t];
+}
+
+__global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) {
+    __shared__ unsigned waveCount[kWaves];
+    const unsigned long long offset = a.offsets[blockIdx.x];
+    if (offset >= (unsigned long long)a.cap) return;   // (the whole workgroup: nothing of this chunk fits)
+    const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const long long i = (long long)blockIdx.x * kLanes + t;
+    const bool match = meterMatches(a, i);
+    const unsigned long long mask = __ballot(match);
+    if (lane == 0) waveCount[wave] = (unsigned)__popcll(mask);
+    __syncthreads();
+    unsigned rank = (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+    for (unsigned w = 0; w < wave; ++w) rank += waveCount[w];
+    const unsigned long long pos = offset + rank;
+    if (match && pos < (unsigned long long)a.cap) a.list[pos] = a.firstGlobal + i;
+}
+
+template <bool kGather>
+__device__ __forceinline__ void meterColumns(const MeterListArgs& a) {
+    const long long k = (long long)blockIdx.x * kLanes + threadIdx.x;
+    if (k >= a.count) return;
+    const long long inst = a.list[k];
+    if (inst < 0 || inst >= a.n) return;
+    const size_t rowWords = (size_t)a.channels * (size_t)a.count;
+    double* const pEnergy = static_cast<double*>(a.packed);
+    uint32_t* const pPeak = reinterpret_cast<uint32_t*>(static_cast<char*>(a.packed) + rowWords * 8);
+    uint32_t* const pFull = pPeak + rowWords;
+    uint32_t* const pNon = pFull + rowWords;
+    char* ch = static_cast<char*>(a.rows);
+    for (int c = 0; c < a.channels; ++c, ch += meterChannelBytes(a.nPad)) {
+        double* energy = reinterpret_cast<double*>(ch + meterEnergyOff(a.nPad)) + inst;
+        uint32_t* peak = reinterpret_cast<uint32_t*>(ch + meterPeakOff(a.nPad)) + inst;
+        uint32_t* fullScale = reinterpret_cast<uint32_t*>(ch + meterFullScaleOff(a.nPad)) + inst;
+        uint32_t* nonfinite = reinterpret_cast<uint32_t*>(ch + meterNonfiniteOff(a.nPad)) + inst;
+        if (kGather) {
+            const size_t at = (size_t)c * (size_t)a.count + (size_t)k;
+            const double e = *energy;
+            const uint32_t p = *peak, f = *fullScale, q = *nonfinite;
+            pEnergy[at] = e;
+            pPeak[at] = p;
+            pFull[at] = f;
+            pNon[at] = q;
+        }
+        if (!kGather || a.reset) {
+            *energy = 0.0;
+            *peak = 0u;
+            *fullScale = 0u;
+            *nonfinite = 0u;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void fx_meter_gather(MeterListArgs a) { meterColumns<true>(a); }
+__global__ __launch_bounds__(kLanes) void fx_meter_zero(MeterListArgs a) { meterColumns<false>(a); }
+
+inline bool badList(const MeterListArgs& a, bool gather) {
+    if (!a.rows || !a.list || a.count < 1 || a.count >= ((long long)1 << 31) || a.n < 1 || a.nPad < a.n) return true;
+    if (a.channels < 1 || a.channels > 4) return true;
+    return gather && !a.packed;
+}
+
+}  // namespace
+
+hipError_t launchMeterSelect(const MeterSelectArgs& a, hipStream_t stream) {
+    if (!a.rows || !a.offsets || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.stat < 0 || a.stat > 3) return hipErrorInvalidValue;
+    if (a.first < 0 || a.nRange < 1 || a.first > a.n - a.nRange || a.cap < 0 || (a.cap > 0 && !a.list) || a.threshold != a.threshold) return hipErrorInvalidValue;
+    const long long chunks = meterSelectChunks(a.nRange);
+    if (chunks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_meter_count, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
+    if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
+    hipLaunchKernelGGL(fx_meter_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchMeterGather(const MeterListArgs& a, hipStream_t stream) {
+    if (badList(a, true)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_meter_gather, dim3((unsigned)((a.count + kLanes - 1) / kLanes)), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchMeterZero(const MeterListArgs& a, hipStream_t stream) {
+    if (badList(a, false)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_meter_zero, dim3((unsigned)((a.count + kLanes - 1) / kLanes)), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace fx

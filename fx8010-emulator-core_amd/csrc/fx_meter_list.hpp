@@ -1,0 +1,60 @@
+// fx_meter_list.hpp — launch interface of the kernels behind the meter queries by list (fxb_meter_select, fxb_meter_read_list,
+// fxb_meter_reset_list; device code: fx_meter_list.hip).
+//
+// The accumulator rows are those of fx_meter.hpp: per channel energy f64 [nPad], peak f32 [nPad], full_scale u32 [nPad],
+// nonfinite u32 [nPad].  A select looks at ONE of the four rows of every channel; the value of an instance is the maximum over the
+// channels, taken in fp64 (include/fx8010_amd.h "Meter queries by list").  The packed side of a gather holds, for `count` list
+// entries, energy f64 [channels][count], then peak f32 [channels][count], full_scale and nonfinite u32 [channels][count]: every
+// row has the pitch `count`, and the 64-bit part comes first so that every part is aligned.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace fx {
+
+constexpr int kMeterSelectChunk = 256;   // instances of one chunk: one workgroup, one count
+constexpr int kMeterScanWidth = 256;     // lanes of the scan: above that many chunks a lane owns several counts and loops
+constexpr long long meterSelectChunks(long long nRange) { return (nRange + kMeterSelectChunk - 1) / kMeterSelectChunk; }
+// bytes of the packed side of a gather
+constexpr size_t meterPackedBytes(int channels, long long count) { return (size_t)channels * (size_t)count * 20; }
+
+struct MeterSelectArgs {
+    const void* rows;              // [channels] x the accumulator rows (device memory)
+    unsigned long long* offsets;   // device memory, meterSelectChunks(nRange) + 1 words: the chunk counts, then their exclusive
+                                   // scan in place, the total M in the last word
+    long long* list;               // device memory, min(cap, nRange) words (may be null when that is 0)
+    long long n, nPad;             // instances, and the pitch of an accumulator row
+    long long first, nRange;       // LOCAL columns first .. first + nRange - 1 are looked at; first + nRange <= n
+    long long firstGlobal;         // the number written for column `first`
+    long long cap;                 // entries of `list` that may be written, >= 0
+    double threshold;              // not NaN; +-Inf allowed
+    int channels;                  // 1..4
+    int stat;                      // 0 energy, 1 peak, 2 full_scale, 3 nonfinite
+    int below;                     // 0: V >= threshold matches; 1: V < threshold
+};
+
+// three launches on `stream`: fx_meter_count (a count per chunk), fx_meter_scan (one workgroup: the exclusive scan and the
+// total), fx_meter_emit (the matching numbers firstGlobal + i at offset + rank, where that is below cap).  Reads the rows and
+// writes nothing but offsets[0 .. chunks] and list[0 .. min(M, cap) - 1].  The order is ascending and the same run to run.
+hipError_t launchMeterSelect(const MeterSelectArgs& a, hipStream_t stream);
+
+struct MeterListArgs {
+    void* rows;               // [channels] x the accumulator rows
+    const long long* list;    // device memory: `count` instance numbers, each in [0, n)
+    void* packed;             // gather: the packed side (above), device memory; zero: unused
+    long long count;          // 1 .. 2^31 - 1
+    long long n, nPad;
+    int channels;             // 1..4
+    int reset;                // gather: zero the accumulators of every listed column behind its read, in the same lane
+};
+
+// packed[..][c][k] = the accumulators of channel c of instance list[k], bit for bit.  Repeats are fine without reset.  An entry
+// outside [0, n) - the runtime refuses such lists - is skipped: its column of the packed side stays as it is.
+hipError_t launchMeterGather(const MeterListArgs& a, hipStream_t stream);
+// the four accumulators of every channel of every listed instance = +0.0, +0.0f, 0, 0.  Stores only; repeats are fine.
+hipError_t launchMeterZero(const MeterListArgs& a, hipStream_t stream);
+
+}  // namespace fx

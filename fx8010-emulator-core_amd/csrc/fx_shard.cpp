@@ -369,6 +369,80 @@ int64_t Sharded::meterSamples() {
     return s;
 }
 
+int64_t Sharded::meterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterSelect(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (nRange == 0) return 0;
+    const bool below = (flags & FXB_METER_BELOW) != 0;
+    if (shards_.size() == 1) {
+        if (const int rc = runOn(0, [&](Batch& b) { return b.reserveMeterSelect(nRange, cap); })) return rc;
+        int64_t m = 0;
+        const int rc = runOn(0, [&](Batch& b) { m = b.meterSelect(stat, threshold, below, first, nRange, first, list, cap); return m < 0 ? (int)m : 0; });
+        return rc != 0 ? rc : m;
+    }
+    // the part of the range every shard owns (local numbers), and where its answer goes: a block of its own of min(cap, part)
+    // numbers - what a shard finds depends on no other shard, so all of them run side by side and cap is applied as they are joined.
+    // (A shard behind the one that fills cap still emits and copies back up to min(cap, part) numbers that are then dropped: the
+    // price of not waiting for the shards in front.  Hosts that ask for short lists pay cap x 8 bytes per shard at the most.)
+    struct Part { int64_t first = 0, count = 0, m = 0; std::vector<int64_t> found; };
+    std::vector<Part> parts(shards_.size());
+    for (size_t k = 0; k < shards_.size(); ++k) {
+        const int64_t lo = std::max(first, shards_[k]->first), hi = std::min(first + nRange, shards_[k]->first + shards_[k]->count);
+        if (hi <= lo) continue;
+        parts[k].first = lo - shards_[k]->first;
+        parts[k].count = hi - lo;
+        parts[k].found.resize((size_t)std::min(cap, parts[k].count));
+    }
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterSelect(parts[(size_t)k].count, cap); })) return rc;
+    const int rc = fan([&](int k, Batch& b) {
+        Part& p = parts[(size_t)k];
+        if (p.count == 0) return 0;
+        p.m = b.meterSelect(stat, threshold, below, p.first, p.count, shards_[(size_t)k]->first + p.first, p.found.data(), cap);
+        return p.m < 0 ? (int)p.m : 0;
+    });
+    if (rc != 0) return rc;
+    int64_t total = 0, written = 0;
+    for (const Part& p : parts) {
+        const int64_t take = std::min(std::min(p.m, (int64_t)p.found.size()), cap - written);
+        if (take > 0) std::memcpy(list + written, p.found.data(), (size_t)take * 8);
+        written += std::max<int64_t>(take, 0);
+        total += p.m;
+    }
+    return total;
+}
+
+int Sharded::meterReadList(const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterList("meter_read_list", list, count, n_, reset, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (count == 0) return 0;
+    const bool one = shards_.size() == 1;
+    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    // every shard is asked for its staging first: with reset, no shard zeroes a word unless all of them can answer
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(countOf(k), true); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterReadList(listOf(k), posOf(k), countOf(k), count, energy, peak, fullScale, nonfinite, reset); });
+}
+
+int Sharded::meterResetList(const int64_t* list, int64_t count) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterList("meter_reset_list", list, count, n_, false, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (count == 0) return 0;
+    const bool one = shards_.size() == 1;
+    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(countOf(k), false); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterResetList(listOf(k), countOf(k)); });
+}
+
 int Sharded::busSetGains(const float* gains, int ramp) {
     Serial serial(api_);
     lastError_.clear();
@@ -893,6 +967,7 @@ int64_t Sharded::info(int what) {
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
         what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
         what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS || what == FXB_INFO_TRAM_LIST_SETS || what == FXB_INFO_TRAM_LIST_GETS ||
+        what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

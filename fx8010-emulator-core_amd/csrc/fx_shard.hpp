@@ -83,6 +83,14 @@ public:
     int meterEnable(bool on);
     int meterRead(double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
     int64_t meterSamples();
+    // meter queries by list (Batch "Meter queries by list"): global instance numbers throughout.  The arguments are checked for
+    // the whole handle first; then every shard is asked for the staging of its part (of the range, of the list) before any shard
+    // launches or changes a word.  select: each shard answers for the part of the range it owns, the parts are concatenated in
+    // shard order - ascending - up to cap, the return value is the sum; a shard whose part is empty launches nothing.  read / reset:
+    // each shard gets the entries that fall to it with local numbers and their columns; a shard without an entry launches nothing.
+    int64_t meterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
+    int meterReadList(const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
+    int meterResetList(const int64_t* list, int64_t count);
     // bus gains (Batch::busSetGains ...): `gains` is [channels][all instances] by global instance, checked as a whole (every value
     // finite) before any shard is posted; every shard reserves its blocks first and only when all of them could is any shard's
     // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.

@@ -311,6 +311,29 @@ public:
         if (s < 0) throw std::runtime_error(std::string("FX8010Batch::meterSamples: ") + fxb_last_error(h_));
         return s;
     }
+    // Meter queries by list (include/fx8010_amd.h "Meter queries by list"): meterSelect returns the global instances of first ..
+    // first + nRange - 1 (nRange < 0: up to the last) whose meter `stat` (FXB_METER_ENERGY ...), the maximum over the channels, is
+    // >= threshold - with FXB_METER_BELOW: < threshold - ascending, at most `cap` of them (cap < 0: all); *matches, when given,
+    // gets their number M, which may exceed cap.  meterReadList fills [channels][list.size()] arrays (a null pointer skips one)
+    // and, with reset, zeroes the listed columns.  Both are synchronous.  meterResetList is stream-ordered behind the queued
+    // blocks (sync() covers it); meterSamples() is not changed by either.
+    std::vector<int64_t> meterSelect(int stat, double threshold, unsigned flags = 0, int64_t first = 0, int64_t nRange = -1, int64_t cap = -1, int64_t* matches = nullptr) {
+        if (nRange < 0) nRange = n_ - first;
+        if (cap < 0) cap = nRange > 0 ? nRange : 0;
+        std::vector<int64_t> list((size_t)(cap < nRange ? cap : (nRange > 0 ? nRange : 0)));
+        const int64_t m = fxb_meter_select(h_, stat, threshold, first, nRange, list.empty() ? nullptr : list.data(), (int64_t)list.size(), flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterSelect: ") + fxb_last_error(h_));
+        if (matches) *matches = m;
+        if ((size_t)m < list.size()) list.resize((size_t)m);
+        return list;
+    }
+    void meterReadList(const std::vector<int64_t>& list, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset = false) {
+        if (fxb_meter_read_list(h_, list.data(), (int64_t)list.size(), energy, peak, fullScale, nonfinite, reset ? 1 : 0) < 0)
+            throw std::runtime_error(std::string("FX8010Batch::meterReadList: ") + fxb_last_error(h_));
+    }
+    void meterResetList(const std::vector<int64_t>& list) {
+        if (fxb_meter_reset_list(h_, list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::meterResetList: ") + fxb_last_error(h_));
+    }
     // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
     // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
     // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and

@@ -29,10 +29,13 @@ INFO = {
     "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
     "register_list_sets": 50, "register_list_gets": 51, "xlate_sum_groups": 52, "xlate_sum_links": 53, "xlate_quiet_repairs": 54,
     "tram_list_sets": 55, "tram_list_gets": 56,
+    "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
 TRAM_LOGICAL, TRAM_BROADCAST = 1, 2  # FXB_TRAM_* of include/fx8010_amd.h
+METER_ENERGY, METER_PEAK, METER_FULL_SCALE, METER_NONFINITE = 0, 1, 2, 3  # FXB_METER_* of include/fx8010_amd.h: the `stat` of meter_select
+METER_BELOW = 1
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -49,7 +52,7 @@ SYMBOLS = [
     "fxb_bus_set_feeds", "fxb_bus_set_feed_gains", "fxb_bus_get_feeds", "fxb_process_block_bus_feed", "fxb_process_block_bus_feed_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances", "fxb_load_instances_rotated",
-    "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples",
+    "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples", "fxb_meter_select", "fxb_meter_read_list", "fxb_meter_reset_list",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -119,6 +122,7 @@ def load():
     sig("fxb_load_instances_rotated", i32, vp, vp, i64, vp, i64)
     sig("fxb_set_registers_list", i32, vp, vp, i32, vp, i64, vp); sig("fxb_get_registers_list", i32, vp, vp, i32, vp, i64, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
+    sig("fxb_meter_select", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_read_list", i32, vp, vp, i64, vp, vp, vp, vp, i32); sig("fxb_meter_reset_list", i32, vp, vp, i64)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -918,6 +922,40 @@ class Batch(_Reports):
         self._check(self._lib.fxb_meter_read(self._h, *[C.c_void_p(out[k].ctypes.data) for k in ("energy", "peak", "full_scale", "nonfinite")],
                                              1 if reset else 0), "meter_read")
         return out
+
+    def meter_select(self, stat, threshold, below=False, first=0, n_range=None, cap=None):
+        """(list, M): the global instance numbers in first .. first + n_range - 1 whose meter `stat` (METER_ENERGY, METER_PEAK,
+        METER_FULL_SCALE, METER_NONFINITE), taken as the maximum over the channels, is >= threshold - with below: < threshold -
+        compacted on the device into an ascending int64 list (include/fx8010_amd.h "Meter queries by list").  M is the number of
+        matches; the list holds the min(M, cap) smallest.  n_range None: up to the last instance; cap None: n_range; cap 0 is a
+        count query.  Exact: no rounding anywhere.  Synchronous; changes nothing."""
+        first = int(first)
+        n_range = self.n - first if n_range is None else int(n_range)
+        cap = n_range if cap is None else int(cap)
+        out = np.empty(max(min(cap, n_range), 0), dtype=np.int64)
+        m = self._check(int(self._lib.fxb_meter_select(self._h, int(stat), float(threshold), first, n_range, C.c_void_p(out.ctypes.data) if out.size else None,
+                                                       cap, METER_BELOW if below else 0)), "meter_select")
+        return out[:min(m, out.size)], m
+
+    def meter_read_list(self, instances, reset=False):
+        """meter_read for the listed global instances only: {"energy", "peak", "full_scale", "nonfinite"}, each [channels,
+        len(instances)], column k for instances[k], bit for bit what meter_read holds there - gathered on the device.  Synchronous.
+        reset: the listed columns are zero afterwards, in the lane that read them (no instance may then be listed twice)."""
+        lst = self._instance_list(instances)
+        shape = (self.channels, lst.size)
+        out = {"energy": np.zeros(shape, dtype=np.float64), "peak": np.zeros(shape, dtype=np.float32),
+               "full_scale": np.zeros(shape, dtype=np.uint32), "nonfinite": np.zeros(shape, dtype=np.uint32)}
+        self._check(self._lib.fxb_meter_read_list(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
+                                                  *[C.c_void_p(out[k].ctypes.data) if lst.size else None for k in ("energy", "peak", "full_scale", "nonfinite")],
+                                                  1 if reset else 0), "meter_read_list")
+        return out
+
+    def meter_reset_list(self, instances):
+        """Zero the meters of the listed global instances only - a slot reused at note-on.  Stream-ordered behind the queued blocks
+        and in front of later ones - it does not wait for them; sync(), meter_read, meter_read_list and meter_select cover it.
+        meter_samples() stays the handle-wide count since the last full reset."""
+        lst = self._instance_list(instances)
+        return self._check(self._lib.fxb_meter_reset_list(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size)), "meter_reset_list")
 
     def meter_samples(self):
         """sample periods metered since the last reset"""

@@ -711,6 +711,52 @@ int fxb_process_block_imajor_dev(fxb_handle* h, const float* d_in, float* d_out,
 int fxb_meter_enable(fxb_handle* h, int on);
 int fxb_meter_read(fxb_handle* h, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset);
 int64_t fxb_meter_samples(fxb_handle* h);
+/* Meter queries by list: the meters are what the device produces for the host to act on - which voices went non-finite (mute
+ * them: fxb_bus_set_gains_list), which have decayed below a level (their slots are free: fxb_reset_instances,
+ * fxb_set_tram_list), what the figures of these twenty voices are.  The answer to each is a short list; fxb_meter_read moves every
+ * row of every instance and can only zero every accumulator.  These calls select, read and reset by list, on the GPU.
+ *
+ * fxb_meter_select: the definition.  v(c, n) is accumulator `stat` (FXB_METER_ENERGY, _PEAK, _FULL_SCALE, _NONFINITE) of channel c
+ *   and global instance n, taken as a real number - the conversions of a float or a uint32 to double are exact.  V(n) = max over
+ *   the handle's channels of v(c, n).  No rounding occurs anywhere.  Instance n in first .. first + n_range - 1 matches when
+ *   V(n) >= threshold, or, with FXB_METER_BELOW, when V(n) < threshold.  M is the number of matches.  The call writes the
+ *   min(M, cap) SMALLEST matching global instance numbers to `list`, ascending, and returns M; M may exceed cap, and `list` beyond
+ *   min(M, cap) is not touched.  cap == 0 is a count query.  n_range == 0 returns 0 without a launch.  The list is compacted on
+ *   the device - per-wavefront counts, an exclusive scan over the chunk counts, an emit pass; no atomics decide a position - so
+ *   it is the same run to run, and only min(M, cap) numbers cross PCIe.
+ *   Synchronous: it waits as fxb_sync does, which covers a list reset still in flight, and it changes nothing.
+ *   threshold may be +-Inf; NaN is FX_E_ARG.  Also FX_E_ARG, with nothing launched: metering off, stat outside 0..3, an unknown
+ *   flag bit, first < 0, n_range < 0 or first + n_range > N, cap < 0, a null list with cap > 0.  FX_E_MEMORY when the staging -
+ *   min(cap, n_range) instance numbers plus a count per chunk of 256 instances, in device memory and pinned, grown on demand in
+ *   the call and freed with the handle - cannot be allocated.
+ *   Sharded handles: each shard answers for the part of the range it owns; the parts are concatenated in shard order, which is
+ *   ascending; cap applies to the whole result and the return value is the sum.  A shard whose part is empty launches nothing.
+ * fxb_meter_read_list: every array is [num_channels][count] with a row pitch of exactly `count`; column k belongs to list[k]; any
+ *   array pointer may be NULL.  The values are, bit for bit, those fxb_meter_read puts at [c][list[k]].  Synchronous.  Repeats are
+ *   allowed when reset == 0.  With reset != 0 the four accumulators of every listed (channel, instance) are zero afterwards and
+ *   nothing else changes; a repeated instance is then FX_E_ARG; the read and the zeroing of one column happen in one lane of one
+ *   launch.  count == 0 returns 0.  FX_E_ARG otherwise as for fxb_get_registers_list: a negative count, a null list with
+ *   count > 0, an instance outside 0..N-1, count >= 2^31, metering off.  FX_E_MEMORY when the staging cannot be allocated: nothing
+ *   is zeroed on any shard.
+ * fxb_meter_reset_list: the four accumulators of every channel of the listed instances become +0.0, +0.0f, 0, 0 - a slot reused
+ *   at note-on gets a fresh meter without wiping everyone's.  Repeats are allowed.  STREAM-ORDERED, in the frame of
+ *   fxb_set_registers_list: it runs on the handle's stream behind every block queued so far on whichever stream - that block's
+ *   meter launch included - and in front of every block queued later; it waits on the host only for a previous list or instance
+ *   call whose staging it reuses.  The caller's list is free on return.  fxb_sync, fxb_meter_read, fxb_meter_read_list and
+ *   fxb_meter_select cover it.  Refusals as for fxb_meter_read_list.  Sharded handles: every shard is asked for its staging before
+ *   any shard changes a word; a shard without an entry launches nothing.
+ * fxb_meter_samples stays the handle-wide count of sample periods since the last FULL reset (fxb_meter_read with reset, a program
+ *   load, fxb_meter_enable): the list calls do not change it - a host that resets a voice by list knows when it did.  Neither do
+ *   they change instance state, gains, taps, tracks, code or any other counter.
+ * FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS count the calls that launched, summed over shards. */
+#define FXB_METER_ENERGY     0
+#define FXB_METER_PEAK       1
+#define FXB_METER_FULL_SCALE 2
+#define FXB_METER_NONFINITE  3
+#define FXB_METER_BELOW (1u << 0)   /* select V < threshold instead of V >= threshold */
+int64_t fxb_meter_select(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
+int fxb_meter_read_list(fxb_handle* h, const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset);
+int fxb_meter_reset_list(fxb_handle* h, const int64_t* list, int64_t count);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -806,7 +852,10 @@ enum {
     FXB_INFO_XLATE_QUIET_REPAIRS = 54, /* how often the last launch re-did a sum group with its saturations (a lane's partial sum above the group's
                                           threshold), summed over wavefronts; a repair does not leave the loop; waits for that launch (summed over shards) */
     FXB_INFO_TRAM_LIST_SETS = 55,      /* launches of the kernel fx_tram_scatter - by fxb_set_tram_list - since creation (summed over shards) */
-    FXB_INFO_TRAM_LIST_GETS = 56       /* launches of the kernel fx_tram_gather - by fxb_get_tram_list - since creation (summed over shards) */
+    FXB_INFO_TRAM_LIST_GETS = 56,      /* launches of the kernel fx_tram_gather - by fxb_get_tram_list - since creation (summed over shards) */
+    FXB_INFO_METER_SELECTS = 57,       /* calls of fxb_meter_select that launched (fx_meter_count / _scan / _emit) since creation (summed over shards) */
+    FXB_INFO_METER_LIST_READS = 58,    /* calls of fxb_meter_read_list that launched (fx_meter_gather) since creation (summed over shards) */
+    FXB_INFO_METER_LIST_RESETS = 59    /* calls of fxb_meter_reset_list that launched (fx_meter_zero) since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
