@@ -101,6 +101,10 @@ Batch::~Batch() {
     freeBlock(hRegList_, true);
     freeBlock(tramStage_, false);
     freeBlock(hTramStage_, true);
+    freeBlock(trackList_, false);
+    freeBlock(hTrackList_, true);
+    if (evTrackCopy_) (void)hipEventDestroy(evTrackCopy_);
+    if (evTrackList_) (void)hipEventDestroy(evTrackList_);
     freeBlock(meterStage_, false);
     freeBlock(hMeterStage_, true);
     if (evInst_) (void)hipEventDestroy(evInst_);
@@ -484,6 +488,7 @@ int Batch::setRegisterTrack(const std::string& key, const float* values, int nSt
     if (!dState_) return fail(FX_E_NOTREADY, "no program loaded");
     if (pitch <= 0) pitch = n_;
     if (perInstance && pitch < n_) return fail(FX_E_ARG, "track: pitch below the instance count");
+    if (listScheduled(r)) return fail(FX_E_ARG, "track: register '" + key + "' has list schedules armed (set_register_tracks_list)");
     size_t slot = 0;
     while (slot < trackRegs_.size() && trackRegs_[slot] != r) ++slot;
     if (slot == trackRegs_.size()) {
@@ -507,31 +512,77 @@ int Batch::setRegisterTrack(const std::string& key, const float* values, int nSt
 }
 
 // the events of the armed schedules, sorted by sample, and their values -> dTracks_ (on the launch stream, ahead of the kernel);
-// the schedules are one-shot
+// the schedules are one-shot.  A register with list schedules (fx_batch_tracks.cpp) contributes the sorted union of the samples
+// at which its schedules have a step inside the block; each of those events owns a row of nPad words BEHIND the part of the
+// buffer that the host image covers - the header copy does not touch them, the device fills them (expandTrackLists).  The host
+// image ends with the ranges of fx_track_scatter: per schedule, one per step inside the block and key.
 int Batch::uploadTracks(int nSamples, hipStream_t s) {
     if (!tracksArmed() && tracksClear_ && dTracks_) return 0;  // nothing armed and the device list already says so
-    struct Due { uint32_t sample, slot, step; };
+    struct Due { uint32_t sample, slot, step; int64_t row; };   // row >= 0: an event of a list-armed register, its row
     std::vector<Due> due;
     std::vector<int> used(pendingTracks_.size(), 0);
     size_t valueWords = 0;
+    // list schedules: the events of every register, its first row, the rows in all
+    std::vector<std::vector<int>> listEvents(trackRegs_.size());
+    for (const ListSchedule& sch : listSchedules_) {
+        if (sch.list.empty()) continue;
+        const int inside = sch.stepsInside(nSamples);
+        for (const int slot : sch.slots)
+            for (int q = 0; q < inside; ++q) listEvents[(size_t)slot].push_back(sch.first + q * sch.period);
+    }
+    std::vector<size_t> firstRow(trackRegs_.size(), 0);
+    ListExpansion x;
+    for (size_t k = 0; k < listEvents.size(); ++k) {
+        std::vector<int>& ev = listEvents[k];
+        std::sort(ev.begin(), ev.end());
+        ev.erase(std::unique(ev.begin(), ev.end()), ev.end());
+        firstRow[k] = x.totalRows;
+        if (ev.empty()) continue;
+        x.hold.stateRow[x.hold.nRegs] = trackRegs_[k];   // (a register's row is its number: StateLayout)
+        x.hold.firstRow[x.hold.nRegs] = (int)x.totalRows;
+        x.hold.rowCount[x.hold.nRegs] = (int)ev.size();
+        ++x.hold.nRegs;
+        x.totalRows += ev.size();
+    }
     for (size_t k = 0; k < pendingTracks_.size(); ++k) {
         const PendingTrack& t = pendingTracks_[k];
+        for (size_t e = 0; e < listEvents[k].size(); ++e) due.push_back({(uint32_t)listEvents[k][e], (uint32_t)k, 0u, (int64_t)(firstRow[k] + e)});
         if (t.steps <= 0) continue;
         used[k] = std::min(t.steps, (nSamples + t.period - 1) / t.period);  // changes that fall inside this block
-        for (int q = 0; q < used[k]; ++q) due.push_back({(uint32_t)q * (uint32_t)t.period, (uint32_t)k, (uint32_t)q});
+        for (int q = 0; q < used[k]; ++q) due.push_back({(uint32_t)q * (uint32_t)t.period, (uint32_t)k, (uint32_t)q, -1});
         valueWords += t.perInstance ? (size_t)used[k] * (size_t)nPad_ : (size_t)used[k];
     }
     std::stable_sort(due.begin(), due.end(), [](const Due& a, const Due& b) { return a.sample < b.sample; });  // (same sample: by slot, as armed)
+    // the ranges: a step runs from its own event up to the same schedule's next one, the last step inside to the register's last event
+    std::vector<TrackRange> ranges;
+    for (size_t j = 0; j < listSchedules_.size(); ++j) {
+        const ListSchedule& sch = listSchedules_[j];
+        const int inside = sch.list.empty() ? 0 : sch.stepsInside(nSamples);
+        if (inside == 0) continue;
+        x.launches.push_back({j, ranges.size(), inside * (int)sch.regs.size()});
+        for (int q = 0; q < inside; ++q)
+            for (size_t k = 0; k < sch.regs.size(); ++k) {
+                const size_t slot = (size_t)sch.slots[k];
+                const std::vector<int>& ev = listEvents[slot];
+                const size_t lo = (size_t)(std::lower_bound(ev.begin(), ev.end(), sch.first + q * sch.period) - ev.begin());
+                const size_t hi = q + 1 < inside ? (size_t)(std::lower_bound(ev.begin(), ev.end(), sch.first + (q + 1) * sch.period) - ev.begin()) : ev.size();
+                ranges.push_back({q * (int)sch.regs.size() + (int)k, (int)(firstRow[slot] + lo), (int)(firstRow[slot] + hi), 0});
+            }
+    }
+    static_assert(sizeof(TrackRange) == 16, "TrackRange layout");
     const size_t listWords = (due.size() + 1) * 4;
-    const size_t words = listWords + valueWords;
-    if (words * 4 > tracksCap_) {
+    const size_t rangesAt = (listWords + valueWords + 3) & ~(size_t)3;
+    const size_t words = rangesAt + ranges.size() * 4;   // the host image; a multiple of 4: the rows behind it are 16-byte aligned
+    const size_t bytes = (words + x.totalRows * (size_t)nPad_) * 4;
+    if (x.totalRows > 0 && bytes >= ((size_t)1 << 32)) return fail(FX_E_MEMORY, "tracks: the event rows of this block would pass 4 GiB");
+    if (bytes > tracksCap_) {
         waitLastLaunch();
         (void)hipFree(dTracks_);
         dTracks_ = nullptr;
         tracksCap_ = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dTracks_), words * 4 + 256);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dTracks_), bytes + 256);
         if (e != hipSuccess) return hipFail(e, "hipMalloc tracks");
-        tracksCap_ = words * 4 + 256;
+        tracksCap_ = bytes + 256;
     }
     waitLastLaunch();  // trackStage_ / dTracks_ of the previous block are free again
     trackStage_.assign(words, 0);
@@ -539,9 +590,13 @@ int Batch::uploadTracks(int nSamples, hipStream_t s) {
     size_t at = listWords;
     for (size_t k = 0; k < pendingTracks_.size(); ++k) {
         PendingTrack& t = pendingTracks_[k];
+        const int reg = trackRegs_[k];
+        if (!listEvents[k].empty()) {   // (as a per-instance track)
+            forcedLane_[(size_t)reg] = 1;
+            laneWritten_[(size_t)reg] = 1;
+        }
         if (t.steps <= 0) continue;
         valuesAt[k] = at;
-        const int reg = trackRegs_[k];
         if (t.perInstance) {
             for (int q = 0; q < used[k]; ++q) std::memcpy(&trackStage_[at + (size_t)q * (size_t)nPad_], &t.values[(size_t)q * (size_t)n_], (size_t)n_ * 4);
             at += (size_t)used[k] * (size_t)nPad_;
@@ -558,19 +613,29 @@ int Batch::uploadTracks(int nSamples, hipStream_t s) {
     for (size_t i = 0; i < due.size(); ++i) {
         const Due& d = due[i];
         const PendingTrack& t = pendingTracks_[d.slot];
-        const size_t value = valuesAt[d.slot] + (t.perInstance ? (size_t)d.step * (size_t)nPad_ : (size_t)d.step);
-        const TrackEvent ev{d.sample, d.slot, (uint32_t)(value * 4), t.perInstance ? (uint32_t)(nPad_ * 4) : 4u};
+        const bool row = d.row >= 0 || t.perInstance;
+        const size_t value = d.row >= 0 ? words + (size_t)d.row * (size_t)nPad_ : valuesAt[d.slot] + (t.perInstance ? (size_t)d.step * (size_t)nPad_ : (size_t)d.step);
+        const TrackEvent ev{d.sample, d.slot, (uint32_t)(value * 4), row ? (uint32_t)(nPad_ * 4) : 4u};
         std::memcpy(&trackStage_[i * 4], &ev, sizeof(ev));
     }
     const TrackEvent closing{0xffffffffu, 0, 0, 4};
     std::memcpy(&trackStage_[due.size() * 4], &closing, sizeof(closing));
+    if (!ranges.empty()) std::memcpy(&trackStage_[rangesAt], ranges.data(), ranges.size() * sizeof(TrackRange));
     for (PendingTrack& t : pendingTracks_) {
         t.steps = 0;
         t.values.clear();
     }
     tracksClear_ = due.empty();
     hipError_t e = hipMemcpyAsync(dTracks_, trackStage_.data(), words * 4, hipMemcpyHostToDevice, s);
-    return e == hipSuccess ? 0 : hipFail(e, "tracks upload");
+    if (e != hipSuccess) {
+        (void)finishTrackLists(s, false);
+        return hipFail(e, "tracks upload");
+    }
+    x.rowsAt = words;
+    for (ListExpansion::Launch& l : x.launches) l.rangesAt = rangesAt + l.rangesAt * 4;   // (ranges -> words of the buffer)
+    const int rc = expandTrackLists(x, s);
+    const int rc2 = finishTrackLists(s, rc == 0 && x.totalRows > 0);
+    return rc != 0 ? rc : rc2;
 }
 
 // ---- state snapshot ------------------------------------------------------------------------------------------------------------
@@ -913,6 +978,7 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_SELECTS) return meterSelects_;
     if (what == FXB_INFO_METER_LIST_READS) return meterListReads_;
     if (what == FXB_INFO_METER_LIST_RESETS) return meterListResets_;
+    if (what == FXB_INFO_TRACK_LIST_EXPANDS) return trackListExpands_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

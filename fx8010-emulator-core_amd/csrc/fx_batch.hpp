@@ -22,6 +22,7 @@
 #include "fx_instances.hpp"
 #include "fx_registers.hpp"
 #include "fx_tram.hpp"
+#include "fx_tracks.hpp"
 #include "fx_xlate.hpp"
 #include "fx_decode.hpp"
 #include "fx_kernel.hpp"
@@ -284,6 +285,23 @@ public:
     int reserveRegisterList(int nKeys, int64_t count);
     int setRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* values);
     int getRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, float* values);
+    // Register tracks by list (fx_tracks.hpp; include/fx8010_amd.h "Register tracks by list"; fx_batch_tracks.cpp): one call arms one
+    // LIST SCHEDULE for the next block - step q falls due at sample first + q * period, where register regs[k] of instance list[i]
+    // takes values[(q * nKeys + k) * total + pos[i]] (pos null: i, total == count).  `list` holds `count` instance numbers of THIS
+    // batch.  checkTrackList holds the refusals that read nothing but the arguments (Sharded asks for the whole handle);
+    // checkTrackListArm those that read what is armed and the program, and changes nothing; reserveTrackList is the allocating
+    // half (the staging pair, the events, the track buffer for every step of everything armed: FX_E_MEMORY changes nothing);
+    // armTrackList then cannot fail for want of memory.  count == 0 is a shard that owns none of the entries: its registers become
+    // trackable all the same (every shard runs the same code) and the schedule counts towards kMaxListSchedules, but nothing is
+    // staged and nothing will be launched for it.  Arming waits on the HOST only for the expansion that last read the staging
+    // (evTrackList_, behind the last fx_track_scatter), never for a block.
+    static constexpr int kMaxListSchedules = 64;
+    static int checkTrackList(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const float* values, int nSteps, int first, int period, std::string* why);
+    int checkTrackListArm(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t firstGlobal, std::string* why);
+    int reserveTrackList(const std::vector<int>& regs, int64_t count, int nSteps);
+    int armTrackList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* values, int nSteps, int first, int period);
+    int clearTrackLists();
+    bool listScheduled(int reg) const;   // an armed list schedule names the register
     // Delay-line windows by list (fx_tram.hpp; include/fx8010_amd.h "Delay-line windows by list"; fx_batch_tram.cpp).  `list` holds
     // `count` instance numbers of THIS batch, `pos` the window of the caller's values each of them has (null: entry i has window
     // i); `in` is a set (stride 0: one window for all, FXB_TRAM_BROADCAST), `out` a get.  checkTramList holds the refusals that read
@@ -401,7 +419,45 @@ private:
     size_t tracksCap_ = 0;                 // bytes
     bool tracksClear_ = false;             // the device header holds no armed schedule
     std::vector<uint32_t> trackStage_;     // host image of dTracks_ for the block being launched
-    bool tracksArmed() const { for (const PendingTrack& t : pendingTracks_) if (t.steps > 0) return true; return false; }
+    bool tracksArmed() const { if (!listSchedules_.empty()) return true; for (const PendingTrack& t : pendingTracks_) if (t.steps > 0) return true; return false; }
+    // list schedules (fx_batch_tracks.cpp): what is armed for the next block, in arming order.  The lists, the values and the rows
+    // of all of them lie in ONE staging pair of 32-bit words (pinned hTrackList_, the master copy; device trackList_), each
+    // schedule's part at `at`: [count] instance numbers (64-bit), [steps][keys][count] values, [keys] state rows; a part is
+    // copied to the device on stream_ when it is armed (evTrackCopy_ behind the copy).  A block expands them (expandTrackLists,
+    // called by uploadTracks) or applies them at its cuts (applyTrackListsAt, the tiers without in-kernel tracks), records
+    // evTrackList_ behind the last kernel that reads the staging and drops them: the next arming starts at word 0 behind a host
+    // wait for that event.
+    struct ListSchedule {
+        std::vector<int> regs, slots;    // registers and their track slots
+        std::vector<int64_t> list;       // local instance numbers (the refusal of a voice named twice for one register)
+        int steps = 0, first = 0, period = 1;
+        size_t at = 0;                   // word offset of its part of the staging
+        int64_t count() const { return (int64_t)list.size(); }
+        size_t valuesAt() const { return at + list.size() * 2; }
+        size_t rowsAt() const { return valuesAt() + (size_t)steps * regs.size() * list.size(); }
+        int stepsInside(int nSamples) const { return first >= nSamples ? 0 : (int)std::min<int64_t>(steps, ((int64_t)nSamples - 1 - first) / period + 1); }
+    };
+    std::vector<ListSchedule> listSchedules_;
+    Block<uint32_t> trackList_, hTrackList_;
+    size_t trackListUsed_ = 0;             // words of the staging that armed schedules occupy
+    hipEvent_t evTrackCopy_ = nullptr;     // behind the most recent copy of a part to the device (stream_)
+    hipEvent_t evTrackList_ = nullptr;     // behind the last kernel that read the staging
+    bool trackListBusy_ = false;           // ... which may still be running
+    int64_t trackListExpands_ = 0;         // FXB_INFO_TRACK_LIST_EXPANDS
+    static size_t trackListPartWords(size_t nKeys, int64_t count, int nSteps) { return (((size_t)count * 2 + (size_t)nSteps * nKeys * (size_t)count + nKeys) + 1) & ~(size_t)1; }
+    size_t trackBufferWorstBytes(const std::vector<int>* moreRegs, int moreSteps) const;
+    int growTrackBuffer(size_t bytes);
+    // the list part of uploadTracks: hold and scatter on the block's stream behind the header copy; `rowsAt` is the word of dTracks_
+    // where the first event row lies, `tabAt` where the ranges of the schedules lie (in the header image, built by uploadTracks)
+    struct ListExpansion {
+        TrackHoldArgs hold{};
+        struct Launch { size_t schedule, rangesAt; int nRanges; };
+        std::vector<Launch> launches;
+        size_t rowsAt = 0, totalRows = 0;
+    };
+    int expandTrackLists(const ListExpansion& x, hipStream_t s);
+    int applyTrackListsAt(std::vector<ListSchedule>& schedules, int sample);   // a cut of processWithTrackFallback
+    int finishTrackLists(hipStream_t s, bool launched);                        // evTrackList_ behind what was launched; the staging starts over
     uint32_t* dScratch_ = nullptr;  // small device scratch: fill lists, reductions
     // output meters: the accumulator rows (fx_meter.hpp), null while metering is off
     void* dMeter_ = nullptr;

@@ -83,26 +83,38 @@ int Batch::processWithTrackFallback(const float* dIn, float* dOut, int nSamples,
     std::vector<PendingTrack> tracks;
     tracks.swap(pendingTracks_);
     pendingTracks_.resize(trackRegs_.size());
+    // (list schedules, fx_batch_tracks.cpp: their steps are applied at the cuts by the scatter of the register list sets)
+    std::vector<ListSchedule> lists;
+    lists.swap(listSchedules_);
     std::vector<int> cuts{0, nSamples};
     for (const PendingTrack& t : tracks)
         for (int k = 0; k < t.steps && (int64_t)k * t.period < nSamples; ++k) cuts.push_back(k * t.period);
+    bool listSteps = false;
+    for (const ListSchedule& l : lists)
+        for (int q = 0; q < (l.list.empty() ? 0 : l.stepsInside(nSamples)); ++q) {
+            cuts.push_back(l.first + q * l.period);
+            listSteps = true;
+        }
     std::sort(cuts.begin(), cuts.end());
     cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
     const size_t rowFloats = (size_t)prog_.numChannels * (size_t)pitch;   // floats per sample period
-    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+    int rc = 0;
+    for (size_t c = 0; c + 1 < cuts.size() && rc == 0; ++c) {
         const int lo = cuts[c], hi = cuts[c + 1];
-        for (size_t k = 0; k < tracks.size(); ++k) {
+        for (size_t k = 0; k < tracks.size() && rc == 0; ++k) {
             const PendingTrack& t = tracks[k];
             if (t.steps <= 0 || lo % t.period != 0 || lo / t.period >= t.steps) continue;
             const std::string& name = prog_.regs[(size_t)trackRegs_[k]].name;
-            const int rc = t.perInstance ? setRegisterArray(name, &t.values[(size_t)(lo / t.period) * (size_t)n_]) : setRegister(name, t.values[(size_t)(lo / t.period)]);
-            if (rc != 0) return rc < 0 ? rc : fail(FX_E_ARG, "track: register vanished");
+            rc = t.perInstance ? setRegisterArray(name, &t.values[(size_t)(lo / t.period) * (size_t)n_]) : setRegister(name, t.values[(size_t)(lo / t.period)]);
+            if (rc > 0) rc = fail(FX_E_ARG, "track: register vanished");
         }
+        if (rc == 0) rc = applyTrackListsAt(lists, lo);
         controlHeat_ = 0;  // these writes are the schedule, not a moving slider
-        const int rc = processDevice(dIn + (size_t)lo * rowFloats, dOut + (size_t)lo * rowFloats, hi - lo, stream, pitch);
-        if (rc != 0) return rc;
+        if (rc == 0) rc = processDevice(dIn + (size_t)lo * rowFloats, dOut + (size_t)lo * rowFloats, hi - lo, stream, pitch);
     }
-    return 0;
+    // (the staging is free again behind the last scatter, which ran on the handle's stream)
+    const int rc2 = finishTrackLists(stream_, listSteps);
+    return rc != 0 ? rc : rc2;
 }
 
 // The refusals of every entry point, written once: a call that is refused has changed nothing and launches nothing.

@@ -322,6 +322,10 @@ int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, c
 int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.getRegistersList(keys, n_keys, list, count, values); }) : FX_E_ARG;
 }
+int fxb_set_register_tracks_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values, int n_steps, int first, int period) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.setRegisterTracksList(keys, n_keys, list, count, values, n_steps, first, period); }) : FX_E_ARG;
+}
+int fxb_clear_register_tracks_list(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.clearRegisterTracksList(); }) : FX_E_ARG; }
 int fxb_set_tram_list(fxb_handle* h, int which, const int64_t* list, int64_t count, int first, int n_words, const float* values, unsigned flags) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.setTramList(which, list, count, first, n_words, values, flags); }) : FX_E_ARG;
 }

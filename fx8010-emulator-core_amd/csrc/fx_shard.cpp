@@ -916,6 +916,43 @@ int Sharded::registersList(bool set, const char* const* keys, int nKeys, const i
     return fan([&](int k, Batch& b) { return b.setRegistersList(regs, listOf(k), posOf(k), countOf(k), count, in); });
 }
 
+int Sharded::setRegisterTracksList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* values, int nSteps, int first, int period) {
+    Serial serial(api_);
+    lastError_.clear();
+    const char* name = "set_register_tracks_list";
+    if (nKeys < 0 || count < 0) { lastError_ = std::string(name) + ": a negative n_keys or count"; return FX_E_ARG; }
+    if (nKeys > 0 && !keys) { lastError_ = std::string(name) + ": null keys"; return FX_E_ARG; }
+    if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
+    // (the program is replicated: the front shard's register numbers are every shard's)
+    std::vector<int> regs;
+    if (const int rc = front().resolveRegisters(keys, nKeys, &regs)) { lastError_ = front().lastError(); return rc; }
+    // everything that reads nothing but the arguments, for the whole handle and with the caller's indices
+    if (Batch::checkTrackList(regs, list, count, n_, values, nSteps, first, period, &lastError_) != 0) return FX_E_ARG;
+    if (count == 0 || nKeys == 0) return 0;
+    const bool one = shards_.size() == 1;
+    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
+    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
+    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
+    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    // every shard is asked first - what is armed on it, the program, then its staging and its track buffer; only when all of
+    // them could is anything armed anywhere (staging that has grown stays: it is no state)
+    int rc = fan([&](int k, Batch& b) {
+        std::string why;
+        const int r = b.checkTrackListArm(regs, listOf(k), countOf(k), shards_[(size_t)k]->first, &why);
+        if (r != 0) b.noteError(why);
+        return r;
+    });
+    if (rc == 0) rc = fan([&](int k, Batch& b) { return b.reserveTrackList(regs, countOf(k), nSteps); });
+    if (rc != 0) return rc;
+    return fan([&](int k, Batch& b) { return b.armTrackList(regs, listOf(k), posOf(k), countOf(k), count, values, nSteps, first, period); });
+}
+
+int Sharded::clearRegisterTracksList() {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int, Batch& b) { return b.clearTrackLists(); });
+}
+
 int Sharded::tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set) {
     Serial serial(api_);
     lastError_.clear();
@@ -967,7 +1004,7 @@ int64_t Sharded::info(int what) {
     if (what == FXB_INFO_GRID || what == FXB_INFO_HOST_STAGED_BLOCKS || what == FXB_INFO_HOST_INPLACE_BLOCKS || what == FXB_INFO_BUS_BLOCKS ||
         what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
         what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS || what == FXB_INFO_TRAM_LIST_SETS || what == FXB_INFO_TRAM_LIST_GETS ||
-        what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS ||
+        what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS || what == FXB_INFO_TRACK_LIST_EXPANDS ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

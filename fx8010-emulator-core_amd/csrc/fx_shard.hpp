@@ -148,6 +148,11 @@ public:
     int setRegistersList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* values) {
         return registersList(true, keys, nKeys, list, count, values, nullptr);
     }
+    // list schedules (include/fx8010_amd.h "Register tracks by list"): keys resolved on the front shard, the whole call checked
+    // before any shard is posted, every shard asked (what is armed, its staging, its track buffer) before any arms; a shard takes
+    // its entries with their columns of every step - one without entries makes the registers trackable and stages nothing
+    int setRegisterTracksList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* values, int nSteps, int first, int period);
+    int clearRegisterTracksList();
     int getRegistersList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, float* values) {
         return registersList(false, keys, nKeys, list, count, nullptr, values);
     }

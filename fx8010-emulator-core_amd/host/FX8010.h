@@ -352,6 +352,18 @@ public:
         if (fxb_set_registers_list(h_, names.data(), (int)names.size(), list.data(), (int64_t)list.size(), values.data()) != 0)
             throw std::runtime_error(std::string("FX8010Batch::setRegistersList: ") + fxb_last_error(h_));
     }
+    // Register tracks by list (include/fx8010_amd.h "Register tracks by list"): arms one list schedule for the next process call.
+    // values[(q * keys.size() + k) * list.size() + i] is what register keys[k] of instance list[i] takes at sample
+    // first + q * period; the number of steps follows from values.size().  The other voices keep what they hold.
+    void setRegisterTracksList(const std::vector<std::string>& keys, const std::vector<int64_t>& list, const std::vector<float>& values, int first = 0, int period = 1) {
+        const size_t perStep = keys.size() * list.size();
+        if (perStep == 0 || values.empty() || values.size() % perStep != 0) throw std::runtime_error("FX8010Batch::setRegisterTracksList: values must hold steps x keys x list words");
+        std::vector<const char*> names;
+        for (const std::string& k : keys) names.push_back(k.c_str());
+        if (fxb_set_register_tracks_list(h_, names.data(), (int)names.size(), list.data(), (int64_t)list.size(), values.data(), (int)(values.size() / perStep), first, period) != 0)
+            throw std::runtime_error(std::string("FX8010Batch::setRegisterTracksList: ") + fxb_last_error(h_));
+    }
+    void clearRegisterTracksList() { fxb_clear_register_tracks_list(h_); }
     std::vector<float> getRegistersList(const std::vector<std::string>& keys, const std::vector<int64_t>& list) {
         std::vector<const char*> names;
         for (const std::string& k : keys) names.push_back(k.c_str());

@@ -29,7 +29,7 @@ INFO = {
     "bus_feed_blocks": 44, "instance_rings": 45, "instance_rotations": 46, "xlate_quiet": 47, "xlate_quiet_left": 48, "gain_list_sets": 49,
     "register_list_sets": 50, "register_list_gets": 51, "xlate_sum_groups": 52, "xlate_sum_links": 53, "xlate_quiet_repairs": 54,
     "tram_list_sets": 55, "tram_list_gets": 56,
-    "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59,
+    "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59, "track_list_expands": 60,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -43,7 +43,7 @@ SYMBOLS = [
     "fx_instruction_counter", "fx_error_count", "fx_error_desc", "fx_error_row", "fx_control_count", "fx_control_at",
     "fx_meta_get", "fx_set_option", "fxb_set_option", "fxp_set_option", "fx_set_channels", "fx_get_channels", "fx_ready", "fx_last_error", "fx_last_create_error",
     "fxb_create", "fxb_create_sharded", "fxb_create_on_devices", "fxb_shard_count", "fxb_shard_info", "fxb_shard_kernel_ms", "fxb_shard_plan", "fxb_process_block_dev_shards", "fxb_destroy", "fxb_load_file", "fxb_load_text", "fxb_set_register", "fxb_set_register_i",
-    "fxb_get_register_i", "fxb_set_registers_list", "fxb_get_registers_list", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_set_tram_list", "fxb_get_tram_list", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
+    "fxb_get_register_i", "fxb_set_registers_list", "fxb_get_registers_list", "fxb_set_register_tracks_list", "fxb_clear_register_tracks_list", "fxb_set_register_track", "fxb_set_register_array", "fxb_get_register_array", "fxb_seed_noise_i", "fxb_prepare", "fxb_state_size", "fxb_save_state", "fxb_load_state", "fxb_get_tram_i", "fxb_get_cursors_i", "fxb_set_tram_list", "fxb_get_tram_list", "fxb_process_block", "fxb_process_block_dev", "fxb_sync",
     "fxb_process_block_pitched", "fxb_process_block_dev_pitched",
     "fxb_bus_groups", "fxb_process_block_bus", "fxb_process_block_bus_dev", "fxb_bus_set_gains", "fxb_bus_get_gains",
     "fxb_bus_set_gains_list", "fxb_bus_set_send_gains_list", "fxb_bus_set_feed_gains_list",
@@ -121,6 +121,7 @@ def load():
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
     sig("fxb_load_instances_rotated", i32, vp, vp, i64, vp, i64)
     sig("fxb_set_registers_list", i32, vp, vp, i32, vp, i64, vp); sig("fxb_get_registers_list", i32, vp, vp, i32, vp, i64, vp)
+    sig("fxb_set_register_tracks_list", i32, vp, vp, i32, vp, i64, vp, i32, i32, i32); sig("fxb_clear_register_tracks_list", i32, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_meter_select", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_read_list", i32, vp, vp, i64, vp, vp, vp, vp, i32); sig("fxb_meter_reset_list", i32, vp, vp, i64)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
@@ -454,6 +455,25 @@ class Batch(_Reports):
             raise ValueError("set_registers_list: values must be [len(keys), len(instances)]")
         return self._check(self._lib.fxb_set_registers_list(self._h, table, n_keys, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
                                                             C.c_void_p(v.ctypes.data) if v.size else None), "set_registers_list")
+
+    def set_register_tracks_list(self, keys, instances, values, first=0, period=1):
+        """Arms one list schedule for the next process call (include/fx8010_amd.h "Register tracks by list"): values is float32
+        [steps, len(keys), len(instances)] ([steps, len(instances)] for one key given as a string), as bit patterns; step q falls
+        due at sample first + q * period, where register keys[k] of instance instances[i] takes values[q, k, i].  The other
+        voices keep what they hold; steps beyond the block are dropped.  Returns 0, or 1 when a key is no register."""
+        table, n_keys = self._key_table(keys)
+        lst = self._instance_list(instances)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        per_step = n_keys * lst.size
+        if v.ndim < 1 or v.shape[0] < 1 or v.size != v.shape[0] * per_step:
+            raise ValueError("set_register_tracks_list: values must be [steps, len(keys), len(instances)]")
+        return self._check(self._lib.fxb_set_register_tracks_list(self._h, table, n_keys, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
+                                                                  C.c_void_p(v.ctypes.data) if v.size else None, int(v.shape[0]), int(first), int(period)),
+                           "set_register_tracks_list")
+
+    def clear_register_tracks_list(self):
+        """drops every armed list schedule"""
+        return self._check(self._lib.fxb_clear_register_tracks_list(self._h), "clear_register_tracks_list")
 
     def get_registers_list(self, keys, instances):
         """float32 [len(keys), len(instances)]: what get_register_i returns for every (key, instance), bit for bit, with one

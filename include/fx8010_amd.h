@@ -286,6 +286,48 @@ int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count
  * FXB_INFO_REGISTER_LIST_SETS / _GETS count the launches of the two kernels (fx_reg_scatter, fx_reg_gather). */
 int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values);
 int fxb_get_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, float* values);
+/* Register tracks by list: a change of a program parameter AT A GIVEN SAMPLE of the next block, for the voices a host names - a
+ * note-on at sample 13 of a 32-sample block, a glide, an envelope segment for the handful of voices that are moving.  The dense
+ * form, fxb_set_register_track(..., per_instance = 1), wants n_steps * N floats from the host, a value for every voice that does
+ * not move included; cutting the block and calling fxb_set_registers_list at each cut costs a launch floor per piece.
+ *
+ * One call arms one LIST SCHEDULE for the next fxb_process_block* call (one-shot, as tracks are).  Step q (0 <= q < n_steps) falls
+ * due at sample first + q * period of that block; there, register keys[k] of global instance list[i] takes
+ * values[(q * n_keys + k) * count + i] - [step][key][entry], the register lists' [key][entry] per step.  Values are 32-bit
+ * patterns: NaN payloads, -0 and denormals arrive as given.  Steps that fall at or beyond the block's length are dropped.
+ * Afterwards a listed voice holds its last applied step, every other voice what it held.
+ * DEFINITION: a block with list schedules armed leaves the caller's PCM and the handle in exactly the state that this sequence
+ *   would have left: cut the block at every sample where a step falls due; in front of each piece call
+ *   fxb_set_registers_list(keys, n_keys, list, count, <that step's values>) for every schedule with a step due there, in arming
+ *   order.  "The state": the words on the device, fxb_save_state, what every get call returns, what the library knows about the
+ *   registers.
+ * Several schedules may be armed for one block, with different lists, `first` and `period`, also on the same register - two
+ *   voices with note-ons at different samples - up to 64 per handle; together with fxb_set_register_track at most 16 registers
+ *   have schedules.  fxb_clear_register_tracks_list drops every armed list schedule (returns 0).
+ * Returns 0 - also for count == 0 or n_keys == 0, which arm nothing - or, with nothing armed and nothing changed, every shard
+ *   asked before any arms, fxb_last_error naming the argument (for a list entry the caller's index): FX_E_ARG for a negative
+ *   count or n_keys; null keys / list / values with something to do; n_steps < 1, period < 1 or first < 0;
+ *   n_steps * n_keys * count >= 2^31; an instance outside 0..N-1 or listed twice; two keys that name one register; a 65th
+ *   schedule or a 17th register with schedules; a register that has a schedule armed through fxb_set_register_track (and
+ *   fxb_set_register_track refuses a register with list schedules armed); an instance that an armed list schedule already names
+ *   for the same register; a register the program itself can change - the result of an instruction, the CCR, an input or an
+ *   output register (named in the message): for such a register "the others keep what they have" is no value known at the head
+ *   of the block.  1 for a key that is no register; FX_E_NOTREADY without a program; FX_E_MEMORY when the staging
+ *   (2 * count + n_steps * n_keys * count + n_keys words per schedule, device and pinned) or the track buffer (one row of N
+ *   words, padded to 256, per step and key of everything armed; below 4 GiB) could not be grown - both grow in this call,
+ *   never inside a block.
+ * Ordering: the call waits on the host only for the expansion of the previous block's schedules (two small kernels at the head
+ *   of that block), not for the block.  The caller's arrays are free on return.  The block reads the registers' values at its
+ *   own head: a fxb_set_registers_list queued between the arming and the block shows in what the other voices hold.
+ * Code: as with fxb_set_register_track, the first schedule of a register makes it trackable, which asks for other code once; a
+ *   real-time host arms once before fxb_prepare.  Arming a list schedule for a register that is trackable never translates
+ *   again, and FXB_INFO_XLATE_CODE_HASH equals that with dense per-instance tracks on the same registers.
+ * Sharded handles: every shard takes its entries with their columns of every step; on a shard without entries the registers
+ *   become trackable all the same (one code for all shards) and nothing is staged or launched.
+ * FXB_INFO_TRACK_LIST_EXPANDS counts the blocks that launched the expansion (fx_track_hold, fx_track_scatter). */
+int fxb_set_register_tracks_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count,
+                                 const float* values, int n_steps, int first, int period);
+int fxb_clear_register_tracks_list(fxb_handle* h);
 /* Delay-line windows by list: a window of ONE delay line of the instances a host names, written or read on the GPU - the burst
  * that excites a string or comb voice at note-on, the zeros that cut a reverb tail without touching the filter registers, an
  * impulse response or loop to pre-fill, a look at what a loop holds now.  fxb_get_tram_i handles one instance per call behind a
@@ -855,7 +897,8 @@ enum {
     FXB_INFO_TRAM_LIST_GETS = 56,      /* launches of the kernel fx_tram_gather - by fxb_get_tram_list - since creation (summed over shards) */
     FXB_INFO_METER_SELECTS = 57,       /* calls of fxb_meter_select that launched (fx_meter_count / _scan / _emit) since creation (summed over shards) */
     FXB_INFO_METER_LIST_READS = 58,    /* calls of fxb_meter_read_list that launched (fx_meter_gather) since creation (summed over shards) */
-    FXB_INFO_METER_LIST_RESETS = 59    /* calls of fxb_meter_reset_list that launched (fx_meter_zero) since creation (summed over shards) */
+    FXB_INFO_METER_LIST_RESETS = 59,   /* calls of fxb_meter_reset_list that launched (fx_meter_zero) since creation (summed over shards) */
+    FXB_INFO_TRACK_LIST_EXPANDS = 60   /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter

@@ -175,6 +175,8 @@ def run(seed, verbose=False, edit=None):
             pos += S
             plans = []
             pool = names[:3] if rng.integers(0, 2) else list(dict.fromkeys(names))   # (a few registers again and again, or any: up to sixteen get a slot)
+            if rng.integers(0, 2):
+                pool = [r for r in pool if str(r) != "c"]   # (every other time the control is left to the list schedules below)
             for name in rng.choice(pool, size=int(rng.integers(1, min(len(pool), 5) + 1)), replace=False):
                 period = int(rng.choice([1, 2, 3, 8]))
                 steps = int(rng.integers(1, S // period + 3))
@@ -186,6 +188,24 @@ def run(seed, verbose=False, edit=None):
                 plans.append((str(name), period, vals))
                 if verbose:
                     print("  track", name, "period", period, "steps", steps, "per-instance" if vals.ndim == 2 else "broadcast", "S", S)
+            # list schedules beside them (fxb_set_register_tracks_list): a few voices of a register that has no dense schedule in this
+            # block; the twin is the cut block - the oracle of a listed voice gets the step's value in front of the due sample.  A
+            # register the program writes, or a seventeenth one, is refused: then nothing is armed
+            lists = []
+            free = sorted([r for r in dict.fromkeys(["c"] + [str(r) for r in pool]) if r not in [p[0] for p in plans]], key=lambda r: not r.startswith("c"))   # (the controls first: they are only read)
+            for name in free[:int(rng.integers(0, 3))]:
+                count = int(rng.integers(1, N + 1))
+                L = np.sort(rng.permutation(N)[:count]).astype(np.int64) if rng.integers(0, 2) else rng.permutation(N)[:count].astype(np.int64)
+                first, period = int(rng.integers(0, S + 2)), int(rng.choice([1, 2, 3, 8]))
+                steps = int(rng.integers(1, S // period + 3))
+                vals = np.array([[value(rng) for _ in range(count)] for _ in range(steps)], dtype=np.float32)
+                try:
+                    if b.set_register_tracks_list(name, L, vals, first=first, period=period) == 0:
+                        lists.append((name, first, period, vals, {int(i): k for k, i in enumerate(L)}))
+                except RuntimeError:
+                    pass
+                if verbose:
+                    print("  list schedule", name, "first", first, "period", period, "steps", steps, "voices", count, "S", S, "armed" if lists and lists[-1][0] == name else "refused: " + b.last_error())
             y = process(b, xs)
             if verbose:
                 for name, period, vals in plans:
@@ -198,6 +218,9 @@ def run(seed, verbose=False, edit=None):
                         if t % period == 0 and t // period < vals.shape[0]:
                             v = vals[t // period]
                             oracles[n].set_register(name, float(v if vals.ndim == 1 else v[n]))
+                    for name, first, period, vals, where in lists:
+                        if n in where and t >= first and (t - first) % period == 0 and (t - first) // period < vals.shape[0]:
+                            oracles[n].set_register(name, float(vals[(t - first) // period, where[n]]))
                     ref[t] = oracles[n].process_block(xs[t:t + 1, n].copy())[0]
                 if oracles[n].ood_flags():
                     return True

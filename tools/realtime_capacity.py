@@ -18,6 +18,7 @@ replays every block of the run for sampled instances (same PCM, same slider sche
 fxb_set_registers_list, fxb_set_register_array and fxb_set_register_i by turns in one process (register_paths;
 profiles/register_list_realtime.txt).
 
+    python tools/realtime_capacity.py --track-list [--blocks 3000] [--register-instances 131072,458752] [--track-out FILE]
     python tools/realtime_capacity.py --register-list [--blocks 3000] [--register-instances 131072,458752] [--register-out FILE]
 """
 import argparse
@@ -284,6 +285,140 @@ def register_paths(torch, A, progs, n, blocks, warm, stretch, log, clock=lambda:
     return out
 
 
+TRACK_KEY, TRACK_LIST, TRACK_STEPS, TRACK_PERIOD = "decay", 1024, 4, 8
+
+
+def track_paths(torch, A, progs, n, blocks, warm, stretch, log, only=None):
+    """--track-list: 32-sample blocks of config5 from pinned host buffers, four handles by turns in stretches in one process: no
+    schedule; a list schedule of 1 024 voices x 1 register x 4 steps (period 8) armed in front of every block; the same schedule
+    as a dense per_instance track (fxb_set_register_track, 4 x N floats - the rows are ready-made: the host's work of knowing
+    every voice's value is not in the timed region); the block cut in four with fxb_set_registers_list at the cuts.  The arming
+    is inside the block's time.  All four handles have the register trackable from the start, so all four run the same code.
+    only: the one path of a profiler run."""
+    import numpy as np
+
+    text = progs.config5()
+    lib = A.load()
+    names = ("none", "list %d" % TRACK_LIST, "dense", "cut")
+    paths = []
+    rng = np.random.default_rng(7)
+    keys = (C.c_char_p * 1)(TRACK_KEY.encode())
+    ring = [progs.stimulus(n, BLOCK, first_sample=k * BLOCK) for k in range(RING)]
+    xin = [torch.empty((BLOCK, n), dtype=torch.float32).pin_memory() for _ in range(RING)]
+    for t, r in zip(xin, ring):
+        t.numpy()[...] = r
+    piece = BLOCK // TRACK_STEPS
+    assert piece == TRACK_PERIOD
+    for name in names:
+        if only and name.split()[0] != only:
+            continue
+        b = A.Batch(n, 1, 0)
+        if not b.load_text(text):
+            raise RuntimeError("load failed: %s" % b.errors())
+        row = rng.uniform(0.1, 0.4, n).astype(np.float32)
+        assert b.set_register_array(TRACK_KEY, row) == 0
+        # trackable from the start: a schedule with nothing due inside any block
+        assert b.set_register_tracks_list([TRACK_KEY], [0], np.zeros((1, 1, 1), dtype=np.float32), first=1 << 20) == 0
+        b.process_block(ring[0])
+        b.prepare(BLOCK, True)
+        b.prepare(piece, True)
+        yout = torch.empty((BLOCK, n), dtype=torch.float32).pin_memory()
+        lists = [np.ascontiguousarray(rng.permutation(n)[:TRACK_LIST].astype(np.int64)) for _ in range(RING)]
+        values = [np.ascontiguousarray(rng.uniform(0.1, 0.4, (TRACK_STEPS, 1, TRACK_LIST)).astype(np.float32)) for _ in range(RING)]
+        dense = None
+        if name == "dense":
+            dense = []
+            for L, v in zip(lists, values):
+                d = np.tile(row, (TRACK_STEPS, 1))
+                d[:, L] = v[:, 0, :]
+                dense.append(np.ascontiguousarray(d))
+        paths.append({"name": name, "b": b, "yout": yout, "lists": lists, "values": values, "dense": dense, "times": [], "k": 0})
+
+    def fptr(t, sample=0):
+        return C.cast(t.data_ptr() + sample * n * 4, C.POINTER(C.c_float))
+
+    def block(p, timed):
+        b, k, h = p["b"], p["k"], p["b"]._h
+        p["k"] += 1
+        L, v = p["lists"][k % RING], p["values"][k % RING]
+        x, y = xin[k % RING], p["yout"]
+        t0 = time.perf_counter_ns()
+        kind = p["name"].split()[0]
+        if kind == "cut":
+            for q in range(TRACK_STEPS):
+                rc = lib.fxb_set_registers_list(h, keys, 1, C.c_void_p(L.ctypes.data), TRACK_LIST, C.c_void_p(v[q].ctypes.data))
+                assert rc == 0, (rc, b.last_error())
+                rc = lib.fxb_process_block(h, fptr(x, q * piece), fptr(y, q * piece), piece)
+                assert rc == 0, (rc, b.last_error())
+        else:
+            if kind == "list":
+                rc = lib.fxb_set_register_tracks_list(h, keys, 1, C.c_void_p(L.ctypes.data), TRACK_LIST, C.c_void_p(v.ctypes.data), TRACK_STEPS, 0, TRACK_PERIOD)
+                assert rc == 0, (rc, b.last_error())
+            elif kind == "dense":
+                rc = lib.fxb_set_register_track(h, TRACK_KEY.encode(), C.c_void_p(p["dense"][k % RING].ctypes.data), TRACK_STEPS, TRACK_PERIOD, 1)
+                assert rc == 0, (rc, b.last_error())
+            rc = lib.fxb_process_block(h, fptr(x), fptr(y), BLOCK)
+            if rc != 0:
+                raise RuntimeError("block %d failed (%d): %s" % (k, rc, b.last_error()))
+        if timed:
+            p["times"].append((time.perf_counter_ns() - t0) * 1e-3)
+
+    for p in paths:
+        for _ in range(warm):
+            block(p, False)
+        p["b"].prepare(BLOCK, True)
+        p["builds"] = (p["b"].info("xlate_builds"), p["b"].info("xlate_background_builds"))
+    gc.collect()
+    gc.disable()
+    try:
+        done = 0
+        while done < blocks:
+            for p in paths:
+                for _ in range(stretch):
+                    block(p, True)
+            done += stretch
+    finally:
+        gc.enable()
+    out = {"instances": n, "rows": []}
+    for p in paths:
+        b = p["b"]
+        r = percentiles(p["times"])
+        r.update({"path": p["name"], "instances": n, "within_budget_p999": r["p999_us"] <= BUDGET_US, "track_list_expands": b.info("track_list_expands"), "tier": b.tier_note(),
+                  "code_hash": b.info("xlate_code_hash"), "translations_in_timed_region": [b.info("xlate_builds") - p["builds"][0], b.info("xlate_background_builds") - p["builds"][1]]})
+        out["rows"].append(r)
+        log("%-10s N=%7d  median %7.1f  p99 %7.1f  p99.9 %7.1f  max %8.1f us  %s  %d expansions  translations in the timed region %s  code %016x" % (
+            p["name"], n, r["median_us"], r["p99_us"], r["p999_us"], r["max_us"], "REAL TIME" if r["within_budget_p999"] else "over budget", r["track_list_expands"],
+            r["translations_in_timed_region"], r["code_hash"] & 0xffffffffffffffff))
+        b.close()
+    return out
+
+
+def track_main(args, torch, A, progs):
+    lines = []
+
+    def keep(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    if args.trace_run:   # under rocprofv3 --kernel-trace --stats: the list path alone, a run of its own
+        track_paths(torch, A, progs, args.trace_instances, 200, 50, 200, keep, only="list")
+        return
+    keep("32-sample blocks of config5 (pinned host buffers, fxb_process_block) against %.3f us: no schedule; fxb_set_register_tracks_list of %d voices x 1 register (%s) x %d steps, "
+         "period %d; the same schedule through fxb_set_register_track(per_instance = 1); the block cut in %d with fxb_set_registers_list at the cuts - armed in front of every "
+         "block, inside the timed region, by turns in stretches of %d blocks in one process, %d blocks per point after %d warm-up blocks; the register is trackable on all "
+         "four handles; %s" % (BUDGET_US, TRACK_LIST, TRACK_KEY, TRACK_STEPS, TRACK_PERIOD, TRACK_STEPS, args.stretch, args.blocks, args.warmup, torch.cuda.get_device_name(0)))
+    out = [track_paths(torch, A, progs, n, args.blocks, args.warmup, args.stretch, keep) for n in [int(v) for v in args.register_instances.split(",") if v]]
+    for point in out:
+        med = {r["path"].split()[0]: r["median_us"] for r in point["rows"]}
+        keep("           N=%7d  median over no schedule: list %+.1f us, dense %+.1f us, cut %+.1f us" % (point["instances"], med["list"] - med["none"], med["dense"] - med["none"], med["cut"] - med["none"]))
+    if args.track_out:
+        with open(args.track_out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
 def register_main(args, torch, A, progs):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from bus_capacity import shader_clock_reader
@@ -316,6 +451,8 @@ def register_main(args, torch, A, progs):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--register-list", action="store_true", help="the four register-write paths by turns (register_paths) instead of the capacity sweep")
+    ap.add_argument("--track-list", action="store_true", help="no schedule / list schedule / dense per-instance track / cut block by turns (track_paths) instead of the capacity sweep")
+    ap.add_argument("--track-out", default="", help="keep the lines of --track-list in this text file")
     ap.add_argument("--register-instances", default="131072,458752")
     ap.add_argument("--register-out", default="", help="keep the lines of --register-list in this text file")
     ap.add_argument("--stretch", type=int, default=250, help="--register-list: blocks of one path before the next takes its turn")
@@ -335,6 +472,8 @@ def main():
     import fx8010_programs as progs
     if args.register_list:
         return register_main(args, torch, A, progs)
+    if args.track_list:
+        return track_main(args, torch, A, progs)
     inst = [int(v) for v in args.instances.split(",") if v]
     dev_inst = [int(v) for v in args.device_instances.split(",") if v] or [4096, 65536, 131072, 262144, 393216, 458752, 524288, 557056, 589824]
     log = lambda s: print(s, flush=True)
