@@ -77,6 +77,9 @@ Batch::~Batch() {
     freeBlock(bus_, false);
     freeBlock(busStage_, false);
     (void)hipFree(dMeter_);
+    (void)hipFree(dTarget_);
+    (void)hipFree(dMatch_);
+    releaseMeterTarget();
     (void)hipFree(dGain_[0]);
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
@@ -161,7 +164,8 @@ int Batch::setOption(unsigned option, bool on) {
 
 int Batch::afterLoad(bool ok) {
     (void)hipSetDevice(device_);
-    if (dMeter_) (void)meterReset();   // a program load resets the meters and keeps them enabled
+    if (dTarget_) (void)clearMeterTarget();   // a program load drops the target of the program that was
+    if (dMeter_) (void)meterReset();          // ... resets the meters and keeps them enabled
     // registers may have been created even when the load failed; keep host mirrors in step
     const size_t old = hostValue_.size();
     hostValue_.resize(prog_.regs.size());
@@ -848,6 +852,8 @@ float Batch::lastKernelMs() {
 int Batch::meterReset() {
     waitLastLaunch();
     hipError_t e = hipMemsetAsync(dMeter_, 0, meterChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
+    // (all six: the match rows of a target as well; the target position stays)
+    if (e == hipSuccess && dMatch_) e = hipMemsetAsync(dMatch_, 0, matchChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     meterSamples_ = 0;
     return e == hipSuccess ? 0 : hipFail(e, "zeroing the meter rows");
@@ -859,6 +865,7 @@ int Batch::meterEnable(bool on) {
     waitLastLaunch();
     (void)hipStreamSynchronize(stream_);
     if (!on) {
+        (void)clearMeterTarget();
         (void)hipFree(dMeter_);
         dMeter_ = nullptr;
         meterSamples_ = 0;
@@ -979,6 +986,9 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_LIST_READS) return meterListReads_;
     if (what == FXB_INFO_METER_LIST_RESETS) return meterListResets_;
     if (what == FXB_INFO_TRACK_LIST_EXPANDS) return trackListExpands_;
+    if (what == FXB_INFO_METER_TARGET_LAUNCHES) return meterTargetLaunches_;
+    if (what == FXB_INFO_METER_MATCH_SELECTS) return matchSelects_;
+    if (what == FXB_INFO_METER_MATCH_BESTS) return matchBests_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

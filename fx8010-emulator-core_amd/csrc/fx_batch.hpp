@@ -332,6 +332,31 @@ public:
     int64_t meterSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
     int meterReadList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
     int meterResetList(const int64_t* list, int64_t count);
+    // Target meters (fx_meter.hpp MeterTargetArgs; include/fx8010_amd.h "Target meters"; fx_batch_meter_target.cpp).  Split
+    // check / reserve / act like the list calls.  checkMeterTarget is the refusal of the whole handle's arguments (nTotal:
+    // instances of the whole handle).  reserveMeterTarget allocates what a set needs for THIS batch - the block of the target
+    // columns its instances firstGlobal .. firstGlobal + n - 1 use, the match rows where there are none - and keeps it aside;
+    // FX_E_MEMORY or FX_E_ARG (metering off, the 32-bit row stride) changes nothing.  releaseMeterTarget frees what was kept
+    // aside.  setMeterTarget waits as sync() does, copies this batch's columns out of the caller's [nSamples][channels][cols]
+    // block, zeroes the match rows, takes the reserved blocks into force and sets the position to 0.  While a target is set
+    // launchBlock launches fx_meter_target in place of fx_meter and advances the position, per launch.
+    static int checkMeterTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags, int channels, int64_t nTotal, std::string* why);
+    int reserveMeterTarget(int64_t nSamples, int64_t group, int64_t firstGlobal);
+    void releaseMeterTarget();
+    int setMeterTarget(const float* target, int64_t nSamples, int64_t group, int64_t firstGlobal, int64_t cols, bool loop);
+    int clearMeterTarget();
+    bool meterTargetSet() const { return dTarget_ != nullptr; }
+    int meterTargetSeek(int64_t pos);
+    int64_t meterTargetPos() const { return dTarget_ ? targetPos_ : (int64_t)-3; }
+    int meterReadMatch(double* err, double* cross, bool reset, int64_t rowPitch = 0);
+    // select over V = the channel sum of match row `stat`: everything else as meterSelect, whose staging it shares
+    static int checkMatchSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
+    int64_t matchSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
+    // the best member of every group this batch has a part of: groups firstGlobal / group .. (firstGlobal + n - 1) / group, their
+    // count is meterBestGroups; winner / value get one entry each (global instance numbers).  Synchronous.
+    int64_t meterBestGroups(int64_t group, int64_t firstGlobal) const { return (firstGlobal + n_ - 1) / group - firstGlobal / group + 1; }
+    int reserveMeterBest(int64_t group, int64_t firstGlobal);
+    int meterBest(int stat, int64_t group, int64_t firstGlobal, bool largest, int64_t* winner, double* value);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -824,6 +849,18 @@ private:
     Block<unsigned long long> meterStage_, hMeterStage_;
     int reserveMeterStage(size_t words, bool needEvent);
     int64_t meterSelects_ = 0, meterListReads_ = 0, meterListResets_ = 0;   // FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS
+    int64_t runSelect(bool match, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
+    // target meters (fx_batch_meter_target.cpp): the target block and the match rows in force (null: no target), the blocks a
+    // set has reserved and not yet taken, the shape of the target, and the position of the next queued block
+    float* dTarget_ = nullptr;
+    void* dMatch_ = nullptr;
+    float* targetNew_ = nullptr;
+    void* matchNew_ = nullptr;
+    int64_t targetSamples_ = 0, targetCols_ = 0, targetGroup_ = 1, targetFirstGlobal_ = 0, targetPos_ = 0;
+    bool targetLoop_ = false;
+    int zeroMatchRows();   // queued on stream_ and waited for
+    MeterTargetArgs meterTargetArgs(const MeterArgs& m) const;   // of the block that is about to be queued
+    int64_t meterTargetLaunches_ = 0, matchSelects_ = 0, matchBests_ = 0;   // FXB_INFO_METER_TARGET_LAUNCHES / _MATCH_SELECTS / _MATCH_BESTS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

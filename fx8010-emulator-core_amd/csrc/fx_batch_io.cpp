@@ -317,8 +317,17 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
             m.pitch = pitch;
             m.samples = nSamples;
             m.channels = prog_.numChannels;
-            if ((e = launchMeter(m, s)) != hipSuccess) return hipFail(e, "launch fx_meter");
-            ++meterLaunches_;
+            if (dTarget_) {
+                // a target is set: fx_meter_target in place of fx_meter - the block is read once - and the target position moves
+                // on by this launch's samples, so that however a stream is cut every sample meets the same target row
+                if ((e = launchMeterTarget(meterTargetArgs(m), s)) != hipSuccess) return hipFail(e, "launch fx_meter_target");
+                ++meterTargetLaunches_;
+                targetPos_ += nSamples;
+                if (targetLoop_) targetPos_ %= targetSamples_;
+            } else {
+                if ((e = launchMeter(m, s)) != hipSuccess) return hipFail(e, "launch fx_meter");
+                ++meterLaunches_;
+            }
             meterSamples_ += nSamples;
         }
         if (e == hipSuccess && timed) e = hipEventRecord(ev1_, s);

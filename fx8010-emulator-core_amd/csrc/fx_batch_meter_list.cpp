@@ -89,8 +89,15 @@ int Batch::reserveMeterSelect(int64_t nRange, int64_t cap) { return reserveMeter
 int Batch::reserveMeterList(int64_t count, bool gather) { return reserveMeterStage(count > 0 ? listWords(prog_.numChannels, count, gather) : 0, !gather); }
 
 int64_t Batch::meterSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
+    return runSelect(false, stat, threshold, below, first, nRange, firstGlobal, list, cap);
+}
+
+// match: the select over the match rows of a target (fx_batch_meter_target.cpp) - the same staging, copies and counts of words,
+// another predicate on the device
+int64_t Batch::runSelect(bool match, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
     (void)hipSetDevice(device_);
     if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
+    if (match && !dTarget_) return fail(FX_E_ARG, "meter target: no target is set (fxb_meter_set_target)");
     if (nRange == 0) return 0;
     if (selectWords(nRange, cap) > meterStage_.cap || selectWords(nRange, cap) > hMeterStage_.cap) return fail(FX_E_ARG, "meter_select: no staging reserved (reserveMeterSelect)");
     const int rc = sync();
@@ -112,8 +119,13 @@ int64_t Batch::meterSelect(int stat, double threshold, bool below, int64_t first
     a.channels = prog_.numChannels;
     a.stat = stat;
     a.below = below ? 1 : 0;
-    hipError_t e = launchMeterSelect(a, stream_);
-    if (e == hipSuccess) ++meterSelects_;
+    hipError_t e;
+    if (match) {
+        const MatchSelectArgs b{dMatch_, a.offsets, a.list, a.n, a.nPad, a.first, a.nRange, a.firstGlobal, a.cap, a.threshold, a.channels, a.stat, a.below};
+        if ((e = launchMatchSelect(b, stream_)) == hipSuccess) ++matchSelects_;
+    } else if ((e = launchMeterSelect(a, stream_)) == hipSuccess) {
+        ++meterSelects_;
+    }
     // the total and the head of the list in one copy; the rest of a long list once the total says how long it is
     const int64_t head = std::min(room, kSelectHead);
     unsigned long long* const hTotal = hMeterStage_.p + chunks;
@@ -202,6 +214,11 @@ int Batch::meterResetList(const int64_t* list, int64_t count) {
     if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
     if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
     if (e == hipSuccess) e = launchMeterZero(a, stream_);
+    // (a slot reused gets fresh meters, all of them: the listed columns of the match rows of a target, inside the same frame)
+    if (e == hipSuccess && dMatch_) {
+        a.rows = dMatch_;
+        e = launchMatchZero(a, stream_);
+    }
     if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(stream_);   // (nothing may still read the staging)

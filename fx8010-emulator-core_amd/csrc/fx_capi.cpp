@@ -296,6 +296,21 @@ int fxb_meter_read_list(fxb_handle* h, const int64_t* list, int64_t count, doubl
 int fxb_meter_reset_list(fxb_handle* h, const int64_t* list, int64_t count) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterResetList(list, count); }) : FX_E_ARG;
 }
+int fxb_meter_set_target(fxb_handle* h, const float* target, int64_t n_samples, int64_t group, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterSetTarget(target, n_samples, group, flags); }) : FX_E_ARG;
+}
+int fxb_meter_clear_target(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterClearTarget(); }) : FX_E_ARG; }
+int fxb_meter_target_seek(fxb_handle* h, int64_t pos) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterTargetSeek(pos); }) : FX_E_ARG; }
+int64_t fxb_meter_target_pos(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterTargetPos(); }) : FX_E_ARG; }
+int fxb_meter_read_match(fxb_handle* h, double* err, double* cross, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadMatch(err, cross, reset != 0); }) : FX_E_ARG;
+}
+int64_t fxb_meter_select_match(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelectMatch(stat, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
+}
+int fxb_meter_best(fxb_handle* h, int stat, int64_t group, int64_t* winner, double* value, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterBest(stat, group, winner, value, flags); }) : FX_E_ARG;
+}
 int64_t fxb_meter_samples(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSamples(); }) : FX_E_ARG; }
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }

@@ -39,4 +39,29 @@ struct MeterArgs {
 // reads the accumulators once, walks the samples of every column in order, writes them back once
 hipError_t launchMeter(const MeterArgs& a, hipStream_t stream);
 
+// Target meters (include/fx8010_amd.h "Target meters"): two further fp64 accumulators per (channel, instance) against a reference
+// signal held on the device.  The match rows are a block of their own - per channel err f64 [nPad], then cross f64 [nPad], all
+// +0.0 after a reset - so that a handle without a target carries nothing of them.
+constexpr size_t kMatchBytesPerColumn = 16;
+constexpr size_t matchChannelBytes(long long nPad) { return kMatchBytesPerColumn * (size_t)nPad; }
+constexpr size_t matchErrOff(long long) { return 0; }
+constexpr size_t matchCrossOff(long long nPad) { return 8 * (size_t)nPad; }
+
+struct MeterTargetArgs {
+    MeterArgs m;             // the block and the four accumulators, as for launchMeter
+    void* match;             // [channels] x the match rows above (device memory)
+    const float* target;     // [tSamples][channels][tCols] (device memory): the target columns this batch's instances use
+    long long tSamples;      // >= 1
+    long long tCols;         // columns of a target row; channels * tCols * 4 < 2^32
+    long long group;         // >= 1: instance i is compared with column (firstGlobal + i) / group - firstColumn
+    long long firstGlobal;   // the global number of column 0 of y
+    long long firstColumn;   // firstGlobal / group
+    long long pos;           // target position of sample 0 of the block, >= 0; with loop below tSamples
+    int loop;                // 0: samples at positions >= tSamples change the four only; 1: the position wraps
+};
+
+// fx_meter with the two match accumulators beside the four: launched INSTEAD of launchMeter while a target is set, so that the
+// block is read once.  The four are taken by the same code (meterTake), for every sample.
+hipError_t launchMeterTarget(const MeterTargetArgs& a, hipStream_t stream);
+
 }  // namespace fx

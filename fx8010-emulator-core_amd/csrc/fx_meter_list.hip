@@ -29,6 +29,16 @@
 // Resource usage (-O3, gfx950, from -Rpass-analysis=kernel-resource-usage), VGPRs / scratch bytes per lane / LDS bytes per
 // workgroup: fx_meter_count 14 / 0 / 16, fx_meter_scan 16 / 0 / 2 048, fx_meter_emit 16 / 0 / 16, fx_meter_gather 33 / 0 / 0,
 // fx_meter_zero 18 / 0 / 0; eight wavefronts per SIMD each.
+//
+// The queries over the match rows of a target (fx_meter_list.hpp, second half).  fx_match_count / fx_match_emit are the bodies of
+// fx_meter_count / fx_meter_emit with another predicate - V is the SUM over the channels of one fp64 row, added in channel order -
+// picked by the type of the argument struct (matchesRange is overloaded); the scan is shared as it is.  fx_meter_best gives a
+// group of instances to one wavefront: a strided pass keeps the best (V, n) per lane under the total order "V, then n", a
+// butterfly of five-plus-one shuffles reduces the pairs, lane 0 stores.  Only compares decide, and the minimum under a total
+// order does not depend on the shape of the tree.  A group below 64 instances leaves lanes idle: the known cliff of one
+// wavefront per group, as for the mix of small groups.  fx_match_zero stores +0.0 into the listed columns.  Resource usage as
+// above: fx_match_count 8 / 0 / 16, fx_match_emit 14 / 0 / 16, fx_meter_best 20 / 0 / 0, fx_match_zero 6 / 0 / 0; eight wavefronts
+// per SIMD each.
 #include <hip/hip_runtime.h>
 
 #include "fx_meter.hpp"
@@ -60,10 +70,34 @@ __device__ __forceinline__ bool meterMatches(const MeterSelectArgs& a, long long
     return a.below ? best < a.threshold : best >= a.threshold;
 }
 
-__global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) {
+// (the bodies of the count and the emit take the predicate through their argument type: matchesRange is overloaded, so the
+// select over the match rows of a target - MatchSelectArgs, below - runs the same code with the channel-sum predicate)
+__device__ __forceinline__ bool matchesRange(const MeterSelectArgs& a, long long i) { return meterMatches(a, i); }
+
+// V(n) over the match rows: ((v0 + v1) + v2) + v3 in fp64, in channel order, starting from v0
+__device__ __forceinline__ double matchValue(const void* rows, long long nPad, int channels, int stat, long long col) {
+    const char* ch = static_cast<const char*>(rows) + (stat == 0 ? matchErrOff(nPad) : matchCrossOff(nPad));
+    double sum = reinterpret_cast<const double*>(ch)[col];
+    for (int c = 1; c < channels; ++c) {
+        ch += matchChannelBytes(nPad);
+        sum = sum + reinterpret_cast<const double*>(ch)[col];
+    }
+    return sum;
+}
+
+__device__ __forceinline__ bool matchesRange(const MatchSelectArgs& a, long long i) {
+    if (i >= a.nRange) return false;
+    const long long col = a.first + i;
+    if (col >= a.n) return false;
+    const double v = matchValue(a.rows, a.nPad, a.channels, a.stat, col);
+    return a.below ? v < a.threshold : v >= a.threshold;
+}
+
+template <class Args>
+__device__ __forceinline__ void selectCount(const Args& a) {
     __shared__ unsigned waveCount[kWaves];
     const unsigned t = threadIdx.x;
-    const bool match = meterMatches(a, (long long)blockIdx.x * kLanes + t);
+    const bool match = matchesRange(a, (long long)blockIdx.x * kLanes + t);
     const unsigned long long mask = __ballot(match);
     if ((t & 63u) == 0) waveCount[t >> 6] = (unsigned)__popcll(mask);
     __syncthreads();
@@ -73,6 +107,9 @@ __global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) {
         a.offsets[blockIdx.x] = sum;
     }
 }
+
+__global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) { selectCount(a); }
+__global__ __launch_bounds__(kLanes) void fx_match_count(MatchSelectArgs a) { selectCount(a); }
 
 // one workgroup: offsets[0 .. chunks - 1] counts -> their exclusive scan, offsets[chunks] = the total.  Lane t owns the `per`
 // consecutive counts from t * per on: the loads of one lane are independent, so their latencies overlap
@@ -101,13 +138,14 @@ __global__ __launch_bounds__(kLanes) void fx_meter_scan(unsigned long long* offs
     if (t == kLanes - 1) offsets[chunks] = s[t];
 }
 
-__global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) {
+template <class Args>
+__device__ __forceinline__ void selectEmit(const Args& a) {
     __shared__ unsigned waveCount[kWaves];
     const unsigned long long offset = a.offsets[blockIdx.x];
     if (offset >= (unsigned long long)a.cap) return;   // (the whole workgroup: nothing of this chunk fits)
     const unsigned t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const long long i = (long long)blockIdx.x * kLanes + t;
-    const bool match = meterMatches(a, i);
+    const bool match = matchesRange(a, i);
     const unsigned long long mask = __ballot(match);
     if (lane == 0) waveCount[wave] = (unsigned)__popcll(mask);
     __syncthreads();
@@ -115,6 +153,62 @@ __global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) {
     for (unsigned w = 0; w < wave; ++w) rank += waveCount[w];
     const unsigned long long pos = offset + rank;
     if (match && pos < (unsigned long long)a.cap) a.list[pos] = a.firstGlobal + i;
+}
+
+__global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) { selectEmit(a); }
+__global__ __launch_bounds__(kLanes) void fx_match_emit(MatchSelectArgs a) { selectEmit(a); }
+
+// fx_meter_best: wavefront w of the grid owns group firstGroup + w.  Its local members are the columns lo .. hi - 1; lane l
+// looks at lo + l, lo + l + 64, ... and keeps the best (V, n).  kNone marks a lane that has seen no member (a group below 64).
+constexpr long long kNone = 0x7fffffffffffffffll;
+__device__ __forceinline__ bool bestBeats(double v, long long k, double bv, long long bk, bool largest) {
+    if (k == kNone) return false;
+    if (bk == kNone) return true;
+    if (v != bv) return largest ? v > bv : v < bv;
+    return k < bk;
+}
+
+__global__ __launch_bounds__(kLanes) void fx_meter_best(MeterBestArgs a) {
+    const unsigned lane = threadIdx.x & 63u;
+    const long long g = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6);   // (uniform in a wavefront)
+    if (g >= a.groups) return;
+    const long long from = (a.firstGroup + g) * a.group - a.firstGlobal;   // may lie in front of this batch's columns
+    const long long lo = from > 0 ? from : 0, hi = from + a.group < a.n ? from + a.group : a.n;
+    const bool largest = a.largest != 0;
+    double bv = 0.0;
+    long long bk = kNone;
+    for (long long col = lo + lane; col < hi; col += 64) {
+        const double v = matchValue(a.rows, a.nPad, a.channels, a.stat, col);
+        if (bestBeats(v, col, bv, bk, largest)) {
+            bv = v;
+            bk = col;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(bv, d, 64);
+        const long long ok = __shfl_xor(bk, d, 64);
+        if (bestBeats(ov, ok, bv, bk, largest)) {
+            bv = ov;
+            bk = ok;
+        }
+    }
+    if (lane == 0) {
+        a.winner[g] = bk == kNone ? -1 : a.firstGlobal + bk;
+        a.value[g] = bv;
+    }
+}
+
+// the match rows of the listed columns: stores only
+__global__ __launch_bounds__(kLanes) void fx_match_zero(MeterListArgs a) {
+    const long long k = (long long)blockIdx.x * kLanes + threadIdx.x;
+    if (k >= a.count) return;
+    const long long inst = a.list[k];
+    if (inst < 0 || inst >= a.n) return;
+    char* ch = static_cast<char*>(a.rows);
+    for (int c = 0; c < a.channels; ++c, ch += matchChannelBytes(a.nPad)) {
+        reinterpret_cast<double*>(ch + matchErrOff(a.nPad))[inst] = 0.0;
+        reinterpret_cast<double*>(ch + matchCrossOff(a.nPad))[inst] = 0.0;
+    }
 }
 
 template <bool kGather>
@@ -175,6 +269,38 @@ hipError_t launchMeterSelect(const MeterSelectArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
     if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
     hipLaunchKernelGGL(fx_meter_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchMatchSelect(const MatchSelectArgs& a, hipStream_t stream) {
+    if (!a.rows || !a.offsets || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.stat < 0 || a.stat > 1) return hipErrorInvalidValue;
+    if (a.first < 0 || a.nRange < 1 || a.first > a.n - a.nRange || a.cap < 0 || (a.cap > 0 && !a.list) || a.threshold != a.threshold) return hipErrorInvalidValue;
+    const long long chunks = meterSelectChunks(a.nRange);
+    if (chunks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_match_count, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
+    if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
+    hipLaunchKernelGGL(fx_match_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchMeterBest(const MeterBestArgs& a, hipStream_t stream) {
+    if (!a.rows || !a.winner || !a.value || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.stat < 0 || a.stat > 1) return hipErrorInvalidValue;
+    if (a.group < 1 || a.firstGlobal < 0 || a.firstGroup != a.firstGlobal / a.group || a.groups != (a.firstGlobal + a.n - 1) / a.group - a.firstGroup + 1) return hipErrorInvalidValue;
+    const long long blocks = (a.groups + kWaves - 1) / kWaves;
+    if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_meter_best, dim3((unsigned)blocks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchMatchZero(const MeterListArgs& a, hipStream_t stream) {
+    if (badList(a, false)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_match_zero, dim3((unsigned)((a.count + kLanes - 1) / kLanes)), dim3(kLanes), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -57,4 +57,46 @@ hipError_t launchMeterGather(const MeterListArgs& a, hipStream_t stream);
 // the four accumulators of every channel of every listed instance = +0.0, +0.0f, 0, 0.  Stores only; repeats are fine.
 hipError_t launchMeterZero(const MeterListArgs& a, hipStream_t stream);
 
+// ---- queries over the match rows of a target (fx_meter.hpp; include/fx8010_amd.h "Target meters") -----------------------------
+// The value of an instance is V(n) = ((v(0,n) + v(1,n)) + v(2,n)) + v(3,n) over the channels in fp64, in channel order, starting
+// from v(0,n): a sum, not the maximum of the select above.  No match accumulator is ever NaN or infinite.
+
+struct MatchSelectArgs {
+    const void* rows;              // [channels] x the match rows (device memory)
+    unsigned long long* offsets;   // as MeterSelectArgs
+    long long* list;
+    long long n, nPad;
+    long long first, nRange;
+    long long firstGlobal;
+    long long cap;
+    double threshold;
+    int channels;                  // 1..4
+    int stat;                      // 0 err, 1 cross
+    int below;
+};
+// the three launches of launchMeterSelect with the channel-sum predicate over the match rows
+hipError_t launchMatchSelect(const MatchSelectArgs& a, hipStream_t stream);
+
+struct MeterBestArgs {
+    const void* rows;         // [channels] x the match rows
+    long long* winner;        // device memory, `groups` words: the GLOBAL instance number of the best local member of each group
+    double* value;            // device memory, `groups` words: its V
+    long long n, nPad;
+    long long firstGlobal;    // the global number of local column 0
+    long long group;          // >= 1: group g holds the global instances g * group .. (g + 1) * group - 1
+    long long firstGroup;     // firstGlobal / group: winner[0] belongs to it
+    long long groups;         // (firstGlobal + n - 1) / group - firstGroup + 1: every one of them has a local member
+    int channels;             // 1..4
+    int stat;                 // 0 err, 1 cross
+    int largest;              // 0: the smallest V wins; 1: the largest.  Ties go to the smallest instance number
+};
+// fx_meter_best: one wavefront per group.  The lanes stride the group's local members keeping the best (V, n) under the total
+// order "V, then n"; a 64-lane shuffle reduction of the pair; lane 0 stores.  Only compares decide: the tree shape cannot change
+// a bit.  No atomics, no workgroup waits for another.  Groups below 64 leave lanes idle.
+hipError_t launchMeterBest(const MeterBestArgs& a, hipStream_t stream);
+
+// err and cross of every channel of every listed instance = +0.0 (MeterListArgs with rows = the match rows; packed, reset
+// unused).  Stores only; repeats are fine; an entry outside [0, n) is skipped.
+hipError_t launchMatchZero(const MeterListArgs& a, hipStream_t stream);
+
 }  // namespace fx

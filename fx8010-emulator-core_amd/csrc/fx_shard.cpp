@@ -370,16 +370,28 @@ int64_t Sharded::meterSamples() {
 }
 
 int64_t Sharded::meterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+    return selectRange(false, stat, threshold, first, nRange, list, cap, flags);
+}
+int64_t Sharded::meterSelectMatch(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+    return selectRange(true, stat, threshold, first, nRange, list, cap, flags);
+}
+
+// match: over the match rows of a target (Batch::matchSelect) - other refusals and another predicate, the same ranges and joins
+int64_t Sharded::selectRange(bool match, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
     Serial serial(api_);
     lastError_.clear();
-    if (Batch::checkMeterSelect(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
+    if ((match ? Batch::checkMatchSelect : Batch::checkMeterSelect)(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (match && !front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
     if (nRange == 0) return 0;
     const bool below = (flags & FXB_METER_BELOW) != 0;
     if (shards_.size() == 1) {
         if (const int rc = runOn(0, [&](Batch& b) { return b.reserveMeterSelect(nRange, cap); })) return rc;
         int64_t m = 0;
-        const int rc = runOn(0, [&](Batch& b) { m = b.meterSelect(stat, threshold, below, first, nRange, first, list, cap); return m < 0 ? (int)m : 0; });
+        const int rc = runOn(0, [&](Batch& b) {
+            m = match ? b.matchSelect(stat, threshold, below, first, nRange, first, list, cap) : b.meterSelect(stat, threshold, below, first, nRange, first, list, cap);
+            return m < 0 ? (int)m : 0;
+        });
         return rc != 0 ? rc : m;
     }
     // the part of the range every shard owns (local numbers), and where its answer goes: a block of its own of min(cap, part)
@@ -399,7 +411,8 @@ int64_t Sharded::meterSelect(int stat, double threshold, int64_t first, int64_t 
     const int rc = fan([&](int k, Batch& b) {
         Part& p = parts[(size_t)k];
         if (p.count == 0) return 0;
-        p.m = b.meterSelect(stat, threshold, below, p.first, p.count, shards_[(size_t)k]->first + p.first, p.found.data(), cap);
+        const int64_t firstGlobal = shards_[(size_t)k]->first + p.first;
+        p.m = match ? b.matchSelect(stat, threshold, below, p.first, p.count, firstGlobal, p.found.data(), cap) : b.meterSelect(stat, threshold, below, p.first, p.count, firstGlobal, p.found.data(), cap);
         return p.m < 0 ? (int)p.m : 0;
     });
     if (rc != 0) return rc;
@@ -441,6 +454,88 @@ int Sharded::meterResetList(const int64_t* list, int64_t count) {
     auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
     if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(countOf(k), false); })) return rc;
     return fan([&](int k, Batch& b) { return b.meterResetList(listOf(k), countOf(k)); });
+}
+
+int Sharded::meterSetTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (Batch::checkMeterTarget(target, nSamples, group, flags, front().channels(), n_, &lastError_) != 0) return FX_E_ARG;
+    // (group >= N is one column for everyone: the same as group = N, which keeps the kernels' products small)
+    const int64_t g = std::min(group, n_), cols = (n_ + g - 1) / g;
+    const bool loop = (flags & FXB_METER_TARGET_LOOP) != 0;
+    if (const int rc = reserveOnAll([&](int k, Batch& b) { return b.reserveMeterTarget(nSamples, g, shards_[(size_t)k]->first); }, [](Batch& b) { b.releaseMeterTarget(); })) return rc;
+    return fan([&](int k, Batch& b) { return b.setMeterTarget(target, nSamples, g, shards_[(size_t)k]->first, cols, loop); });
+}
+int Sharded::meterClearTarget() {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([](int, Batch& b) { return b.clearMeterTarget(); });
+}
+int Sharded::meterTargetSeek(int64_t pos) {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int, Batch& b) { return b.meterTargetSeek(pos); });
+}
+int64_t Sharded::meterTargetPos() {
+    Serial serial(api_);
+    lastError_.clear();
+    const int64_t p = front().meterTargetPos();
+    if (p < 0) lastError_ = "meter target: no target is set (fxb_meter_set_target)";
+    return p;
+}
+int Sharded::meterReadMatch(double* err, double* cross, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        return b.meterReadMatch(err ? err + first : nullptr, cross ? cross + first : nullptr, reset, n_);
+    });
+}
+int Sharded::meterBest(int stat, int64_t group, int64_t* winner, double* value, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (group < 1) { lastError_ = "meter_best: group must be at least 1"; return FX_E_ARG; }
+    if (flags & ~(unsigned)FXB_MATCH_LARGEST) { lastError_ = "meter_best: flags has an unknown bit"; return FX_E_ARG; }
+    if (stat < FXB_MATCH_ERROR || stat > FXB_MATCH_CROSS) { lastError_ = "meter_best: stat must be 0 or 1 (FXB_MATCH_ERROR, FXB_MATCH_CROSS)"; return FX_E_ARG; }
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (!front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
+    const int64_t g = std::min(group, n_);
+    const bool largest = (flags & FXB_MATCH_LARGEST) != 0;
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterBest(g, shards_[(size_t)k]->first); })) return rc;
+    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.meterBest(stat, g, 0, largest, winner, value); });
+    // every shard's partial winners side by side; then the groups in order, a group that straddles joined by (V, then n)
+    struct Part { std::vector<int64_t> winner; std::vector<double> value; };
+    std::vector<Part> parts(shards_.size());
+    for (size_t k = 0; k < shards_.size(); ++k) {
+        const size_t groups = (size_t)shards_[k]->batch->meterBestGroups(g, shards_[k]->first);
+        parts[k].winner.resize(groups);
+        parts[k].value.resize(groups);
+    }
+    if (const int rc = fan([&](int k, Batch& b) { return b.meterBest(stat, g, shards_[(size_t)k]->first, largest, parts[(size_t)k].winner.data(), parts[(size_t)k].value.data()); })) return rc;
+    int64_t done = -1;       // the last group written
+    double held = 0.0;       // ... and its value so far
+    for (size_t k = 0; k < shards_.size(); ++k) {
+        const int64_t firstGroup = shards_[k]->first / g;
+        for (size_t i = 0; i < parts[k].winner.size(); ++i) {
+            const int64_t at = firstGroup + (int64_t)i, w = parts[k].winner[i];
+            const double v = parts[k].value[i];
+            if (at > done) {
+                if (winner) winner[at] = w;
+                if (value) value[at] = v;
+                held = v;
+                done = at;
+                continue;
+            }
+            // (the group's members on the shards in front have smaller numbers: a tie stays with them)
+            const bool better = v != held && (largest ? v > held : v < held);
+            if (!better) continue;
+            if (winner) winner[at] = w;
+            if (value) value[at] = v;
+            held = v;
+        }
+    }
+    return 0;
 }
 
 int Sharded::busSetGains(const float* gains, int ramp) {
@@ -1005,6 +1100,7 @@ int64_t Sharded::info(int what) {
         what == FXB_INFO_METER_LAUNCHES || what == FXB_INFO_BUS_GAIN_BLOCKS || what == FXB_INFO_BUS_TAP_BLOCKS || what == FXB_INFO_BUS_SEND_BLOCKS || what == FXB_INFO_BUS_FEED_BLOCKS || what == FXB_INFO_IMAJOR_BLOCKS || what == FXB_INFO_INSTANCE_GATHERS || what == FXB_INFO_INSTANCE_SCATTERS || what == FXB_INFO_INSTANCE_ROTATIONS || what == FXB_INFO_GAIN_LIST_SETS ||
         what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS || what == FXB_INFO_TRAM_LIST_SETS || what == FXB_INFO_TRAM_LIST_GETS ||
         what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS || what == FXB_INFO_TRACK_LIST_EXPANDS ||
+        what == FXB_INFO_METER_TARGET_LAUNCHES || what == FXB_INFO_METER_MATCH_SELECTS || what == FXB_INFO_METER_MATCH_BESTS ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

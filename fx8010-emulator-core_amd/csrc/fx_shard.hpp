@@ -91,6 +91,19 @@ public:
     int64_t meterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     int meterReadList(const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset);
     int meterResetList(const int64_t* list, int64_t count);
+    // target meters (Batch "Target meters"): `target` is the caller's [nSamples][channels][G] block by GLOBAL group column.  The
+    // arguments are checked for the whole handle; every shard reserves the block of the columns ITS instances use (shards need
+    // no alignment to `group`) and its match rows before any shard changes - FX_E_MEMORY leaves no target anywhere new and the
+    // old one in force.  seek fans out, pos is shard 0's.  readMatch gives each shard its columns like meterRead; selectMatch is
+    // meterSelect with the other predicate; best: each shard answers for the parts of the groups it owns and the partial
+    // winners of a group that straddles shards are joined by the same order (V, then the instance number).
+    int meterSetTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags);
+    int meterClearTarget();
+    int meterTargetSeek(int64_t pos);
+    int64_t meterTargetPos();
+    int meterReadMatch(double* err, double* cross, bool reset);
+    int64_t meterSelectMatch(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
+    int meterBest(int stat, int64_t group, int64_t* winner, double* value, unsigned flags);
     // bus gains (Batch::busSetGains ...): `gains` is [channels][all instances] by global instance, checked as a whole (every value
     // finite) before any shard is posted; every shard reserves its blocks first and only when all of them could is any shard's
     // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.
@@ -179,6 +192,7 @@ public:
 
 private:
     int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
+    int64_t selectRange(bool match, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     int registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out);
     int tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set);
     struct Worker {

@@ -334,6 +334,35 @@ public:
     void meterResetList(const std::vector<int64_t>& list) {
         if (fxb_meter_reset_list(h_, list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::meterResetList: ") + fxb_last_error(h_));
     }
+    // Target meters (include/fx8010_amd.h "Target meters"): target is [nSamples][channels][ceil(N / group)]; while one is set the
+    // meters also accumulate the squared error against it and the cross product with it.  meterReadMatch fills
+    // [channels][instances] arrays; meterSelectMatch is meterSelect over the channel SUM of FXB_MATCH_ERROR / FXB_MATCH_CROSS;
+    // meterBest fills [ceil(N / group)] winners and values (a null pointer skips one).
+    void meterSetTarget(const float* target, int64_t nSamples, int64_t group = 1, unsigned flags = 0) {
+        if (fxb_meter_set_target(h_, target, nSamples, group, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::meterSetTarget: ") + fxb_last_error(h_));
+    }
+    void meterClearTarget() {
+        if (fxb_meter_clear_target(h_) < 0) throw std::runtime_error(std::string("FX8010Batch::meterClearTarget: ") + fxb_last_error(h_));
+    }
+    void meterTargetSeek(int64_t pos) {
+        if (fxb_meter_target_seek(h_, pos) < 0) throw std::runtime_error(std::string("FX8010Batch::meterTargetSeek: ") + fxb_last_error(h_));
+    }
+    int64_t meterTargetPos() {
+        const int64_t p = fxb_meter_target_pos(h_);
+        if (p < 0) throw std::runtime_error(std::string("FX8010Batch::meterTargetPos: ") + fxb_last_error(h_));
+        return p;
+    }
+    void meterReadMatch(double* err, double* cross, bool reset = false) {
+        if (fxb_meter_read_match(h_, err, cross, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterReadMatch: ") + fxb_last_error(h_));
+    }
+    int64_t meterSelectMatch(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags = 0) {
+        const int64_t m = fxb_meter_select_match(h_, stat, threshold, first, nRange, list, cap, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterSelectMatch: ") + fxb_last_error(h_));
+        return m;
+    }
+    void meterBest(int stat, int64_t group, int64_t* winner, double* value, unsigned flags = 0) {
+        if (fxb_meter_best(h_, stat, group, winner, value, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::meterBest: ") + fxb_last_error(h_));
+    }
     // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
     // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
     // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and

@@ -30,12 +30,16 @@ INFO = {
     "register_list_sets": 50, "register_list_gets": 51, "xlate_sum_groups": 52, "xlate_sum_links": 53, "xlate_quiet_repairs": 54,
     "tram_list_sets": 55, "tram_list_gets": 56,
     "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59, "track_list_expands": 60,
+    "meter_target_launches": 61, "meter_match_selects": 62, "meter_match_bests": 63,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
 TRAM_LOGICAL, TRAM_BROADCAST = 1, 2  # FXB_TRAM_* of include/fx8010_amd.h
 METER_ENERGY, METER_PEAK, METER_FULL_SCALE, METER_NONFINITE = 0, 1, 2, 3  # FXB_METER_* of include/fx8010_amd.h: the `stat` of meter_select
 METER_BELOW = 1
+METER_TARGET_LOOP = 1  # FXB_METER_TARGET_LOOP: the flag of meter_set_target
+MATCH_ERROR, MATCH_CROSS = 0, 1  # FXB_MATCH_*: the `stat` of meter_select_match and meter_best
+MATCH_LARGEST = 2  # FXB_MATCH_LARGEST: the flag of meter_best
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -53,6 +57,7 @@ SYMBOLS = [
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances", "fxb_load_instances_rotated",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples", "fxb_meter_select", "fxb_meter_read_list", "fxb_meter_reset_list",
+    "fxb_meter_set_target", "fxb_meter_clear_target", "fxb_meter_target_seek", "fxb_meter_target_pos", "fxb_meter_read_match", "fxb_meter_select_match", "fxb_meter_best",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -124,6 +129,8 @@ def load():
     sig("fxb_set_register_tracks_list", i32, vp, vp, i32, vp, i64, vp, i32, i32, i32); sig("fxb_clear_register_tracks_list", i32, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
     sig("fxb_meter_select", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_read_list", i32, vp, vp, i64, vp, vp, vp, vp, i32); sig("fxb_meter_reset_list", i32, vp, vp, i64)
+    sig("fxb_meter_set_target", i32, vp, vp, i64, i64, C.c_uint); sig("fxb_meter_clear_target", i32, vp); sig("fxb_meter_target_seek", i32, vp, i64); sig("fxb_meter_target_pos", i64, vp)
+    sig("fxb_meter_read_match", i32, vp, vp, vp, i32); sig("fxb_meter_select_match", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_best", i32, vp, i32, i64, vp, vp, C.c_uint)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -976,6 +983,58 @@ class Batch(_Reports):
         meter_samples() stays the handle-wide count since the last full reset."""
         lst = self._instance_list(instances)
         return self._check(self._lib.fxb_meter_reset_list(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size)), "meter_reset_list")
+
+    def meter_set_target(self, target, group=1, loop=False):
+        """Set the target of the meters: `target` is [n_samples, channels, G] float32 with G = ceil(N / group); instance n is
+        compared with column n // group (include/fx8010_amd.h "Target meters").  From now on the meter launch of every block also
+        accumulates, per channel and instance, the squared error against the target and the cross product with it.  Synchronous;
+        the position starts at 0.  loop: the target repeats; without it samples past its end change neither figure."""
+        group = int(group)
+        t = np.ascontiguousarray(target, dtype=np.float32)
+        g = -(-self.n // min(max(group, 1), self.n))
+        if t.ndim != 3 or t.shape[1:] != (self.channels, g):
+            raise ValueError("meter_set_target: target must be [n_samples, %d, %d]" % (self.channels, g))
+        return self._check(self._lib.fxb_meter_set_target(self._h, C.c_void_p(t.ctypes.data), int(t.shape[0]), group, METER_TARGET_LOOP if loop else 0), "meter_set_target")
+
+    def meter_clear_target(self):
+        """Drop the target: the target block and the two match rows are freed; the four meters go on."""
+        return self._check(self._lib.fxb_meter_clear_target(self._h), "meter_clear_target")
+
+    def meter_target_seek(self, pos):
+        """the target position of the next queued block (host-side, no wait)"""
+        return self._check(self._lib.fxb_meter_target_seek(self._h, int(pos)), "meter_target_seek")
+
+    def meter_target_pos(self):
+        """the target position the next queued block starts at"""
+        return self._check(int(self._lib.fxb_meter_target_pos(self._h)), "meter_target_pos")
+
+    def meter_read_match(self, reset=False):
+        """{"err": float64, "cross": float64}, each [channels, N] by global instance: the squared error against the target and the
+        cross product with it, accumulated since the last reset.  Synchronous; reset zeroes these two rows only."""
+        shape = (self.channels, self.n)
+        out = {"err": np.empty(shape, dtype=np.float64), "cross": np.empty(shape, dtype=np.float64)}
+        self._check(self._lib.fxb_meter_read_match(self._h, C.c_void_p(out["err"].ctypes.data), C.c_void_p(out["cross"].ctypes.data), 1 if reset else 0), "meter_read_match")
+        return out
+
+    def meter_select_match(self, stat, threshold, below=False, first=0, n_range=None, cap=None):
+        """meter_select over the match figures: V is the SUM over the channels of `stat` (MATCH_ERROR, MATCH_CROSS).  (list, M)."""
+        first = int(first)
+        n_range = self.n - first if n_range is None else int(n_range)
+        cap = n_range if cap is None else int(cap)
+        out = np.empty(max(min(cap, n_range), 0), dtype=np.int64)
+        m = self._check(int(self._lib.fxb_meter_select_match(self._h, int(stat), float(threshold), first, n_range, C.c_void_p(out.ctypes.data) if out.size else None,
+                                                             cap, METER_BELOW if below else 0)), "meter_select_match")
+        return out[:min(m, out.size)], m
+
+    def meter_best(self, stat=MATCH_ERROR, group=None, largest=False):
+        """(winner int64 [G], value float64 [G]) with G = ceil(N / group): per group of `group` consecutive instances (None: all of
+        them) the instance whose V - the channel sum of `stat` - is the smallest (largest: the largest), ties to the smallest
+        number, and that V.  Found on the device; 16 bytes per group come back.  Synchronous."""
+        group = self.n if group is None else int(group)
+        g = -(-self.n // min(max(group, 1), self.n))
+        winner, value = np.full(g, -1, dtype=np.int64), np.zeros(g, dtype=np.float64)
+        self._check(self._lib.fxb_meter_best(self._h, int(stat), group, C.c_void_p(winner.ctypes.data), C.c_void_p(value.ctypes.data), MATCH_LARGEST if largest else 0), "meter_best")
+        return winner, value
 
     def meter_samples(self):
         """sample periods metered since the last reset"""

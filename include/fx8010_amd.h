@@ -799,6 +799,81 @@ int64_t fxb_meter_samples(fxb_handle* h);
 int64_t fxb_meter_select(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
 int fxb_meter_read_list(fxb_handle* h, const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* full_scale, uint32_t* nonfinite, int reset);
 int fxb_meter_reset_list(fxb_handle* h, const int64_t* list, int64_t count);
+/* Target meters: the error of every instance against a reference signal, on the device.  A parameter sweep (FXB_BUS_SHARED_IN: one
+ * signal through N instances that differ in their controls) asks which setting comes closest to a wanted response; with a target
+ * set, the meter launch of every block also accumulates the squared error and the cross product against it, and three queries
+ * bring back the verdict - never the [S][C][N] output words.  With no target set nothing changes: the same kernel, the same
+ * arguments, no allocation.
+ *
+ * The definition.  fxb_meter_set_target(h, target, n_samples, group, flags):
+ *   `target` is host memory [n_samples][num_channels][G], with G = ceil(N / group) and 1 <= group.  Instance n (global) is
+ *   compared with column n / group.  group == 1 gives one target per instance.  group >= N gives one target for all instances.
+ *   The handle keeps a TARGET POSITION p, set to 0 by this call.  Each (channel c, instance n) has two further accumulators:
+ *   `err` (fp64), +0.0 after a reset; `cross` (fp64), +0.0 after a reset.
+ *   For every output word y of that column, in sample order, let q be the target position of that sample.  The target position
+ *   of a sample is the handle's position when its block was QUEUED, plus the sample's index in the block.
+ *     - Without FXB_METER_TARGET_LOOP, a sample with q >= n_samples changes neither accumulator.
+ *     - With FXB_METER_TARGET_LOOP, q is taken mod n_samples.
+ *     - Otherwise t = target[q][c][n / group] and ok = |y| < +Inf && |t| < +Inf.
+ *     - If !ok, neither accumulator changes.  The existing `nonfinite` counter already says that y was bad.
+ *     - If ok:
+ *         d = (double)y - (double)t  (one rounding);
+ *         e = d * d  (one rounding);
+ *         err = err + e  (one rounding, never fused with the multiply);
+ *         cross = cross + (double)y * (double)t  (the product of two fp32 values is exact; one rounding).
+ *   The four existing accumulators are taken exactly as now, for every sample.  After a block of S samples the position is
+ *   p + S.  With LOOP it is reduced mod n_samples.  Without LOOP it is not clamped.
+ *   No accumulator can become NaN or infinite for finite fp32 inputs: |d| < 2^129, so e < 2^258.  That keeps `>=` and `<`
+ *   complements in the select.
+ *   The figures do not depend on how a stream is cut - blocks of 16 + 17 samples, the pieces of the bus scratch and of a large
+ *   host block, the segments of an armed control track, the shards: the position advances per launch, beside the count of
+ *   fxb_meter_samples.
+ *
+ * fxb_meter_set_target is synchronous and waits as fxb_sync does.  It allocates the target block on every shard, and the match
+ *   rows (16 bytes per instance and channel, [channel]{err[nPad], cross[nPad]}) where there are none.  It copies the target,
+ *   zeroes the match rows and sets p = 0.  A shard keeps only the target columns its instances use: floor(first / group) ..
+ *   floor((first + n - 1) / group); shards therefore need NO alignment to `group`, unlike bus blocks.  All allocation for the
+ *   feature happens here, never in a block.  On FX_E_MEMORY no new target is set on any shard and the handle stays usable (a
+ *   target that was in force stays in force).  FX_E_ARG, with nothing changed, for: metering off; a null `target`;
+ *   n_samples < 1; group < 1; an unknown flag bit; num_channels * G_shard * 4 >= 2^32 (the kernel uses a 32-bit row stride);
+ *   n_samples * num_channels * G >= 2^31 words.
+ * Resets.  fxb_meter_clear_target drops the target; so do fxb_meter_enable(h, 0) and a program load (fxb_load_file /
+ *   fxb_load_text).  All three free the target block and the match rows.  fxb_meter_read(..., reset = 1) zeroes the match rows
+ *   as well and leaves p alone.  fxb_meter_reset_list zeroes the listed columns of the match rows as well - a reused slot gets
+ *   fresh meters, all of them - by a launch of its own (fx_match_zero) queued beside fx_meter_zero, inside the same event frame.
+ * fxb_meter_target_seek: the position of the next queued block; host-side, no wait.  Accepts 0 <= pos <= n_samples; with LOOP,
+ *   pos must be < n_samples.  FX_E_ARG when no target is set.
+ * fxb_meter_target_pos: p, or FX_E_ARG when no target is set.
+ * fxb_meter_read_match behaves as fxb_meter_read does, on the two new rows: [num_channels][N] by global instance, either
+ *   pointer may be NULL; `reset` zeroes only the two new rows.  FX_E_ARG when no target is set.
+ * V(n) for select and best.  v(c, n) is accumulator `stat` (FXB_MATCH_ERROR, FXB_MATCH_CROSS).
+ *   V(n) = ((v(0,n) + v(1,n)) + v(2,n)) + v(3,n) over the handle's channels, in fp64, in channel order, starting from v(0,n).
+ *   This is a sum, not the maximum of fxb_meter_select: an error over a stereo pair is a sum.  It is still one fixed sequence of
+ *   IEEE operations.
+ * fxb_meter_select_match: everything else is as fxb_meter_select, refusals included: the ordered compaction, FXB_METER_BELOW,
+ *   cap and range rules, and shard concatenation.  `stat` must be 0 or 1.  FX_E_ARG when no target is set.  fxb_meter_select
+ *   itself keeps refusing stat = 4.
+ * fxb_meter_best: groups are those of the bus calls: group g is instances g * group .. min((g + 1) * group, N) - 1, and
+ *   G = ceil(N / group).  winner[g] is the instance of group g with the smallest V, or with FXB_MATCH_LARGEST the largest.  Ties
+ *   go to the smallest instance number.  value[g] is that V.  Either pointer may be NULL.  It is synchronous, and 16 * G bytes
+ *   cross PCIe.  `group` need not equal the target's group.  Sharded handles: each shard answers for the parts of groups it
+ *   owns, and the host joins partial winners by the same order; the result equals the single handle's.  FX_E_ARG for
+ *   group < 1, an unknown flag, `stat` outside 0..1, or no target set.  One wavefront works on a group: groups below 64
+ *   instances leave lanes idle - a known cliff, like the mix of small groups.
+ * FXB_INFO_METER_TARGET_LAUNCHES counts the launches of the kernel fx_meter_target, FXB_INFO_METER_LAUNCHES those of fx_meter:
+ *   a block is metered by one or the other.  FXB_INFO_METER_MATCH_SELECTS / _MATCH_BESTS count the calls that launched.  All
+ *   are summed over shards. */
+#define FXB_METER_TARGET_LOOP (1u << 0)
+int     fxb_meter_set_target(fxb_handle* h, const float* target, int64_t n_samples, int64_t group, unsigned flags);
+int     fxb_meter_clear_target(fxb_handle* h);
+int     fxb_meter_target_seek(fxb_handle* h, int64_t pos);     /* position of the next queued block; host-side, no wait */
+int64_t fxb_meter_target_pos(fxb_handle* h);
+int     fxb_meter_read_match(fxb_handle* h, double* err, double* cross, int reset);       /* [C][N]; pointers may be NULL */
+#define FXB_MATCH_ERROR 0
+#define FXB_MATCH_CROSS 1
+#define FXB_MATCH_LARGEST (1u << 1)
+int64_t fxb_meter_select_match(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
+int     fxb_meter_best(fxb_handle* h, int stat, int64_t group, int64_t* winner, double* value, unsigned flags);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -898,6 +973,9 @@ enum {
     FXB_INFO_METER_SELECTS = 57,       /* calls of fxb_meter_select that launched (fx_meter_count / _scan / _emit) since creation (summed over shards) */
     FXB_INFO_METER_LIST_READS = 58,    /* calls of fxb_meter_read_list that launched (fx_meter_gather) since creation (summed over shards) */
     FXB_INFO_METER_LIST_RESETS = 59,   /* calls of fxb_meter_reset_list that launched (fx_meter_zero) since creation (summed over shards) */
+    FXB_INFO_METER_TARGET_LAUNCHES = 61, /* launches of the kernel fx_meter_target - the meter launch of a block while a target is set (fxb_meter_set_target) - since creation (summed over shards) */
+    FXB_INFO_METER_MATCH_SELECTS = 62,   /* calls of fxb_meter_select_match that launched (fx_match_count / fx_meter_scan / fx_match_emit) since creation (summed over shards) */
+    FXB_INFO_METER_MATCH_BESTS = 63,     /* calls of fxb_meter_best that launched (fx_meter_best) since creation (summed over shards) */
     FXB_INFO_TRACK_LIST_EXPANDS = 60   /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
 };
 int64_t fxb_info(fxb_handle* h, int what);
