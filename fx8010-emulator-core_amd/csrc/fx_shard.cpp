@@ -1056,7 +1056,7 @@ int Sharded::tramList(int which, const int64_t* list, int64_t count, int first, 
     if (Batch::checkTramList(set, which, list, count, n_, first, nWords, values, flags, &lastError_) != 0) return FX_E_ARG;
     if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
     const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = (one || count == 0) ? std::vector<ListPart>(shards_.size()) : splitList(list, count);
+    const std::vector<ListPart> parts = (one || count == 0 || nWords == 0) ? std::vector<ListPart>(shards_.size()) : splitList(list, count);   // (n_words == 0: the list may be null, and no entry moves)
     auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
     auto posOf = [&](int k) { return (one || (flags & FXB_TRAM_BROADCAST)) ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
     auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };

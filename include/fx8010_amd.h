@@ -205,7 +205,9 @@ int fxb_load_state(fxb_handle* h, const void* buf, int64_t bytes);
  *   run, fxb_sync covers it.  On a sharded handle a pair that crosses shards goes through pinned host memory and the call blocks.
  *   What the host knows about the registers does not change (a register it holds as one value is equal in src and dst already).
  * fxb_reset_instances: every listed instance takes the state of a freshly created one - registers at the value of the last
- *   broadcast fxb_set_register (the program's initial value if there was none; per-instance writes to that instance are gone),
+ *   broadcast fxb_set_register (the program's initial value if there was none; per-instance writes to that instance are gone;
+ *   the last applied step of a broadcast fxb_set_register_track counts as a broadcast write, per-instance tracks, arrays and
+ *   list sets do not),
  *   latches 0, the LFSR at the reference's seeds, flags 0, counter 0, delay memory 0 - EXCEPT the four delay-line positions, which
  *   are kept.  Translated code keeps the positions of a program whose delay-line instructions all run unconditionally in scalar
  *   registers, one set for the wavefront: all instances of such a batch must agree on them.  Kept positions are also what the
@@ -355,7 +357,9 @@ int fxb_clear_register_tracks_list(fxb_handle* h);
  * Size: the windows are staged in a block of the library's own of at most 64 MiB (device, and as much pinned), grown on demand
  *   in the call.  A call whose windows exceed it runs in pieces along the list; a SET of several pieces blocks on the host between
  *   them.  The calls are made for tens to thousands of voices times a few thousand words.
- * Returns 0 - also for count == 0, or n_words == 0 without FXB_TRAM_LOGICAL, once the other arguments have been checked - or, with
+ * Returns 0 - also for count == 0, or n_words == 0 without FXB_TRAM_LOGICAL, once the other arguments have been checked (the
+ *   entries of a list that is given included: n_words == 0 with an instance outside 0..N-1, or one listed twice in a set, is
+ *   FX_E_ARG; a null list or null values are fine when no word moves) - or, with
  *   nothing launched and nothing changed on any shard: FX_E_ARG (fxb_last_error names the argument, and for a list entry the
  *   caller's index) for a null list or values with something to do, a negative count, count >= 2^31, `which` outside 0..1, an
  *   unknown flag bit, FXB_TRAM_BROADCAST on a get, an instance outside 0..N-1, an instance listed twice in a set (two lanes

@@ -691,6 +691,11 @@ float fxo_get_register(fxo_t* f, const char* key) {            /* :256-266 */
     int i = find_reg(f, key, strlen(key));
     return i < 0 ? 1.0f : f->regs[i].value;
 }
+/* the same as a bit pattern (ours): a float that travels through a caller's float conversions loses a signalling NaN */
+uint32_t fxo_get_register_bits(fxo_t* f, const char* key) {
+    float v = fxo_get_register(f, key);
+    uint32_t u; memcpy(&u, &v, 4); return u;
+}
 int64_t fxo_instruction_counter(fxo_t* f) { return f->icount; } /* :986-989 */
 int fxo_ready(fxo_t* f) { return f->ready; }
 int fxo_channels(fxo_t* f) { return f->channels; }
@@ -706,6 +711,44 @@ int fxo_tram(fxo_t* f, int which, float* out, int n) {
     return n;
 }
 void fxo_cursors(fxo_t* f, int out4[4]) { out4[0] = f->iw; out4[1] = f->ir; out4[2] = f->xw; out4[3] = f->xr; }
+/* The writing side of the three readers above, and a deep copy: ours, for tests that model per-instance state operations of the
+ * product (copy, reset, load, windows of delay memory).  process() knows nothing of them. */
+int fxo_set_tram(fxo_t* f, int which, int first, const float* words, int n) {
+    const int have = which ? MAX_XDELAY_SIZE : MAX_IDELAY_SIZE;
+    if ((which != 0 && which != 1) || first < 0 || n < 0 || first > have || n > have - first) return 0;   /* a window outside the line: nothing written */
+    if (n == 0) return 0;
+    if (which && !f->xtram) f->xtram = (float*)calloc(MAX_XDELAY_SIZE, sizeof(float));
+    memcpy((which ? f->xtram : f->itram) + first, words, (size_t)n * sizeof(float));     /* bit patterns: NaN payloads as given */
+    return n;
+}
+void fxo_set_cursors(fxo_t* f, const int in4[4]) { f->iw = in4[0]; f->ir = in4[1]; f->xw = in4[2]; f->xr = in4[3]; }
+static char* xstrdup0(const char* s) { return s ? xstrdup_n(s, strlen(s)) : NULL; }
+fxo_t* fxo_clone(fxo_t* f) {
+    if (!f) return NULL;
+    fxo_t* g = (fxo_t*)malloc(sizeof(fxo_t));
+    memcpy(g, f, sizeof(fxo_t));   /* scalars: sizes, positions, accumulator, counter, LFSR words, tables, flags, options */
+    g->capregs = f->nregs; g->capins = f->nins; g->caperrs = f->nerrs; g->capctl = f->nctl;
+    g->regs = (gpr_t*)malloc(sizeof(gpr_t) * (size_t)(f->nregs ? f->nregs : 1));
+    for (int i = 0; i < f->nregs; ++i) { g->regs[i] = f->regs[i]; g->regs[i].name = xstrdup0(f->regs[i].name); }
+    g->ins = (ins_t*)malloc(sizeof(ins_t) * (size_t)(f->nins ? f->nins : 1));
+    if (f->nins) memcpy(g->ins, f->ins, sizeof(ins_t) * (size_t)f->nins);
+    g->errs = (err_t*)malloc(sizeof(err_t) * (size_t)(f->nerrs ? f->nerrs : 1));
+    for (int i = 0; i < f->nerrs; ++i) { g->errs[i].row = f->errs[i].row; g->errs[i].desc = xstrdup0(f->errs[i].desc); }
+    g->controls = (char**)malloc(sizeof(char*) * (size_t)(f->nctl ? f->nctl : 1));
+    for (int i = 0; i < f->nctl; ++i) g->controls[i] = xstrdup0(f->controls[i]);
+    for (int i = 0; i < 6; ++i) { g->meta_key[i] = xstrdup0(f->meta_key[i]); g->meta_val[i] = xstrdup0(f->meta_val[i]); }
+    const size_t ch = (size_t)(f->channels > 0 ? f->channels : 1);
+    g->outbuf = (float*)malloc(ch * sizeof(float));
+    memcpy(g->outbuf, f->outbuf, ch * sizeof(float));
+    g->itram = (float*)malloc(MAX_IDELAY_SIZE * sizeof(float));
+    memcpy(g->itram, f->itram, MAX_IDELAY_SIZE * sizeof(float));
+    g->xtram = NULL;
+    if (f->xtram) {
+        g->xtram = (float*)malloc(MAX_XDELAY_SIZE * sizeof(float));
+        memcpy(g->xtram, f->xtram, MAX_XDELAY_SIZE * sizeof(float));
+    }
+    return g;
+}
 void fxo_lfsr(fxo_t* f, int32_t out2[2]) { out2[0] = f->g_x1; out2[1] = f->g_x2; }
 int fxo_error_count(fxo_t* f) { return f->nerrs; }
 const char* fxo_error_desc(fxo_t* f, int i) { return (i < 0 || i >= f->nerrs) ? "" : f->errs[i].desc; }

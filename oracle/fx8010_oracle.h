@@ -43,6 +43,7 @@ void fxo_process(fxo_t*, const float* in, float* out);               /* one samp
 void fxo_process_block(fxo_t*, const float* in, float* out, int S);  /* [S][channels] */
 int fxo_set_register(fxo_t*, const char* key, float v);              /* 0 found, 1 not found */
 float fxo_get_register(fxo_t*, const char* key);                     /* 1.0f when not found */
+uint32_t fxo_get_register_bits(fxo_t*, const char* key);              /* the same as a 32-bit pattern: signalling NaNs as they are */
 int64_t fxo_instruction_counter(fxo_t*);
 int fxo_ready(fxo_t*);
 int fxo_channels(fxo_t*);
@@ -54,6 +55,15 @@ void fxo_set_option(fxo_t*, unsigned option, int on);   /* before loading: FXO_O
 int fxo_tram(fxo_t*, int which, float* out, int n);
 void fxo_cursors(fxo_t*, int out4[4]);
 void fxo_lfsr(fxo_t*, int32_t out2[2]);
+/* their writing side, for tests that model the product's per-instance state operations (process() is untouched):
+ * fxo_clone      a new object that is a deep copy - program, registers, CCR, latches, delay memory, positions, LFSR words, flags,
+ *                counter, options; NULL for NULL.  Destroyed like any other.
+ * fxo_set_tram   words[0..n-1] as bit patterns into slots first .. first+n-1 of line `which`; returns the count written, 0 and
+ *                nothing written for a window outside the line's array (8192 / 1048576 slots) or a `which` outside 0..1
+ * fxo_set_cursors the counterpart of fxo_cursors */
+fxo_t* fxo_clone(fxo_t*);
+int fxo_set_tram(fxo_t*, int which, int first, const float* words, int n);
+void fxo_set_cursors(fxo_t*, const int in4[4]);
 
 int fxo_error_count(fxo_t*);
 const char* fxo_error_desc(fxo_t*, int i);

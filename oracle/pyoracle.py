@@ -199,6 +199,14 @@ class Oracle(_Base):
             lib.fxo_cursors.restype = None
             lib.fxo_lfsr.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
             lib.fxo_lfsr.restype = None
+            lib.fxo_get_register_bits.argtypes = [C.c_void_p, C.c_char_p]
+            lib.fxo_get_register_bits.restype = C.c_uint32
+            lib.fxo_clone.argtypes = [C.c_void_p]
+            lib.fxo_clone.restype = C.c_void_p
+            lib.fxo_set_tram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+            lib.fxo_set_tram.restype = C.c_int
+            lib.fxo_set_cursors.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+            lib.fxo_set_cursors.restype = None
             cls._lib = lib
         return cls._lib
 
@@ -232,6 +240,29 @@ class Oracle(_Base):
         buf = (C.c_int * 4)()
         self._lib.fxo_cursors(self._h, buf)
         return list(buf)
+
+    def get_register_word(self, key):
+        """the register's 32-bit pattern as the object holds it (get_register_bits goes through a C float return value and a python
+        float, which quiets a signalling NaN - on both checkers alike, which is what comparing the two wants)"""
+        return int(self._lib.fxo_get_register_bits(self._h, key.encode()))
+
+    def clone(self):
+        """a new Oracle that is a deep copy: program, registers, CCR, latches, delay memory, positions, LFSR, flags, counter, options"""
+        h = self._lib.fxo_clone(self._h)
+        if not h:
+            raise RuntimeError("clone failed")
+        o = Oracle.__new__(Oracle)
+        o.channels, o._h, o._tmp = self.channels, h, []
+        return o
+
+    def set_tram(self, which, first, words):
+        """words (float32, as bit patterns) into slots first .. first+len-1 of line `which`; the count written (0: refused)"""
+        w = np.ascontiguousarray(words, dtype=np.float32)
+        return int(self._lib.fxo_set_tram(self._h, int(which), int(first), w.ctypes.data_as(C.c_void_p), int(w.size)))
+
+    def set_cursors(self, four):
+        buf = (C.c_int * 4)(*[int(v) for v in four])
+        self._lib.fxo_set_cursors(self._h, buf)
 
     def lfsr(self):
         buf = (C.c_int32 * 2)()

@@ -485,9 +485,20 @@ def test_two_shards_on_one_gpu_equal_the_single_handle(gpu, monkeypatch):
                      ("which = 2", lib.fxb_set_tram_list(many._h, 2, p(across), across.size, 0, 7, p(v), 0)),
                      ("an unknown flag", lib.fxb_set_tram_list(many._h, 0, p(across), across.size, 0, 7, p(v), 8)),
                      ("broadcast on a get", lib.fxb_get_tram_list(many._h, 0, p(across), across.size, 0, 7, p(out), BROADCAST)),
-                     ("null values", lib.fxb_set_tram_list(many._h, 0, p(across), across.size, 0, 7, None, 0))):
+                     ("null values", lib.fxb_set_tram_list(many._h, 0, p(across), across.size, 0, 7, None, 0)),
+                     # n_words == 0 moves no word, but a list that is given is checked all the same ("once the other arguments have
+                     # been checked"): tools/fuzz_voices.py seeds 3, 4 and 10 found these three accepted
+                     ("an instance listed twice, n_words = 0", lib.fxb_set_tram_list(many._h, 1, p(twice), twice.size, 11, 0, p(v), 0)),
+                     ("an instance of N, n_words = 0", lib.fxb_set_tram_list(many._h, 1, p(beyond), beyond.size, 0, 0, None, 0)),
+                     ("an instance of N, n_words = 0, get", lib.fxb_get_tram_list(many._h, 0, p(beyond), beyond.size, 3, 0, p(out), 0))):
         assert rc == FX_E_ARG and many.last_error(), (what, rc)
         assert (many.info("tram_list_sets"), many.info("tram_list_gets")) == seen and not out.any(), what
+    # ... and without a list there is nothing to check: no word moves, on any shard
+    for what, rc in (("n_words = 0, no list, set", lib.fxb_set_tram_list(many._h, 0, None, 5, 7, 0, None, 0)),
+                     ("n_words = 0, no list, get", lib.fxb_get_tram_list(many._h, 1, None, 5, 0, 0, None, 0)),
+                     ("n_words = 0, a good list", lib.fxb_set_tram_list(many._h, 0, p(across), across.size, 7, 0, None, 0))):
+        assert rc == 0, (what, rc, many.last_error())
+        assert (many.info("tram_list_sets"), many.info("tram_list_gets")) == seen, what
     assert np.array_equal(many.save_state(), image) and np.array_equal(many.save_state(), one.save_state())
     for h in (many, one):
         h.close()

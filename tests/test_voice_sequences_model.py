@@ -1,0 +1,174 @@
+"""tools/fuzz_voices.py with the model alone (no GPU): what the seed ranges that tests/test_gpu_voice_sequences.py runs on the device
+actually reach.  A range whose programs do not load, whose sequences mostly end early outside the parity domain, or that never
+draws a rotated load at another position tests nothing, however green it is - so the counts are asserted here, where they cost a
+second.  "Accepted" and "refused" are the model's own reading of include/fx8010_amd.h; the GPU tests then hold the library to it."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("tools", "oracle", os.path.join("fx8010-emulator-core_amd", "python")):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+import fuzz_voices  # noqa: E402
+import fx8010_programs as progs  # noqa: E402
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def whole_state(o):
+    return (o.registers(), o.cursors(), o.lfsr(), o.instruction_counter(), o.ood_flags(), bits(o.tram(0, 64)).tobytes(), bits(o.tram(1, 64)).tobytes())
+
+
+def clear(monkeypatch):
+    for k in [k for k in os.environ if k.startswith("FX_")]:
+        monkeypatch.delenv(k, raising=False)
+
+
+@pytest.mark.parametrize("name", sorted(fuzz_voices.SLICES))
+def test_the_seed_ranges_cover_every_operation(name, monkeypatch):
+    """every program loads; at most 10 % of the sequences leave the parity domain; every kind of call was accepted at least 10
+    times and refused at least 3 times; rotated loads at another position and logical windows that wrap occur"""
+    clear(monkeypatch)
+    first, count, env = fuzz_voices.SLICES[name]
+    assert count >= 12
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cover = fuzz_voices.new_cover()
+    seen = {"copy": 0, "loaded_back_at_once": 0}
+    x = progs.stimulus(1, 24)[:, 0].copy()
+
+    def probe(kind, handle, pairs):
+        # the model's own consistency: after a copy, source and destination produce equal outputs on equal input (and are equal);
+        # a record loaded back at once changes nothing
+        for a, b in pairs:
+            a, b = (handle.o[a], handle.o[b]) if kind == "copy" else (a, b)
+            assert whole_state(a) == whole_state(b), (kind, name)
+            ca, cb = a.clone(), b.clone()
+            assert np.array_equal(bits(ca.process_block(x)), bits(cb.process_block(x))), (kind, name)
+            assert whole_state(ca) == whole_state(cb), (kind, name)
+            seen[kind] += 1
+
+    for seed in range(first, first + count):
+        assert fuzz_voices.run(seed, device=False, cover=cover, probe=probe), seed
+    assert cover["sequences"] == count and cover["loaded"] == count, cover
+    assert cover["left_domain"] * 10 <= count, cover
+    for kind in fuzz_voices.KINDS:
+        assert cover[kind][0] >= 10 and cover[kind][1] >= 3, (kind, cover[kind])
+    assert cover["blocks"] >= 10 and cover["state_reads"] >= 10, cover
+    assert cover["rotated_nonzero"] >= 5 and cover["logical_wrap"] >= 5, cover
+    assert cover["second_handles"] >= 3, cover
+    assert seen["copy"] >= 10 and seen["loaded_back_at_once"] >= 3, seen
+
+
+def test_every_generator_and_every_kind_of_line_occurs():
+    """the main range draws all four generators; rings, lines that are no rings and (in the DANE range) the DANE model"""
+    first, count, _ = fuzz_voices.SLICES["main"]
+    kinds = set()
+    for seed in range(first, first + count):
+        rng = np.random.default_rng(990000 + seed)
+        text, options = fuzz_voices.generate(seed, rng, seed % 4)
+        prog = fuzz_voices.Program(text, options)
+        assert prog.loads, seed
+        for w in (0, 1):
+            if prog.A[w] > 0:
+                kinds.add(("dane" if prog.dane else "reference", "ring" if prog.ring[w] else "no ring"))
+    assert kinds == {("reference", "ring"), ("reference", "no ring"), ("dane", "ring")}, kinds
+
+
+def test_the_sabotage_switches_only_touch_the_model(monkeypatch):
+    """each FX_FUZZ_BREAK name changes what the model computes for the main range (so the GPU detection test has something to find);
+    an unknown name changes nothing"""
+    clear(monkeypatch)
+    first, count, _ = fuzz_voices.SLICES["main"]
+
+    def digest():
+        out = []
+
+        def probe(kind, handle, pairs):
+            pass
+
+        for seed in range(first, first + count):
+            finals = []
+            orig = fuzz_voices.Handle.__init__
+
+            def keep(self, *a, **k):
+                orig(self, *a, **k)
+                finals.append(self)
+
+            monkeypatch.setattr(fuzz_voices.Handle, "__init__", keep)
+            assert fuzz_voices.run(seed, device=False, cover=fuzz_voices.new_cover(), probe=probe)
+            monkeypatch.setattr(fuzz_voices.Handle, "__init__", orig)
+            out.append([whole_state(h.o[n]) for h in finals for n in h.tracked])
+        return out
+
+    plain = digest()
+    monkeypatch.setenv("FX_FUZZ_BREAK", "no_such_switch")
+    assert digest() == plain
+    for name in fuzz_voices.BREAKS:
+        monkeypatch.setenv("FX_FUZZ_BREAK", name)
+        assert digest() != plain, name
+
+
+RING = ("itramsize 7 \nxtramsize 5 \ninput in 0\noutput out 0\ncontrol c = 0.5\nstatic noise\nstatic a\nstatic b\nstatic t\n"
+        "idelay read, a, at, 0\nxdelay read, b, at, 0\nmacs t, a, b, c\nmacs t, t, noise, 0.125\nidelay write, in, at, 0\n"
+        "xdelay write, t, at, 0\nmacs out, t, in, 0.5\nend")
+
+
+def test_the_model_operations_one_by_one():
+    """the methods of fuzz_voices.Handle the runner applies, on a hand-written program with two rings: a copy is its source; a
+    reset is a fresh object at the last broadcast values with the positions kept; a record loaded at another position carries on
+    like the saved instance (the header's promise for fxb_load_instances_rotated), its rings rotated by the distance; a logical
+    window lands at the header's slots"""
+    prog = fuzz_voices.Program(RING, 0)
+    assert prog.loads and prog.ring == [True, True] and prog.A == [7, 5]
+    h = fuzz_voices.Handle(prog, 4, [0, 1, 2, 3], False, 1)
+    x = progs.stimulus(4, 60)
+    for n in h.tracked:
+        h.o[n].seed_noise(17 + n, -9 * n)
+        h.o[n].process_block(x[:9, n].copy())
+    # copy
+    h.model_copy([0, 0], [1, 2])
+    assert whole_state(h.o[1]) == whole_state(h.o[0]) == whole_state(h.o[2]) and h.o[1] is not h.o[0]
+    # list set, then reset: per-instance values are gone, the broadcast one stays, positions stay, memory and counter are fresh
+    h.broadcast["c"] = 0.25
+    h.model_set_registers(["c", "t"], [3, 2], np.array([[0.75, -0.5], [0.1, 0.2]], np.float32))
+    assert h.o[3].get_register("c") == 0.75 and h.o[2].get_register("c") == -0.5 and h.o[0].get_register("c") == 0.5
+    kept = h.o[3].cursors()
+    h.model_reset([3])
+    assert h.o[3].get_register("c") == 0.25 and h.o[3].get_register("t") == 0.0 and h.o[3].cursors() == kept != [0, 0, 0, 0]
+    assert h.o[3].instruction_counter() == 0 and not bits(h.o[3].tram(0, 7)).any()
+    # a record of instance 0, then 11 more samples on everyone: a plain load is refused, a rotated one rotates both rings
+    record = h.o[0].clone()
+    for n in h.tracked:
+        h.o[n].process_block(x[9:20, n].copy())
+    assert h.model_load([record], [1], False)[1] is not None
+    new, why, where = h.model_load([record], [1], True)
+    assert why is None and new[1][1]
+    d, bad = h.rotation(record, h.o[1])
+    assert d == [11 % 7, 11 % 5] and bad == []
+    loaded = new[1][0]
+    assert loaded.cursors() == h.o[1].cursors()
+    for w in (0, 1):
+        assert np.array_equal(bits(loaded.tram(w, prog.A[w])), np.roll(bits(record.tram(w, prog.A[w])), d[w]))
+    twin = record.clone()
+    assert np.array_equal(bits(loaded.process_block(x[20:60, 1].copy())), bits(twin.process_block(x[20:60, 1].copy())))
+    assert loaded.registers() == twin.registers() and loaded.lfsr() == twin.lfsr() and loaded.instruction_counter() == twin.instruction_counter()
+    # unrotated by d = 0: a record loaded where it was saved is the record
+    again = h.o[2].clone()
+    new, why, _ = h.model_load([again], [2], True)
+    assert why is None and not new[2][1] and whole_state(new[2][0]) == whole_state(again)
+    # logical word 0 is the word the last delay write stored: slot (p - 1) mod Z; a window of Z words wraps
+    o = h.o[0]
+    p = o.cursors()[0]
+    slots = h.window_slots(o, 0, 0, 7, True)
+    assert list(slots) == [(p - 1 - a) % 7 for a in range(7)] and sorted(slots) == list(range(7))
+    assert bits(o.tram(0, 7))[slots[0]] == bits(x[19:20, 0])[0]
+    words = np.arange(1, 8, dtype=np.float32)
+    h.model_set_window(o, 0, slots, words)
+    assert np.array_equal(h.line_of(o, 0)[slots], words)
+    assert list(h.window_slots(o, 1, 2, 3, False)) == [2, 3, 4]

@@ -1,6 +1,7 @@
 """Shrink a failing sequence of tools/fuzz_api.py: delete instructions of its program one at a time as long as the sequence still
 fails (the host calls stay the same: they come from the seed's random stream).  Prints the reduced program.
-    [FX_FUZZ_PANEL=1 ...] python tools/fuzz_api_reduce.py <seed>"""
+    [FX_FUZZ_PANEL=1 ...] python tools/fuzz_api_reduce.py <seed>
+    [FX_KERNEL=asm ...]   python tools/fuzz_api_reduce.py <seed> voices      a sequence of tools/fuzz_voices.py instead"""
 import contextlib
 import io
 import os
@@ -8,7 +9,10 @@ import sys
 
 ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-import fuzz_api as F  # noqa: E402
+if len(sys.argv) > 2 and sys.argv[2] == "voices":
+    import fuzz_voices as F  # noqa: E402
+else:
+    import fuzz_api as F  # noqa: E402
 
 DECL = ("input", "output", "control", "static", "itramsize", "xtramsize", "name", "engine", "comment", "end")
 

@@ -67,4 +67,10 @@ run "api control panel"        FX_FUZZ_PANEL=1 timeout -k 10 900 python3 tools/f
 run "api control panel, interpreter"  FX_FUZZ_PANEL=1 FX_KERNEL=asm timeout -k 10 900 python3 tools/fuzz_api.py 2700000 $((600*K))
 run "api control panel, wild registers"  FX_FUZZ_PANEL=1 FX_FUZZ_WILD=1 timeout -k 10 900 python3 tools/fuzz_api.py 2800000 $((2000*K))
 run "api control panel, two shards"      FX_FUZZ_PANEL=1 FX_FUZZ_SHARDS=2 timeout -k 10 900 python3 tools/fuzz_api.py 2900000 $((1000*K))
+run "voices"                   timeout -k 10 900 python3 tools/fuzz_voices.py 2000000 $((3000*K))
+run "voices interpreter"       FX_KERNEL=asm timeout -k 10 900 python3 tools/fuzz_voices.py 2100000 $((2000*K))
+run "voices HIP kernel"        FX_KERNEL=hip timeout -k 10 900 python3 tools/fuzz_voices.py 2200000 $((2000*K))
+run "voices two shards"        FX_FUZZ_SHARDS=2 timeout -k 10 900 python3 tools/fuzz_voices.py 2300000 $((2000*K))
+run "voices wild words"        FX_FUZZ_WILD=1 timeout -k 10 900 python3 tools/fuzz_voices.py 2400000 $((2000*K))
+run "voices DANE"              FX_FUZZ_GEN=3 timeout -k 10 900 python3 tools/fuzz_voices.py 2500000 $((2000*K))
 echo done
