@@ -351,6 +351,7 @@ void Batch::markControls() {
     for (const std::string& name : prog_.controls) {
         const int r = prog_.findRegister(name);
         if (r < 0 || forcedLane_[(size_t)r] || intrinsicLane(r) || !readByProgram(r) || !movableControl(r)) continue;
+        // (not noteRegisterWritten: nothing has been written - the row is for company, laneWritten_ stays)
         forcedLane_[(size_t)r] = 1;
         lowDirty_ = true;
     }
@@ -741,6 +742,7 @@ int Batch::loadStateColumns(const uint8_t* image, const SnapshotHeader& hdr, int
             }
             laneWritten_[(size_t)r] = 0;
         } else {
+            // (not noteRegisterWritten: the cold set has been marked changed once, above, for the whole image)
             if (!forcedLane_[(size_t)r] && readByProgram(r)) { forcedLane_[(size_t)r] = 1; lowDirty_ = true; }
             laneWritten_[(size_t)r] = 1;
         }

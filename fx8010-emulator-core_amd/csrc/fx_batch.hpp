@@ -35,6 +35,16 @@ namespace fx {
 
 inline uint32_t bitsOf(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
+// One column of a by-list call, either way between the caller's array and the staging: element i of the staging is element pos[i]
+// of the caller's column (pos null: i), `bytes` each.  toCaller: `to` is the caller's column, else it is the staging.
+inline void copyColumn(void* to, const void* from, const int64_t* pos, size_t count, size_t bytes, bool toCaller) {
+    if (!pos) { std::memcpy(to, from, count * bytes); return; }
+    for (size_t i = 0; i < count; ++i) {
+        const size_t theirs = (size_t)pos[i] * bytes, ours = i * bytes;
+        std::memcpy(static_cast<char*>(to) + (toCaller ? theirs : ours), static_cast<const char*>(from) + (toCaller ? ours : theirs), bytes);
+    }
+}
+
 class Batch {
 public:
     // throws std::runtime_error when no HIP device is usable (there is no CPU fallback)
@@ -234,12 +244,34 @@ public:
     }
     int saveStateColumns(uint8_t* image, const SnapshotHeader& hdr, int64_t first);
     int loadStateColumns(const uint8_t* image, const SnapshotHeader& hdr, int64_t first);
+    // THE BY-LIST FRAME (fx_batch_list.cpp) - what every call below that changes device state by a list of instances has in common:
+    //   check    the refusals that read nothing but the arguments, for the whole handle and with the caller's indices (the static
+    //            check... functions, on checkList; Sharded asks before any shard is posted);
+    //   reserve  the allocating half, on every shard before any shard changes a word (the reserve... functions, on
+    //            reserveListStage: the event, the device block, the pinned block - FX_E_MEMORY changes nothing);
+    //   stage    the host waits for the previous instance call or list set only (waitPreviousInstCall: its lists are in the staging
+    //            this one is about to fill - between two sets of a real-time host lies a block, so that wait is over before it
+    //            starts) and copies the list and the caller's columns into pinned staging: the caller's arrays are free on return;
+    //   order    the handle's stream waits for every block queued so far on whatever stream (orderBehindQueuedBlocks: ev1_, evBus_);
+    //   fence    the kernels run on the handle's stream and evInst_ is recorded behind them (closeInstCall): a block on another
+    //            stream (launchBlock), the host in waitLastLaunch - every register call, every state access - and sync are ordered
+    //            behind it.  A failure on the way waits for the stream first: nothing may still read the staging.
+    // checkList: what is wrong with `list` and at which entry - the first one in list order outside 0..range-1, else (unique) the
+    // first one in list order that repeats an earlier one.  Repeats are found in a bitmap over the range where that is the cheaper
+    // one to clear (a real-time list of a thousand entries out of half a million: 56 KiB), else in a sorted copy (a few entries
+    // out of millions); both name the same entry.
+    struct ListFault {
+        enum Kind { kNone, kOutside, kRepeat } kind = kNone;
+        int64_t entry = -1;
+        explicit operator bool() const { return kind != kNone; }
+    };
+    static ListFault checkList(const int64_t* list, int64_t count, int64_t range, bool unique);
+    static std::string listOutside(const std::string& name, const ListFault& f, int64_t range);   // "<name>: entry i of the list is outside 0..range-1"
     // Per-instance state calls (fx_instances.hpp; include/fx8010_amd.h "Per-instance state").  A RECORD is the W = stateRows +
     // iSlots + xSlots words of one instance, packed: the state rows in the order of the whole-batch image, then the iTRAM slots, then
     // the xTRAM slots.  An instance image is a SnapshotHeader with kInstanceMagic and n = the number of records, then the records.
     // Every list here holds instance numbers of THIS batch; Sharded splits the caller's global lists.  All of them lower the program
-    // first, run on the handle's own stream behind every block queued so far on whatever stream (ev1_, evBus_), and every later
-    // block, state access and sync is ordered behind them (evInst_).
+    // first and run inside the by-list frame (above).
     static constexpr uint32_t kInstanceMagic = 0x49535846u;   // "FXSI"
     // the refusals that read nothing but the lists (Sharded asks for the whole batch): 0, or FX_E_ARG and why.  dst null: one list
     // whose entries must be distinct; else src may repeat, dst may not and may not appear in src
@@ -273,15 +305,13 @@ public:
     // everything (checkRegisterList) and, for a set, has called reserveRegisterList - the allocating half (device and pinned staging,
     // the event: FX_E_MEMORY changes nothing).  count == 0 is a shard that owns none of the entries: nothing is launched and nothing
     // changes.  setRegistersList leaves the batch as count * nKeys calls of setRegisterAt would, without their wait: the words are
-    // scattered on the handle's stream behind every block queued so far on whatever stream (ev1_, evBus_) and in front of evInst_,
-    // the event of the instance calls - every later block, state access and sync is ordered behind it as behind a copy of
-    // instances.  getRegistersList is synchronous and equals getRegisterAt word for word: a register that lives on the host only is
-    // answered from hostValue_, the others by one gather.
+    // scattered inside the by-list frame.  getRegistersList is synchronous and equals getRegisterAt word for word: a register that
+    // lives on the host only is answered from hostValue_, the others by one gather.
     bool stateReady() const { return dState_ != nullptr; }
     int resolveRegisters(const char* const* keys, int nKeys, std::vector<int>* regs);   // 0, or 1 and lastError names the key
-    // the refusals that read nothing but the arguments (Sharded asks for the whole handle): every instance in 0..n-1 and, unique
-    // (a set), no instance and no register twice
-    static int checkRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const void* values, bool unique, std::string* why);
+    // the refusals that read nothing but the arguments (Sharded asks for the whole handle), in the name of the call `name`: every
+    // instance in 0..n-1 and, unique (a set), no instance and no register twice
+    static int checkRegisterList(const char* name, const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const void* values, bool unique, std::string* why);
     int reserveRegisterList(int nKeys, int64_t count);
     int setRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* values);
     int getRegistersList(const std::vector<int>& regs, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, float* values);
@@ -308,10 +338,9 @@ public:
     // nothing but the arguments (Sharded asks for the whole handle); reserveTramList lowers the program, refuses a window the line
     // does not have, and is the allocating half (staging, the event: FX_E_MEMORY changes nothing) - count == 0 there still checks
     // the window, so that every shard is asked before any shard changes a word.  tramList with count == 0 is a shard that owns
-    // none of the entries: nothing is launched and nothing changes.  A set is queued on the handle's stream behind every block
-    // queued so far on whatever stream (ev1_, evBus_) and in front of evInst_, as a register list set is; it waits on the HOST for
-    // the previous list or instance call (the staging is reused), so a call of several pieces blocks between them.  A get is
-    // synchronous.  There is no host mirror of delay memory: nothing else changes.
+    // none of the entries: nothing is launched and nothing changes.  A set runs inside the by-list frame, once per piece: a call of
+    // several pieces blocks between them (the staging is reused).  A get is synchronous.  There is no host mirror of delay memory:
+    // nothing else changes.
     static int checkTramList(bool set, int which, const int64_t* list, int64_t count, int64_t n, int first, int nWords, const void* values, unsigned flags, std::string* why);
     int reserveTramList(bool set, int which, int64_t count, int first, int nWords, unsigned flags);
     int tramList(int which, const int64_t* list, const int64_t* pos, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags);
@@ -321,10 +350,8 @@ public:
     // what falls to THIS batch - nothing to do there reserves nothing.  meterSelect looks at the local columns first .. first +
     // nRange - 1, writes the min(M, cap) smallest matching numbers firstGlobal + (column - first) to `list`, ascending, and returns
     // M; nothing beyond min(M, cap) is touched.  meterReadList writes column pos[i] (null: i) of the caller's [channels][total]
-    // arrays for list[i].  Both are synchronous.  meterResetList is queued on the handle's stream behind every block queued so
-    // far on whatever stream (ev1_, evBus_) and in front of evInst_, as a register list set is; it waits on the HOST only for the
-    // previous list or instance call.  With count == 0 (a shard that owns no entry) nothing is launched and nothing changes.
-    // None of them touches meterSamples_.
+    // arrays for list[i].  Both are synchronous.  meterResetList runs inside the by-list frame.  With count == 0 (a shard that owns
+    // no entry) nothing is launched and nothing changes.  None of them touches meterSamples_.
     static int checkMeterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
     static int checkMeterList(const char* name, const int64_t* list, int64_t count, int64_t n, bool unique, std::string* why);
     int reserveMeterSelect(int64_t nRange, int64_t cap);
@@ -830,22 +857,39 @@ private:
     bool instLaunched_ = false;          // ... which may still be running
     int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS
     int64_t instRotations_ = 0;                    // FXB_INFO_INSTANCE_ROTATIONS
+    // the by-list frame (fx_batch_list.cpp; "THE BY-LIST FRAME" above), shared by the instance calls and the list sets.
+    // reserveListStage: `ev` on first use where wanted (texts[0] names it in FX_E_MEMORY), the capacity test, a wait for the call
+    // that may still be reading the blocks that go (`ev` / `busy`), then the device block (texts[1]), then the pinned one (texts[2]).
+    template <class T> int reserveListStage(Block<T>& dev, Block<T>& host, size_t words, hipEvent_t& ev, bool& busy, bool needEvent, const char* const (&texts)[3]) {
+        if (needEvent && !ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; return hipFail(hipErrorOutOfMemory, texts[0]); }
+        if (words <= dev.cap && words <= host.cap) return 0;
+        // (the previous list set may still be reading the blocks that go)
+        if (busy && hipEventSynchronize(ev) == hipSuccess) busy = false;
+        const int rc = growBlock(dev, words, false, texts[1]);
+        return rc != 0 ? rc : growBlock(host, words, true, texts[2]);
+    }
+    int waitPreviousInstCall(const char* what);       // the host wait on evInst_ while instLaunched_
+    hipError_t orderBehindQueuedBlocks();             // stream_ waits for ev1_ and evBus_: every block queued so far, on whichever stream
+    int closeInstCall(hipError_t e, const char* what);   // evInst_ behind what was queued; any failure: wait for stream_, then hipFail(what)
+    // what the host knows after a per-instance write to register r, as after setRegisterAt (the row stays valid for every other
+    // instance: setRegister's invariant): the first such write to a register the code in force has folded in asks for other code
+    void noteRegisterWritten(int r);
+    void noteRegistersWritten(const std::vector<int>& regs) { for (const int r : regs) noteRegisterWritten(r); }
     // register calls by list (fx_batch_registers.cpp): one staging pair of 32-bit words, [count] instance numbers (64-bit), then
-    // [nKeys][count] values, then [nKeys] rows - grown by reserveRegisterList and reused: a call first waits on the HOST for the
-    // previous instance call or list set (evInst_, instLaunched_)
+    // [nKeys][count] values, then [nKeys] rows - grown by reserveRegisterList and reused inside the frame
     Block<uint32_t> regList_, hRegList_;
     static size_t regListWords(int nKeys, int64_t count) { return (size_t)count * 2 + (size_t)nKeys * (size_t)count + (size_t)nKeys; }
     int stageRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, RegListArgs* a);
     int64_t regListSets_ = 0, regListGets_ = 0;    // FXB_INFO_REGISTER_LIST_SETS / _GETS
     // delay-line windows by list (fx_batch_tram.cpp): a staging pair of 32-bit words of its own - [entries] instance numbers
-    // (64-bit), then the windows of a piece, at most kInstScratchBytes of them - grown by reserveTramList and reused: a piece first
-    // waits on the HOST for the previous instance call or list set (evInst_, instLaunched_)
+    // (64-bit), then the windows of a piece, at most kInstScratchBytes of them - grown by reserveTramList and reused inside the
+    // frame, piece by piece
     Block<uint32_t> tramStage_, hTramStage_;
     int64_t tramEntriesPerPiece(int nWords) const { return (int64_t)std::max<size_t>(kInstScratchBytes / ((size_t)nWords * 4), 1); }
     int64_t tramListSets_ = 0, tramListGets_ = 0;  // FXB_INFO_TRAM_LIST_SETS / _GETS
     // meter queries by list (fx_batch_meter_list.cpp): one staging pair of 64-bit words for the three calls - a select's chunk
     // offsets, total and list; a list call's list and packed rows - grown by the reserve... functions and reused: the synchronous
-    // calls have drained everything, a reset first waits on the HOST for the previous instance call or list set (evInst_)
+    // calls have drained everything, a reset runs inside the frame
     Block<unsigned long long> meterStage_, hMeterStage_;
     int reserveMeterStage(size_t words, bool needEvent);
     int64_t meterSelects_ = 0, meterListReads_ = 0, meterListResets_ = 0;   // FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS

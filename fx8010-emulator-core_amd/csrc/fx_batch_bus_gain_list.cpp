@@ -25,49 +25,25 @@
 namespace fx {
 
 // The refusals that read nothing but the arguments (Sharded asks for the whole handle, before any shard is posted): every index
-// in 0..range-1, no index twice (a bitmap or a sorted copy), every value finite.
+// in 0..range-1, no index twice (checkList), every value finite.
 int Batch::checkGainList(const int64_t* list, int64_t count, int64_t range, const float* gains, int channels, const char* what, std::string* why) {
     const std::string name(what);
     if (count < 0) { *why = name + ": count < 0"; return FX_E_ARG; }
     if (count == 0) return 0;
     if (!list || !gains) { *why = name + ": a null list or null gains"; return FX_E_ARG; }
-    for (int64_t k = 0; k < count; ++k)
-        if (list[k] < 0 || list[k] >= range) { *why = name + ": entry " + std::to_string(k) + " of the list is outside 0.." + std::to_string(range - 1); return FX_E_ARG; }
-    // repeats: a bitmap over the range where that is the cheaper one to clear (a real-time list of a thousand faders out of half a
-    // million instances: 56 KiB), else a sorted copy (a few entries out of millions)
-    int64_t twice = -1;
-    if ((range + 63) / 64 <= 16 * count) {
-        std::vector<uint64_t> seen((size_t)((range + 63) / 64), 0);
-        for (int64_t k = 0; k < count && twice < 0; ++k) {
-            uint64_t& word = seen[(size_t)(list[k] >> 6)];
-            const uint64_t bit = (uint64_t)1 << (list[k] & 63);
-            if (word & bit) twice = list[k];
-            word |= bit;
-        }
-    } else {
-        std::vector<int64_t> sorted(list, list + count);
-        std::sort(sorted.begin(), sorted.end());
-        const auto at = std::adjacent_find(sorted.begin(), sorted.end());
-        if (at != sorted.end()) twice = *at;
-    }
-    if (twice >= 0) { *why = name + ": index " + std::to_string(twice) + " is listed more than once"; return FX_E_ARG; }
+    const ListFault f = checkList(list, count, range, true);
+    if (f.kind == ListFault::kOutside) { *why = listOutside(name, f, range); return FX_E_ARG; }
+    if (f) { *why = name + ": index " + std::to_string(list[f.entry]) + " is listed more than once"; return FX_E_ARG; }
     if (!gainsFinite(gains, channels, count, count)) { *why = name + ": every gain must be finite"; return FX_E_ARG; }
     return 0;
 }
 
 int Batch::busReserveGainList(int64_t count) {
     (void)hipSetDevice(device_);
-    if (!evList_) {
-        const hipError_t e = hipEventCreateWithFlags(&evList_, hipEventDisableTiming);
-        if (e != hipSuccess) { evList_ = nullptr; return hipFail(hipErrorOutOfMemory, "gain list event"); }
-    }
+    // (the reserve step of the by-list frame, with this file's own event: the sets here are ordered behind evBus_ only)
     const size_t words = (size_t)std::max<int64_t>(count, 0) * ((size_t)prog_.numChannels + 1);
-    if (words <= gainList_.cap && words <= hGainList_.cap) return 0;
-    // (the previous list set may still be reading the blocks that go)
-    if (listCopied_ && hipEventSynchronize(evList_) == hipSuccess) listCopied_ = false;
-    int rc = growBlock(gainList_, words, false, "hipMalloc gain list staging");
-    if (rc == 0) rc = growBlock(hGainList_, words, true, "pinned staging of the gain list");
-    return rc;
+    static const char* const kTexts[3] = {"gain list event", "hipMalloc gain list staging", "pinned staging of the gain list"};
+    return reserveListStage(gainList_, hGainList_, words, evList_, listCopied_, true, kTexts);
 }
 
 int Batch::setGainList(const GainListTarget& t, const int64_t* list, const int64_t* pos, int64_t count, int64_t total, const float* gains, int ramp) {
@@ -79,8 +55,7 @@ int Batch::setGainList(const GainListTarget& t, const int64_t* list, const int64
         listCopied_ = false;
         uint32_t* stage = hGainList_.p;
         for (size_t i = 0; i < k; ++i) stage[i] = (uint32_t)list[i];
-        for (size_t c = 0; c < ch; ++c)
-            for (size_t i = 0; i < k; ++i) std::memcpy(&stage[k * (1 + c) + i], gains + c * (size_t)total + (size_t)(pos ? pos[i] : (int64_t)i), 4);
+        for (size_t c = 0; c < ch; ++c) copyColumn(&stage[k * (1 + c)], gains + c * (size_t)total, pos, k, 4, false);
     }
     const bool swap = ramp != 0 && !t.ramp->pending;   // a := b everywhere: the old b becomes a, the other block takes its words and is b
     const int target = t.ramp->writeTarget(ramp);

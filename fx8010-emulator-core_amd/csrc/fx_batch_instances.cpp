@@ -1,15 +1,12 @@
 // fx_batch_instances.cpp — the per-instance state calls of one batch: copy, reset, records to and from the host (fx_batch.hpp
 // "Per-instance state calls", kernels: fx_instances.hip).
 //
-// Every call has the same frame.  beginInstanceCall lowers the program (the delay memory exists from then on), refuses instance
-// numbers outside the batch, waits on the HOST for the previous instance call (its lists and records are in the buffers this one
-// is about to fill - between two calls of a voice pool lies at least a block, so that wait is over before it starts), copies the
-// lists into pinned memory and from there to the device, and makes the handle's stream wait for every block queued so far on
-// whatever stream (ev1_, evBus_).  The kernels then run on the handle's stream, in pieces of at most recordsPerPiece() records on
-// the one record scratch - stream order alone keeps a piece's scatter in front of the next piece's gather.  endInstanceCall
-// records evInst_ behind the last of them: a block on another stream waits for it (launchBlock), the host does in waitLastLaunch
-// and sync.  The rotated load (recordRotations, scatterRecordsRotated) has the frame of the load; its rotation pairs travel with
-// the list, in the place of the second one.
+// Every call runs inside the by-list frame (fx_batch.hpp "THE BY-LIST FRAME", fx_batch_list.cpp).  beginInstanceCall lowers the
+// program (the delay memory exists from then on), refuses instance numbers outside the batch, waits for the previous call, grows
+// and fills the lists and orders the handle's stream behind the queued blocks.  The kernels then run on the handle's stream, in
+// pieces of at most recordsPerPiece() records on the one record scratch - stream order alone keeps a piece's scatter in front of
+// the next piece's gather.  endInstanceCall records evInst_ behind the last of them.  The rotated load (recordRotations,
+// scatterRecordsRotated) has the frame of the load; its rotation pairs travel with the list, in the place of the second one.
 #include "fx_batch.hpp"
 
 #include <algorithm>
@@ -34,14 +31,14 @@ int Batch::checkInstanceLists(const int64_t* src, const int64_t* dst, int64_t co
     else if (count > 0 && !src && !dst) *why = "instances: a null list";
     else if (count >= ((int64_t)1 << 31)) *why = "instances: more than 2^31 - 1 list entries";
     if (*why) return FX_E_ARG;
-    for (const int64_t* list : {src, dst})
-        for (int64_t k = 0; list && k < count; ++k)
-            if (list[k] < 0 || list[k] >= n) { *why = "instances: an instance number outside the batch"; return FX_E_ARG; }
-    if (!dst || count == 0) return 0;
+    // (src may repeat; the order of the refusals: either list outside the batch, a destination twice, a destination as a source)
+    const ListFault fs = src ? checkList(src, count, n, false) : ListFault{}, fd = dst ? checkList(dst, count, n, true) : ListFault{};
+    if (fs || fd.kind == ListFault::kOutside) { *why = "instances: an instance number outside the batch"; return FX_E_ARG; }
+    if (fd) { *why = "instances: a destination is listed twice"; return FX_E_ARG; }
+    if (!dst || !src) return 0;
     std::vector<int64_t> sorted(dst, dst + count);
     std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { *why = "instances: a destination is listed twice"; return FX_E_ARG; }
-    for (int64_t k = 0; src && k < count; ++k)
+    for (int64_t k = 0; k < count; ++k)
         if (std::binary_search(sorted.begin(), sorted.end(), src[k])) { *why = "instances: a destination is also a source"; return FX_E_ARG; }
     return 0;
 }
@@ -97,10 +94,7 @@ int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, 
     if (!a || count < 1) return fail(FX_E_ARG, "instances: a null list");
     hipError_t e = hipSuccess;
     if (!evInst_ && (e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming)) != hipSuccess) { evInst_ = nullptr; return hipFail(e, "instance event"); }
-    if (instLaunched_) {
-        if ((e = hipEventSynchronize(evInst_)) != hipSuccess) return hipFail(e, "waiting for the previous instance call");
-        instLaunched_ = false;
-    }
+    if ((rc = waitPreviousInstCall("waiting for the previous instance call")) != 0) return rc;
     const size_t entries = (size_t)count;
     // (two lists of `entries` each; the previous call, the only user of these blocks, has been waited for)
     if ((rc = growBlock(hInstList_, entries, true, "pinned instance lists", 2 * sizeof(long long))) != 0) return rc;
@@ -113,9 +107,7 @@ int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, 
     if (second) std::memcpy(hInstList_.p + hInstList_.cap, second, entries * 8);
     e = hipMemcpyAsync(instList_.p, hInstList_.p, entries * 8, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess && second) e = hipMemcpyAsync(instList_.p + instList_.cap, hInstList_.p + hInstList_.cap, entries * 8, hipMemcpyHostToDevice, stream_);
-    // behind every block queued so far, on whichever stream it was queued
-    if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
-    if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+    if (e == hipSuccess) e = orderBehindQueuedBlocks();
     if (e != hipSuccess) {
         (void)endInstanceCall(true);   // (the list copies may be on their way)
         return hipFail(e, "instances: lists to the device");
@@ -123,6 +115,8 @@ int Batch::beginInstanceCall(const int64_t* a, const int64_t* b, int64_t count, 
     return 0;
 }
 
+// (closeInstCall with two differences that stay: the event is recorded behind a failed launch too - the pieces in front of it are
+// queued - and a synchronous call waits for the stream and leaves nothing outstanding)
 int Batch::endInstanceCall(bool wait) {
     hipError_t e = hipEventRecord(evInst_, stream_);
     if (e == hipSuccess) instLaunched_ = true;
@@ -361,10 +355,7 @@ void Batch::promoteLoaded(const uint32_t* buf, int64_t total) {
         bool differs = false;
         for (int64_t k = 0; k < total && !differs; ++k) differs = buf[(size_t)k * W + (size_t)r] != held;
         if (!differs) continue;
-        // as if setRegisterAt had written it (the row is valid for every other instance: setRegister's invariant)
-        if (coldControl(r)) coldSetChanged();
-        if (!forcedLane_[(size_t)r] && readByProgram(r)) { forcedLane_[(size_t)r] = 1; lowDirty_ = true; }
-        laneWritten_[(size_t)r] = 1;
+        noteRegisterWritten(r);   // as if setRegisterAt had written it
     }
 }
 

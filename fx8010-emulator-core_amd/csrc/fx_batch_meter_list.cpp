@@ -3,11 +3,8 @@
 // queries by list", fx_batch.hpp "Meter queries by list", kernels: fx_meter_list.hip).
 //
 // The select and the list read are synchronous: they wait as sync() does - which covers a list reset still in flight - launch on
-// the handle's stream and wait for it.  The list reset rides the frame of the register list set (fx_batch_registers.cpp): it
-// waits on the HOST for the previous instance call or list set only, copies the list into pinned staging (the caller's list is
-// free on return) and from there to the device, makes the handle's stream wait for every block queued so far on whatever stream
-// (ev1_, evBus_ - a block's meter launch sits in front of its ev1_ record), launches fx_meter_zero there and records evInst_ behind
-// it: every later block, on whichever stream, is ordered behind it as behind a copy of instances.
+// the handle's stream and wait for it.  The list reset runs inside the by-list frame (fx_batch.hpp "THE BY-LIST
+// FRAME", fx_batch_list.cpp): the list is staged, fx_meter_zero is the kernel in front of evInst_.
 //
 // One staging pair of 64-bit words serves the three calls - none of them can find it in use: the synchronous two have drained
 // everything, the reset waits for evInst_ first.  A select lays it out as [chunk counts / offsets][the total][the list], so that
@@ -46,26 +43,9 @@ int Batch::checkMeterList(const char* name, const int64_t* list, int64_t count, 
     if (count == 0) return 0;
     if (!list) { *why = who + ": a null list"; return FX_E_ARG; }
     if (count >= ((int64_t)1 << 31)) { *why = who + ": count must stay below 2^31"; return FX_E_ARG; }
-    for (int64_t i = 0; i < count; ++i)
-        if (list[i] < 0 || list[i] >= n) { *why = who + ": entry " + std::to_string(i) + " of the list is outside 0.." + std::to_string(n - 1); return FX_E_ARG; }
-    if (!unique) return 0;
-    // repeats: a bitmap over the instances where that is the cheaper one to clear, else a sorted copy (checkRegisterList)
-    int64_t twice = -1;
-    if ((n + 63) / 64 <= 16 * count) {
-        std::vector<uint64_t> seen((size_t)((n + 63) / 64), 0);
-        for (int64_t i = 0; i < count && twice < 0; ++i) {
-            uint64_t& word = seen[(size_t)(list[i] >> 6)];
-            const uint64_t bit = (uint64_t)1 << (list[i] & 63);
-            if (word & bit) twice = list[i];
-            word |= bit;
-        }
-    } else {
-        std::vector<int64_t> sorted(list, list + count);
-        std::sort(sorted.begin(), sorted.end());
-        const auto at = std::adjacent_find(sorted.begin(), sorted.end());
-        if (at != sorted.end()) twice = *at;
-    }
-    if (twice >= 0) { *why = who + ": instance " + std::to_string(twice) + " is listed more than once (reset)"; return FX_E_ARG; }
+    const ListFault f = checkList(list, count, n, unique);
+    if (f.kind == ListFault::kOutside) { *why = listOutside(who, f, n); return FX_E_ARG; }
+    if (f) { *why = who + ": instance " + std::to_string(list[f.entry]) + " is listed more than once (reset)"; return FX_E_ARG; }
     return 0;
 }
 
@@ -73,16 +53,8 @@ int Batch::reserveMeterStage(size_t words, bool needEvent) {
     (void)hipSetDevice(device_);
     if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
     if (words == 0) return 0;
-    if (needEvent && !evInst_) {
-        const hipError_t e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming);
-        if (e != hipSuccess) { evInst_ = nullptr; return hipFail(hipErrorOutOfMemory, "meter list event"); }
-    }
-    if (words <= meterStage_.cap && words <= hMeterStage_.cap) return 0;
-    // (the previous list reset may still be reading the block that goes)
-    if (instLaunched_ && hipEventSynchronize(evInst_) == hipSuccess) instLaunched_ = false;
-    int rc = growBlock(meterStage_, words, false, "hipMalloc meter list staging");
-    if (rc == 0) rc = growBlock(hMeterStage_, words, true, "pinned staging of the meter list");
-    return rc;
+    static const char* const kTexts[3] = {"meter list event", "hipMalloc meter list staging", "pinned staging of the meter list"};
+    return reserveListStage(meterStage_, hMeterStage_, words, evInst_, instLaunched_, needEvent, kTexts);
 }
 
 int Batch::reserveMeterSelect(int64_t nRange, int64_t cap) { return reserveMeterStage(nRange > 0 ? selectWords(nRange, cap) : 0, false); }
@@ -183,8 +155,7 @@ int Batch::meterReadList(const int64_t* list, const int64_t* pos, int64_t count,
         for (int c = 0; c < channels; ++c) {
             const char* from = part[r] + (size_t)c * k * bytes;
             char* to = out[r] + (size_t)c * (size_t)total * bytes;
-            if (!pos) std::memcpy(to, from, k * bytes);
-            else for (size_t i = 0; i < k; ++i) std::memcpy(to + (size_t)pos[i] * bytes, from + i * bytes, bytes);
+            copyColumn(to, from, pos, k, bytes, true);
         }
     }
     return 0;
@@ -196,11 +167,7 @@ int Batch::meterResetList(const int64_t* list, int64_t count) {
     if (count == 0) return 0;
     const size_t k = (size_t)count;
     if (k > meterStage_.cap || k > hMeterStage_.cap || !evInst_) return fail(FX_E_ARG, "meter_reset_list: no staging reserved (reserveMeterList)");
-    if (instLaunched_) {
-        const hipError_t e = hipEventSynchronize(evInst_);
-        if (e != hipSuccess) return hipFail(e, "meter_reset_list: waiting for the previous call");
-        instLaunched_ = false;
-    }
+    if (const int rc = waitPreviousInstCall("meter_reset_list: waiting for the previous call")) return rc;
     std::memcpy(hMeterStage_.p, list, k * 8);
     MeterListArgs a{};
     a.rows = dMeter_;
@@ -210,21 +177,14 @@ int Batch::meterResetList(const int64_t* list, int64_t count) {
     a.nPad = nPad_;
     a.channels = prog_.numChannels;
     hipError_t e = hipMemcpyAsync(meterStage_.p, hMeterStage_.p, k * 8, hipMemcpyHostToDevice, stream_);
-    // behind every block queued so far, on whichever stream it was queued - its meter launch included
-    if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
-    if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+    if (e == hipSuccess) e = orderBehindQueuedBlocks();   // (a block's meter launch sits in front of its ev1_ record)
     if (e == hipSuccess) e = launchMeterZero(a, stream_);
     // (a slot reused gets fresh meters, all of them: the listed columns of the match rows of a target, inside the same frame)
     if (e == hipSuccess && dMatch_) {
         a.rows = dMatch_;
         e = launchMatchZero(a, stream_);
     }
-    if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(stream_);   // (nothing may still read the staging)
-        return hipFail(e, "meter_reset_list: queueing the zeroing");
-    }
-    instLaunched_ = true;
+    if (const int failed = closeInstCall(e, "meter_reset_list: queueing the zeroing")) return failed;
     ++meterListResets_;
     return 0;
 }

@@ -2,14 +2,9 @@
 // device, and the gather back (include/fx8010_amd.h "Register sets by list", fx_batch.hpp "Register calls by list", kernels:
 // fx_registers.hip).
 //
-// A set rides the frame of the per-instance state calls (fx_batch_instances.cpp) without their lowering: it waits on the HOST for
-// the previous instance call or list set (its lists are in the staging this one is about to fill - between two sets of a real-time
-// host lies a block, so that wait is over before it starts), copies the list, the caller's columns and the rows into pinned
-// staging (the caller's arrays are free on return) and from there to the device, makes the handle's stream wait for every block
-// queued so far on whatever stream (ev1_, evBus_), launches fx_reg_scatter there and records evInst_ behind it.  Everything that
-// is ordered behind a copy of instances is then ordered behind the set: a block on another stream (launchBlock), the host in
-// waitLastLaunch - every register call, every state access - and in sync.  The bookkeeping of setRegisterAt follows, per register,
-// once the scatter is queued: a refusal or a failed launch has changed nothing the host knows.
+// A set runs inside the by-list frame (fx_batch.hpp "THE BY-LIST FRAME", fx_batch_list.cpp) without the lowering of the instance
+// calls: the list, the caller's columns and the rows are staged, fx_reg_scatter is the kernel in front of evInst_.  The bookkeeping
+// of setRegisterAt follows, per register, once the scatter is queued: a refusal or a failed launch has changed nothing the host knows.
 //
 // The program is NOT lowered here: the state rows exist from the load on and hold every register's value for every instance
 // (setRegister's invariant), also for a register the code in force has folded in.  The first per-instance write to such a register
@@ -33,63 +28,35 @@ int Batch::resolveRegisters(const char* const* keys, int nKeys, std::vector<int>
     return 0;
 }
 
-int Batch::checkRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const void* values, bool unique, std::string* why) {
-    const std::string name(unique ? "set_registers_list" : "get_registers_list");
+int Batch::checkRegisterList(const char* what, const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t n, const void* values, bool unique, std::string* why) {
+    const std::string name(what);
     if (count < 0) { *why = name + ": count < 0"; return FX_E_ARG; }
     if (count == 0 || regs.empty()) return 0;
     if (!list || !values) { *why = name + ": a null list or null values"; return FX_E_ARG; }
     if ((int64_t)regs.size() * count >= ((int64_t)1 << 31) || count >= ((int64_t)1 << 31)) { *why = name + ": n_keys * count must stay below 2^31"; return FX_E_ARG; }
-    for (int64_t i = 0; i < count; ++i)
-        if (list[i] < 0 || list[i] >= n) { *why = name + ": entry " + std::to_string(i) + " of the list is outside 0.." + std::to_string(n - 1); return FX_E_ARG; }
+    // (the order of the refusals: an entry outside the batch, a register twice, an instance twice)
+    const ListFault f = checkList(list, count, n, unique);
+    if (f.kind == ListFault::kOutside) { *why = listOutside(name, f, n); return FX_E_ARG; }
     if (!unique) return 0;
     std::vector<int> sortedRegs(regs);
     std::sort(sortedRegs.begin(), sortedRegs.end());
     if (std::adjacent_find(sortedRegs.begin(), sortedRegs.end()) != sortedRegs.end()) { *why = name + ": two keys name the same register"; return FX_E_ARG; }
-    // repeats: a bitmap over the instances where that is the cheaper one to clear, else a sorted copy (checkGainList)
-    int64_t twice = -1;
-    if ((n + 63) / 64 <= 16 * count) {
-        std::vector<uint64_t> seen((size_t)((n + 63) / 64), 0);
-        for (int64_t i = 0; i < count && twice < 0; ++i) {
-            uint64_t& word = seen[(size_t)(list[i] >> 6)];
-            const uint64_t bit = (uint64_t)1 << (list[i] & 63);
-            if (word & bit) twice = list[i];
-            word |= bit;
-        }
-    } else {
-        std::vector<int64_t> sorted(list, list + count);
-        std::sort(sorted.begin(), sorted.end());
-        const auto at = std::adjacent_find(sorted.begin(), sorted.end());
-        if (at != sorted.end()) twice = *at;
-    }
-    if (twice >= 0) { *why = name + ": instance " + std::to_string(twice) + " is listed more than once"; return FX_E_ARG; }
+    if (f) { *why = name + ": instance " + std::to_string(list[f.entry]) + " is listed more than once"; return FX_E_ARG; }
     return 0;
 }
 
 int Batch::reserveRegisterList(int nKeys, int64_t count) {
     (void)hipSetDevice(device_);
     if (nKeys < 1 || count < 1) return 0;
-    if (!evInst_) {
-        const hipError_t e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming);
-        if (e != hipSuccess) { evInst_ = nullptr; return hipFail(hipErrorOutOfMemory, "register list event"); }
-    }
-    const size_t words = regListWords(nKeys, count);
-    if (words <= regList_.cap && words <= hRegList_.cap) return 0;
-    // (the previous list set may still be reading the blocks that go)
-    if (instLaunched_ && hipEventSynchronize(evInst_) == hipSuccess) instLaunched_ = false;
-    int rc = growBlock(regList_, words, false, "hipMalloc register list staging");
-    if (rc == 0) rc = growBlock(hRegList_, words, true, "pinned staging of the register list");
-    return rc;
+    static const char* const kTexts[3] = {"register list event", "hipMalloc register list staging", "pinned staging of the register list"};
+    return reserveListStage(regList_, hRegList_, regListWords(nKeys, count), evInst_, instLaunched_, true, kTexts);
 }
 
 // the list and the rows into the pinned staging, the device pointers of all three parts into *a (the values are the caller's to fill)
 int Batch::stageRegisterList(const std::vector<int>& regs, const int64_t* list, int64_t count, RegListArgs* a) {
     const size_t k = (size_t)count, nk = regs.size(), words = regListWords((int)nk, count);
     if (words > regList_.cap || words > hRegList_.cap || !evInst_) return fail(FX_E_ARG, "registers by list: no staging reserved (reserveRegisterList)");
-    if (instLaunched_) {
-        const hipError_t e = hipEventSynchronize(evInst_);
-        if (e != hipSuccess) return hipFail(e, "registers by list: waiting for the previous call");
-        instLaunched_ = false;
-    }
+    if (const int rc = waitPreviousInstCall("registers by list: waiting for the previous call")) return rc;
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == 4, "register list staging");
     std::memcpy(hRegList_.p, list, k * 8);
     std::memcpy(hRegList_.p + k * 2 + nk * k, regs.data(), nk * 4);   // (a register's row is its number: StateLayout)
@@ -115,29 +82,13 @@ int Batch::setRegistersList(const std::vector<int>& regs, const int64_t* list, c
     if (rc != 0) return rc;
     const size_t k = (size_t)count, nk = regs.size(), words = regListWords((int)nk, count);
     uint32_t* stage = hRegList_.p + k * 2;
-    for (size_t j = 0; j < nk; ++j)
-        for (size_t i = 0; i < k; ++i) std::memcpy(&stage[j * k + i], values + j * (size_t)total + (size_t)(pos ? pos[i] : (int64_t)i), 4);
+    for (size_t j = 0; j < nk; ++j) copyColumn(&stage[j * k], values + j * (size_t)total, pos, k, 4, false);
     hipError_t e = hipMemcpyAsync(regList_.p, hRegList_.p, words * 4, hipMemcpyHostToDevice, stream_);
-    // behind every block queued so far, on whichever stream it was queued
-    if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
-    if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+    if (e == hipSuccess) e = orderBehindQueuedBlocks();
     if (e == hipSuccess) e = launchRegScatter(a, stream_);
-    if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(stream_);   // (nothing may still read the staging)
-        return hipFail(e, "registers by list: queueing the scatter");
-    }
-    instLaunched_ = true;
+    if (const int failed = closeInstCall(e, "registers by list: queueing the scatter")) return failed;
     ++regListSets_;
-    // what setRegisterAt does for each of them (the rows are valid for every other instance: setRegister's invariant)
-    for (const int r : regs) {
-        if (coldControl(r)) coldSetChanged();
-        if (!forcedLane_[(size_t)r] && !intrinsicLane(r) && readByProgram(r)) {
-            forcedLane_[(size_t)r] = 1;
-            lowDirty_ = true;
-        }
-        laneWritten_[(size_t)r] = 1;
-    }
+    noteRegistersWritten(regs);   // once the scatter is queued: a refusal or a failed launch has changed nothing the host knows
     return 0;
 }
 
@@ -174,8 +125,7 @@ int Batch::getRegistersList(const std::vector<int>& regs, const int64_t* list, c
     if (e == hipSuccess) e = se;
     if (e != hipSuccess) return hipFail(e, "registers by list: the gather");
     const uint32_t* stage = hRegList_.p + k * 2;
-    for (size_t j = 0; j < nk; ++j)
-        for (size_t i = 0; i < k; ++i) std::memcpy(values + keyOf[j] * (size_t)total + (size_t)(pos ? pos[i] : (int64_t)i), &stage[j * k + i], 4);
+    for (size_t j = 0; j < nk; ++j) copyColumn(values + keyOf[j] * (size_t)total, &stage[j * k], pos, k, 4, true);
     return 0;
 }
 

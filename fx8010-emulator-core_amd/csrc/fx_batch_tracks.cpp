@@ -37,12 +37,7 @@ int Batch::checkTrackList(const std::vector<int>& regs, const int64_t* list, int
         return FX_E_ARG;
     }
     // the list and the keys: what a register list set refuses
-    if (checkRegisterList(regs, list, count, n, values, true, why) != 0) {
-        const std::string theirs("set_registers_list");
-        if (why->compare(0, theirs.size(), theirs) == 0) why->replace(0, theirs.size(), name);
-        return FX_E_ARG;
-    }
-    return 0;
+    return checkRegisterList("set_register_tracks_list", regs, list, count, n, values, true, why);
 }
 
 int Batch::checkTrackListArm(const std::vector<int>& regs, const int64_t* list, int64_t count, int64_t firstGlobal, std::string* why) {
@@ -168,8 +163,7 @@ int Batch::armTrackList(const std::vector<int>& regs, const int64_t* list, const
         static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == 4, "track list staging");
         std::memcpy(stage, list, k * 8);
         uint32_t* v = stage + k * 2;
-        for (size_t row = 0; row < (size_t)nSteps * nk; ++row)
-            for (size_t i = 0; i < k; ++i) std::memcpy(&v[row * k + i], values + row * (size_t)total + (size_t)(pos ? pos[i] : (int64_t)i), 4);
+        for (size_t row = 0; row < (size_t)nSteps * nk; ++row) copyColumn(&v[row * k], values + row * (size_t)total, pos, k, 4, false);
         std::memcpy(v + (size_t)nSteps * nk * k, regs.data(), nk * 4);   // (a register's row is its number: StateLayout)
         if (part > k * 2 + (size_t)nSteps * nk * k + nk) stage[part - 1] = 0;
         hipError_t e = hipMemcpyAsync(trackList_.p + sch.at, stage, part * 4, hipMemcpyHostToDevice, stream_);
@@ -249,8 +243,8 @@ int Batch::expandTrackLists(const ListExpansion& x, hipStream_t s) {
     return 0;
 }
 
-// the steps due at `sample`, in arming order, through the scatter of the register list sets and in their place in the order of
-// things (setRegistersList): behind every block queued so far, in front of evInst_
+// the steps due at `sample`, in arming order, through the scatter of the register list sets and in their place in the by-list frame
+// (setRegistersList; nothing to stage, so no host wait): behind every block queued so far, in front of evInst_
 int Batch::applyTrackListsAt(std::vector<ListSchedule>& schedules, int sample) {
     for (const ListSchedule& sch : schedules) {
         if (sch.list.empty() || sample < sch.first || (sample - sch.first) % sch.period != 0 || (sample - sch.first) / sch.period >= sch.steps) continue;
@@ -265,25 +259,10 @@ int Batch::applyTrackListsAt(std::vector<ListSchedule>& schedules, int sample) {
         a.nPad = nPad_;
         a.nKeys = (int)nk;
         a.stateRows = stateRows_;
-        hipError_t e = hipSuccess;
-        if (launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
-        if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+        hipError_t e = orderBehindQueuedBlocks();
         if (e == hipSuccess) e = launchRegScatter(a, stream_);
-        if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(stream_);
-            return hipFail(e, "register tracks by list: queueing a step");
-        }
-        instLaunched_ = true;
-        // what setRegistersList does for each of them
-        for (const int r : sch.regs) {
-            if (coldControl(r)) coldSetChanged();
-            if (!forcedLane_[(size_t)r] && !intrinsicLane(r) && readByProgram(r)) {
-                forcedLane_[(size_t)r] = 1;
-                lowDirty_ = true;
-            }
-            laneWritten_[(size_t)r] = 1;
-        }
+        if (const int failed = closeInstCall(e, "register tracks by list: queueing a step")) return failed;
+        noteRegistersWritten(sch.regs);
     }
     return 0;
 }

@@ -2,12 +2,8 @@
 // scattered on the device, and the gather back (include/fx8010_amd.h "Delay-line windows by list", fx_batch.hpp "Delay-line
 // windows by list", kernels: fx_tram.hip).
 //
-// A set rides the frame of the register list set (fx_batch_registers.cpp): it waits on the HOST for the previous instance call or
-// list set (its words are in the staging this one is about to fill - between two sets of a real-time host lies a block, so that
-// wait is over before it starts), copies the list and the caller's windows into pinned staging (the caller's arrays are free on
-// return) and from there to the device, makes the handle's stream wait for every block queued so far on whatever stream (ev1_,
-// evBus_), launches fx_tram_scatter there and records evInst_ behind it.  Everything that is ordered behind a copy of instances
-// is then ordered behind the set: a block on another stream (launchBlock), the host in waitLastLaunch and in sync.
+// A set runs inside the by-list frame (fx_batch.hpp "THE BY-LIST FRAME", fx_batch_list.cpp), once per piece: the list and the
+// caller's windows are staged, fx_tram_scatter is the kernel in front of evInst_.
 //
 // Unlike a register set it lowers the program first (reserveTramList): the delay memory and its size come from the lowering.
 // Where a ring stands is NOT looked up here: in logical mode the kernel reads each instance's position word itself, behind the
@@ -42,27 +38,9 @@ int Batch::checkTramList(bool set, int which, const int64_t* list, int64_t count
     if (nWords == 0 && !list) return 0;
     if (!list) { *why = name + ": a null list"; return FX_E_ARG; }
     if (nWords > 0 && !values) { *why = name + ": null values"; return FX_E_ARG; }
-    for (int64_t i = 0; i < count; ++i)
-        if (list[i] < 0 || list[i] >= n) { *why = name + ": entry " + std::to_string(i) + " of the list is outside 0.." + std::to_string(n - 1); return FX_E_ARG; }
-    if (!set) return 0;
-    // repeats: a bitmap over the instances where that is the cheaper one to clear, else a sorted copy (checkRegisterList)
-    int64_t twice = -1;
-    if ((n + 63) / 64 <= 16 * count) {
-        std::vector<uint64_t> seen((size_t)((n + 63) / 64), 0);
-        for (int64_t i = 0; i < count && twice < 0; ++i) {
-            uint64_t& word = seen[(size_t)(list[i] >> 6)];
-            const uint64_t bit = (uint64_t)1 << (list[i] & 63);
-            if (word & bit) twice = i;
-            word |= bit;
-        }
-    } else {
-        std::vector<std::pair<int64_t, int64_t>> sorted((size_t)count);
-        for (int64_t i = 0; i < count; ++i) sorted[(size_t)i] = {list[i], i};
-        std::sort(sorted.begin(), sorted.end());
-        for (size_t i = 1; i < sorted.size() && twice < 0; ++i)
-            if (sorted[i].first == sorted[i - 1].first) twice = sorted[i].second;
-    }
-    if (twice >= 0) { *why = name + ": entry " + std::to_string(twice) + " of the list names instance " + std::to_string(list[twice]) + " a second time"; return FX_E_ARG; }
+    const ListFault f = checkList(list, count, n, set);
+    if (f.kind == ListFault::kOutside) { *why = listOutside(name, f, n); return FX_E_ARG; }
+    if (f) { *why = name + ": entry " + std::to_string(f.entry) + " of the list names instance " + std::to_string(list[f.entry]) + " a second time"; return FX_E_ARG; }
     return 0;
 }
 
@@ -83,18 +61,10 @@ int Batch::reserveTramList(bool set, int which, int64_t count, int first, int nW
         return fail(FX_E_ARG, name + ": first + n_words passes the " + std::to_string(l.slots) + " allocated slots of " + line);
     }
     if (count < 1 || nWords < 1) return 0;
-    if (!evInst_) {
-        const hipError_t e = hipEventCreateWithFlags(&evInst_, hipEventDisableTiming);
-        if (e != hipSuccess) { evInst_ = nullptr; return hipFail(hipErrorOutOfMemory, "tram list event"); }
-    }
     const int64_t entries = std::min(count, tramEntriesPerPiece(nWords));
     const size_t words = (size_t)entries * 2 + ((flags & FXB_TRAM_BROADCAST) ? (size_t)nWords : (size_t)entries * (size_t)nWords);
-    if (words <= tramStage_.cap && words <= hTramStage_.cap) return 0;
-    // (the previous list set may still be reading the blocks that go)
-    if (instLaunched_ && hipEventSynchronize(evInst_) == hipSuccess) instLaunched_ = false;
-    rc = growBlock(tramStage_, words, false, "hipMalloc tram list staging");
-    if (rc == 0) rc = growBlock(hTramStage_, words, true, "pinned staging of the tram list");
-    return rc;
+    static const char* const kTexts[3] = {"tram list event", "hipMalloc tram list staging", "pinned staging of the tram list"};
+    return reserveListStage(tramStage_, hTramStage_, words, evInst_, instLaunched_, true, kTexts);
 }
 
 int Batch::tramList(int which, const int64_t* list, const int64_t* pos, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags) {
@@ -126,11 +96,7 @@ int Batch::tramList(int which, const int64_t* list, const int64_t* pos, int64_t 
     if (!set) waitLastLaunch();
     for (int64_t off = 0; off < count; off += per) {
         const size_t k = (size_t)std::min(per, count - off), valueWords = broadcast ? nw : k * nw;
-        if (instLaunched_) {
-            const hipError_t e = hipEventSynchronize(evInst_);
-            if (e != hipSuccess) return hipFail(e, "tram list: waiting for the previous call");
-            instLaunched_ = false;
-        }
+        if (const int rc = waitPreviousInstCall("tram list: waiting for the previous call")) return rc;
         std::memcpy(hTramStage_.p, list + off, k * 8);
         uint32_t* stage = hTramStage_.p + k * 2;
         a.list = reinterpret_cast<const long long*>(tramStage_.p);   // (hipMalloc aligns the block: the 64-bit part comes first)
@@ -138,20 +104,13 @@ int Batch::tramList(int which, const int64_t* list, const int64_t* pos, int64_t 
         a.count = (long long)k;
         hipError_t e = hipSuccess;
         if (set) {
+            // (a window is one element of the column: the windows of this piece begin at entry `off`)
             if (broadcast) std::memcpy(stage, in, nw * 4);
-            else if (!pos) std::memcpy(stage, in + (size_t)off * nw, k * nw * 4);
-            else for (size_t i = 0; i < k; ++i) std::memcpy(stage + i * nw, in + (size_t)pos[(size_t)off + i] * nw, nw * 4);
+            else copyColumn(stage, pos ? in : in + (size_t)off * nw, pos ? pos + off : nullptr, k, nw * 4, false);
             e = hipMemcpyAsync(tramStage_.p, hTramStage_.p, (k * 2 + valueWords) * 4, hipMemcpyHostToDevice, stream_);
-            // behind every block queued so far, on whichever stream it was queued
-            if (e == hipSuccess && launched_) e = hipStreamWaitEvent(stream_, ev1_, 0);
-            if (e == hipSuccess && busLaunched_) e = hipStreamWaitEvent(stream_, evBus_, 0);
+            if (e == hipSuccess) e = orderBehindQueuedBlocks();
             if (e == hipSuccess) e = launchTramScatter(a, stream_);
-            if (e == hipSuccess) e = hipEventRecord(evInst_, stream_);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(stream_);   // (nothing may still read the staging)
-                return hipFail(e, "tram list: queueing the scatter");
-            }
-            instLaunched_ = true;
+            if (const int failed = closeInstCall(e, "tram list: queueing the scatter")) return failed;
             ++tramListSets_;
         } else {
             e = hipMemcpyAsync(tramStage_.p, hTramStage_.p, k * 8, hipMemcpyHostToDevice, stream_);
@@ -163,8 +122,7 @@ int Batch::tramList(int which, const int64_t* list, const int64_t* pos, int64_t 
             const hipError_t se = hipStreamSynchronize(stream_);
             if (e == hipSuccess) e = se;
             if (e != hipSuccess) return hipFail(e, "tram list: the gather");
-            if (!pos) std::memcpy(out + (size_t)off * nw, stage, k * nw * 4);
-            else for (size_t i = 0; i < k; ++i) std::memcpy(out + (size_t)pos[(size_t)off + i] * nw, stage + i * nw, nw * 4);
+            copyColumn(pos ? out : out + (size_t)off * nw, stage, pos ? pos + off : nullptr, k, nw * 4, true);
         }
     }
     return 0;

@@ -432,14 +432,10 @@ int Sharded::meterReadList(const int64_t* list, int64_t count, double* energy, f
     if (Batch::checkMeterList("meter_read_list", list, count, n_, reset, &lastError_) != 0) return FX_E_ARG;
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
     if (count == 0) return 0;
-    const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    const ShardLists l(*this, list, count);
     // every shard is asked for its staging first: with reset, no shard zeroes a word unless all of them can answer
-    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(countOf(k), true); })) return rc;
-    return fan([&](int k, Batch& b) { return b.meterReadList(listOf(k), posOf(k), countOf(k), count, energy, peak, fullScale, nonfinite, reset); });
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(l.count(k), true); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterReadList(l.list(k), l.pos(k), l.count(k), count, energy, peak, fullScale, nonfinite, reset); });
 }
 
 int Sharded::meterResetList(const int64_t* list, int64_t count) {
@@ -448,12 +444,9 @@ int Sharded::meterResetList(const int64_t* list, int64_t count) {
     if (Batch::checkMeterList("meter_reset_list", list, count, n_, false, &lastError_) != 0) return FX_E_ARG;
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
     if (count == 0) return 0;
-    const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
-    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(countOf(k), false); })) return rc;
-    return fan([&](int k, Batch& b) { return b.meterResetList(listOf(k), countOf(k)); });
+    const ShardLists l(*this, list, count);
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(l.count(k), false); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterResetList(l.list(k), l.count(k)); });
 }
 
 int Sharded::meterSetTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags) {
@@ -565,12 +558,9 @@ int Sharded::busSetTaps(const int64_t* list, int64_t count) {
     if (count == 0) return fan([](int, Batch& b) { return b.busSetTaps(nullptr, nullptr, 0, 0); });
     if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.busSetTaps(list, nullptr, count, count); });
     // every shard reserves the block of its entries first; only when all of them could does any shard's list change
-    const std::vector<ListPart> parts = splitList(list, count);
-    if (const int rc = reserveOnAll([&](int k, Batch& b) { return b.busReserveTaps((int64_t)parts[(size_t)k].list.size()); }, [](Batch& b) { b.busReleaseTaps(); })) return rc;
-    return fan([&](int k, Batch& b) {
-        const ListPart& part = parts[(size_t)k];
-        return b.busSetTaps(part.list.data(), part.pos.data(), (int64_t)part.list.size(), count);
-    });
+    const ShardLists l(*this, list, count);
+    if (const int rc = reserveOnAll([&](int k, Batch& b) { return b.busReserveTaps(l.count(k)); }, [](Batch& b) { b.busReleaseTaps(); })) return rc;
+    return fan([&](int k, Batch& b) { return b.busSetTaps(l.list(k), l.pos(k), l.count(k), count); });
 }
 int64_t Sharded::busGetTaps(int64_t* list, int64_t cap) {
     Serial serial(api_);
@@ -769,11 +759,9 @@ int Sharded::busSetGainList(GainListKind kind, const int64_t* list, int64_t coun
         }
     // every shard reserves its staging first; only when all of them could does any shard's state change (staging that has grown
     // stays: it is no state)
-    if (const int rc = fan([&](int k, Batch& b) { return b.busReserveGainList((int64_t)parts[(size_t)k].list.size()); })) return rc;
-    return fan([&](int k, Batch& b) {
-        const ListPart& part = parts[(size_t)k];
-        return set(b, part.list.data(), part.pos.data(), (int64_t)part.list.size());
-    });
+    const ShardLists l(std::move(parts));
+    if (const int rc = fan([&](int k, Batch& b) { return b.busReserveGainList(l.count(k)); })) return rc;
+    return fan([&](int k, Batch& b) { return set(b, l.list(k), l.pos(k), l.count(k)); });
 }
 
 int64_t Sharded::instructionCounter() {
@@ -927,9 +915,8 @@ int Sharded::resetInstances(const int64_t* list, int64_t count) {
     const char* why = nullptr;
     if (count > 0 && !list) { lastError_ = "instances: a null list"; return FX_E_ARG; }
     if (Batch::checkInstanceLists(nullptr, list, count, n_, &why) != 0) { lastError_ = why; return FX_E_ARG; }
-    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.resetInstances(list, count); });
-    const std::vector<ListPart> parts = splitList(list, count);
-    return fan([&](int k, Batch& b) { return b.resetInstances(parts[(size_t)k].list.data(), (int64_t)parts[(size_t)k].list.size()); });
+    const ShardLists l(*this, list, count);
+    return fan([&](int k, Batch& b) { return b.resetInstances(l.list(k), l.count(k)); });
 }
 
 int Sharded::saveInstances(const int64_t* list, int64_t count, void* buf, int64_t cap) {
@@ -945,9 +932,8 @@ int Sharded::saveInstances(const int64_t* list, int64_t count, void* buf, int64_
     if (!buf || cap < (int64_t)sizeof(hdr) + count * Batch::instanceWords(hdr) * 4) { lastError_ = "save_instances: buffer smaller than fxb_instance_image_size()"; return FX_E_ARG; }
     std::memcpy(buf, &hdr, sizeof(hdr));
     uint32_t* records = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + sizeof(hdr));
-    if (shards_.size() == 1) return runOn(0, [&](Batch& b) { return b.gatherRecords(list, nullptr, count, records); });
-    const std::vector<ListPart> parts = splitList(list, count);
-    return fan([&](int k, Batch& b) { return b.gatherRecords(parts[(size_t)k].list.data(), parts[(size_t)k].pos.data(), (int64_t)parts[(size_t)k].list.size(), records); });
+    const ShardLists l(*this, list, count);
+    return fan([&](int k, Batch& b) { return b.gatherRecords(l.list(k), l.pos(k), l.count(k), records); });
 }
 
 int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated) {
@@ -963,11 +949,7 @@ int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, in
     int rc = runOn(0, [&](Batch& b) { return b.checkInstanceImage(hdr, count, bytes); });
     if (rc != 0 || count == 0) return rc;
     const uint32_t* records = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf) + sizeof(hdr));
-    const bool one = shards_.size() == 1;
-    std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    const ShardLists l(*this, list, count);
     // the delay-line rule on every shard before any shard changes a word
     if (rotated) {
         bool applies = false;
@@ -976,11 +958,11 @@ int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, in
     }
     std::vector<std::vector<int32_t>> rot(shards_.size());   // rotated: per shard, [its entries][2]
     rc = fan([&](int k, Batch& b) {
-        return rotated ? b.recordRotations(listOf(k), posOf(k), countOf(k), records, &rot[(size_t)k]) : b.checkRecordCursors(listOf(k), posOf(k), countOf(k), records);
+        return rotated ? b.recordRotations(l.list(k), l.pos(k), l.count(k), records, &rot[(size_t)k]) : b.checkRecordCursors(l.list(k), l.pos(k), l.count(k), records);
     });
     if (rc != 0) return rc;
     return fan([&](int k, Batch& b) {
-        const int r = rotated ? b.scatterRecordsRotated(listOf(k), posOf(k), countOf(k), records, rot[(size_t)k].data()) : b.scatterRecords(listOf(k), posOf(k), countOf(k), records);
+        const int r = rotated ? b.scatterRecordsRotated(l.list(k), l.pos(k), l.count(k), records, rot[(size_t)k].data()) : b.scatterRecords(l.list(k), l.pos(k), l.count(k), records);
         if (r == 0) b.promoteLoaded(records, count);
         return r;
     });
@@ -998,17 +980,13 @@ int Sharded::registersList(bool set, const char* const* keys, int nKeys, const i
     if (const int rc = front().resolveRegisters(keys, nKeys, &regs)) { lastError_ = front().lastError(); return rc; }
     if (count == 0 || nKeys == 0) return 0;
     const void* values = set ? static_cast<const void*>(in) : static_cast<const void*>(out);
-    if (Batch::checkRegisterList(regs, list, count, n_, values, set, &lastError_) != 0) return FX_E_ARG;
-    const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
-    if (!set) return fan([&](int k, Batch& b) { return b.getRegistersList(regs, listOf(k), posOf(k), countOf(k), count, out); });
+    if (Batch::checkRegisterList(name, regs, list, count, n_, values, set, &lastError_) != 0) return FX_E_ARG;
+    const ShardLists l(*this, list, count);
+    if (!set) return fan([&](int k, Batch& b) { return b.getRegistersList(regs, l.list(k), l.pos(k), l.count(k), count, out); });
     // every shard reserves its staging first; only when all of them could is anything queued or noted anywhere (staging that has
     // grown stays: it is no state)
-    if (const int rc = fan([&](int k, Batch& b) { return b.reserveRegisterList(nKeys, countOf(k)); })) return rc;
-    return fan([&](int k, Batch& b) { return b.setRegistersList(regs, listOf(k), posOf(k), countOf(k), count, in); });
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveRegisterList(nKeys, l.count(k)); })) return rc;
+    return fan([&](int k, Batch& b) { return b.setRegistersList(regs, l.list(k), l.pos(k), l.count(k), count, in); });
 }
 
 int Sharded::setRegisterTracksList(const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* values, int nSteps, int first, int period) {
@@ -1024,22 +1002,18 @@ int Sharded::setRegisterTracksList(const char* const* keys, int nKeys, const int
     // everything that reads nothing but the arguments, for the whole handle and with the caller's indices
     if (Batch::checkTrackList(regs, list, count, n_, values, nSteps, first, period, &lastError_) != 0) return FX_E_ARG;
     if (count == 0 || nKeys == 0) return 0;
-    const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = one ? std::vector<ListPart>(1) : splitList(list, count);
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto posOf = [&](int k) { return one ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    const ShardLists l(*this, list, count);
     // every shard is asked first - what is armed on it, the program, then its staging and its track buffer; only when all of
     // them could is anything armed anywhere (staging that has grown stays: it is no state)
     int rc = fan([&](int k, Batch& b) {
         std::string why;
-        const int r = b.checkTrackListArm(regs, listOf(k), countOf(k), shards_[(size_t)k]->first, &why);
+        const int r = b.checkTrackListArm(regs, l.list(k), l.count(k), shards_[(size_t)k]->first, &why);
         if (r != 0) b.noteError(why);
         return r;
     });
-    if (rc == 0) rc = fan([&](int k, Batch& b) { return b.reserveTrackList(regs, countOf(k), nSteps); });
+    if (rc == 0) rc = fan([&](int k, Batch& b) { return b.reserveTrackList(regs, l.count(k), nSteps); });
     if (rc != 0) return rc;
-    return fan([&](int k, Batch& b) { return b.armTrackList(regs, listOf(k), posOf(k), countOf(k), count, values, nSteps, first, period); });
+    return fan([&](int k, Batch& b) { return b.armTrackList(regs, l.list(k), l.pos(k), l.count(k), count, values, nSteps, first, period); });
 }
 
 int Sharded::clearRegisterTracksList() {
@@ -1055,16 +1029,13 @@ int Sharded::tramList(int which, const int64_t* list, int64_t count, int first, 
     // everything that reads nothing but the arguments, for the whole handle and with the caller's indices
     if (Batch::checkTramList(set, which, list, count, n_, first, nWords, values, flags, &lastError_) != 0) return FX_E_ARG;
     if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
-    const bool one = shards_.size() == 1;
-    const std::vector<ListPart> parts = (one || count == 0 || nWords == 0) ? std::vector<ListPart>(shards_.size()) : splitList(list, count);   // (n_words == 0: the list may be null, and no entry moves)
-    auto listOf = [&](int k) { return one ? list : parts[(size_t)k].list.data(); };
-    auto posOf = [&](int k) { return (one || (flags & FXB_TRAM_BROADCAST)) ? (const int64_t*)nullptr : parts[(size_t)k].pos.data(); };
-    auto countOf = [&](int k) { return one ? count : (int64_t)parts[(size_t)k].list.size(); };
+    ShardLists l(*this, list, count, count != 0 && nWords != 0);   // (n_words == 0: the list may be null, and no entry moves)
+    l.samePos((flags & FXB_TRAM_BROADCAST) != 0);
     // every shard is asked first - the window against its line, its staging; only when all of them could is anything queued
     // anywhere (staging that has grown stays: it is no state)
-    if (const int rc = fan([&](int k, Batch& b) { return b.reserveTramList(set, which, countOf(k), first, nWords, flags); })) return rc;
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveTramList(set, which, l.count(k), first, nWords, flags); })) return rc;
     if (count == 0 || nWords == 0) return 0;
-    return fan([&](int k, Batch& b) { return b.tramList(which, listOf(k), posOf(k), countOf(k), first, nWords, set ? in : nullptr, set ? nullptr : out, flags); });
+    return fan([&](int k, Batch& b) { return b.tramList(which, l.list(k), l.pos(k), l.count(k), first, nWords, set ? in : nullptr, set ? nullptr : out, flags); });
 }
 
 int Sharded::getTramAt(int which, int64_t inst, float* out, int nSlots) {

@@ -210,6 +210,26 @@ private:
     // a global list by shard: per shard the local instance numbers and, for each, its index in the caller's list
     struct ListPart { std::vector<int64_t> list, pos; };
     std::vector<ListPart> splitList(const int64_t* list, int64_t count) const;
+    // The list of a by-list call as the shards see it: shard k gets count(k) local numbers list(k), entry i of them column pos(k)[i]
+    // of the caller's arrays (null: column i).  A handle of one shard passes the caller's list through - a global number is a local
+    // one - with a null pos; several shards hold splitList's parts.  split == false hands no entry to any shard: a call that
+    // moves nothing and still asks every shard (tramList).
+    class ShardLists {
+    public:
+        ShardLists(const Sharded& s, const int64_t* list, int64_t count, bool split = true) : whole_(list), count_(count), one_(s.shards_.size() == 1) {
+            if (!one_) parts_ = split ? s.splitList(list, count) : std::vector<ListPart>(s.shards_.size());
+        }
+        explicit ShardLists(std::vector<ListPart>&& parts) : parts_(std::move(parts)) {}   // parts the caller has filled, one per shard
+        void samePos(bool on) { samePos_ = on; }   // every entry reads the one column there is (a broadcast): pos(k) is null
+        const int64_t* list(int k) const { return one_ ? whole_ : parts_[(size_t)k].list.data(); }
+        const int64_t* pos(int k) const { return (one_ || samePos_) ? nullptr : parts_[(size_t)k].pos.data(); }
+        int64_t count(int k) const { return one_ ? count_ : (int64_t)parts_[(size_t)k].list.size(); }
+    private:
+        const int64_t* whole_ = nullptr;
+        int64_t count_ = 0;
+        bool one_ = false, samePos_ = false;
+        std::vector<ListPart> parts_;
+    };
     static constexpr size_t kStageBytes = (size_t)64 << 20;
     uint32_t* hStage_ = nullptr;   // pinned (portable) staging of cross-shard copies, allocated on first use and kept
     size_t stageWords_ = 0;

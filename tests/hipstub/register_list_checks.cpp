@@ -274,6 +274,47 @@ void memory(int devices) {
         }
 }
 
+// the one list check (Batch::checkList) at the edges of its two repeat paths: a list of two entries is looked up in a bitmap while
+// the batch has at most 2048 instances (32 words <= 16 * 2) and in a sorted copy from 2049 on; the pair sits on the bit and word
+// edges of the bitmap and, with three shards, in the last one.  Both paths name entry 1, and of several repeats the first in list
+// order; the entries outside the batch are the first and the last of the list.
+void repeatPaths(int devices) {
+    for (const int64_t n : {(int64_t)2048, (int64_t)2049}) {
+        Model m;
+        m.n = n;
+        m.h = create(n, 1, devices);
+        CHECK(m.h != nullptr);
+        if (!m.h) return;
+        CHECK(fxb_load_text(m.h, kMono) == 1);
+        CHECK(m.set({"vol"}, someOf(n, 65)) && fxb_sync(m.h) == 0);
+        const int64_t sets = fxb_info(m.h, FXB_INFO_REGISTER_LIST_SETS);
+        const long scatters = fxstub_reg_scatters();
+        Keys one({"vol"});
+        std::vector<float> values(4, 0.5f);
+        for (const int64_t a : {(int64_t)0, (int64_t)63, (int64_t)64, n - 64, n - 1}) {
+            const std::vector<int64_t> pair{a, a};
+            CHECK(fxb_set_registers_list(m.h, one.table, 1, pair.data(), 2, values.data()) == FX_E_ARG);
+            CHECK(std::strstr(fxb_last_error(m.h), ("instance " + std::to_string(a) + " is listed more than once").c_str()));
+            CHECK(fxb_get_registers_list(m.h, one.table, 1, pair.data(), 2, values.data()) == 0 && sameWord(values[0], values[1]));
+            CHECK(sameWord(values[0], m.rows["vol"][(size_t)a]));
+        }
+        // (four entries: a bitmap on both handles; the sorted copy of two entries is covered above)
+        const std::vector<int64_t> several{5, 9, 9, 5};
+        CHECK(fxb_set_registers_list(m.h, one.table, 1, several.data(), 4, values.data()) == FX_E_ARG);
+        CHECK(std::strstr(fxb_last_error(m.h), "instance 9 is listed more than once"));
+        for (const int64_t bad : {(int64_t)-1, n})
+            for (int at = 0; at <= 1; ++at) {
+                const std::vector<int64_t> list{at == 0 ? bad : 0, at == 1 ? bad : 1};
+                for (int get = 0; get <= 1; ++get) {
+                    const int rc = get ? fxb_get_registers_list(m.h, one.table, 1, list.data(), 2, values.data()) : fxb_set_registers_list(m.h, one.table, 1, list.data(), 2, values.data());
+                    CHECK(rc == FX_E_ARG && std::strstr(fxb_last_error(m.h), ("entry " + std::to_string(at) + " of the list is outside 0.." + std::to_string(n - 1)).c_str()));
+                }
+            }
+        CHECK(fxb_info(m.h, FXB_INFO_REGISTER_LIST_SETS) == sets && fxstub_reg_scatters() == scatters && m.sameRows());
+        fxb_destroy(m.h);
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -281,6 +322,7 @@ int main() {
     for (int devices = 1; devices <= 3; devices += 2) {
         indexing(devices);
         refusals(devices);
+        repeatPaths(devices);
         memory(devices);
         std::printf("  register lists, %d device(s): %d failed check(s) so far\n", devices, g_failures);
     }
