@@ -748,6 +748,11 @@ private:
     // was queued with) and in front of evGain_ (a later block on whatever stream waits for it).
     float* dGain_[2] = {nullptr, nullptr};
     RampPair gainRamp_;
+    // where a piece of a block is on the ramp of its gains, sends or feeds: the BusRampArgs base of the launch's arguments
+    // (fx_bus.hpp); r is the one division of the definition: S is the caller's block, never a piece
+    void setRamp(BusRampArgs& a, const RampPair& pair, int nSamples, int sample0) const {
+        a = BusRampArgs{prog_.numChannels, pair.pending ? 1 : 0, 1.0f / (float)nSamples, nSamples, sample0};
+    }
     bool gainsOn_ = false;
     float* hGain_ = nullptr;        // pinned staging: the caller's columns, and the 1.0f block of a ramp out of "off"
     hipEvent_t evGain_ = nullptr;   // behind the most recent copy into a gain block

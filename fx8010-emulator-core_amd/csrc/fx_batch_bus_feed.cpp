@@ -13,7 +13,6 @@
 #include "fx_batch.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 #include "../../include/fx8010_amd.h"
@@ -118,8 +117,6 @@ int Batch::busSetFeedGains(const float* gains, int ramp) {
     std::vector<float> next(ch * mine, 1.0f);
     if (gains)
         for (size_t c = 0; c < ch && mine > 0; ++c) std::memcpy(&next[c * mine], gains + c * all + (size_t)feed_.first, mine * 4);
-    for (float g : next)
-        if (!std::isfinite(g)) return fail(FX_E_ARG, "bus feeds: every gain must be finite");
     std::vector<float> image(ch * feedGainPitch_, 0.0f);
     for (size_t c = 0; c < ch && mine > 0; ++c) std::memcpy(&image[c * feedGainPitch_], &next[c * mine], mine * 4);
     const int rc = sync();   // (blocks queued with the old weights still read them)
@@ -188,17 +185,13 @@ hipError_t Batch::launchFeed(const FeedRoute& route, size_t first, long long row
     if (feed_.weighted) {
         a.target = reinterpret_cast<const float*>(words + feedOff_[2 + feedRamp_.target]);
         a.current = feedRamp_.pending ? reinterpret_cast<const float*>(words + feedOff_[2 + (feedRamp_.target ^ 1)]) : nullptr;
-        a.ramp = feedRamp_.pending ? 1 : 0;
     }
     a.rows = rows;
     a.n = n_;
     a.m = feed_.sources;
     a.entries = (long long)feed_.columns.size();
     a.gainPitch = (long long)feedGainPitch_;
-    a.channels = prog_.numChannels;
-    a.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
-    a.samples = nSamples;
-    a.sample0 = sample0;
+    setRamp(a, feed_.weighted ? feedRamp_ : RampPair{}, nSamples, sample0);   // (unweighted: never a ramp)
     return launchBusFeed(a, s);
 }
 

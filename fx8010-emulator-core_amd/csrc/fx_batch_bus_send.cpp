@@ -13,7 +13,6 @@
 #include "fx_batch.hpp"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 #include "../../include/fx8010_amd.h"
@@ -140,8 +139,6 @@ int Batch::busSetSendGains(const float* gains, int ramp) {
             const size_t lo = (size_t)send_.offsets[j], count = (size_t)send_.offsets[j + 1] - lo;
             if (count > 0) std::memcpy(&next[c * mine + lo], gains + c * all + (size_t)send_.first[j], count * 4);
         }
-    for (float g : next)
-        if (!std::isfinite(g)) return fail(FX_E_ARG, "bus sends: every gain must be finite");
     const int rc = sync();   // (blocks queued with the old weights still read them)
     if (rc != 0) return rc;
     const int target = sendRamp_.writeTarget(ramp);   // (the state machine of the bus gains)
@@ -207,11 +204,7 @@ hipError_t Batch::launchSends(const Route& route, size_t first, long long rows, 
     a.buses = (long long)send_.column.size();
     a.auxPitch = route.pitch;
     a.columns = route.columns ? 1 : 0;
-    a.channels = prog_.numChannels;
-    a.ramp = sendRamp_.pending ? 1 : 0;
-    a.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
-    a.samples = nSamples;
-    a.sample0 = sample0;
+    setRamp(a, sendRamp_, nSamples, sample0);
     return launchBusSend(a, s);
 }
 

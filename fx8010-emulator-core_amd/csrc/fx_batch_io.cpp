@@ -672,10 +672,7 @@ int Batch::runBus(const float* in, float* out, const float* narrowIn, int64_t na
         gain.target = dGain_[gainRamp_.target];
         gain.current = gainRamp_.pending ? dGain_[gainRamp_.target ^ 1] : nullptr;
         gain.gainPitch = n_;
-        gain.channels = prog_.numChannels;
-        gain.ramp = gainRamp_.pending ? 1 : 0;
-        gain.r = 1.0f / (float)nSamples;   // the one division of the definition: S is the caller's block, never a piece
-        gain.samples = nSamples;
+        setRamp(gain, gainRamp_, nSamples, 0);
     }
     beginBlock(nSamples, pieces);   // ONE block to the bookkeeping of control changes and to the lowering
     if ((rc = ensureLowered()) != 0) return rc;

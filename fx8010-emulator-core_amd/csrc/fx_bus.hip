@@ -7,6 +7,8 @@
 // PARTIAL access of K * 4 bytes per group for K < 64 (each followed by the whole shuffle tree: short groups are slow - K = 1 spends
 // 64 trees on 256 bytes; packing several short groups into one load with a segmented tree of the same bits is open).  Groups above
 // 64 are summed by one wavefront, four loads in flight: a group of a whole row (K = N) is one wavefront walking the row.
+// Shared: treeSum, walkSum; weightOf, termOf, rampAt, RampRows; badRamp, byRampShape.  The plain and the weighted mix stay two
+// written-out kernels: as entries over one inlined body they compile to more VGPRs (35 -> 38, 43 -> 47, 108 -> 120).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -74,6 +76,75 @@ __device__ __forceinline__ float treeSum(float p) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p)));
 }
 
+// The long walk of the published sum order: the whole wavefront sums the `count` words load(m), four 256-byte loads in flight,
+// then the tree (the plain mix above 64 members, the fold of the sends above one chunk).  Idx is the caller's index type.
+template <class Idx, class Load>
+__device__ __forceinline__ float walkSum(const Idx count, const unsigned lane, Load load) {
+    float p = 0.0f;
+    for (Idx m0 = 0; m0 < count; m0 += 256) {
+        float v[4];
+        bool have[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const Idx m = m0 + (Idx)(u * 64) + (Idx)lane;
+            have[u] = m < count;
+            v[u] = have[u] ? load(m) : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p = have[u] ? p + v[u] : p;
+    }
+    return treeSum(p);
+}
+
+// ---- the weights (fx_bus.hpp BusRampArgs), shared by the weighted mix, the sends and the feeds ---------------------------------
+// The weight: (b - a), * t, a + ... and w * y are four roundings (the file is built with -ffp-contract=off); the mute is a
+// select on w in front of the add, so a NaN or Inf of a muted member never reaches the sum.
+template <bool kRamp>
+__device__ __forceinline__ float weightOf(float a, float b, float t, bool atTarget) {
+    if (!kRamp) return b;
+    const float d = b - a;
+    const float m = d * t;
+    const float w = a + m;
+    return atTarget ? b : w;
+}
+
+__device__ __forceinline__ float termOf(float w, float y) {
+    const float prod = w * y;
+    return w == 0.0f ? 0.0f : prod;
+}
+
+// where a row of the piece is on the ramp: t of weightOf, and whether it is the last sample of the CALL (exactly b there)
+__device__ __forceinline__ void rampAt(const BusRampArgs& r, const long long row, float& t, bool& atTarget) {
+    const long long s = row / r.channels + r.sample0;   // the sample of the CALL this row belongs to
+    t = (float)(s + 1) * r.r;
+    atTarget = s == (long long)r.samples - 1;
+}
+
+// The ramp-row frame of the kernels that keep kRows = 8 rows in flight (sends, feeds): per row its place on the ramp and whether it
+// exists (kFull: all do, no predicate anywhere), and the gain rows the group reads.  Row groups begin at a multiple of eight rows,
+// so with kCh = 1 or 2 channels row u is channel u % kCh; kCh = 0 is every other channel count, one gain row per row: gainOf(u).
+template <int kRows, int kCh, bool kFull>
+struct RampRows {
+    static constexpr int kGains = kCh > 0 ? kCh : kRows;
+    float t[kRows];
+    bool atTarget[kRows], rowOk[kRows];
+    long long gainRow[kGains];
+    static constexpr int gainOf(int u) { return kCh > 0 ? u % kGains : u; }
+};
+template <int kRows, int kCh, bool kFull>
+__device__ __forceinline__ RampRows<kRows, kCh, kFull> rampRows(const BusRampArgs& r, const long long gainPitch, const long long rows, const long long row0) {
+    RampRows<kRows, kCh, kFull> f;
+#pragma unroll
+    for (int u = 0; u < kRows; ++u) {
+        rampAt(r, row0 + u, f.t[u], f.atTarget[u]);
+        f.rowOk[u] = kFull || row0 + u < rows;
+        if (kCh == 0) f.gainRow[u] = ((row0 + u) % r.channels) * gainPitch;
+    }
+#pragma unroll
+    for (int c = 0; kCh > 0 && c < decltype(f)::kGains; ++c) f.gainRow[c] = (long long)c * gainPitch;
+    return f;
+}
+
 // grid.x = blocks of 64 groups, grid.y strides over the rows: group g0 + k's sum ends in lane k, one 256-byte store per row
 __global__ __launch_bounds__(64) void fx_bus_mix(BusArgs a) {
     const unsigned lane = threadIdx.x;
@@ -107,20 +178,7 @@ __global__ __launch_bounds__(64) void fx_bus_mix(BusArgs a) {
             for (int k = 0; k < here; ++k) {
                 const long long first = (g0 + k) * K;
                 const long long count = a.n - first < K ? a.n - first : K;
-                float p = 0.0f;
-                for (long long m0 = 0; m0 < count; m0 += 256) {
-                    float v[4];
-                    bool have[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const long long m = m0 + u * 64 + lane;
-                        have[u] = m < count;
-                        v[u] = have[u] ? y[first + m] : 0.0f;   // 256 contiguous bytes per load
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) p = have[u] ? p + v[u] : p;
-                }
-                const float sum = treeSum(p);
+                const float sum = walkSum(count, lane, [&](const long long m) { return y[first + m]; });   // 256 contiguous bytes per load
                 if ((int)lane == k) res = sum;
             }
         }
@@ -135,23 +193,6 @@ __global__ __launch_bounds__(64) void fx_bus_mix(BusArgs a) {
 // group).  The gain words of a wavefront's groups do not depend on the sample, but a workgroup handles ONE row unless a block has
 // more than 65 535 of them (grid.y = rows), so there is nothing to keep in registers across rows: every row re-reads its gains,
 // [C][n] words that 2 * S rows share and the L2 / Infinity Cache hold.  kRamp = false loads the target block only.
-//
-// The weight: (b - a), * t, a + ... and w * y are four roundings (the file is built with -ffp-contract=off); the mute is a
-// select on w in front of the add, so a NaN or Inf of a muted member never reaches the sum.
-template <bool kRamp>
-__device__ __forceinline__ float weightOf(float a, float b, float t, bool atTarget) {
-    if (!kRamp) return b;
-    const float d = b - a;
-    const float m = d * t;
-    const float w = a + m;
-    return atTarget ? b : w;
-}
-
-__device__ __forceinline__ float termOf(float w, float y) {
-    const float prod = w * y;
-    return w == 0.0f ? 0.0f : prod;
-}
-
 template <bool kRamp>
 __global__ __launch_bounds__(64) void fx_bus_mix_gain(BusArgs a, BusGainArgs g) {
     const unsigned lane = threadIdx.x;
@@ -160,10 +201,10 @@ __global__ __launch_bounds__(64) void fx_bus_mix_gain(BusArgs a, BusGainArgs g) 
     const int here = (int)(a.groups - g0 < 64 ? a.groups - g0 : 64);
     for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
         const float* y = a.wide + row * a.n;
-        const long long s = row / g.channels + g.sample0;              // the sample of the CALL this row belongs to
-        const long long gainRow = (row % g.channels) * g.gainPitch;    // its channel's row of the gain blocks
-        const float t = (float)(s + 1) * g.r;
-        const bool atTarget = s == (long long)g.samples - 1;
+        const long long gainRow = (row % g.channels) * g.gainPitch;    // the row's channel's row of the gain blocks
+        float t;
+        bool atTarget;
+        rampAt(g, row, t, atTarget);
         float res = 0.0f;
         if (K <= 64) {
             for (int k0 = 0; k0 < here; k0 += 8) {
@@ -270,8 +311,7 @@ __global__ __launch_bounds__(64) void fx_bus_tap(BusTapArgs a) {
 // lane loads its instance number and its gain words once (256 contiguous bytes per wavefront each) and then issues the eight
 // rows' gathers wide[row][idx] - a 32-bit byte stride of n * 4 apart - before the first add, as fx_bus_tap does; eight partial
 // sums stay in registers.  After the last step come eight trees, and lanes 0..7 store the eight chunk sums to partial[row][chunk].
-// The gain words depend on the row's channel: kCh = 1 and 2 load one and two words per block and step (row groups begin at a
-// multiple of eight rows, so row u of a group is channel u % kCh); kCh = 0 is every other channel count and loads per row.
+// The gain words depend on the row's channel (RampRows): kCh = 1 and 2 load one and two words per block and step, kCh = 0 per row.
 // A ragged last group predicates its loads and stores by row: nothing outside the block's rows is read.  The index and the gain
 // words of step j + 1 are requested behind the gathers of step j, so that only a chunk's first step waits for them.
 constexpr int kSendRows = 8;
@@ -280,23 +320,8 @@ constexpr int kSendRows = 8;
 template <bool kRamp, int kCh, bool kFull>
 __device__ __forceinline__ void sendRowGroup(const BusSendArgs& a, const BusSendChunk ck, const long long row0, const unsigned lane) {
     const uint32_t loadStride = (uint32_t)a.n * 4u;   // (below 2^32: launchBusSend)
-    constexpr int kGains = kCh > 0 ? kCh : kSendRows;
-    float t[kSendRows];
-    bool atTarget[kSendRows], rowOk[kSendRows];
-    long long gainRow[kGains];
-#pragma unroll
-    for (int u = 0; u < kSendRows; ++u) {
-        const long long row = row0 + u;
-        const long long s = row / a.channels + a.sample0;   // the sample of the CALL this row belongs to
-        t[u] = (float)(s + 1) * a.r;
-        atTarget[u] = s == (long long)a.samples - 1;
-        rowOk[u] = kFull || row < a.rows;
-        if (kCh == 0) gainRow[u] = (row % a.channels) * a.gainPitch;
-    }
-    if (kCh > 0) {
-#pragma unroll
-        for (int c = 0; c < kGains; ++c) gainRow[c] = (long long)c * a.gainPitch;
-    }
+    const auto f = rampRows<kSendRows, kCh, kFull>(a, a.gainPitch, a.rows, row0);
+    constexpr int kGains = decltype(f)::kGains;
     float p[kSendRows];
 #pragma unroll
     for (int u = 0; u < kSendRows; ++u) p[u] = 0.0f;
@@ -308,9 +333,9 @@ __device__ __forceinline__ void sendRowGroup(const BusSendArgs& a, const BusSend
         inst = a.idx[e];
 #pragma unroll
         for (int c = 0; c < kGains; ++c) {
-            const bool need = kCh > 0 || rowOk[c];
-            gb[c] = need ? a.target[gainRow[c] + e] : 0.0f;
-            ga[c] = (kRamp && need) ? a.current[gainRow[c] + e] : 0.0f;
+            const bool need = kCh > 0 || f.rowOk[c];
+            gb[c] = need ? a.target[f.gainRow[c] + e] : 0.0f;
+            ga[c] = (kRamp && need) ? a.current[f.gainRow[c] + e] : 0.0f;
         }
     };
     uint32_t inst;
@@ -322,7 +347,7 @@ __device__ __forceinline__ void sendRowGroup(const BusSendArgs& a, const BusSend
         const char* q = base + (size_t)inst * 4u;
 #pragma unroll
         for (int u = 0; u < kSendRows; ++u) {
-            y[u] = rowOk[u] ? *reinterpret_cast<const float*>(q) : 0.0f;
+            y[u] = f.rowOk[u] ? *reinterpret_cast<const float*>(q) : 0.0f;
             q += loadStride;
         }
         // the next step's index and gains go out behind this step's gathers, so that only the first step waits for them
@@ -333,8 +358,8 @@ __device__ __forceinline__ void sendRowGroup(const BusSendArgs& a, const BusSend
         if (m0 + 64u < ck.count) fetch(m0 + 64u, instNext, gaNext, gbNext);
 #pragma unroll
         for (int u = 0; u < kSendRows; ++u) {
-            const int c = kCh > 0 ? u % kGains : u;
-            const float term = termOf(weightOf<kRamp>(ga[c], gb[c], t[u], atTarget[u]), y[u]);
+            const int c = f.gainOf(u);
+            const float term = termOf(weightOf<kRamp>(ga[c], gb[c], f.t[u], f.atTarget[u]), y[u]);
             p[u] = have ? p[u] + term : p[u];
         }
         inst = instNext;
@@ -384,20 +409,7 @@ __global__ __launch_bounds__(64) void fx_bus_send_fold(BusSendArgs a) {
         for (unsigned long long left = wideBuses; left != 0ull; left &= left - 1ull) {
             const int k = __ffsll((long long)left) - 1;
             const uint32_t first = laneWord(b.firstChunk, (unsigned)k), count = laneWord(b.chunks, (unsigned)k);
-            float p = 0.0f;
-            for (uint32_t m0 = 0; m0 < count; m0 += 256u) {
-                float v[4];
-                bool have[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t m = m0 + (uint32_t)u * 64u + lane;
-                    have[u] = m < count;
-                    v[u] = have[u] ? c[first + m] : 0.0f;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) p = have[u] ? p + v[u] : p;
-            }
-            const float sum = treeSum(p);
+            const float sum = walkSum(count, lane, [&](const uint32_t m) { return c[first + m]; });
             if ((int)lane == k) res = sum;
         }
         if (mineHere) a.auxOut[row * a.auxPitch + column] = res;
@@ -460,24 +472,17 @@ __device__ __forceinline__ void feedStoreRow(uint32_t* dstRow, const unsigned i,
 template <bool kMap, int kMode, int kCh, bool kFull>
 __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long long row0, const unsigned lane, const unsigned i, const unsigned end) {
     constexpr bool kWeighted = kMode > 0, kRamp = kMode == 2;
-    constexpr int kGains = kCh > 0 ? kCh : kFeedRows;
     const uint32_t srcStride = (uint32_t)a.m * 4u;   // (below 2^32: launchBusFeed)
-    float t[kFeedRows];
-    bool atTarget[kFeedRows], rowOk[kFeedRows];
-    long long gainRow[kGains];
+    RampRows<kFeedRows, kCh, kFull> f;   // (filled here: built by rampRows, the instantiation <false, 2, 0> takes a VGPR more)
+    constexpr int kGains = f.kGains;
 #pragma unroll
     for (int u = 0; u < kFeedRows; ++u) {
-        const long long row = row0 + u;
-        const long long s = row / a.channels + a.sample0;   // the sample of the CALL this row belongs to
-        t[u] = (float)(s + 1) * a.r;
-        atTarget[u] = s == (long long)a.samples - 1;
-        rowOk[u] = kFull || row < a.rows;
-        if (kCh == 0) gainRow[u] = (row % a.channels) * a.gainPitch;
+        rampAt(a, row0 + u, f.t[u], f.atTarget[u]);
+        f.rowOk[u] = kFull || row0 + u < a.rows;
+        if (kCh == 0) f.gainRow[u] = ((row0 + u) % a.channels) * a.gainPitch;
     }
-    if (kCh > 0) {
 #pragma unroll
-        for (int c = 0; c < kGains; ++c) gainRow[c] = (long long)c * a.gainPitch;
-    }
+    for (int c = 0; kCh > 0 && c < kGains; ++c) f.gainRow[c] = (long long)c * a.gainPitch;
     uint32_t w[kFeedRows][4];
 #pragma unroll
     for (int u = 0; u < kFeedRows; ++u)
@@ -492,9 +497,9 @@ __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long lo
 #pragma unroll
             for (int c = 0; c < kGains; ++c) {
                 float4 b4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a4 = b4;
-                if (kWeighted && (kCh > 0 || rowOk[c])) {
-                    b4 = *reinterpret_cast<const float4*>(a.target + gainRow[c] + i);
-                    if (kRamp) a4 = *reinterpret_cast<const float4*>(a.current + gainRow[c] + i);
+                if (kWeighted && (kCh > 0 || f.rowOk[c])) {
+                    b4 = *reinterpret_cast<const float4*>(a.target + f.gainRow[c] + i);
+                    if (kRamp) a4 = *reinterpret_cast<const float4*>(a.current + f.gainRow[c] + i);
                 }
                 gb[c][0] = b4.x; gb[c][1] = b4.y; gb[c][2] = b4.z; gb[c][3] = b4.w;
                 ga[c][0] = a4.x; ga[c][1] = a4.y; ga[c][2] = a4.z; ga[c][3] = a4.w;
@@ -505,16 +510,16 @@ __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long lo
                 const char* p = base + (size_t)ix[k] * 4u;
 #pragma unroll
                 for (int u = 0; u < kFeedRows; ++u) {
-                    x[u][k] = rowOk[u] ? *reinterpret_cast<const uint32_t*>(p) : 0u;
+                    x[u][k] = f.rowOk[u] ? *reinterpret_cast<const uint32_t*>(p) : 0u;
                     p += srcStride;
                 }
             }
 #pragma unroll
             for (int u = 0; u < kFeedRows; ++u) {
-                const int c = kCh > 0 ? u % kGains : u;
+                const int c = f.gainOf(u);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    w[u][k] = kWeighted ? __builtin_bit_cast(uint32_t, termOf(weightOf<kRamp>(ga[c][k], gb[c][k], t[u], atTarget[u]), __builtin_bit_cast(float, x[u][k])))
+                    w[u][k] = kWeighted ? __builtin_bit_cast(uint32_t, termOf(weightOf<kRamp>(ga[c][k], gb[c][k], f.t[u], f.atTarget[u]), __builtin_bit_cast(float, x[u][k])))
                                         : x[u][k];
             }
         } else {
@@ -539,9 +544,9 @@ __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long lo
                     ix[k] = has[k] ? a.idx[e] : 0u;
 #pragma unroll
                     for (int c = 0; c < kGains; ++c) {
-                        const bool need = kWeighted && has[k] && (kCh > 0 || rowOk[c]);
-                        gb[c][k] = need ? a.target[gainRow[c] + e] : 0.0f;
-                        ga[c][k] = (kRamp && need) ? a.current[gainRow[c] + e] : 0.0f;
+                        const bool need = kWeighted && has[k] && (kCh > 0 || f.rowOk[c]);
+                        gb[c][k] = need ? a.target[f.gainRow[c] + e] : 0.0f;
+                        ga[c][k] = (kRamp && need) ? a.current[f.gainRow[c] + e] : 0.0f;
                     }
                 }
                 uint32_t x[kFeedRows][4];
@@ -550,17 +555,17 @@ __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long lo
                     const char* p = base + (size_t)ix[k] * 4u;
 #pragma unroll
                     for (int u = 0; u < kFeedRows; ++u) {
-                        x[u][k] = (has[k] && rowOk[u]) ? *reinterpret_cast<const uint32_t*>(p) : 0u;
+                        x[u][k] = (has[k] && f.rowOk[u]) ? *reinterpret_cast<const uint32_t*>(p) : 0u;
                         p += srcStride;
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < kFeedRows; ++u) {
-                    const int c = kCh > 0 ? u % kGains : u;
+                    const int c = f.gainOf(u);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const float xf = __builtin_bit_cast(float, x[u][k]);
-                        const float term = kWeighted ? termOf(weightOf<kRamp>(ga[c][k], gb[c][k], t[u], atTarget[u]), xf) : xf;
+                        const float term = kWeighted ? termOf(weightOf<kRamp>(ga[c][k], gb[c][k], f.t[u], f.atTarget[u]), xf) : xf;
                         if (decltype(first)::value) acc[u][k] = has[k] ? term : 0.0f;
                         else acc[u][k] = has[k] ? acc[u][k] + term : acc[u][k];
                     }
@@ -577,7 +582,7 @@ __device__ __forceinline__ void feedRowGroup(const BusFeedArgs& a, const long lo
     uint32_t* dst = a.wide + row0 * a.n;
 #pragma unroll
     for (int u = 0; u < kFeedRows; ++u) {
-        if (rowOk[u]) feedStoreRow(dst, i, end, w[u], lane);   // (the same rows in every lane)
+        if (f.rowOk[u]) feedStoreRow(dst, i, end, w[u], lane);   // (the same rows in every lane)
         dst += a.n;
     }
 }
@@ -593,21 +598,6 @@ __global__ __launch_bounds__(64) void fx_bus_feed(BusFeedArgs a) {
         const long long row0 = grp * kFeedRows;
         if (row0 + kFeedRows <= a.rows) feedRowGroup<kMap, kMode, kCh, true>(a, row0, lane, i, end);
         else feedRowGroup<kMap, kMode, kCh, false>(a, row0, lane, i, end);
-    }
-}
-
-template <bool kMap>
-void launchFeedVariant(const BusFeedArgs& a, dim3 grid, hipStream_t stream) {
-    if (!a.target) {
-        hipLaunchKernelGGL((fx_bus_feed<kMap, 0, 1>), grid, dim3(64), 0, stream, a);
-    } else if (a.ramp) {
-        if (a.channels == 1) hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 1>), grid, dim3(64), 0, stream, a);
-        else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 2>), grid, dim3(64), 0, stream, a);
-        else hipLaunchKernelGGL((fx_bus_feed<kMap, 2, 0>), grid, dim3(64), 0, stream, a);
-    } else {
-        if (a.channels == 1) hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 1>), grid, dim3(64), 0, stream, a);
-        else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 2>), grid, dim3(64), 0, stream, a);
-        else hipLaunchKernelGGL((fx_bus_feed<kMap, 1, 0>), grid, dim3(64), 0, stream, a);
     }
 }
 
@@ -639,6 +629,26 @@ __global__ __launch_bounds__(64) void fx_gain_scatter(GainScatterArgs g) {
 
 inline bool badArgs(const BusArgs& a) { return a.rows < 1 || a.n < 1 || a.group < 1 || a.group > a.n || a.groups != (a.n + a.group - 1) / a.group || a.narrowPitch < a.groups || !a.wide; }
 
+// the ramp block of a launch over `rows` rows: whole samples always; weighted, the piece lies inside the caller's block and a
+// pending ramp has its a block (haveCurrent); unweighted (feeds only) nothing else is read, and a ramp is refused
+inline bool badRamp(const BusRampArgs& r, long long rows, bool weighted, bool haveCurrent) {
+    if (r.channels < 1 || rows % r.channels != 0) return true;
+    if (!weighted) return r.ramp != 0;
+    return r.samples < 1 || r.sample0 < 0 || (long long)r.sample0 + rows / r.channels > (long long)r.samples || (r.ramp && !haveCurrent);
+}
+
+// the one ladder from (ramp pending, channels) to a kernel's <kRamp, kCh> instantiation: launch(kRamp, kCh), as integral_constants
+template <class Launch>
+void byRampShape(const BusRampArgs& r, Launch launch) {
+    const auto byChannels = [&](auto kRamp) {
+        if (r.channels == 1) launch(kRamp, std::integral_constant<int, 1>{});
+        else if (r.channels == 2) launch(kRamp, std::integral_constant<int, 2>{});
+        else launch(kRamp, std::integral_constant<int, 0>{});
+    };
+    if (r.ramp) byChannels(std::true_type{});
+    else byChannels(std::false_type{});
+}
+
 }  // namespace
 
 hipError_t launchBusExpand(const BusArgs& a, hipStream_t stream) {
@@ -653,29 +663,21 @@ hipError_t launchBusExpand(const BusArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launchBusMix(const BusArgs& a, hipStream_t stream) {
+// either mix: g null is the plain one
+static hipError_t launchMix(const BusArgs& a, const BusGainArgs* g, hipStream_t stream) {
     if (badArgs(a) || !a.narrowOut) return hipErrorInvalidValue;
+    if (g && (!g->target || g->gainPitch < a.n || badRamp(*g, a.rows, true, g->current != nullptr))) return hipErrorInvalidValue;
     const long long blocks = (a.groups + 63) / 64;
     if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks, (unsigned)(a.rows < 65535 ? a.rows : 65535));
     (void)hipGetLastError();
-    hipLaunchKernelGGL(fx_bus_mix, grid, dim3(64), 0, stream, a);
+    if (!g) hipLaunchKernelGGL(fx_bus_mix, grid, dim3(64), 0, stream, a);
+    else if (g->ramp) hipLaunchKernelGGL(fx_bus_mix_gain<true>, grid, dim3(64), 0, stream, a, *g);
+    else hipLaunchKernelGGL(fx_bus_mix_gain<false>, grid, dim3(64), 0, stream, a, *g);
     return hipGetLastError();
 }
-
-hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t stream) {
-    if (badArgs(a) || !a.narrowOut) return hipErrorInvalidValue;
-    if (!g.target || (g.ramp && !g.current) || g.channels < 1 || a.rows % g.channels != 0 || g.gainPitch < a.n || g.samples < 1 || g.sample0 < 0 ||
-        (long long)g.sample0 + a.rows / g.channels > (long long)g.samples)
-        return hipErrorInvalidValue;
-    const long long blocks = (a.groups + 63) / 64;
-    if (blocks >= ((long long)1 << 31)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks, (unsigned)(a.rows < 65535 ? a.rows : 65535));
-    (void)hipGetLastError();
-    if (g.ramp) hipLaunchKernelGGL(fx_bus_mix_gain<true>, grid, dim3(64), 0, stream, a, g);
-    else hipLaunchKernelGGL(fx_bus_mix_gain<false>, grid, dim3(64), 0, stream, a, g);
-    return hipGetLastError();
-}
+hipError_t launchBusMix(const BusArgs& a, hipStream_t stream) { return launchMix(a, nullptr, stream); }
+hipError_t launchBusMixGain(const BusArgs& a, const BusGainArgs& g, hipStream_t stream) { return launchMix(a, &g, stream); }
 
 hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream) {
     constexpr long long kMostTaps = 65536;
@@ -693,23 +695,16 @@ hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream) {
     constexpr long long kMostBuses = 65536, kMostEntries = (long long)1 << 24;
     if (!a.wide || !a.bus || !a.auxOut || a.rows < 1 || a.n < 1 || a.n >= ((long long)1 << 30) || a.buses < 1 || a.buses > kMostBuses || a.auxPitch < a.buses ||
         a.auxPitch > kMostBuses || a.entries < 0 || a.entries > kMostEntries || a.chunks < 0 || a.chunks > a.entries || a.chunks > kMostEntries / kSendChunk + kMostBuses ||
-        (a.entries > 0) != (a.chunks > 0) || a.channels < 1 || a.rows % a.channels != 0 || a.samples < 1 || a.sample0 < 0 ||
-        (long long)a.sample0 + a.rows / a.channels > (long long)a.samples)
+        (a.entries > 0) != (a.chunks > 0) || badRamp(a, a.rows, true, a.current || a.chunks == 0))   // (without a chunk nothing reads a)
         return hipErrorInvalidValue;
-    if (a.chunks > 0 && (!a.idx || !a.target || (a.ramp && !a.current) || !a.chunk || !a.partial || a.gainPitch < a.entries)) return hipErrorInvalidValue;
+    if (a.chunks > 0 && (!a.idx || !a.target || !a.chunk || !a.partial || a.gainPitch < a.entries)) return hipErrorInvalidValue;
     (void)hipGetLastError();
     if (a.chunks > 0) {
         const long long groups = (a.rows + kSendRows - 1) / kSendRows;
         const dim3 grid((unsigned)a.chunks, (unsigned)(groups < 65535 ? groups : 65535));
-        if (a.ramp) {
-            if (a.channels == 1) hipLaunchKernelGGL((fx_bus_send_chunks<true, 1>), grid, dim3(64), 0, stream, a);
-            else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_send_chunks<true, 2>), grid, dim3(64), 0, stream, a);
-            else hipLaunchKernelGGL((fx_bus_send_chunks<true, 0>), grid, dim3(64), 0, stream, a);
-        } else {
-            if (a.channels == 1) hipLaunchKernelGGL((fx_bus_send_chunks<false, 1>), grid, dim3(64), 0, stream, a);
-            else if (a.channels == 2) hipLaunchKernelGGL((fx_bus_send_chunks<false, 2>), grid, dim3(64), 0, stream, a);
-            else hipLaunchKernelGGL((fx_bus_send_chunks<false, 0>), grid, dim3(64), 0, stream, a);
-        }
+        byRampShape(a, [&](auto kRamp, auto kCh) {
+            hipLaunchKernelGGL((fx_bus_send_chunks<decltype(kRamp)::value, decltype(kCh)::value>), grid, dim3(64), 0, stream, a);
+        });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -724,20 +719,22 @@ hipError_t launchBusFeed(const BusFeedArgs& a, hipStream_t stream) {
     const bool map = !a.off;
     const long long n4 = (a.n + 3) / 4 * 4;
     if (!a.src || !a.wide || a.rows < 1 || a.n < 1 || a.n >= ((long long)1 << 30) || a.m < 1 || a.m >= ((long long)1 << 30) || a.entries < 0 || a.entries > kMostEntries ||
-        (map && a.entries != a.n) || (a.entries > 0 && !a.idx) || !aligned16(a.off) || !aligned16(a.idx) || a.channels < 1 || a.rows % a.channels != 0)
+        (map && a.entries != a.n) || (a.entries > 0 && !a.idx) || !aligned16(a.off) || !aligned16(a.idx) || badRamp(a, a.rows, a.target != nullptr, a.current != nullptr))
         return hipErrorInvalidValue;
-    if (a.target) {
-        if ((a.ramp && !a.current) || a.gainPitch < a.entries || a.samples < 1 || a.sample0 < 0 || (long long)a.sample0 + a.rows / a.channels > (long long)a.samples)
-            return hipErrorInvalidValue;
-        if (map && (a.gainPitch < n4 || a.gainPitch % 4 != 0 || !aligned16(a.target) || !aligned16(a.current))) return hipErrorInvalidValue;
-    } else if (a.ramp) {
-        return hipErrorInvalidValue;
-    }
+    if (a.target && (a.gainPitch < a.entries || (map && (a.gainPitch < n4 || a.gainPitch % 4 != 0 || !aligned16(a.target) || !aligned16(a.current))))) return hipErrorInvalidValue;
     const long long groups = (a.rows + kFeedRows - 1) / kFeedRows;
     const dim3 grid((unsigned)((a.n + kFeedSpan - 1) / kFeedSpan), (unsigned)(groups < 65535 ? groups : 65535));
     (void)hipGetLastError();
-    if (map) launchFeedVariant<true>(a, grid, stream);
-    else launchFeedVariant<false>(a, grid, stream);
+    // unweighted: one instantiation; weighted: kMode = 1 or 2 by the ramp, on the ladder of the sends
+    const auto launch = [&](auto kMap) {
+        constexpr bool kM = decltype(kMap)::value;
+        if (!a.target) hipLaunchKernelGGL((fx_bus_feed<kM, 0, 1>), grid, dim3(64), 0, stream, a);
+        else byRampShape(a, [&](auto kRamp, auto kCh) {
+            hipLaunchKernelGGL((fx_bus_feed<kM, decltype(kRamp)::value ? 2 : 1, decltype(kCh)::value>), grid, dim3(64), 0, stream, a);
+        });
+    };
+    if (map) launch(std::true_type{});
+    else launch(std::false_type{});
     return hipGetLastError();
 }
 

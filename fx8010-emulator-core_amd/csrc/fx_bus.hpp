@@ -30,16 +30,21 @@ hipError_t launchBusExpand(const BusArgs& a, hipStream_t stream);
 // fp32, round to nearest, never fused, denormals kept.
 hipError_t launchBusMix(const BusArgs& a, hipStream_t stream);
 
-// The gains of a weighted mix (include/fx8010_amd.h "Bus gains"): two blocks [channels][gainPitch] by instance, device memory.
-struct BusGainArgs {
-    const float* current;    // a: read only while a ramp is pending (may be null otherwise)
-    const float* target;     // b
-    long long gainPitch;     // floats per channel row of both blocks (>= n)
+// Where the rows of a weighted launch are in the caller's block and on its ramp: the base of the arguments of the gains, the
+// sends and the feeds, so that each of them has these fields under these names.
+struct BusRampArgs {
     int channels;            // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
     int ramp;                // 1: a ramp is pending, w = a + (b - a) * ((float)(s + 1) * r) and exactly b at s == samples - 1; 0: w = b
     float r;                 // 1.0f / (float)samples, divided once on the host
     int samples;             // S of the caller's block, never a piece's
     int sample0;             // first sample of this piece within the block
+};
+
+// The gains of a weighted mix (include/fx8010_amd.h "Bus gains"): two blocks [channels][gainPitch] by instance, device memory.
+struct BusGainArgs : BusRampArgs {
+    const float* current;    // a: read only while a ramp is pending (may be null otherwise)
+    const float* target;     // b
+    long long gainPitch;     // floats per channel row of both blocks (>= n)
 };
 
 // narrowOut[r][g] = the sum of launchBusMix over the terms (w == 0.0f ? +0.0f : w * wide[r][i]) instead of wide[r][i]: a member
@@ -69,7 +74,7 @@ hipError_t launchBusTap(const BusTapArgs& a, hipStream_t stream);
 constexpr long long kSendChunk = 1024;   // part of the contract, not a tuning knob
 struct BusSendChunk { uint32_t first, count; };          // entries first .. first + count - 1, 1 <= count <= kSendChunk
 struct BusSendBus { uint32_t firstChunk, chunks, column; };   // Q = chunks (0: an empty bus); column of auxOut where `columns` is set
-struct BusSendArgs {
+struct BusSendArgs : BusRampArgs {
     const float* wide;            // [rows][n] per-instance scratch, rows packed (device memory)
     const uint32_t* idx;          // [entries] instance numbers of this batch, each below n (device memory; the caller has checked them)
     const float* current;         // a: [channels][gainPitch] by entry, read only while a ramp is pending (may be null otherwise)
@@ -86,11 +91,6 @@ struct BusSendArgs {
     long long buses;              // of this batch, 1 <= buses <= 65 536
     long long auxPitch;           // floats per row of auxOut (>= buses; with `columns`, above every column)
     int columns;                  // 1: bus j goes to column bus[j].column; 0: to column j
-    int channels;                 // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
-    int ramp;                     // as BusGainArgs
-    float r;
-    int samples;
-    int sample0;
 };
 
 // partial[r][q] = the sum of chunk q's terms (w == 0.0f ? +0.0f : w * wide[r][idx[e]]) in the order of launchBusMix, then
@@ -106,7 +106,7 @@ hipError_t launchBusSend(const BusSendArgs& a, hipStream_t stream);
 //   target  b: [channels][gainPitch] by entry; null: UNWEIGHTED (words move as bit patterns)
 //   current a: read only while a ramp is pending
 // gainPitch >= entries (the map form: >= ceil4(n) and a multiple of 4).
-struct BusFeedArgs {
+struct BusFeedArgs : BusRampArgs {   // (unweighted: channels only, ramp 0)
     const uint32_t* src;     // [rows][m] source words, rows packed (device memory: every word is gathered many times)
     uint32_t* wide;          // [rows][n] per-instance scratch, rows packed (device memory)
     const uint32_t* off;
@@ -118,11 +118,6 @@ struct BusFeedArgs {
     long long m;             // source columns, m >= 1; m * 4 < 2^32
     long long entries;       // E of this batch, <= 2^24 (the map form: n)
     long long gainPitch;
-    int channels;            // C: row r of the piece is sample r / C + sample0 of the call, channel r % C
-    int ramp;                // as BusGainArgs
-    float r;
-    int samples;
-    int sample0;
 };
 
 // wide[r][i] = the word of the definition: +0.0f for no entry, term_0 for one, ((term_0 + term_1) + term_2) + ... in entry order

@@ -586,9 +586,7 @@ int Sharded::busSetSends(int64_t nAux, const int64_t* offsets, const int64_t* me
     for (int64_t e = 0; e < entries; ++e)
         if (members[e] < 0 || members[e] >= n_) { lastError_ = "bus sends: a member outside 0..N-1"; return FX_E_ARG; }
     const size_t ch = (size_t)front().channels();
-    if (gains)
-        for (size_t i = 0; i < ch * (size_t)entries; ++i)
-            if (!std::isfinite(gains[i])) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
+    if (gains && !Batch::gainsFinite(gains, (int)ch, entries, entries)) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
     // a bus is summed where its members live: no collective on the data path, and no bits that depend on the split
     std::vector<int> owner((size_t)nAux, 0);
     for (int64_t b = 0; b < nAux; ++b)
@@ -636,10 +634,9 @@ int Sharded::busSetSendGains(const float* gains, int ramp) {
     lastError_.clear();
     if (ramp != 0 && ramp != 1) { lastError_ = "bus sends: ramp must be 0 or 1"; return FX_E_ARG; }
     if (front().busSendBuses() < 1) { lastError_ = "bus sends: sends are off (fxb_bus_set_sends)"; return FX_E_ARG; }
-    const size_t words = (size_t)front().channels() * (size_t)front().busSendEntries();
-    if (words > 0 && !gains) { lastError_ = "null buffer"; return FX_E_ARG; }
-    for (size_t i = 0; i < words; ++i)
-        if (!std::isfinite(gains[i])) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
+    const int64_t entries = front().busSendEntries();
+    if (entries > 0 && !gains) { lastError_ = "null buffer"; return FX_E_ARG; }
+    if (!Batch::gainsFinite(gains, front().channels(), entries, entries)) { lastError_ = "bus sends: every gain must be finite"; return FX_E_ARG; }
     return fan([&](int, Batch& b) { return b.busSetSendGains(gains, ramp); });
 }
 int64_t Sharded::busGetSends(int64_t* nAux, int64_t* offsets, int64_t offCap, int64_t* members, float* gains, int64_t cap) {
@@ -668,9 +665,7 @@ int Sharded::busSetFeeds(int64_t nSrc, const int64_t* offsets, const int64_t* so
     if (entries > 0 && !sources) { lastError_ = "bus feeds: null sources"; return FX_E_ARG; }
     for (int64_t e = 0; e < entries; ++e)
         if (sources[e] < 0 || sources[e] >= nSrc) { lastError_ = "bus feeds: a source outside 0..M-1"; return FX_E_ARG; }
-    if (gains)
-        for (size_t i = 0; i < ch * (size_t)entries; ++i)
-            if (!std::isfinite(gains[i])) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
+    if (gains && !Batch::gainsFinite(gains, (int)ch, entries, entries)) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
     // a shard's instances own a contiguous run of the entries
     std::vector<Batch::FeedSet> parts(shards_.size());
     for (size_t k = 0; k < parts.size(); ++k) {
@@ -701,9 +696,7 @@ int Sharded::busSetFeedGains(const float* gains, int ramp) {
     lastError_.clear();
     if (ramp != 0 && ramp != 1) { lastError_ = "bus feeds: ramp must be 0 or 1"; return FX_E_ARG; }
     if (front().busFeedSources() < 1) { lastError_ = "bus feeds: feeds are off (fxb_bus_set_feeds)"; return FX_E_ARG; }
-    const size_t words = gains ? (size_t)front().channels() * (size_t)front().busFeedEntries() : 0;
-    for (size_t i = 0; i < words; ++i)
-        if (!std::isfinite(gains[i])) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
+    if (gains && !Batch::gainsFinite(gains, front().channels(), front().busFeedEntries(), front().busFeedEntries())) { lastError_ = "bus feeds: every gain must be finite"; return FX_E_ARG; }
     return fan([&](int, Batch& b) { return b.busSetFeedGains(gains, ramp); });
 }
 int64_t Sharded::busGetFeeds(int64_t* nSrc, int64_t* offsets, int64_t offCap, int64_t* sources, float* gains, int64_t cap) {

@@ -14,6 +14,7 @@ from test_bus_send_stub import send_model, structure
 from test_bus_stub import expand, mix_model, same_words
 from test_bus_tap_stub import same_bits, tap_list
 from test_gpu_bus import NONFINITE, cutoffs, group_input, handles, program, register_names, same_state
+from test_gpu_bus_feed import channels_of
 from test_gpu_bus_tap import kernel_tier, right_tier  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +89,36 @@ def test_sends_bit_exact(gpu, kernel_tier, N, K, channels):
     block(1, off2, mem2, h1, h1, False)
     same_state(gpu, b, plain, names, sorted({0, min(63, N - 1), min(64, N - 1), N - 1}), tram=1000)
     assert b.info("bus_send_blocks") == 8 and b.info("bus_blocks") == 8 and b.info("bus_tap_blocks") == 2 and right_tier(b, kernel_tier)
+    for h in (plain, b):
+        h.close()
+
+
+def test_sends_at_three_channels_and_a_bus_of_257_chunks(gpu):
+    """N = 200, K = 63, three channels - the send kernel's frame of one gain row per row, for channel counts other than 1 and 2 -
+    and buses of 0, 1, 1 025 and 262 145 entries: 262 145 = 256 * 1 024 + 1 is 257 chunks, the second 256-chunk step of the fold's
+    walk, with a one-entry last chunk.  A block of 3 samples is nine rows: one full group of the kernel's eight and a ragged one.
+    Static gains, then a ramp"""
+    N, K, channels, S = 200, 63, 3, 3
+    rng = np.random.default_rng(47)
+    text = channels_of(progs.config3(), channels)
+    plain, b = handles(gpu, text, N, channels, 2)
+    G = plain.bus_groups(K)
+    offsets, members = structure(rng, N, (0, 1, 1025, 262145))
+    E = int(offsets[-1])
+    g0, g1 = gains_for(rng, channels, E), gains_for(rng, channels, E)
+    assert b.bus_set_sends(offsets, members, g0) == 0 and sends_are(b, offsets, members, g0)
+    for step, ramp in enumerate((False, True)):
+        if ramp:
+            assert b.bus_set_send_gains(g1, True) == 0
+        xg = group_input(G, S, channels, step * S)
+        y = plain.process_block(expand(xg, K, N))
+        out, aux = b.process_block_bus(xg, K, True, True, aux=True)
+        assert same_words(out, mix_model(y, K)), "ramp %d: the mix" % ramp
+        want = send_model(y, offsets, members, g0, g1 if ramp else g0, ramp, S)
+        bad = np.argwhere(aux.view(np.uint32) != want.view(np.uint32))
+        assert bad.size == 0, "ramp %d: aux [sample, channel, bus] %s of %d words, got %r want %r" % (ramp, bad[:4].tolist(), want.size, aux[tuple(bad[0])], want[tuple(bad[0])])
+    assert sends_are(b, offsets, members, g1) and b.info("bus_send_blocks") == 2 and b.info("bus_blocks") == 2
+    same_state(gpu, b, plain, register_names(gpu, text, channels), (0, 63, 64, N - 1), tram=1000)
     for h in (plain, b):
         h.close()
 
