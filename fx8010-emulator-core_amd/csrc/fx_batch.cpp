@@ -80,6 +80,8 @@ Batch::~Batch() {
     (void)hipFree(dTarget_);
     (void)hipFree(dMatch_);
     releaseMeterTarget();
+    (void)hipFree(dLevel_);
+    releaseMeterLevel();
     (void)hipFree(dGain_[0]);
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
@@ -856,6 +858,8 @@ int Batch::meterReset() {
     hipError_t e = hipMemsetAsync(dMeter_, 0, meterChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
     // (all six: the match rows of a target as well; the target position stays)
     if (e == hipSuccess && dMatch_) e = hipMemsetAsync(dMatch_, 0, matchChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
+    // (... and the two level rows; the mode and its parameters stay)
+    if (e == hipSuccess && dLevel_) e = hipMemsetAsync(dLevel_, 0, levelChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     meterSamples_ = 0;
     return e == hipSuccess ? 0 : hipFail(e, "zeroing the meter rows");
@@ -868,6 +872,7 @@ int Batch::meterEnable(bool on) {
     (void)hipStreamSynchronize(stream_);
     if (!on) {
         (void)clearMeterTarget();
+        (void)clearMeterLevel();
         (void)hipFree(dMeter_);
         dMeter_ = nullptr;
         meterSamples_ = 0;
@@ -991,6 +996,9 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_TARGET_LAUNCHES) return meterTargetLaunches_;
     if (what == FXB_INFO_METER_MATCH_SELECTS) return matchSelects_;
     if (what == FXB_INFO_METER_MATCH_BESTS) return matchBests_;
+    if (what == FXB_INFO_METER_LEVEL_LAUNCHES) return meterLevelLaunches_;
+    if (what == FXB_INFO_METER_LEVEL_SELECTS) return levelSelects_;
+    if (what == FXB_INFO_METER_LEVEL_LIST_READS) return levelListReads_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

@@ -384,6 +384,25 @@ public:
     int64_t meterBestGroups(int64_t group, int64_t firstGlobal) const { return (firstGlobal + n_ - 1) / group - firstGlobal / group + 1; }
     int reserveMeterBest(int64_t group, int64_t firstGlobal);
     int meterBest(int stat, int64_t group, int64_t firstGlobal, bool largest, int64_t* winner, double* value);
+    // Level meters (fx_meter.hpp LevelParams; include/fx8010_amd.h "Level meters"; fx_batch_meter_level.cpp).  Split check /
+    // reserve / act like the target meters.  checkMeterLevel refuses for the whole handle and canonicalises -0.0 to +0.0.
+    // reserveMeterLevel is the allocating half - the level rows, where there are none - and keeps them aside; FX_E_MEMORY or
+    // FX_E_ARG (metering off) changes nothing.  setMeterLevel takes them into force zeroed - the first call waits as sync() does -
+    // and sets the two parameters, which travel by value with every launch queued from then on; a call while the mode is on
+    // changes only them.  While the mode is on launchBlock launches fx_meter_level / fx_meter_target_level in place of fx_meter /
+    // fx_meter_target.  The reads and the select are synchronous and share the staging of the meter queries by list.
+    static int checkMeterLevel(float* release, float* floor, unsigned flags, std::string* why);
+    int reserveMeterLevel();
+    void releaseMeterLevel();
+    int setMeterLevel(float release, float floor);
+    int clearMeterLevel();
+    bool meterLevelOn() const { return dLevel_ != nullptr; }
+    int getMeterLevel(float* release, float* floor);
+    int meterReadLevel(float* level, uint32_t* quiet, bool reset, int64_t rowPitch = 0);
+    int meterReadLevelList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, float* level, uint32_t* quiet, bool reset);
+    // select over V = the channel maximum of `level` (stat 0) or the channel MINIMUM of `quiet` (stat 1): everything else as meterSelect
+    static int checkLevelSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
+    int64_t levelSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -898,7 +917,8 @@ private:
     Block<unsigned long long> meterStage_, hMeterStage_;
     int reserveMeterStage(size_t words, bool needEvent);
     int64_t meterSelects_ = 0, meterListReads_ = 0, meterListResets_ = 0;   // FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS
-    int64_t runSelect(bool match, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
+    enum class SelectRows { kMeter, kMatch, kLevel };   // which rows a select looks at, and with which predicate
+    int64_t runSelect(SelectRows rows, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
     // target meters (fx_batch_meter_target.cpp): the target block and the match rows in force (null: no target), the blocks a
     // set has reserved and not yet taken, the shape of the target, and the position of the next queued block
     float* dTarget_ = nullptr;
@@ -910,6 +930,14 @@ private:
     int zeroMatchRows();   // queued on stream_ and waited for
     MeterTargetArgs meterTargetArgs(const MeterArgs& m) const;   // of the block that is about to be queued
     int64_t meterTargetLaunches_ = 0, matchSelects_ = 0, matchBests_ = 0;   // FXB_INFO_METER_TARGET_LAUNCHES / _MATCH_SELECTS / _MATCH_BESTS
+    // level meters (fx_batch_meter_level.cpp): the level rows in force (null: the mode is off), the block a set has reserved and
+    // not yet taken, and the two parameters of the launches queued from now on
+    void* dLevel_ = nullptr;
+    void* levelNew_ = nullptr;
+    float levelRelease_ = 0.0f, levelFloor_ = 0.0f;
+    int zeroLevelRows();   // queued on stream_ and waited for
+    LevelParams levelParams() const { return LevelParams{dLevel_, levelRelease_, levelFloor_}; }
+    int64_t meterLevelLaunches_ = 0, levelSelects_ = 0, levelListReads_ = 0;   // FXB_INFO_METER_LEVEL_LAUNCHES / _LEVEL_SELECTS / _LEVEL_LIST_READS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

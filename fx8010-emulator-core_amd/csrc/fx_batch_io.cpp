@@ -320,12 +320,23 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
             if (dTarget_) {
                 // a target is set: fx_meter_target in place of fx_meter - the block is read once - and the target position moves
                 // on by this launch's samples, so that however a stream is cut every sample meets the same target row
-                if ((e = launchMeterTarget(meterTargetArgs(m), s)) != hipSuccess) return hipFail(e, "launch fx_meter_target");
+                // (with level meters on, fx_meter_target_level: the same block read once, two more accumulators)
+                if (dLevel_) {
+                    if ((e = launchMeterTargetLevel(MeterTargetLevelArgs{meterTargetArgs(m), levelParams()}, s)) != hipSuccess) return hipFail(e, "launch fx_meter_target_level");
+                    ++meterLevelLaunches_;
+                } else if ((e = launchMeterTarget(meterTargetArgs(m), s)) != hipSuccess) {
+                    return hipFail(e, "launch fx_meter_target");
+                }
                 ++meterTargetLaunches_;
                 targetPos_ += nSamples;
                 if (targetLoop_) targetPos_ %= targetSamples_;
             } else {
-                if ((e = launchMeter(m, s)) != hipSuccess) return hipFail(e, "launch fx_meter");
+                if (dLevel_) {
+                    if ((e = launchMeterLevel(MeterLevelArgs{m, levelParams()}, s)) != hipSuccess) return hipFail(e, "launch fx_meter_level");
+                    ++meterLevelLaunches_;
+                } else if ((e = launchMeter(m, s)) != hipSuccess) {
+                    return hipFail(e, "launch fx_meter");
+                }
                 ++meterLaunches_;
             }
             meterSamples_ += nSamples;

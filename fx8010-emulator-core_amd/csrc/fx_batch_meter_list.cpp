@@ -61,15 +61,16 @@ int Batch::reserveMeterSelect(int64_t nRange, int64_t cap) { return reserveMeter
 int Batch::reserveMeterList(int64_t count, bool gather) { return reserveMeterStage(count > 0 ? listWords(prog_.numChannels, count, gather) : 0, !gather); }
 
 int64_t Batch::meterSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
-    return runSelect(false, stat, threshold, below, first, nRange, firstGlobal, list, cap);
+    return runSelect(SelectRows::kMeter, stat, threshold, below, first, nRange, firstGlobal, list, cap);
 }
 
-// match: the select over the match rows of a target (fx_batch_meter_target.cpp) - the same staging, copies and counts of words,
-// another predicate on the device
-int64_t Batch::runSelect(bool match, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
+// rows: kMatch is the select over the match rows of a target (fx_batch_meter_target.cpp), kLevel the one over the level rows
+// (fx_batch_meter_level.cpp) - the same staging, copies and counts of words, another predicate on the device
+int64_t Batch::runSelect(SelectRows rows, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
     (void)hipSetDevice(device_);
     if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
-    if (match && !dTarget_) return fail(FX_E_ARG, "meter target: no target is set (fxb_meter_set_target)");
+    if (rows == SelectRows::kMatch && !dTarget_) return fail(FX_E_ARG, "meter target: no target is set (fxb_meter_set_target)");
+    if (rows == SelectRows::kLevel && !dLevel_) return fail(FX_E_ARG, "level meters: the mode is off (fxb_meter_set_level)");
     if (nRange == 0) return 0;
     if (selectWords(nRange, cap) > meterStage_.cap || selectWords(nRange, cap) > hMeterStage_.cap) return fail(FX_E_ARG, "meter_select: no staging reserved (reserveMeterSelect)");
     const int rc = sync();
@@ -92,9 +93,12 @@ int64_t Batch::runSelect(bool match, int stat, double threshold, bool below, int
     a.stat = stat;
     a.below = below ? 1 : 0;
     hipError_t e;
-    if (match) {
+    if (rows == SelectRows::kMatch) {
         const MatchSelectArgs b{dMatch_, a.offsets, a.list, a.n, a.nPad, a.first, a.nRange, a.firstGlobal, a.cap, a.threshold, a.channels, a.stat, a.below};
         if ((e = launchMatchSelect(b, stream_)) == hipSuccess) ++matchSelects_;
+    } else if (rows == SelectRows::kLevel) {
+        const LevelSelectArgs b{dLevel_, a.offsets, a.list, a.n, a.nPad, a.first, a.nRange, a.firstGlobal, a.cap, a.threshold, a.channels, a.stat, a.below};
+        if ((e = launchLevelSelect(b, stream_)) == hipSuccess) ++levelSelects_;
     } else if ((e = launchMeterSelect(a, stream_)) == hipSuccess) {
         ++meterSelects_;
     }
@@ -183,6 +187,11 @@ int Batch::meterResetList(const int64_t* list, int64_t count) {
     if (e == hipSuccess && dMatch_) {
         a.rows = dMatch_;
         e = launchMatchZero(a, stream_);
+    }
+    // (... and those of the level rows)
+    if (e == hipSuccess && dLevel_) {
+        a.rows = dLevel_;
+        e = launchLevelZero(a, stream_);
     }
     if (const int failed = closeInstCall(e, "meter_reset_list: queueing the zeroing")) return failed;
     ++meterListResets_;

@@ -170,7 +170,7 @@ int Batch::meterReadMatch(double* err, double* cross, bool reset, int64_t rowPit
 }
 
 int64_t Batch::matchSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
-    return runSelect(true, stat, threshold, below, first, nRange, firstGlobal, list, cap);
+    return runSelect(SelectRows::kMatch, stat, threshold, below, first, nRange, firstGlobal, list, cap);
 }
 
 int Batch::reserveMeterBest(int64_t group, int64_t firstGlobal) {

@@ -311,6 +311,22 @@ int64_t fxb_meter_select_match(fxb_handle* h, int stat, double threshold, int64_
 int fxb_meter_best(fxb_handle* h, int stat, int64_t group, int64_t* winner, double* value, unsigned flags) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterBest(stat, group, winner, value, flags); }) : FX_E_ARG;
 }
+int fxb_meter_set_level(fxb_handle* h, float release, float floor, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterSetLevel(release, floor, flags); }) : FX_E_ARG;
+}
+int fxb_meter_clear_level(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterClearLevel(); }) : FX_E_ARG; }
+int fxb_meter_get_level(fxb_handle* h, float* release, float* floor) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterGetLevel(release, floor); }) : FX_E_ARG;
+}
+int fxb_meter_read_level(fxb_handle* h, float* level, uint32_t* quiet, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadLevel(level, quiet, reset != 0); }) : FX_E_ARG;
+}
+int fxb_meter_read_level_list(fxb_handle* h, const int64_t* list, int64_t count, float* level, uint32_t* quiet, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadLevelList(list, count, level, quiet, reset != 0); }) : FX_E_ARG;
+}
+int64_t fxb_meter_select_level(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelectLevel(stat, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
+}
 int64_t fxb_meter_samples(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSamples(); }) : FX_E_ARG; }
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }

@@ -64,4 +64,33 @@ struct MeterTargetArgs {
 // block is read once.  The four are taken by the same code (meterTake), for every sample.
 hipError_t launchMeterTarget(const MeterTargetArgs& a, hipStream_t stream);
 
+// Level meters (include/fx8010_amd.h "Level meters"): two further accumulators per (channel, instance) that fall as well as rise.
+// For every output word, with fin and w as above: d = level * release (ONE fp32 multiply, denormals kept), level = max(w, d) - both
+// non-negative and finite, so the larger bit pattern - loud = !fin || w >= floor, quiet = loud ? 0 : quiet + 1, saturating at
+// 0xFFFFFFFF.  The level rows are a block of their own - per channel level f32 [nPad], then quiet u32 [nPad], all zero after a
+// reset - so that a handle without level meters carries nothing of them.  release and floor travel by value in every launch.
+constexpr size_t kLevelBytesPerColumn = 8;
+constexpr size_t levelChannelBytes(long long nPad) { return kLevelBytesPerColumn * (size_t)nPad; }
+constexpr size_t levelLevelOff(long long) { return 0; }
+constexpr size_t levelQuietOff(long long nPad) { return 4 * (size_t)nPad; }
+
+struct LevelParams {
+    void* rows;       // [channels] x the level rows above (device memory)
+    float release;    // finite, +0.0f <= release <= 1 (never -0.0f: the product must keep a clear sign bit)
+    float floor;      // finite, +0.0f <= floor
+};
+struct MeterLevelArgs {
+    MeterArgs m;      // the block and the four accumulators, as for launchMeter
+    LevelParams l;
+};
+struct MeterTargetLevelArgs {
+    MeterTargetArgs t;   // the block, the four and the two match accumulators, as for launchMeterTarget
+    LevelParams l;
+};
+
+// fx_meter_level / fx_meter_target_level: launched INSTEAD of fx_meter / fx_meter_target while level meters are on.  The four
+// (and the two of a target) are taken by the same code, for every sample; the two level accumulators by levelTake.
+hipError_t launchMeterLevel(const MeterLevelArgs& a, hipStream_t stream);
+hipError_t launchMeterTargetLevel(const MeterTargetLevelArgs& a, hipStream_t stream);
+
 }  // namespace fx

@@ -39,6 +39,12 @@
 // wavefront per group, as for the mix of small groups.  fx_match_zero stores +0.0 into the listed columns.  Resource usage as
 // above: fx_match_count 8 / 0 / 16, fx_match_emit 14 / 0 / 16, fx_meter_best 20 / 0 / 0, fx_match_zero 6 / 0 / 0; eight wavefronts
 // per SIMD each.
+//
+// The queries over the level rows (fx_meter_list.hpp, third part).  fx_level_count / fx_level_emit are the same two bodies with a
+// third predicate, picked by LevelSelectArgs: V is the maximum over the channels of the envelope or the MINIMUM over the channels of
+// the quiet run, both exact in fp64.  fx_level_gather / fx_level_zero are the one-lane-per-list-entry form of meterColumns on the
+// two level rows: the lane that has read a column stores its zeros.  Resource usage as above: fx_level_count 10 / 0 / 16,
+// fx_level_emit 14 / 0 / 16, fx_level_gather 11 / 0 / 0, fx_level_zero 6 / 0 / 0; eight wavefronts per SIMD each.
 #include <hip/hip_runtime.h>
 
 #include "fx_meter.hpp"
@@ -93,6 +99,25 @@ __device__ __forceinline__ bool matchesRange(const MatchSelectArgs& a, long long
     return a.below ? v < a.threshold : v >= a.threshold;
 }
 
+// V(n) over the level rows: the maximum of the envelopes, the MINIMUM of the quiet runs - both exact in fp64
+__device__ __forceinline__ bool matchesRange(const LevelSelectArgs& a, long long i) {
+    if (i >= a.nRange) return false;
+    const long long col = a.first + i;
+    if (col >= a.n) return false;
+    const char* ch = static_cast<const char*>(a.rows);
+    double best = 0.0;
+    for (int c = 0; c < a.channels; ++c, ch += levelChannelBytes(a.nPad)) {
+        if (a.stat == 0) {
+            const double v = (double)reinterpret_cast<const float*>(ch + levelLevelOff(a.nPad))[col];
+            best = (c == 0 || v > best) ? v : best;
+        } else {
+            const double v = (double)reinterpret_cast<const uint32_t*>(ch + levelQuietOff(a.nPad))[col];
+            best = (c == 0 || v < best) ? v : best;
+        }
+    }
+    return a.below ? best < a.threshold : best >= a.threshold;
+}
+
 template <class Args>
 __device__ __forceinline__ void selectCount(const Args& a) {
     __shared__ unsigned waveCount[kWaves];
@@ -110,6 +135,7 @@ __device__ __forceinline__ void selectCount(const Args& a) {
 
 __global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) { selectCount(a); }
 __global__ __launch_bounds__(kLanes) void fx_match_count(MatchSelectArgs a) { selectCount(a); }
+__global__ __launch_bounds__(kLanes) void fx_level_count(LevelSelectArgs a) { selectCount(a); }
 
 // one workgroup: offsets[0 .. chunks - 1] counts -> their exclusive scan, offsets[chunks] = the total.  Lane t owns the `per`
 // consecutive counts from t * per on: the loads of one lane are independent, so their latencies overlap
@@ -157,6 +183,7 @@ __device__ __forceinline__ void selectEmit(const Args& a) {
 
 __global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) { selectEmit(a); }
 __global__ __launch_bounds__(kLanes) void fx_match_emit(MatchSelectArgs a) { selectEmit(a); }
+__global__ __launch_bounds__(kLanes) void fx_level_emit(LevelSelectArgs a) { selectEmit(a); }
 
 // fx_meter_best: wavefront w of the grid owns group firstGroup + w.  Its local members are the columns lo .. hi - 1; lane l
 // looks at lo + l, lo + l + 64, ... and keeps the best (V, n).  kNone marks a lane that has seen no member (a group below 64).
@@ -249,6 +276,36 @@ __device__ __forceinline__ void meterColumns(const MeterListArgs& a) {
 __global__ __launch_bounds__(kLanes) void fx_meter_gather(MeterListArgs a) { meterColumns<true>(a); }
 __global__ __launch_bounds__(kLanes) void fx_meter_zero(MeterListArgs a) { meterColumns<false>(a); }
 
+// meterColumns on the two level rows: the packed side is level [channels][count], then quiet [channels][count]
+template <bool kGather>
+__device__ __forceinline__ void levelColumns(const MeterListArgs& a) {
+    const long long k = (long long)blockIdx.x * kLanes + threadIdx.x;
+    if (k >= a.count) return;
+    const long long inst = a.list[k];
+    if (inst < 0 || inst >= a.n) return;
+    const size_t rowWords = (size_t)a.channels * (size_t)a.count;
+    uint32_t* const pLevel = static_cast<uint32_t*>(a.packed);
+    uint32_t* const pQuiet = pLevel + rowWords;
+    char* ch = static_cast<char*>(a.rows);
+    for (int c = 0; c < a.channels; ++c, ch += levelChannelBytes(a.nPad)) {
+        uint32_t* level = reinterpret_cast<uint32_t*>(ch + levelLevelOff(a.nPad)) + inst;
+        uint32_t* quiet = reinterpret_cast<uint32_t*>(ch + levelQuietOff(a.nPad)) + inst;
+        if (kGather) {
+            const size_t at = (size_t)c * (size_t)a.count + (size_t)k;
+            const uint32_t l = *level, q = *quiet;
+            pLevel[at] = l;
+            pQuiet[at] = q;
+        }
+        if (!kGather || a.reset) {
+            *level = 0u;
+            *quiet = 0u;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void fx_level_gather(MeterListArgs a) { levelColumns<true>(a); }
+__global__ __launch_bounds__(kLanes) void fx_level_zero(MeterListArgs a) { levelColumns<false>(a); }
+
 inline bool badList(const MeterListArgs& a, bool gather) {
     if (!a.rows || !a.list || a.count < 1 || a.count >= ((long long)1 << 31) || a.n < 1 || a.nPad < a.n) return true;
     if (a.channels < 1 || a.channels > 4) return true;
@@ -284,6 +341,35 @@ hipError_t launchMatchSelect(const MatchSelectArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
     if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
     hipLaunchKernelGGL(fx_match_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchLevelSelect(const LevelSelectArgs& a, hipStream_t stream) {
+    if (!a.rows || !a.offsets || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.stat < 0 || a.stat > 1) return hipErrorInvalidValue;
+    if (a.first < 0 || a.nRange < 1 || a.first > a.n - a.nRange || a.cap < 0 || (a.cap > 0 && !a.list) || a.threshold != a.threshold) return hipErrorInvalidValue;
+    const long long chunks = meterSelectChunks(a.nRange);
+    if (chunks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_level_count, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
+    if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
+    hipLaunchKernelGGL(fx_level_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchLevelGather(const MeterListArgs& a, hipStream_t stream) {
+    if (badList(a, true)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_level_gather, dim3((unsigned)((a.count + kLanes - 1) / kLanes)), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchLevelZero(const MeterListArgs& a, hipStream_t stream) {
+    if (badList(a, false)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_level_zero, dim3((unsigned)((a.count + kLanes - 1) / kLanes)), dim3(kLanes), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -99,4 +99,32 @@ hipError_t launchMeterBest(const MeterBestArgs& a, hipStream_t stream);
 // unused).  Stores only; repeats are fine; an entry outside [0, n) is skipped.
 hipError_t launchMatchZero(const MeterListArgs& a, hipStream_t stream);
 
+// ---- queries over the level rows (fx_meter.hpp; include/fx8010_amd.h "Level meters") ------------------------------------------
+// The value of an instance: stat 0 (envelope) the MAXIMUM over the channels of (double)level, stat 1 (quiet run) the MINIMUM over
+// the channels of (double)quiet - a voice has been quiet for k samples only if every channel has.  Both convert to fp64 without
+// rounding and no level is ever NaN, so V >= t and V < t stay complements.
+
+struct LevelSelectArgs {
+    const void* rows;              // [channels] x the level rows (device memory)
+    unsigned long long* offsets;   // as MeterSelectArgs
+    long long* list;
+    long long n, nPad;
+    long long first, nRange;
+    long long firstGlobal;
+    long long cap;
+    double threshold;
+    int channels;                  // 1..4
+    int stat;                      // 0 envelope, 1 quiet run
+    int below;
+};
+// the three launches of launchMeterSelect (fx_level_count / fx_meter_scan / fx_level_emit) with the predicate above
+hipError_t launchLevelSelect(const LevelSelectArgs& a, hipStream_t stream);
+
+// bytes of the packed side of a level gather: level f32 [channels][count], then quiet u32 [channels][count]
+constexpr size_t levelPackedBytes(int channels, long long count) { return (size_t)channels * (size_t)count * 8; }
+// fx_level_gather / fx_level_zero: launchMeterGather / launchMeterZero on the two level rows (MeterListArgs with rows = the level
+// rows and the packed side above).  One lane per list entry; with `reset` the lane that has read a column stores its zeros.
+hipError_t launchLevelGather(const MeterListArgs& a, hipStream_t stream);
+hipError_t launchLevelZero(const MeterListArgs& a, hipStream_t stream);
+
 }  // namespace fx

@@ -370,26 +370,36 @@ int64_t Sharded::meterSamples() {
 }
 
 int64_t Sharded::meterSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
-    return selectRange(false, stat, threshold, first, nRange, list, cap, flags);
+    return selectRange(SelectRows::kMeter, stat, threshold, first, nRange, list, cap, flags);
 }
 int64_t Sharded::meterSelectMatch(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
-    return selectRange(true, stat, threshold, first, nRange, list, cap, flags);
+    return selectRange(SelectRows::kMatch, stat, threshold, first, nRange, list, cap, flags);
+}
+int64_t Sharded::meterSelectLevel(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+    return selectRange(SelectRows::kLevel, stat, threshold, first, nRange, list, cap, flags);
 }
 
-// match: over the match rows of a target (Batch::matchSelect) - other refusals and another predicate, the same ranges and joins
-int64_t Sharded::selectRange(bool match, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+// rows: kMatch over the match rows of a target (Batch::matchSelect), kLevel over the level rows (Batch::levelSelect) - other
+// refusals and another predicate, the same ranges and joins
+int64_t Sharded::selectRange(SelectRows rows, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
     Serial serial(api_);
     lastError_.clear();
-    if ((match ? Batch::checkMatchSelect : Batch::checkMeterSelect)(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
+    const bool match = rows == SelectRows::kMatch, level = rows == SelectRows::kLevel;
+    if ((match ? Batch::checkMatchSelect : level ? Batch::checkLevelSelect : Batch::checkMeterSelect)(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
     if (match && !front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
+    if (level && !front().meterLevelOn()) { lastError_ = "level meters: the mode is off (fxb_meter_set_level)"; return FX_E_ARG; }
     if (nRange == 0) return 0;
     const bool below = (flags & FXB_METER_BELOW) != 0;
+    const auto select = [&](Batch& b, int64_t from, int64_t count, int64_t firstGlobal, int64_t* out) {
+        return match ? b.matchSelect(stat, threshold, below, from, count, firstGlobal, out, cap)
+                     : level ? b.levelSelect(stat, threshold, below, from, count, firstGlobal, out, cap) : b.meterSelect(stat, threshold, below, from, count, firstGlobal, out, cap);
+    };
     if (shards_.size() == 1) {
         if (const int rc = runOn(0, [&](Batch& b) { return b.reserveMeterSelect(nRange, cap); })) return rc;
         int64_t m = 0;
         const int rc = runOn(0, [&](Batch& b) {
-            m = match ? b.matchSelect(stat, threshold, below, first, nRange, first, list, cap) : b.meterSelect(stat, threshold, below, first, nRange, first, list, cap);
+            m = select(b, first, nRange, first, list);
             return m < 0 ? (int)m : 0;
         });
         return rc != 0 ? rc : m;
@@ -411,8 +421,7 @@ int64_t Sharded::selectRange(bool match, int stat, double threshold, int64_t fir
     const int rc = fan([&](int k, Batch& b) {
         Part& p = parts[(size_t)k];
         if (p.count == 0) return 0;
-        const int64_t firstGlobal = shards_[(size_t)k]->first + p.first;
-        p.m = match ? b.matchSelect(stat, threshold, below, p.first, p.count, firstGlobal, p.found.data(), cap) : b.meterSelect(stat, threshold, below, p.first, p.count, firstGlobal, p.found.data(), cap);
+        p.m = select(b, p.first, p.count, shards_[(size_t)k]->first + p.first, p.found.data());
         return p.m < 0 ? (int)p.m : 0;
     });
     if (rc != 0) return rc;
@@ -447,6 +456,45 @@ int Sharded::meterResetList(const int64_t* list, int64_t count) {
     const ShardLists l(*this, list, count);
     if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(l.count(k), false); })) return rc;
     return fan([&](int k, Batch& b) { return b.meterResetList(l.list(k), l.count(k)); });
+}
+
+int Sharded::meterSetLevel(float release, float floor, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (Batch::checkMeterLevel(&release, &floor, flags, &lastError_) != 0) return FX_E_ARG;
+    if (const int rc = reserveOnAll([](int, Batch& b) { return b.reserveMeterLevel(); }, [](Batch& b) { b.releaseMeterLevel(); })) return rc;
+    return fan([&](int, Batch& b) { return b.setMeterLevel(release, floor); });
+}
+int Sharded::meterClearLevel() {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([](int, Batch& b) { return b.clearMeterLevel(); });
+}
+int Sharded::meterGetLevel(float* release, float* floor) {
+    Serial serial(api_);
+    lastError_.clear();
+    return runOn(0, [&](Batch& b) { return b.getMeterLevel(release, floor); });
+}
+int Sharded::meterReadLevel(float* level, uint32_t* quiet, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        return b.meterReadLevel(level ? level + first : nullptr, quiet ? quiet + first : nullptr, reset, n_);
+    });
+}
+int Sharded::meterReadLevelList(const int64_t* list, int64_t count, float* level, uint32_t* quiet, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterList("meter_read_level_list", list, count, n_, reset, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (!front().meterLevelOn()) { lastError_ = "level meters: the mode is off (fxb_meter_set_level)"; return FX_E_ARG; }
+    if (count == 0) return 0;
+    const ShardLists l(*this, list, count);
+    // every shard is asked for its staging first: with reset, no shard zeroes a word unless all of them can answer
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(l.count(k), true); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterReadLevelList(l.list(k), l.pos(k), l.count(k), count, level, quiet, reset); });
 }
 
 int Sharded::meterSetTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags) {
@@ -1065,6 +1113,7 @@ int64_t Sharded::info(int what) {
         what == FXB_INFO_REGISTER_LIST_SETS || what == FXB_INFO_REGISTER_LIST_GETS || what == FXB_INFO_TRAM_LIST_SETS || what == FXB_INFO_TRAM_LIST_GETS ||
         what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS || what == FXB_INFO_TRACK_LIST_EXPANDS ||
         what == FXB_INFO_METER_TARGET_LAUNCHES || what == FXB_INFO_METER_MATCH_SELECTS || what == FXB_INFO_METER_MATCH_BESTS ||
+        what == FXB_INFO_METER_LEVEL_LAUNCHES || what == FXB_INFO_METER_LEVEL_SELECTS || what == FXB_INFO_METER_LEVEL_LIST_READS ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

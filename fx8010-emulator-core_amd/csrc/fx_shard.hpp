@@ -104,6 +104,16 @@ public:
     int meterReadMatch(double* err, double* cross, bool reset);
     int64_t meterSelectMatch(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     int meterBest(int stat, int64_t group, int64_t* winner, double* value, unsigned flags);
+    // level meters (Batch "Level meters"): the arguments are checked for the whole handle; every shard reserves its level rows
+    // before any shard changes - FX_E_MEMORY leaves the mode off everywhere (or, with the mode on, as it was).  get is shard 0's.
+    // readLevel gives each shard its columns like meterRead, readLevelList its entries like meterReadList; selectLevel is
+    // meterSelect with the level predicate.
+    int meterSetLevel(float release, float floor, unsigned flags);
+    int meterClearLevel();
+    int meterGetLevel(float* release, float* floor);
+    int meterReadLevel(float* level, uint32_t* quiet, bool reset);
+    int meterReadLevelList(const int64_t* list, int64_t count, float* level, uint32_t* quiet, bool reset);
+    int64_t meterSelectLevel(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     // bus gains (Batch::busSetGains ...): `gains` is [channels][all instances] by global instance, checked as a whole (every value
     // finite) before any shard is posted; every shard reserves its blocks first and only when all of them could is any shard's
     // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.
@@ -192,7 +202,8 @@ public:
 
 private:
     int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
-    int64_t selectRange(bool match, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
+    enum class SelectRows { kMeter, kMatch, kLevel };
+    int64_t selectRange(SelectRows rows, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     int registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out);
     int tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set);
     struct Worker {

@@ -363,6 +363,27 @@ public:
     void meterBest(int stat, int64_t group, int64_t* winner, double* value, unsigned flags = 0) {
         if (fxb_meter_best(h_, stat, group, winner, value, flags) < 0) throw std::runtime_error(std::string("FX8010Batch::meterBest: ") + fxb_last_error(h_));
     }
+    // Level meters (include/fx8010_amd.h "Level meters"): an envelope with instant attack and exponential release and the count of
+    // consecutive samples below `floor`, per channel and instance.  meterReadLevel fills [channels][instances] arrays,
+    // meterReadLevelList [channels][list.size()]; meterSelectLevel is meterSelect over the channel maximum of FXB_LEVEL_ENVELOPE or
+    // the channel minimum of FXB_LEVEL_QUIET.
+    void meterSetLevel(float release, float floor = 0.0f) {
+        if (fxb_meter_set_level(h_, release, floor, 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterSetLevel: ") + fxb_last_error(h_));
+    }
+    void meterClearLevel() {
+        if (fxb_meter_clear_level(h_) < 0) throw std::runtime_error(std::string("FX8010Batch::meterClearLevel: ") + fxb_last_error(h_));
+    }
+    void meterReadLevel(float* level, uint32_t* quiet, bool reset = false) {
+        if (fxb_meter_read_level(h_, level, quiet, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterReadLevel: ") + fxb_last_error(h_));
+    }
+    void meterReadLevelList(const std::vector<int64_t>& list, float* level, uint32_t* quiet, bool reset = false) {
+        if (fxb_meter_read_level_list(h_, list.data(), (int64_t)list.size(), level, quiet, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterReadLevelList: ") + fxb_last_error(h_));
+    }
+    int64_t meterSelectLevel(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags = 0) {
+        const int64_t m = fxb_meter_select_level(h_, stat, threshold, first, nRange, list, cap, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterSelectLevel: ") + fxb_last_error(h_));
+        return m;
+    }
     // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
     // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
     // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and

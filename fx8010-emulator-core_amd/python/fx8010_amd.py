@@ -31,6 +31,7 @@ INFO = {
     "tram_list_sets": 55, "tram_list_gets": 56,
     "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59, "track_list_expands": 60,
     "meter_target_launches": 61, "meter_match_selects": 62, "meter_match_bests": 63,
+    "meter_level_launches": 64, "meter_level_selects": 65, "meter_level_list_reads": 66,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -40,6 +41,7 @@ METER_BELOW = 1
 METER_TARGET_LOOP = 1  # FXB_METER_TARGET_LOOP: the flag of meter_set_target
 MATCH_ERROR, MATCH_CROSS = 0, 1  # FXB_MATCH_*: the `stat` of meter_select_match and meter_best
 MATCH_LARGEST = 2  # FXB_MATCH_LARGEST: the flag of meter_best
+LEVEL_ENVELOPE, LEVEL_QUIET = 0, 1  # FXB_LEVEL_*: the `stat` of meter_select_level
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -58,6 +60,7 @@ SYMBOLS = [
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances", "fxb_load_instances_rotated",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples", "fxb_meter_select", "fxb_meter_read_list", "fxb_meter_reset_list",
     "fxb_meter_set_target", "fxb_meter_clear_target", "fxb_meter_target_seek", "fxb_meter_target_pos", "fxb_meter_read_match", "fxb_meter_select_match", "fxb_meter_best",
+    "fxb_meter_set_level", "fxb_meter_clear_level", "fxb_meter_get_level", "fxb_meter_read_level", "fxb_meter_read_level_list", "fxb_meter_select_level",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -131,6 +134,8 @@ def load():
     sig("fxb_meter_select", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_read_list", i32, vp, vp, i64, vp, vp, vp, vp, i32); sig("fxb_meter_reset_list", i32, vp, vp, i64)
     sig("fxb_meter_set_target", i32, vp, vp, i64, i64, C.c_uint); sig("fxb_meter_clear_target", i32, vp); sig("fxb_meter_target_seek", i32, vp, i64); sig("fxb_meter_target_pos", i64, vp)
     sig("fxb_meter_read_match", i32, vp, vp, vp, i32); sig("fxb_meter_select_match", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_best", i32, vp, i32, i64, vp, vp, C.c_uint)
+    sig("fxb_meter_set_level", i32, vp, f32, f32, C.c_uint); sig("fxb_meter_clear_level", i32, vp); sig("fxb_meter_get_level", i32, vp, vp, vp)
+    sig("fxb_meter_read_level", i32, vp, vp, vp, i32); sig("fxb_meter_read_level_list", i32, vp, vp, i64, vp, vp, i32); sig("fxb_meter_select_level", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -1035,6 +1040,52 @@ class Batch(_Reports):
         winner, value = np.full(g, -1, dtype=np.int64), np.zeros(g, dtype=np.float64)
         self._check(self._lib.fxb_meter_best(self._h, int(stat), group, C.c_void_p(winner.ctypes.data), C.c_void_p(value.ctypes.data), MATCH_LARGEST if largest else 0), "meter_best")
         return winner, value
+
+    def meter_set_level(self, release, floor=0.0):
+        """Turn the level meters on (include/fx8010_amd.h "Level meters"): from now on the meter launch of every block also keeps,
+        per channel and instance, an envelope - level = max(|y|, level * release) per sample - and the count of consecutive samples
+        with |y| < floor.  0 <= release <= 1 (from a time constant: np.float32(np.exp(-1 / (tau * rate)))), floor >= 0.  The first
+        call waits as sync() does and allocates; a call while the mode is on changes the parameters of later blocks only."""
+        return self._check(self._lib.fxb_meter_set_level(self._h, float(release), float(floor), 0), "meter_set_level")
+
+    def meter_clear_level(self):
+        """Turn the level meters off: the two rows are freed; the other meters go on."""
+        return self._check(self._lib.fxb_meter_clear_level(self._h), "meter_clear_level")
+
+    def meter_get_level(self):
+        """(release, floor) in force; an error while the level meters are off"""
+        release, floor = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._lib.fxb_meter_get_level(self._h, C.byref(release), C.byref(floor)), "meter_get_level")
+        return release.value, floor.value
+
+    def meter_read_level(self, reset=False):
+        """{"level": float32, "quiet": uint32}, each [channels, N] by global instance.  Synchronous; reset zeroes these two rows only."""
+        shape = (self.channels, self.n)
+        out = {"level": np.empty(shape, dtype=np.float32), "quiet": np.empty(shape, dtype=np.uint32)}
+        self._check(self._lib.fxb_meter_read_level(self._h, C.c_void_p(out["level"].ctypes.data), C.c_void_p(out["quiet"].ctypes.data), 1 if reset else 0), "meter_read_level")
+        return out
+
+    def meter_read_level_list(self, instances, reset=False):
+        """{"level", "quiet"}, each [channels, len(instances)]: the level meters of the listed instances, gathered on the device.
+        An instance may repeat unless reset is set."""
+        lst = self._instance_list(instances)
+        shape = (self.channels, int(lst.size))
+        out = {"level": np.empty(shape, dtype=np.float32), "quiet": np.empty(shape, dtype=np.uint32)}
+        self._check(self._lib.fxb_meter_read_level_list(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size),
+                                                        C.c_void_p(out["level"].ctypes.data) if lst.size else None, C.c_void_p(out["quiet"].ctypes.data) if lst.size else None,
+                                                        1 if reset else 0), "meter_read_level_list")
+        return out
+
+    def meter_select_level(self, stat, threshold, below=False, first=0, n_range=None, cap=None):
+        """meter_select over the level meters: V is the maximum over the channels of the envelope (LEVEL_ENVELOPE) or the MINIMUM
+        over the channels of the quiet run (LEVEL_QUIET).  (list, M)."""
+        first = int(first)
+        n_range = self.n - first if n_range is None else int(n_range)
+        cap = n_range if cap is None else int(cap)
+        out = np.empty(max(min(cap, n_range), 0), dtype=np.int64)
+        m = self._check(int(self._lib.fxb_meter_select_level(self._h, int(stat), float(threshold), first, n_range, C.c_void_p(out.ctypes.data) if out.size else None,
+                                                             cap, METER_BELOW if below else 0)), "meter_select_level")
+        return out[:min(m, out.size)], m
 
     def meter_samples(self):
         """sample periods metered since the last reset"""

@@ -878,6 +878,70 @@ int     fxb_meter_read_match(fxb_handle* h, double* err, double* cross, int rese
 #define FXB_MATCH_LARGEST (1u << 1)
 int64_t fxb_meter_select_match(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
 int     fxb_meter_best(fxb_handle* h, int stat, int64_t group, int64_t* winner, double* value, unsigned flags);
+/* Level meters: an envelope that falls and a quiet-run count per instance, on the device.  The six accumulators above only grow
+ * after a reset - `peak` is a running maximum - so they cannot say which voices have STOPPED sounding.  With the level mode on, the
+ * meter launch of every block also takes two accumulators that fall as well as rise: a PPM-style level with instant attack and
+ * exponential release, and the number of consecutive samples below a floor ("below -80 dB for 4 800 samples: the slot is free").
+ * Both are sample-by-sample recurrences carried in device memory.  With the mode off nothing changes: the same kernels, the same
+ * arguments, no allocation.
+ *
+ * The definition.  fxb_meter_set_level(h, release, floor, flags) turns the mode on.  `release` is an fp32 value, finite, with
+ *   0 <= release <= 1; `floor` is an fp32 value, finite, with floor >= 0; `flags` must be 0.  Each (channel c, instance n) gets two
+ *   further accumulators: `level` (fp32), +0.0f after a reset; `quiet` (uint32), 0 after a reset.  For every output word y of that
+ *   column, in sample order, with fin and w exactly those of "Output meters":
+ *       fin   = |y| < +Inf
+ *       w     = fin ? |y| : +0.0f
+ *       d     = level * release      (one fp32 multiply, one rounding, denormals kept, never fused with anything)
+ *       level = max(w, d)            (both are non-negative and finite: the larger bit pattern)
+ *       loud  = !fin || w >= floor   (fp32 compare; a NaN or an infinity is loud)
+ *       quiet = loud ? 0 : (quiet == 0xFFFFFFFF ? quiet : quiet + 1)
+ *   The four existing accumulators are taken exactly as now, for every sample; with a target set, `err` and `cross` are too.
+ *   Consequences:
+ *     - release = 1 makes `level` the running peak since the reset: it equals `peak` bit for bit.
+ *     - release = 0 makes `level` the magnitude of the last sample (+0 where that sample is not finite).
+ *     - floor = 0 turns the counter off: it stays 0.
+ *     - A non-finite voice is never "quiet".  It is found with FXB_METER_NONFINITE.
+ *     - With a release close to 1 the envelope of a silent voice can come to rest at a small denormal instead of 0, because
+ *       x * release rounds back to x once x * (1 - release) is at most half a denormal step (with release = 0.999 it stops
+ *       falling at the bit pattern 500, with 0.93 at 7).  Compare it with a threshold, never with 0.
+ *     - The figures do not depend on how a stream is cut - blocks of 16 + 17 samples against 33, the pieces of the bus scratch
+ *       and of a large host block, the segments of an armed control track, the shards.
+ *
+ * fxb_meter_set_level: the first call waits as fxb_sync does.  It allocates and zeroes the level rows on every shard - per
+ *   channel level f32 [nPad], then quiet u32 [nPad], a block of their own: 8 bytes per instance and channel.  Every shard is asked
+ *   before any shard changes, so FX_E_MEMORY leaves the mode off everywhere and the handle usable.  All allocation for the feature
+ *   happens here, never in a block.  A call while the mode is on changes only the two parameters, for blocks queued after it, and
+ *   keeps the accumulators; it does not wait.  The parameters travel by value in each launch's arguments.  FX_E_ARG, with nothing
+ *   changed, for: metering off; a NaN, infinite or out-of-range `release`; a NaN, infinite or negative `floor` (-0.0 is taken as
+ *   0, for both); a non-zero flag.
+ * Resets.  fxb_meter_clear_level and fxb_meter_enable(h, 0) free the rows.  A program load zeroes the rows and keeps the mode and
+ *   its parameters, as it does for the four accumulators.  fxb_meter_read(..., reset = 1) zeroes the level rows as well;
+ *   fxb_meter_read_level(..., reset = 1) zeroes only the level rows.  fxb_meter_reset_list zeroes the listed columns of the level
+ *   rows too - a reused slot gets fresh meters, all of them - by one more stores-only launch (fx_level_zero) queued beside
+ *   fx_meter_zero / fx_match_zero, inside the same event frame.  Instance copy, reset, save and load leave the level rows alone,
+ *   as they leave every meter alone.
+ * fxb_meter_get_level: the two parameters in force (either pointer may be NULL); FX_E_ARG while level meters are off.
+ * fxb_meter_read_level / fxb_meter_read_level_list are fxb_meter_read / fxb_meter_read_list on the two new rows:
+ *   [num_channels][N] and [num_channels][count] by (global) instance, either pointer may be NULL, synchronous.  A list may repeat
+ *   an instance unless reset != 0; with reset, one lane of one launch reads and zeroes the same column.  The refusals are the
+ *   same; FX_E_ARG while level meters are off.
+ * fxb_meter_select_level: FXB_LEVEL_ENVELOPE: V(n) = the maximum over the channels of (double)level.  FXB_LEVEL_QUIET: V(n) = the
+ *   MINIMUM over the channels of (double)quiet - a voice has been quiet for k samples only if every channel has.  Everything else
+ *   is fxb_meter_select's: the ordered compaction without atomics, FXB_METER_BELOW, the cap, range and NaN-threshold rules, shard
+ *   concatenation, cap == 0 as a count query.  `stat` outside 0..1 is FX_E_ARG; so are level meters off.  fxb_meter_select and
+ *   fxb_meter_select_match keep their own `stat` ranges.
+ * FXB_INFO_METER_LEVEL_LAUNCHES counts the meter launches that took the level rows (fx_meter_level, fx_meter_target_level).
+ *   FXB_INFO_METER_LAUNCHES keeps counting the meter launches of blocks without a target, FXB_INFO_METER_TARGET_LAUNCHES those
+ *   with one, whichever kernel ran: a block is still metered by exactly one launch.  FXB_INFO_METER_LEVEL_SELECTS /
+ *   _LEVEL_LIST_READS count the calls that launched.  All are summed over shards. */
+#define FXB_LEVEL_ENVELOPE 0
+#define FXB_LEVEL_QUIET    1
+int     fxb_meter_set_level(fxb_handle* h, float release, float floor, unsigned flags);
+int     fxb_meter_clear_level(fxb_handle* h);
+int     fxb_meter_get_level(fxb_handle* h, float* release, float* floor);        /* FX_E_ARG while level meters are off */
+int     fxb_meter_read_level(fxb_handle* h, float* level, uint32_t* quiet, int reset);          /* [C][N]; pointers may be NULL */
+int     fxb_meter_read_level_list(fxb_handle* h, const int64_t* list, int64_t count, float* level, uint32_t* quiet, int reset); /* [C][count] */
+int64_t fxb_meter_select_level(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -980,6 +1044,9 @@ enum {
     FXB_INFO_METER_TARGET_LAUNCHES = 61, /* launches of the kernel fx_meter_target - the meter launch of a block while a target is set (fxb_meter_set_target) - since creation (summed over shards) */
     FXB_INFO_METER_MATCH_SELECTS = 62,   /* calls of fxb_meter_select_match that launched (fx_match_count / fx_meter_scan / fx_match_emit) since creation (summed over shards) */
     FXB_INFO_METER_MATCH_BESTS = 63,     /* calls of fxb_meter_best that launched (fx_meter_best) since creation (summed over shards) */
+    FXB_INFO_METER_LEVEL_LAUNCHES = 64,  /* meter launches that took the level rows (fx_meter_level, fx_meter_target_level) since creation (summed over shards) */
+    FXB_INFO_METER_LEVEL_SELECTS = 65,   /* calls of fxb_meter_select_level that launched (fx_level_count / fx_meter_scan / fx_level_emit) since creation (summed over shards) */
+    FXB_INFO_METER_LEVEL_LIST_READS = 66, /* calls of fxb_meter_read_level_list that launched (fx_level_gather) since creation (summed over shards) */
     FXB_INFO_TRACK_LIST_EXPANDS = 60   /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
 };
 int64_t fxb_info(fxb_handle* h, int what);
