@@ -21,32 +21,10 @@ from test_bus_stub import CSRC, FX_E_ARG, FX_E_MEMORY, MIX_OUT, PROGRAM, ROOT, S
 from test_bus_gain_stub import gain_mix_model, gain_weights, gains_for  # noqa: E402
 from test_bus_tap_stub import same_bits, signal, tap_list  # noqa: E402
 from test_bus_send_stub import send_model, structure  # noqa: E402
+from route_models import feed_model  # noqa: E402,F401  (the models live there; the tests of them stay here)
 
 MOST_ENTRIES = 1 << 24
 COUNTS = (0, 1, 2, 5, 65)   # entries of an instance: none, the moved word, one add, a short list, more than a wavefront is wide
-
-
-def feed_model(src, offsets, sources, a, b, ramp, S):
-    """src: [S, C, M], a / b: [C, E] (b None: unweighted) -> [S, C, N]: the definition of include/fx8010_amd.h "Bus feeds".
-    Instance n owns the entries offsets[n] .. offsets[n+1] - 1; entry e has x = src[s, c, sources[e]] and the term x (unweighted)
-    or (w == 0 ? +0.0 : w * x) with the weights of "Bus gains" by entry; the word is +0.0 for no entry, term_0 for one (a select:
-    the pattern moves), else ((term_0 + term_1) + term_2) + ... (numpy adds float32 arrays in float32, round to nearest, one
-    rounding per add, denormals kept)"""
-    src = np.ascontiguousarray(src, dtype=np.float32)
-    offsets, sources = np.asarray(offsets, dtype=np.int64), np.asarray(sources, dtype=np.int64)
-    assert src.ndim == 3 and src.shape[0] == S
-    N = offsets.size - 1
-    count = np.diff(offsets)
-    out = np.zeros(src.shape[:2] + (N,), dtype=np.float32)
-    w = None if b is None else gain_weights(b if a is None else a, b, ramp, S)   # [S, C, E]
-    with np.errstate(all="ignore"):
-        for k in range(int(count.max()) if N else 0):
-            has = k < count
-            e = np.where(has, offsets[:-1] + k, 0)
-            x = src[:, :, sources[e]]
-            term = x if w is None else np.where(w[:, :, e] == 0.0, np.float32(0.0), w[:, :, e] * x).astype(np.float32)
-            out = np.where(has, term if k == 0 else out + term, out)
-    return np.ascontiguousarray(out, dtype=np.float32)
 
 
 def feed_structure(rng, N, M, counts=COUNTS):

@@ -16,42 +16,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_bus_stub import CSRC, FX_E_ARG, FX_E_MEMORY, MIX_OUT, PROGRAM, ROOT, SHARED_IN, STEREO, Pinned, bus, expand, mix_model, same_words, stub_library  # noqa: E402
+from route_models import DENORMAL, TINY, HUGE, gain_weights, gain_mix_model, gains_for  # noqa: E402,F401  (the models live there; the tests of them stay here)
 
 SHAPES = ((1, 1), (5, 2), (65, 64), (200, 63), (200, 65), (777, 130), (300, 1000))   # (N, K)
-DENORMAL, TINY, HUGE = np.float32(1e-41), np.float32(2.0 ** -126), np.float32(1e30)
-
-
-def gain_weights(a, b, ramp, S):
-    """[S, C, N] float32: the weight of every member at every sample of a call of S samples (numpy works on float32 arrays in
-    float32, round to nearest, one rounding per operation, denormals kept)"""
-    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
-    if not ramp:
-        return np.ascontiguousarray(np.broadcast_to(b, (S,) + b.shape))
-    r = np.float32(1.0) / np.float32(S)
-    t = np.arange(1, S + 1).astype(np.float32) * r          # (float)(s + 1) * r
-    with np.errstate(all="ignore"):
-        d = b - a
-        w = a[None] + d[None] * t[:, None, None]
-    w[S - 1] = b
-    return np.ascontiguousarray(w, dtype=np.float32)
-
-
-def gain_mix_model(y, a, b, ramp, S, K):
-    """y: [S, C, N], a / b: [C, N] -> [S, C, G]: the definition of include/fx8010_amd.h "Bus gains" feeding mix_model"""
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    assert y.shape[0] == S and y.ndim == 3
-    w = gain_weights(a, b, ramp, S)
-    with np.errstate(all="ignore"):
-        term = np.where(w == 0.0, np.float32(0.0), w * y).astype(np.float32)
-    return mix_model(term, K)
-
-
-def gains_for(rng, C_, N, special=True):
-    g = (rng.standard_normal((C_, N)) * 10.0 ** rng.integers(-3, 2, (C_, N))).astype(np.float32)
-    if special:
-        for i, v in enumerate((np.float32(0.0), np.float32(-0.0), np.float32(-1.5), DENORMAL, TINY, HUGE, -HUGE)):
-            g[(i // N) % C_, (i * 3) % N] = v   # (for N = 1 the last one stays)
-    return g
 
 
 def signal(rng, shape):

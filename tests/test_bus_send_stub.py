@@ -21,47 +21,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_bus_stub import CSRC, FX_E_ARG, FX_E_MEMORY, MIX_OUT, PROGRAM, ROOT, SHARED_IN, STEREO, Pinned, expand, mix_model, same_words, stub_library  # noqa: E402
 from test_bus_gain_stub import SHAPES, gain_mix_model, gain_weights, gains_for  # noqa: E402
 from test_bus_tap_stub import same_bits, signal, tap_list  # noqa: E402
+from route_models import CHUNK, tree, send_model  # noqa: E402,F401  (the models live there; the tests of them stay here)
 
-CHUNK = 1024
 SIZES = (0, 1, 63, 64, 65, 1024, 1025, 2049)   # the lane boundary, the chunk boundary, Q = 2 and Q = 3 with a one-entry last chunk
 MOST_BUSES, MOST_ENTRIES = 65536, 1 << 24
-
-
-def tree(seq):
-    """T of include/fx8010_amd.h "Bus sends" over the last axis, [..., L] -> [...]: 64 partial sums start at +0.0; v[j*64+l],
-    where it exists, is added to p[l] for j ascending; then p[l] = p[l] + p[l+step] for l < step, step = 32 .. 1; T is p[0]
-    (numpy adds float32 arrays in float32, round to nearest, one rounding per add, denormals kept)"""
-    seq = np.ascontiguousarray(seq, dtype=np.float32)
-    L = seq.shape[-1]
-    p = np.zeros(seq.shape[:-1] + (64,), dtype=np.float32)
-    with np.errstate(all="ignore"):
-        for j in range(-(-L // 64)):
-            w = min(64, L - j * 64)
-            p[..., :w] = p[..., :w] + seq[..., j * 64:j * 64 + w]
-        for step in (32, 16, 8, 4, 2, 1):
-            p[..., :step] = p[..., :step] + p[..., step:2 * step]
-    return np.ascontiguousarray(p[..., 0])
-
-
-def send_model(y, offsets, members, a, b, ramp, S):
-    """y: [S, C, N], a / b: [C, E] -> [S, C, A]: the definition of include/fx8010_amd.h "Bus sends".  The weights are those of
-    "Bus gains" by entry; the positions of a bus are cut into chunks of 1 024, a bus of one chunk is that chunk's T, a larger one
-    T over its chunk sums, an empty one +0.0"""
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    offsets, members = np.asarray(offsets, dtype=np.int64), np.asarray(members, dtype=np.int64)
-    assert y.ndim == 3 and y.shape[0] == S
-    A = offsets.size - 1
-    w = gain_weights(a, b, ramp, S)   # [S, C, E]
-    with np.errstate(all="ignore"):
-        term = np.where(w == 0.0, np.float32(0.0), w * y[:, :, members[:offsets[-1]]]).astype(np.float32)
-    out = np.zeros(y.shape[:2] + (A,), dtype=np.float32)
-    for bus in range(A):
-        lo, hi = int(offsets[bus]), int(offsets[bus + 1])
-        if hi - lo <= CHUNK:
-            out[:, :, bus] = tree(term[:, :, lo:hi])
-        else:
-            out[:, :, bus] = tree(np.stack([tree(term[:, :, q:min(q + CHUNK, hi)]) for q in range(lo, hi, CHUNK)], axis=-1))
-    return out
 
 
 def structure(rng, N, sizes):

@@ -12,6 +12,7 @@ import sys
 
 import numpy as np
 import pytest
+from route_models import mix_model, expand, same_words  # noqa: E402,F401  (the models live there; the tests of them stay here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fx8010-emulator-core_amd", "csrc")
@@ -20,46 +21,6 @@ SHARED_IN, MIX_OUT = 1, 2
 HIP_LAUNCH_FAILURE = 719
 PROGRAM = "input in 0\noutput out 0\ncontrol vol = 0.5\nstatic a\nmacs a, a, vol, in\nmacs out, a, in, 0.25\nend"
 STEREO = PROGRAM.replace("output out 0", "input in1 1\noutput out 0\noutput out1 1").replace("\nend", "\nmacs out1, in1, a, 0.5\nend")
-
-
-def mix_model(y, K):
-    """[..., N] -> [..., G]: every group's sum in the order include/fx8010_amd.h fixes, in fp32 (numpy adds float32 arrays in
-    float32, round to nearest, one rounding per add): 64 partial sums start at +0.0; member m = j * 64 + l of a group, where it
-    exists, is added to p[l] for j ascending; then p[l] = p[l] + p[l + step] for l < step, step = 32 ... 1; the sum is p[0].
-    Only the lanes below W = min(64, K) are held: no member is ever added to a lane at or above K, so those lanes are +0.0 when
-    the tree starts, a tree step can only give them +0.0 + +0.0, and where a step reads one of them it adds that +0.0."""
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    N = y.shape[-1]
-    K = min(int(K), N)
-    G, J, W = -(-N // K), -(-K // 64), min(64, K)
-    lead = y.shape[:-1]
-    members = np.zeros(lead + (G * K,), dtype=np.float32)
-    members[..., :N] = y
-    exists = np.arange(G * K) < N
-    members, exists = members.reshape(lead + (G, K)), exists.reshape(G, K)
-    p = np.zeros(lead + (G, W), dtype=np.float32)
-    with np.errstate(all="ignore"):
-        for j in range(J):
-            w = min(64, K - j * 64)
-            p[..., :w] = np.where(exists[:, j * 64:j * 64 + w], p[..., :w] + members[..., j * 64:j * 64 + w], p[..., :w])
-        for step in (32, 16, 8, 4, 2, 1):
-            held = min(step, W)                      # lanes l < step that are held
-            paired = max(0, min(W - step, step))     # ... whose partner l + step is held as well
-            other = np.zeros(lead + (G, held), dtype=np.float32)
-            other[..., :paired] = p[..., step:step + paired]
-            p[..., :held] = p[..., :held] + other
-    return np.ascontiguousarray(p[..., 0])
-
-
-def expand(x, K, N):
-    """[..., G] -> [..., N]: instance n hears column n // K"""
-    return np.ascontiguousarray(x[..., np.arange(N) // min(int(K), N)])
-
-
-def same_words(got, want):
-    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
-    nan = np.isnan(want)
-    return got.shape == want.shape and (np.isnan(got) == nan).all() and (got.view(np.uint32)[~nan] == want.view(np.uint32)[~nan]).all()
 
 
 def test_mix_model_is_the_order_it_says():

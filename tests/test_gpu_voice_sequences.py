@@ -29,7 +29,16 @@ TIERS = {
     "hip_2_per_lane": {"FX_KERNEL": "hip", "FX_INST_PER_LANE": "2"},
     "two_shards": {"FX_FUZZ_SHARDS": "2"},
 }
-CASES = [("main", t) for t in TIERS] + [("wild", "default"), ("dane", "default"), ("dane", "asm")]
+CASES = [("main", t) for t in TIERS] + [("wild", "default"), ("dane", "default"), ("dane", "asm"), ("staged", "default"), ("staged", "two_shards")]
+
+
+def ran_staged_code(cover, count):
+    """the staged range must not pass green on plain code: FXB_INFO_WAVES_PER_WG behind every device block (cover["staged_blocks"])"""
+    sb = cover["staged_blocks"]
+    assert sb["kernels"] and all(k >= 9 for k in sb["kernels"]), sb                # staged blocks ran translated code
+    assert sb["sequences"] == count, sb                                            # every sequence ran at least one staged block
+    assert sb["plain"][1] > sb["plain"][0], sb                                     # among blocks that armed no schedule, staged ones outnumber the others
+    assert sb["scheduled"][1] == 0 and sb["scheduled"][0] > 0, sb                  # a block with a track or a list schedule runs one wavefront per workgroup
 
 
 def set_env(monkeypatch, env):
@@ -44,12 +53,16 @@ def test_voice_sequences(gpu, slice_name, tier, monkeypatch):
     """20 sequences of 36 steps per case, every bit compared equal, and the same range once more with the model alone (half a
     second).  Measured on an MI355X, seconds per case: main-default 2.13, main-asm 1.62, main-hip 1.68, main-hip_2_per_lane 1.67,
     main-two_shards 1.85, wild-default 1.53, dane-default 1.63, dane-asm 1.53 (about 65 ms per sequence on the device: 20 is what
-    a second buys, 12 is the floor)."""
+    a second buys, 12 is the floor).
+    The staged range (generator 4 under FX_STAGES=4) also asserts that it ran staged code: ran_staged_code().  Measured:
+    staged-default 1.16 s, staged-two_shards 1.34 s; of the 151 device blocks that armed no schedule 114 ran staged (all on kernel
+    13) and 37 one wavefront per workgroup - behind their handle's first schedule, which ends staged code for that handle
+     -, the 31 blocks with a schedule one wavefront per workgroup, 20 of 20 sequences ran a staged block."""
     import fuzz_voices
     first, count, env = fuzz_voices.SLICES[slice_name]
     assert count >= 12
     set_env(monkeypatch, dict(env, **TIERS[tier]))
-    cover = fuzz_voices.new_cover()
+    cover = fuzz_voices.new_cover(stages=True)
     bad = [s for s in range(first, first + count) if not fuzz_voices.run(s, cover=cover)]
     assert bad == [], bad
     assert cover["loaded"] == count and cover["left_domain"] * 10 <= count, cover
@@ -57,7 +70,7 @@ def test_voice_sequences(gpu, slice_name, tier, monkeypatch):
     # stands at the same place of the random stream in front of every step and counts the same calls, accepted and refused
     alone = fuzz_voices.new_cover()
     assert all(fuzz_voices.run(s, device=False, cover=alone) for s in range(first, first + count))
-    device_only = ("kernels", "sharded_handles")
+    device_only = ("kernels", "sharded_handles", "staged_blocks")
     assert {k: v for k, v in cover.items() if k not in device_only} == {k: v for k, v in alone.items() if k not in device_only}
     if tier == "two_shards":
         assert cover["sharded_handles"] >= 5, cover      # (N of 1, 63 and 64 is one wavefront: one batch)
@@ -71,6 +84,9 @@ def test_voice_sequences(gpu, slice_name, tier, monkeypatch):
         assert kernels and all(1 <= k <= 8 for k in kernels), kernels
     else:
         assert sum(v for k, v in kernels.items() if k >= 9) * 2 > sum(kernels.values()), kernels
+    print("staged blocks:", cover["staged_blocks"], "kernels:", kernels)
+    if slice_name == "staged":
+        ran_staged_code(cover, count)
 
 
 # switch -> what a report that notices THAT aspect says (the state reads name what differs; the list gets name themselves)
@@ -99,6 +115,24 @@ def test_a_wrong_model_is_noticed(gpu, switch, monkeypatch, capsys):
     assert len(reports) == len(noticed)
     # noticed in its own aspect, not through whatever the wrong state upsets later (a load refused, a block that differs)
     assert [r for r in reports if any(word in r for word in ASPECT[switch])], reports
+
+
+def test_a_wrong_model_is_noticed_between_staged_blocks(gpu, monkeypatch, capsys):
+    """the position rows live in stage 0 of staged code: a model whose reset zeroes them (FX_FUZZ_BREAK=reset_zeroes_positions)
+    must be reported on the staged range too, in its own aspect - and the range must have run staged code while it was.
+    Measured on an MI355X: 0.74 s; 7 of the 20 sequences notice; 104 staged and 31 other blocks without a
+    schedule, 26 with one."""
+    import fuzz_voices
+    first, count, env = fuzz_voices.SLICES["staged"]
+    set_env(monkeypatch, dict(env, FX_FUZZ_BREAK="reset_zeroes_positions"))
+    cover = fuzz_voices.new_cover(stages=True)
+    noticed = [s for s in range(first, first + count) if not fuzz_voices.run(s, cover=cover)]
+    assert noticed
+    reports = [line for line in capsys.readouterr().out.split("\n") if line.startswith("MISMATCH")]
+    assert len(reports) == len(noticed)
+    assert [r for r in reports if any(word in r for word in ASPECT["reset_zeroes_positions"])], reports
+    print("noticed by", len(noticed), "sequences; staged blocks:", cover["staged_blocks"])
+    ran_staged_code(cover, count)
 
 
 @pytest.mark.parametrize("mode, env", [("default", {}), ("asm", {"FX_KERNEL": "asm"}), ("hip", {"FX_KERNEL": "hip"}), ("two_shards", {"FX_FUZZ_SHARDS": "2"}),

@@ -13,6 +13,7 @@ import sys
 
 import numpy as np
 import pytest
+from route_models import FIELDS, meter_zero, meter_model, same_meters  # noqa: E402,F401  (the models live there; the tests of them stay here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fx8010-emulator-core_amd", "csrc")
@@ -21,41 +22,6 @@ SHARED_IN, MIX_OUT = 1, 2
 PROGRAM = "input in 0\noutput out 0\ncontrol vol = 0.5\nstatic a\nmacs a, a, vol, in\nmacs out, a, in, 0.25\nend"
 STEREO = PROGRAM.replace("output out 0", "input in1 1\noutput out 0\noutput out1 1").replace("\nend", "\nmacs out1, in1, a, 0.5\nend")
 MORE = "static zz\nmacs zz, zz, 0.5, 0.5\nend"   # a further load that succeeds: registers and instructions accumulate over loads
-FIELDS = ("energy", "peak", "full_scale", "nonfinite")
-
-
-def meter_zero(channels, N):
-    return {"energy": np.zeros((channels, N), dtype=np.float64), "peak": np.zeros((channels, N), dtype=np.float32),
-            "full_scale": np.zeros((channels, N), dtype=np.uint32), "nonfinite": np.zeros((channels, N), dtype=np.uint32)}
-
-
-def meter_model(y, acc=None):
-    """The definition of include/fx8010_amd.h, restated: y [S, channels, N] float32 is taken sample by sample into the four
-    accumulators `acc` (a new set when None).  One fp64 add of an exact product per sample; max; two saturating counts."""
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    S, channels, N = y.shape
-    acc = meter_zero(channels, N) if acc is None else {k: v.copy() for k, v in acc.items()}
-    with np.errstate(all="ignore"):
-        mag = np.abs(y)
-        fin = mag < np.float32(np.inf)                        # false for NaN and +-Inf
-        w = np.where(fin, mag, np.float32(0.0)).astype(np.float32)
-        for s in range(S):
-            wd = w[s].astype(np.float64)
-            acc["energy"] = acc["energy"] + wd * wd           # the product is exact: one rounding, in the add
-        if S:
-            acc["peak"] = np.maximum(acc["peak"], w.max(axis=0))
-        for key, hit in (("full_scale", fin & (mag >= np.float32(1.0))), ("nonfinite", ~fin)):
-            acc[key] = np.minimum(acc[key].astype(np.uint64) + hit.sum(axis=0, dtype=np.uint64), 0xFFFFFFFF).astype(np.uint32)
-    return acc
-
-
-def same_meters(got, want):
-    """bit for bit: fp64 and fp32 words are compared as integers"""
-    views = {"energy": np.uint64, "peak": np.uint32, "full_scale": np.uint32, "nonfinite": np.uint32}
-    for k in FIELDS:
-        if got[k].shape != want[k].shape or got[k].dtype != want[k].dtype or not np.array_equal(got[k].view(views[k]), want[k].view(views[k])):
-            return False
-    return True
 
 
 def test_meter_model_splits_and_counts():

@@ -63,6 +63,12 @@ def test_the_seed_ranges_cover_every_operation(name, monkeypatch):
     assert cover["rotated_nonzero"] >= 5 and cover["logical_wrap"] >= 5, cover
     assert cover["second_handles"] >= 3, cover
     assert seen["copy"] >= 10 and seen["loaded_back_at_once"] >= 3, seen
+    if name in STREAMS_BEFORE_GENERATOR_4:
+        assert cover["stream"] == STREAMS_BEFORE_GENERATOR_4[name], "the %s range no longer walks the sequences it walked" % name
+
+
+# cover["stream"] of the three ranges that existed before generator 4, computed with the file of the commit before it
+STREAMS_BEFORE_GENERATOR_4 = {"main": 848044523, "wild": 3596380567, "dane": 2584936414}
 
 
 def test_every_generator_and_every_kind_of_line_occurs():
@@ -78,6 +84,56 @@ def test_every_generator_and_every_kind_of_line_occurs():
             if prog.A[w] > 0:
                 kinds.add(("dane" if prog.dane else "reference", "ring" if prog.ring[w] else "no ring"))
     assert kinds == {("reference", "ring"), ("reference", "no ring"), ("dane", "ring")}, kinds
+
+
+def test_every_program_of_the_staged_range_is_cut_into_stages(monkeypatch):
+    """the staged range (generator 4) exists to run the by-list calls between blocks of STAGED code: every one of its programs is
+    cut into two to four stages by the front end when four are asked, as the slice's FX_STAGES=4 asks of the batch - and the
+    programs meet stage 0 with what the calls touch: delay lines and noise occur among them"""
+    clear(monkeypatch)
+    first, count, env = fuzz_voices.SLICES["staged"]
+    assert env == {"FX_FUZZ_GEN": "4", "FX_STAGES": "4", "FX_FUZZ_TRACKS_FROM": "12"}
+    cuts, with_lines, with_noise = [], 0, 0
+    for seed in range(first, first + count):
+        rng = np.random.default_rng(990000 + seed)
+        text, options = fuzz_voices.generate(seed, rng, 4)
+        assert options == 0
+        cuts.append(fuzz_voices.stages_cut(text, 4))
+        with_lines += "idelay write" in text
+        with_noise += any("noise" in l for l in text.split("\n") if not l.startswith("static"))
+    assert all(2 <= k <= 4 for k in cuts), cuts
+    assert len(set(cuts)) >= 2, cuts
+    assert with_lines >= 5 and with_noise >= 5, (with_lines, with_noise)
+    assert fuzz_voices.stages_cut(progs.config3(), 4) == 1      # (the helper says 1 for a program the planner cannot cut)
+    # a handle that has armed a schedule runs no staged code any more (its register stays trackable: DESIGN.md section 4.5), so the
+    # range arms them from step 12 on: most blocks without a schedule come in front of their handle's first one
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cover = fuzz_voices.new_cover()
+    assert all(fuzz_voices.run(seed, device=False, cover=cover) for seed in range(first, first + count))
+    before, behind = cover["plain_blocks"]
+    assert before >= 2 * behind and behind >= 10, cover["plain_blocks"]
+
+
+# sha256 over repr((seed, generator, options, text)) of generators 0 .. 3 on every seed of the main range, computed with
+# tools/fuzz_voices.py as it stood BEFORE generator 4 was added (the parent commit's file, not this one's)
+MAIN_TEXTS_BEFORE_GENERATOR_4 = "9a4e1aff290181c6b020fdc8ca86a042481ed9e380647151628ea8876da6aa4f"
+
+
+def test_generators_0_to_3_draw_what_they_drew_before_generator_4():
+    """the existing slices must walk exactly the sequences they walked: the program texts of generators 0 .. 3 over the main range
+    are those of the commit before generator 4 (whose cover and stream digests then follow, every later draw coming from the same
+    random stream)"""
+    import hashlib
+    first, count, env = fuzz_voices.SLICES["main"]
+    assert (first, count, env) == (0, 20, {})
+    h = hashlib.sha256()
+    for seed in range(first, first + count):
+        for gen in range(4):
+            rng = np.random.default_rng(990000 + seed)
+            text, options = fuzz_voices.generate(seed, rng, gen)
+            h.update(repr((seed, gen, options, text)).encode())
+    assert h.hexdigest() == MAIN_TEXTS_BEFORE_GENERATOR_4
 
 
 def test_the_sabotage_switches_only_touch_the_model(monkeypatch):

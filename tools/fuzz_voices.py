@@ -9,7 +9,13 @@ fxb_load_instances, fxb_load_instances_rotated, fxb_set_tram_list / fxb_get_tram
 samples, broadcast / per-instance / array register writes, dense control tracks, list schedules and fxb_prepare, as
 tools/fuzz_api.py draws them.  Programs come from four generators by seed (seed % 4): stress_fuzz.random_program (ring lines that
 move uniformly), stress_fuzz.random_program2 (write offsets, delay instructions in SKIP shadows: lines that are no rings, positions
-that differ per lane), fuzz_tram.random_tram_program in the reference model and in the DANE model.
+that differ per lane), fuzz_tram.random_tram_program in the reference model and in the DANE model.  A fifth generator is reached
+through FX_FUZZ_GEN=4 only: fuzz_stages.random_program, the feed-forward programs the stage planner CUTS (delay lines, noise, SKIP,
+LOG / EXP) - the first of at most 8 draws that the front end cuts into two or more stages when four are asked.
+
+The seed ranges of the test suite (SLICES): main (seeds 0.., the four generators by seed), wild (FX_FUZZ_WILD=1), dane (generator 3)
+and staged (generator 4 under FX_STAGES=4, schedules from step 12 on: the by-list calls between blocks of staged code;
+cover["staged_blocks"] counts, per device block, whether it ran as a pipeline of stages).
 
 The MODEL is written from the contract in include/fx8010_amd.h: one oracle object per TRACKED instance (0, N-1, N//2 and the
 instances the list operations of the sequence mostly name, at most 12), the last broadcast value per register (a reset needs it),
@@ -22,9 +28,10 @@ or without a device, so both runs walk the same sequence; cover["stream"] is a d
 step, which tests/test_gpu_voice_sequences.py compares between the two.
 
 Environment: FX_KERNEL / FX_INST_PER_LANE select the tier as everywhere; FX_FUZZ_SHARDS=n a multi-shard handle; FX_FUZZ_WILD=1
-list sets and windows carry values beyond +-1, denormals, +-0, NaN payloads and Inf; FX_FUZZ_GEN=<0..3> pins the generator
-(3: the DANE model); FX_FUZZ_BREAK=<name> makes the MODEL wrong in one respect (BREAKS below) - the detection tests show that
-the sequences notice each; it never touches the library.
+list sets and windows carry values beyond +-1, denormals, +-0, NaN payloads and Inf; FX_FUZZ_GEN=<0..4> pins the generator
+(3: the DANE model, 4: programs the stage planner cuts); FX_FUZZ_BREAK=<name> makes the MODEL wrong in one respect (BREAKS below) - the detection tests show that
+the sequences notice each; it never touches the library.  FX_FUZZ_TRACKS_FROM=<step>: the steps in front of it run a plain block
+where they would arm schedules (the staged range: a handle that has armed one runs no staged code any more).
 """
 import os
 import sys
@@ -59,9 +66,18 @@ WILD_WORDS = np.array([0x40200000, 0xC0400000, 0x3F800001, 0x42C80000, 0x7149F2C
 WILD_TRAM_ONLY = np.array([0x7F812345, 0xFFA00000], dtype=np.uint32)
 
 
-def new_cover():
+def new_cover(stages=False):
+    """stages: also count, per device block, whether it ran as a pipeline of stages (cover["staged_blocks"]: only a run with a
+    device fills it, so a caller that compares a device run with the model alone asks for it and leaves it out of the comparison)"""
     c = {k: [0, 0] for k in KINDS}
     c.update(sequences=0, loaded=0, left_domain=0, rotated_nonzero=0, logical_wrap=0, blocks=0, state_reads=0, second_handles=0, kernels={}, sharded_handles=0, stream=0)
+    # device blocks by FXB_INFO_WAVES_PER_WG behind them: plain / scheduled = [one wavefront per workgroup, a pipeline of stages] of the
+    # blocks that armed no schedule / a track or a list schedule; kernels: FXB_INFO_KERNEL of the staged ones; sequences: those
+    # in which at least one block was staged
+    if stages:
+        c["staged_blocks"] = {"plain": [0, 0], "scheduled": [0, 0], "kernels": {}, "sequences": 0}
+    # the model's side of it (no device needed): blocks that armed no schedule, on a handle that [never armed one so far, has armed one]
+    c["plain_blocks"] = [0, 0]
     return c
 
 
@@ -69,7 +85,9 @@ COVER = new_cover()
 
 # the seed ranges of the test suite: tests/test_gpu_voice_sequences.py runs them on the device, tier by tier, and
 # tests/test_voice_sequences_model.py counts what the same sequences cover with the model alone.  name: (first, count, environment)
-SLICES = {"main": (0, 20, {}), "wild": (300, 20, {"FX_FUZZ_WILD": "1"}), "dane": (200, 20, {"FX_FUZZ_GEN": "3"})}
+SLICES = {"main": (0, 20, {}), "wild": (300, 20, {"FX_FUZZ_WILD": "1"}), "dane": (200, 20, {"FX_FUZZ_GEN": "3"}),
+          "staged": (463, 20, {"FX_FUZZ_GEN": "4", "FX_STAGES": "4", "FX_FUZZ_TRACKS_FROM": "12"})}
+STAGED_DRAWS, STAGED_ASKED = 8, 4
 
 
 class Mismatch(Exception):
@@ -86,7 +104,25 @@ def generate(seed, rng, gen):
         return stress_fuzz.random_program(rng, int(rng.integers(6, 70)), int(rng.integers(3, 30))), 0
     if gen == 1:
         return stress_fuzz.random_program2(rng, int(rng.integers(6, 70)), int(rng.integers(3, 30))), 0
+    if gen == 4:
+        import fuzz_stages      # (here: it brings torch along where there is one, which the other generators need not wait for)
+        for _ in range(STAGED_DRAWS):
+            text = fuzz_stages.random_program(rng, int(rng.integers(3, 9)), int(rng.integers(3, 9)))
+            if stages_cut(text, STAGED_ASKED) >= 2:
+                break
+        return text, 0
     return fuzz_tram.random_tram_program(rng, gen == 3), (A.OPT_TRAM_DANE if gen == 3 else 0)
+
+
+def stages_cut(text, asked):
+    """how many stages the front end cuts a program into when `asked` are asked for (no GPU); 1 where it refuses"""
+    fe = A.FrontEnd(1)
+    if not fe.load_text(text):
+        return 1
+    try:
+        return fe.translate_staged(asked)[2]
+    except RuntimeError:
+        return 1
 
 
 class Program:
@@ -164,6 +200,7 @@ class Handle:
         self.broadcast = {}
         self.x = P.stimulus(N, 1700, first_sample=first_sample)
         self.pos = 0
+        self.trackable = False      # a schedule has been armed: a register of this handle is trackable from then on
 
     def take(self, S):
         xs = self.x[self.pos:self.pos + S]
@@ -328,6 +365,8 @@ def _run(seed, verbose, device, cover, wild, shards, probe, edit):
     records = []      # (entries: [oracle clone or None], image or None)
     pool = prog.names if len(prog.names) <= 8 else list(dict.fromkeys(prog.controls + [str(v) for v in rng.choice(prog.names, size=6, replace=False)] + ["out", "ccr"]))
     step = -1
+    ran_staged = []      # (not empty: a block of this sequence ran as a pipeline of stages)
+    tracks_from = int(os.environ.get("FX_FUZZ_TRACKS_FROM", "0"))
     if verbose:
         print(text)
         print("N", N, "tracked", H.tracked, "names", pool, "A", prog.A, "Z", prog.Z, "ring", prog.ring, "tram_ops", prog.tram_ops, "dane", prog.dane)
@@ -426,9 +465,20 @@ def _run(seed, verbose, device, cover, wild, shards, probe, edit):
     def block(h, S, plans=(), lists=()):
         xs = h.take(S)
         cover["blocks"] += 1
+        if plans or lists:
+            h.trackable = True
+        else:
+            cover["plain_blocks"][int(h.trackable)] += 1
         y = h.b.process_block(xs) if h.b is not None else None
         if h.b is not None:
             cover["kernels"][h.b.info("kernel")] = cover["kernels"].get(h.b.info("kernel"), 0) + 1      # (FXB_INFO_KERNEL: the tier the block ran on)
+        if h.b is not None and "staged_blocks" in cover:
+            staged, sb = h.b.info("waves_per_wg") >= 2, cover["staged_blocks"]
+            sb["scheduled" if plans or lists else "plain"][int(staged)] += 1
+            if staged:
+                sb["kernels"][h.b.info("kernel")] = sb["kernels"].get(h.b.info("kernel"), 0) + 1
+                sb["sequences"] += int(not ran_staged)
+                ran_staged.append(seed)
         for n in h.tracked:
             o = h.o[n]
             if not plans and not lists:
@@ -520,6 +570,12 @@ def _run(seed, verbose, device, cover, wild, shards, probe, edit):
             say("prepare", n_samples, wait)
             if b is not None:
                 b.prepare(n_samples, wait)
+        elif op < 32 and step < tracks_from:
+            # (FX_FUZZ_TRACKS_FROM: a register that has had a schedule stays trackable for the life of the handle, and code with a
+            # trackable register is not cut into stages - the staged range keeps its schedules for the later steps)
+            S = int(rng.choice([1, 5, 16, 33]))
+            say("block", S, "in place of a scheduled one, handle", handles.index(h))
+            block(h, S)
         elif op < 32:
             # dense tracks and list schedules of one block (fuzz_api op 12); a list schedule on a register the program itself can
             # change is refused and arms nothing
@@ -755,10 +811,11 @@ def main():
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 100
     if len(sys.argv) > 3 and sys.argv[3] == "verbose":
         return 0 if run(first, True) else 1
-    cover = new_cover()
+    cover = new_cover(stages=True)
     bad = [s for s in range(first, first + count) if not run(s, cover=cover)]
     print("voice fuzz:", count, "sequences (%d programs loaded, %d left the parity domain), failures" % (cover["loaded"], cover["left_domain"]), bad)
-    print("  accepted / refused:", {k: tuple(cover[k]) for k in KINDS}, "rotated loads with d != 0:", cover["rotated_nonzero"], "logical windows that wrap:", cover["logical_wrap"], "blocks by kernel:", cover["kernels"])
+    print("  accepted / refused:", {k: tuple(cover[k]) for k in KINDS}, "rotated loads with d != 0:", cover["rotated_nonzero"], "logical windows that wrap:", cover["logical_wrap"], "blocks by kernel:", cover["kernels"],
+          "blocks by stages [one wavefront, a pipeline]:", cover["staged_blocks"])
     return 1 if bad or cover["loaded"] < count // 2 else 0
 
 
