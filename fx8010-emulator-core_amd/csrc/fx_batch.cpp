@@ -102,6 +102,10 @@ Batch::~Batch() {
     freeBlock(instRec_, false);
     freeBlock(hInstList_, true);
     freeBlock(hInstRec_, true);
+    freeBank();
+    bankRelease();
+    (void)hipFree(bankCells_);
+    freeBlock(bankPairs_, false);
     freeBlock(regList_, false);
     freeBlock(hRegList_, true);
     freeBlock(tramStage_, false);
@@ -168,6 +172,7 @@ int Batch::afterLoad(bool ok) {
     (void)hipSetDevice(device_);
     if (dTarget_) (void)clearMeterTarget();   // a program load drops the target of the program that was
     if (dMeter_) (void)meterReset();          // ... resets the meters and keeps them enabled
+    freeBank();                               // ... and frees the record bank: its slots hold records of the program that was
     // registers may have been created even when the load failed; keep host mirrors in step
     const size_t old = hostValue_.size();
     hostValue_.resize(prog_.regs.size());
@@ -999,6 +1004,10 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_LEVEL_LAUNCHES) return meterLevelLaunches_;
     if (what == FXB_INFO_METER_LEVEL_SELECTS) return levelSelects_;
     if (what == FXB_INFO_METER_LEVEL_LIST_READS) return levelListReads_;
+    if (what == FXB_INFO_BANK_SLOTS) return bankSlots_;
+    if (what == FXB_INFO_BANK_STORES) return bankStores_;
+    if (what == FXB_INFO_BANK_RECALLS) return bankRecalls_;
+    if (what == FXB_INFO_BANK_BYTES) return bankSlots_ * bankWords_ * 4;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

@@ -299,6 +299,35 @@ public:
     // what the host knows about the registers follows a load of these `total` records (of all shards: every shard ends up with
     // the same rows): a register with a value other than hostValue_ in any record becomes per-instance, as after setRegisterAt
     void promoteLoaded(const uint32_t* buf, int64_t total);
+    // Record bank (fx_bank.hpp; include/fx8010_amd.h "Record banks"; fx_batch_bank.cpp): nSlots packed records in device memory
+    // of this batch's GPU.  store and recall run inside the by-list frame on the instance calls' staging (the two 64-bit lists and
+    // nothing else: instance numbers, and slot words - the slot, and in the high half the caller's number of the entry, pos[i] or
+    // i); put and get are synchronous copies.  `list` holds instance numbers of THIS batch; entry i has the slot slots[pos[i]]
+    // (pos null: slots[i]).  Sharded has checked the lists for the whole handle (checkBankLists) and reserved on every shard.
+    static int checkBankLists(const char* who, const int64_t* slots, const int64_t* list, int64_t count, int64_t nSlots, int64_t n, bool uniqueSlots,
+                              std::string* why);
+    // the allocating half of a create: the new bank, zero-filled, beside the one in force (FX_E_MEMORY changes nothing); take
+    // makes it the bank and frees the old one behind everything queued, release frees it unused.  nSlots 0 reserves nothing and
+    // take then leaves the batch without a bank.
+    int bankReserve(int64_t nSlots);
+    void bankTake();
+    void bankRelease();
+    int64_t bankSlots() const { return bankSlots_; }
+    int reserveBankCall(int64_t count);   // the event, the two lists and the pairs of a call of `count` entries
+    int bankStore(const int64_t* slots, const int64_t* list, const int64_t* pos, int64_t count);                     // stream-ordered
+    int bankRecall(const int64_t* slots, const int64_t* list, const int64_t* pos, int64_t count, int64_t serial);    // stream-ordered
+    // what the host knows about the registers follows a recall of these slots (of all shards, like promoteLoaded): a register is
+    // noted as written per instance unless the shadow of every one of the slots holds a known word for it that equals hostValue_'s
+    void bankNoteRecalled(const int64_t* slots, int64_t count);
+    // slot slots[k] <- / -> the W words at records + k * W, synchronous, behind everything queued.  shadow (put): the shadow rows
+    // that go with the records, [count][bankShadowRegs()]; null: every register's word is known, from the record
+    int bankPutRecords(const int64_t* slots, int64_t count, const uint32_t* records, const uint64_t* shadow = nullptr);
+    int bankGetRecords(const int64_t* slots, int64_t count, uint32_t* records);
+    int bankShadowRegs() const { return bankRegs_; }
+    const uint64_t* bankShadowRow(int64_t slot) const { return bankShadow_.data() + (size_t)slot * (size_t)bankRegs_; }
+    // waits for the queued bank calls; out = { recalls refused since the last reset, the key of the most recent refused one
+    // (fx_bank.hpp BankCell), its serial }; reset zeroes the three
+    int bankStatus(uint64_t out[3], bool reset);
     // Register calls by list (fx_registers.hpp; include/fx8010_amd.h "Register sets by list"; fx_batch_registers.cpp).  `regs` holds
     // nKeys register numbers of the program (resolveRegisters), `list` holds `count` instance numbers of THIS batch, `pos` the column
     // of the caller's [nKeys][total] values each of them has (null: entry i has column i and total == count).  The caller has checked
@@ -881,6 +910,22 @@ private:
     bool instLaunched_ = false;          // ... which may still be running
     int64_t instGathers_ = 0, instScatters_ = 0;   // FXB_INFO_INSTANCE_GATHERS / _SCATTERS
     int64_t instRotations_ = 0;                    // FXB_INFO_INSTANCE_ROTATIONS
+    // record bank (fx_batch_bank.cpp): the slots, the cells of the gate (fx_bank.hpp BankCell) and the pairs of a recall - device
+    // memory; bankWords_ is W as it was at the create (a call under another W is refused: the slots would not fit the records).
+    // bankShadow_: per slot and register either the word the host knows the record to hold there, or kBankUnknown.
+    static constexpr uint64_t kBankUnknown = (uint64_t)1 << 32;
+    uint32_t* bank_ = nullptr;
+    uint32_t* bankNew_ = nullptr;
+    unsigned long long* bankCells_ = nullptr;
+    Block<int> bankPairs_;
+    int64_t bankSlots_ = 0, bankNewSlots_ = 0, bankWords_ = 0;
+    int bankRegs_ = 0;
+    std::vector<uint64_t> bankShadow_, bankNewShadow_;
+    int64_t bankStores_ = 0, bankRecalls_ = 0;     // FXB_INFO_BANK_STORES / _RECALLS
+    void freeBank();                               // behind everything queued; a program load and the destructor
+    int bankReady(const char* who);                // lowered, a bank, and W as at the create
+    int beginBankCall(const char* who, const int64_t* slots, const int64_t* list, const int64_t* pos, int64_t count);
+    bool shadowed(int r) const { return !tracked(r) && !intrinsicLane(r); }
     // the by-list frame (fx_batch_list.cpp; "THE BY-LIST FRAME" above), shared by the instance calls and the list sets.
     // reserveListStage: `ev` on first use where wanted (texts[0] names it in FX_E_MEMORY), the capacity test, a wait for the call
     // that may still be reading the blocks that go (`ev` / `busy`), then the device block (texts[1]), then the pinned one (texts[2]).

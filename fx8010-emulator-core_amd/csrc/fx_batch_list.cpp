@@ -1,6 +1,6 @@
 // fx_batch_list.cpp — the by-list frame of one batch (fx_batch.hpp "THE BY-LIST FRAME"): the one list check behind the check...
-// functions of the by-list calls, and the pieces of the staging frame that the instance calls (fx_batch_instances.cpp) and the list
-// sets (fx_batch_registers.cpp, fx_batch_tram.cpp, fx_batch_meter_list.cpp, fx_batch_tracks.cpp) are written in.
+// functions of the by-list calls, and the pieces of the staging frame that the instance calls (fx_batch_instances.cpp), the record
+// bank (fx_batch_bank.cpp) and the list sets (fx_batch_registers.cpp, fx_batch_tram.cpp, fx_batch_meter_list.cpp, fx_batch_tracks.cpp) are written in.
 #include "fx_batch.hpp"
 
 #include <algorithm>

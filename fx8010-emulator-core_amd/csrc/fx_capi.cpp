@@ -347,6 +347,23 @@ int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const 
 int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.loadInstancesRotated(list, count, buf, bytes); }) : FX_E_ARG;
 }
+int fxb_bank_create(fxb_handle* h, int64_t n_slots) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankCreate(n_slots); }) : FX_E_ARG; }
+int64_t fxb_bank_slots(fxb_handle* h) { return h ? h->batch.bankSlots() : 0; }
+int fxb_bank_store(fxb_handle* h, const int64_t* slots, const int64_t* list, int64_t count) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankStore(slots, list, count); }) : FX_E_ARG;
+}
+int fxb_bank_recall(fxb_handle* h, const int64_t* slots, const int64_t* list, int64_t count) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankRecall(slots, list, count); }) : FX_E_ARG;
+}
+int fxb_bank_put(fxb_handle* h, const int64_t* slots, int64_t count, const void* image, int64_t bytes) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankPut(slots, count, image, bytes); }) : FX_E_ARG;
+}
+int fxb_bank_get(fxb_handle* h, const int64_t* slots, int64_t count, void* buf, int64_t cap) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankGet(slots, count, buf, cap); }) : FX_E_ARG;
+}
+int fxb_bank_status(fxb_handle* h, int64_t* refused_calls, int64_t* entry, int* reason, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.bankStatus(refused_calls, entry, reason, reset != 0); }) : FX_E_ARG;
+}
 int fxb_set_registers_list(fxb_handle* h, const char* const* keys, int n_keys, const int64_t* list, int64_t count, const float* values) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.setRegistersList(keys, n_keys, list, count, values); }) : FX_E_ARG;
 }

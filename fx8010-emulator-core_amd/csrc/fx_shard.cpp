@@ -897,6 +897,21 @@ int64_t Sharded::instanceImageBytes(int64_t count) {
     return (int64_t)sizeof(hdr) + count * Batch::instanceWords(hdr) * 4;
 }
 
+int Sharded::growStage(size_t words, const char* who) {
+    if (words <= stageWords_) return 0;
+    if (hStage_ && hipHostFree(hStage_) != hipSuccess) (void)hipGetLastError();
+    hStage_ = nullptr;
+    stageWords_ = 0;
+    if (hipHostMalloc(reinterpret_cast<void**>(&hStage_), words * 4, hipHostMallocPortable) != hipSuccess) {
+        (void)hipGetLastError();
+        hStage_ = nullptr;
+        lastError_ = who;
+        return FX_E_MEMORY;
+    }
+    stageWords_ = words;
+    return 0;
+}
+
 int Sharded::copyInstances(const int64_t* src, const int64_t* dst, int64_t count) {
     Serial serial(api_);
     lastError_.clear();
@@ -922,19 +937,7 @@ int Sharded::copyInstances(const int64_t* src, const int64_t* dst, int64_t count
     Batch::SnapshotHeader hdr;
     if ((rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, 0); })) != 0) return rc;
     const size_t W = (size_t)Batch::instanceWords(hdr), chunk = std::max<size_t>(kStageBytes / (W * 4), 1);
-    const size_t want = std::min(chunk, cross.size()) * W;
-    if (want > stageWords_) {
-        if (hStage_ && hipHostFree(hStage_) != hipSuccess) (void)hipGetLastError();
-        hStage_ = nullptr;
-        stageWords_ = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&hStage_), want * 4, hipHostMallocPortable) != hipSuccess) {
-            (void)hipGetLastError();
-            hStage_ = nullptr;
-            lastError_ = "copy_instances: no pinned staging for the pairs that cross shards";
-            return FX_E_MEMORY;
-        }
-        stageWords_ = want;
-    }
+    if ((rc = growStage(std::min(chunk, cross.size()) * W, "copy_instances: no pinned staging for the pairs that cross shards")) != 0) return rc;
     for (size_t c0 = 0; c0 < cross.size() && rc == 0; c0 += chunk) {
         const size_t m = std::min(chunk, cross.size() - c0);
         std::vector<ListPart> from(shards_.size()), to(shards_.size());
@@ -1009,7 +1012,115 @@ int Sharded::loadRecords(const int64_t* list, int64_t count, const void* buf, in
     });
 }
 
-int Sharded::registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out) {
+// ---- record bank -------------------------------------------------------------------------------------------------------------------
+int Sharded::bankCreate(int64_t nSlots) {
+    Serial serial(api_);
+    lastError_.clear();
+    const int rc = reserveOnAll([&](int, Batch& b) { return b.bankReserve(nSlots); }, [](Batch& b) { b.bankRelease(); });
+    return rc != 0 ? rc : fan([](int, Batch& b) { b.bankTake(); return 0; });
+}
+
+int64_t Sharded::bankSlots() {
+    Serial serial(api_);
+    return front().bankSlots();   // (every shard holds the same bank)
+}
+
+int Sharded::bankChecked(const char* who, const int64_t* slots, const int64_t* list, int64_t count, bool instances, bool uniqueSlots) {
+    lastError_.clear();
+    if (!front().stateReady()) { lastError_ = "no program loaded"; return FX_E_NOTREADY; }
+    std::string why;
+    if (Batch::checkBankLists(who, slots, list, count, front().bankSlots(), instances ? n_ : 0, uniqueSlots, &why) != 0) { lastError_ = why; return FX_E_ARG; }
+    return 0;
+}
+
+int Sharded::bankStore(const int64_t* slots, const int64_t* list, int64_t count) {
+    Serial serial(api_);
+    int rc = bankChecked("bank_store", slots, list, count, true, true);
+    if (rc != 0 || count == 0) return rc;
+    const ShardLists l(*this, list, count);
+    if ((rc = fan([&](int k, Batch& b) { return b.reserveBankCall(l.count(k)); })) != 0) return rc;
+    rc = fan([&](int k, Batch& b) { return b.bankStore(slots, l.list(k), l.pos(k), l.count(k)); });
+    if (rc != 0 || shards_.size() == 1) return rc;
+    // the other shards' copies: owner -> pinned staging -> every other shard, in chunks of the staging block, with the shadow rows
+    Batch::SnapshotHeader hdr;
+    if ((rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, 0); })) != 0) return rc;
+    const size_t W = (size_t)Batch::instanceWords(hdr), chunk = std::max<size_t>(kStageBytes / (W * 4), 1), regs = (size_t)front().bankShadowRegs();
+    if ((rc = growStage(std::min(chunk, (size_t)count) * W, "bank_store: no pinned staging for the copies to the other shards")) != 0) return rc;
+    for (size_t k = 0; k < shards_.size() && rc == 0; ++k) {
+        std::vector<int64_t> own((size_t)l.count((int)k));
+        for (size_t i = 0; i < own.size(); ++i) own[i] = slots[l.pos((int)k)[i]];
+        for (size_t c0 = 0; c0 < own.size() && rc == 0; c0 += chunk) {
+            const int64_t m = (int64_t)std::min(chunk, own.size() - c0);
+            if ((rc = runOn((int)k, [&](Batch& b) { return b.bankGetRecords(own.data() + c0, m, hStage_); })) != 0) break;
+            std::vector<uint64_t> shadow((size_t)m * regs);
+            for (int64_t i = 0; i < m; ++i) std::copy_n(shard((int)k).bankShadowRow(own[c0 + (size_t)i]), regs, shadow.data() + (size_t)i * regs);
+            rc = fan([&](int j, Batch& b) { return j == (int)k ? 0 : b.bankPutRecords(own.data() + c0, m, hStage_, shadow.data()); });
+        }
+    }
+    return rc;
+}
+
+int Sharded::bankRecall(const int64_t* slots, const int64_t* list, int64_t count) {
+    Serial serial(api_);
+    int rc = bankChecked("bank_recall", slots, list, count, true, false);
+    if (rc != 0 || count == 0) return rc;
+    const ShardLists l(*this, list, count);
+    if ((rc = fan([&](int k, Batch& b) { return b.reserveBankCall(l.count(k)); })) != 0) return rc;
+    const int64_t call = ++bankSerial_;
+    // (every shard ends up with the same register rows: each one follows the whole list, like promoteLoaded)
+    return fan([&](int k, Batch& b) {
+        const int r = b.bankRecall(slots, l.list(k), l.pos(k), l.count(k), call);
+        if (r == 0) b.bankNoteRecalled(slots, count);
+        return r;
+    });
+}
+
+int Sharded::bankPut(const int64_t* slots, int64_t count, const void* image, int64_t bytes) {
+    Serial serial(api_);
+    int rc = bankChecked("bank_put", slots, nullptr, count, false, true);
+    if (rc != 0 || count == 0) return rc;
+    Batch::SnapshotHeader hdr;
+    if (!image || bytes < (int64_t)sizeof(hdr)) { lastError_ = "bank_put: no image"; return FX_E_ARG; }
+    std::memcpy(&hdr, image, sizeof(hdr));
+    if ((rc = runOn(0, [&](Batch& b) { return b.checkInstanceImage(hdr, count, bytes); })) != 0) return rc;
+    const uint32_t* records = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(image) + sizeof(hdr));
+    return fan([&](int, Batch& b) { return b.bankPutRecords(slots, count, records); });
+}
+
+int Sharded::bankGet(const int64_t* slots, int64_t count, void* buf, int64_t cap) {
+    Serial serial(api_);
+    int rc = bankChecked("bank_get", slots, nullptr, count, false, false);
+    if (rc != 0) return rc;
+    Batch::SnapshotHeader hdr;
+    if ((rc = runOn(0, [&](Batch& b) { return b.instanceShape(&hdr, count); })) != 0) return rc;
+    if (count == 0 && (!buf || cap < (int64_t)sizeof(hdr))) return 0;   // (nothing to get; a buffer that holds a header gets one)
+    if (!buf || cap < (int64_t)sizeof(hdr) + count * Batch::instanceWords(hdr) * 4) { lastError_ = "bank_get: buffer smaller than fxb_instance_image_size()"; return FX_E_ARG; }
+    std::memcpy(buf, &hdr, sizeof(hdr));
+    uint32_t* records = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf) + sizeof(hdr));
+    return runOn(0, [&](Batch& b) { return b.bankGetRecords(slots, count, records); });
+}
+
+int Sharded::bankStatus(int64_t* refusedCalls, int64_t* entry, int* reason, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    std::vector<uint64_t> part(shards_.size() * 3, 0);
+    const int rc = fan([&](int k, Batch& b) { return b.bankStatus(part.data() + (size_t)k * 3, reset); });
+    if (rc != 0) return rc;
+    uint64_t refused = 0, call = 0, key = ~(uint64_t)0;
+    for (size_t k = 0; k < shards_.size(); ++k) {
+        const uint64_t* p = part.data() + k * 3;
+        if (p[0] == 0) continue;
+        refused += p[0];
+        if (p[2] > call) { call = p[2]; key = p[1]; }
+        else if (p[2] == call) key = std::min(key, p[1]);
+    }
+    if (refusedCalls) *refusedCalls = (int64_t)refused;
+    if (entry) *entry = refused ? (int64_t)(key >> 3) : -1;
+    if (reason) *reason = refused ? (int)(key & 3) : 0;
+    return 0;
+}
+
+int Sharded::registersList(bool set,const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out) {
     Serial serial(api_);
     lastError_.clear();
     const char* name = set ? "set_registers_list" : "get_registers_list";
@@ -1114,6 +1225,7 @@ int64_t Sharded::info(int what) {
         what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS || what == FXB_INFO_TRACK_LIST_EXPANDS ||
         what == FXB_INFO_METER_TARGET_LAUNCHES || what == FXB_INFO_METER_MATCH_SELECTS || what == FXB_INFO_METER_MATCH_BESTS ||
         what == FXB_INFO_METER_LEVEL_LAUNCHES || what == FXB_INFO_METER_LEVEL_SELECTS || what == FXB_INFO_METER_LEVEL_LIST_READS ||
+        what == FXB_INFO_BANK_STORES || what == FXB_INFO_BANK_RECALLS || what == FXB_INFO_BANK_BYTES ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;
         for (int64_t p : part) sum += p;

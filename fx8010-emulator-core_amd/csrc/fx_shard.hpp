@@ -164,6 +164,21 @@ public:
     // ... with the delay memory of every record rotated to its destination's positions (Batch::recordRotations); a program that
     // executes no delay-line instruction or has no delay memory goes the way of loadInstances
     int loadInstancesRotated(const int64_t* list, int64_t count, const void* buf, int64_t bytes) { return loadRecords(list, count, buf, bytes, true); }
+    // record bank (Batch "Record bank"): EVERY shard holds its own copy of the bank, so any instance recalls any slot without
+    // traffic between devices.  create reserves on every shard before any shard changes (FX_E_MEMORY leaves the old bank in force
+    // everywhere).  The lists are checked for the whole handle before any shard is posted.  put goes to every shard.  store
+    // gathers on the shard that owns the instance (stream-ordered); with several shards the stored slots are then copied to the
+    // other shards through the pinned staging of copyInstances, with their register shadow: such a call blocks.  recall splits by
+    // ShardLists and stays stream-ordered on every shard; the device gate holds per shard.  status: the refused recalls summed
+    // over shards (a call refused on two shards counts twice), and of the most recent refused call - by the handle's serial
+    // number - the lowest bad entry on any shard, in the caller's numbering, with its reason.
+    int bankCreate(int64_t nSlots);
+    int64_t bankSlots();
+    int bankStore(const int64_t* slots, const int64_t* list, int64_t count);
+    int bankRecall(const int64_t* slots, const int64_t* list, int64_t count);
+    int bankPut(const int64_t* slots, int64_t count, const void* image, int64_t bytes);
+    int bankGet(const int64_t* slots, int64_t count, void* buf, int64_t cap);
+    int bankStatus(int64_t* refusedCalls, int64_t* entry, int* reason, bool reset);
     // register calls by list (Batch "Register calls by list"): `list` holds GLOBAL instance numbers, `values` is [nKeys][count].
     // The keys are resolved and everything is checked for the whole handle before any shard is posted; each shard gets the
     // entries that fall to it with local numbers and their columns of `values` and, for a set, reserves its staging first
@@ -244,6 +259,9 @@ private:
     static constexpr size_t kStageBytes = (size_t)64 << 20;
     uint32_t* hStage_ = nullptr;   // pinned (portable) staging of cross-shard copies, allocated on first use and kept
     size_t stageWords_ = 0;
+    int growStage(size_t words, const char* who);   // hStage_ of at least `words`; FX_E_MEMORY and why, with the old block gone
+    int bankChecked(const char* who, const int64_t* slots, const int64_t* list, int64_t count, bool instances, bool uniqueSlots);
+    int64_t bankSerial_ = 0;       // recalls of this handle so far: tells the most recent refused one across shards
     // run f(k, batch) on every shard's thread, wait for all; returns the first non-zero result (shard order)
     int fan(const std::function<int(int, Batch&)>& f);
     // run f(batch) on shard k's thread and wait (a single shard: inline, caller's device restored)

@@ -455,6 +455,36 @@ public:
     void loadInstancesRotated(const std::vector<int64_t>& list, const std::vector<uint8_t>& image) {
         if (fxb_load_instances_rotated(h_, list.data(), (int64_t)list.size(), image.data(), (int64_t)image.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::loadInstancesRotated: ") + fxb_last_error(h_));
     }
+    // the record bank (include/fx8010_amd.h "Record banks"): instance records kept on the GPU; store and recall are queued behind the
+    // blocks, the rotations of a recall are worked out on the device, what it refuses shows in bankStatus
+    void bankCreate(int64_t nSlots) {
+        if (fxb_bank_create(h_, nSlots) < 0) throw std::runtime_error(std::string("FX8010Batch::bankCreate: ") + fxb_last_error(h_));
+    }
+    int64_t bankSlots() const { return fxb_bank_slots(h_); }
+    void bankStore(const std::vector<int64_t>& slots, const std::vector<int64_t>& list) {
+        if (slots.size() != list.size()) throw std::invalid_argument("FX8010Batch::bankStore: slots and list must have the same length");
+        if (fxb_bank_store(h_, slots.data(), list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::bankStore: ") + fxb_last_error(h_));
+    }
+    void bankRecall(const std::vector<int64_t>& slots, const std::vector<int64_t>& list) {
+        if (slots.size() != list.size()) throw std::invalid_argument("FX8010Batch::bankRecall: slots and list must have the same length");
+        if (fxb_bank_recall(h_, slots.data(), list.data(), (int64_t)list.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::bankRecall: ") + fxb_last_error(h_));
+    }
+    void bankPut(const std::vector<int64_t>& slots, const std::vector<uint8_t>& image) {
+        if (fxb_bank_put(h_, slots.data(), (int64_t)slots.size(), image.data(), (int64_t)image.size()) < 0) throw std::runtime_error(std::string("FX8010Batch::bankPut: ") + fxb_last_error(h_));
+    }
+    std::vector<uint8_t> bankGet(const std::vector<int64_t>& slots) {
+        const int64_t bytes = fxb_instance_image_size(h_, (int64_t)slots.size());
+        if (bytes < 0) throw std::runtime_error(std::string("FX8010Batch::bankGet: ") + fxb_last_error(h_));
+        std::vector<uint8_t> image((size_t)bytes);
+        if (fxb_bank_get(h_, slots.data(), (int64_t)slots.size(), image.data(), bytes) < 0) throw std::runtime_error(std::string("FX8010Batch::bankGet: ") + fxb_last_error(h_));
+        return image;
+    }
+    struct BankStatus { int64_t refusedCalls = 0, entry = -1; int reason = 0; };   // reason: FXB_BANK_*
+    BankStatus bankStatus(bool reset = false) {
+        BankStatus s;
+        if (fxb_bank_status(h_, &s.refusedCalls, &s.entry, &s.reason, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::bankStatus: ") + fxb_last_error(h_));
+        return s;
+    }
     // generate the code for blocks of nSamples samples now, not in the first process call (callers with a deadline per block)
     void prepare(int nSamples, bool wait = true) {
         if (fxb_prepare(h_, nSamples, wait ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::prepare: ") + fxb_last_error(h_));

@@ -32,6 +32,7 @@ INFO = {
     "meter_selects": 57, "meter_list_reads": 58, "meter_list_resets": 59, "track_list_expands": 60,
     "meter_target_launches": 61, "meter_match_selects": 62, "meter_match_bests": 63,
     "meter_level_launches": 64, "meter_level_selects": 65, "meter_level_list_reads": 66,
+    "bank_slots": 67, "bank_stores": 68, "bank_recalls": 69, "bank_bytes": 70,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -42,6 +43,7 @@ METER_TARGET_LOOP = 1  # FXB_METER_TARGET_LOOP: the flag of meter_set_target
 MATCH_ERROR, MATCH_CROSS = 0, 1  # FXB_MATCH_*: the `stat` of meter_select_match and meter_best
 MATCH_LARGEST = 2  # FXB_MATCH_LARGEST: the flag of meter_best
 LEVEL_ENVELOPE, LEVEL_QUIET = 0, 1  # FXB_LEVEL_*: the `stat` of meter_select_level
+BANK_BAD_POSITION, BANK_PHASE, BANK_NO_RING = 1, 2, 3  # FXB_BANK_*: the `reason` of bank_status
 
 # every symbol include/fx8010_amd.h declares (tests check that the library exports them all)
 SYMBOLS = [
@@ -58,6 +60,7 @@ SYMBOLS = [
     "fxb_bus_set_feeds", "fxb_bus_set_feed_gains", "fxb_bus_get_feeds", "fxb_process_block_bus_feed", "fxb_process_block_bus_feed_dev",
     "fxb_process_block_imajor", "fxb_process_block_imajor_dev",
     "fxb_instance_image_size", "fxb_copy_instances", "fxb_reset_instances", "fxb_save_instances", "fxb_load_instances", "fxb_load_instances_rotated",
+    "fxb_bank_create", "fxb_bank_slots", "fxb_bank_store", "fxb_bank_recall", "fxb_bank_put", "fxb_bank_get", "fxb_bank_status",
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples", "fxb_meter_select", "fxb_meter_read_list", "fxb_meter_reset_list",
     "fxb_meter_set_target", "fxb_meter_clear_target", "fxb_meter_target_seek", "fxb_meter_target_pos", "fxb_meter_read_match", "fxb_meter_select_match", "fxb_meter_best",
     "fxb_meter_set_level", "fxb_meter_clear_level", "fxb_meter_get_level", "fxb_meter_read_level", "fxb_meter_read_level_list", "fxb_meter_select_level",
@@ -128,6 +131,8 @@ def load():
     sig("fxb_instance_image_size", i64, vp, i64); sig("fxb_copy_instances", i32, vp, vp, vp, i64); sig("fxb_reset_instances", i32, vp, vp, i64)
     sig("fxb_save_instances", i32, vp, vp, i64, vp, i64); sig("fxb_load_instances", i32, vp, vp, i64, vp, i64)
     sig("fxb_load_instances_rotated", i32, vp, vp, i64, vp, i64)
+    sig("fxb_bank_create", i32, vp, i64); sig("fxb_bank_slots", i64, vp); sig("fxb_bank_store", i32, vp, vp, vp, i64); sig("fxb_bank_recall", i32, vp, vp, vp, i64)
+    sig("fxb_bank_put", i32, vp, vp, i64, vp, i64); sig("fxb_bank_get", i32, vp, vp, i64, vp, i64); sig("fxb_bank_status", i32, vp, vp, vp, vp, i32)
     sig("fxb_set_registers_list", i32, vp, vp, i32, vp, i64, vp); sig("fxb_get_registers_list", i32, vp, vp, i32, vp, i64, vp)
     sig("fxb_set_register_tracks_list", i32, vp, vp, i32, vp, i64, vp, i32, i32, i32); sig("fxb_clear_register_tracks_list", i32, vp)
     sig("fxb_meter_enable", i32, vp, i32); sig("fxb_meter_read", i32, vp, vp, vp, vp, vp, i32); sig("fxb_meter_samples", i64, vp)
@@ -566,6 +571,52 @@ class Batch(_Reports):
         v = self._instance_list(instances)
         image = np.ascontiguousarray(image, dtype=np.uint8)
         return self._check(self._lib.fxb_load_instances_rotated(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(image.ctypes.data), image.size), "load_instances_rotated")
+
+    # ---- record bank (include/fx8010_amd.h "Record banks"): instance records kept on the GPU, recalled by list
+    def bank_create(self, n_slots):
+        """a bank of n_slots zero-filled records in device memory of the handle's GPU; replaces an existing bank, 0 frees it"""
+        return self._check(self._lib.fxb_bank_create(self._h, int(n_slots)), "bank_create")
+
+    def bank_slots(self):
+        return int(self._lib.fxb_bank_slots(self._h))
+
+    def _bank_lists(self, name, slots, instances):
+        s, v = self._instance_list(slots), self._instance_list(instances)
+        if s.size != v.size:
+            raise ValueError("%s: slots and instances must have the same length" % name)
+        return s, v
+
+    def bank_store(self, slots, instances):
+        """slot slots[k] takes the record of instance instances[k] (instances may repeat, slots may not); stream-ordered"""
+        s, v = self._bank_lists("bank_store", slots, instances)
+        return self._check(self._lib.fxb_bank_store(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(v.ctypes.data), s.size), "bank_store")
+
+    def bank_recall(self, slots, instances):
+        """instance instances[k] takes the record in slot slots[k] under the rule of load_instances_rotated, the rotations worked
+        out on the GPU (slots may repeat, destinations may not); stream-ordered, returns once queued.  What the device refuses
+        changes nothing and shows in bank_status()."""
+        s, v = self._bank_lists("bank_recall", slots, instances)
+        return self._check(self._lib.fxb_bank_recall(self._h, C.c_void_p(s.ctypes.data), C.c_void_p(v.ctypes.data), s.size), "bank_recall")
+
+    def bank_put(self, slots, image):
+        """the records of an instance image (save_instances, bank_get) into the listed slots, record k into slots[k]; synchronous"""
+        s = self._instance_list(slots)
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        return self._check(self._lib.fxb_bank_put(self._h, C.c_void_p(s.ctypes.data), s.size, C.c_void_p(image.ctypes.data), image.size), "bank_put")
+
+    def bank_get(self, slots):
+        """an instance image (numpy uint8) of the listed slots, as save_instances gives one of instances; synchronous"""
+        s = self._instance_list(slots)
+        buf = np.empty(self.instance_image_size(s.size), dtype=np.uint8)
+        self._check(self._lib.fxb_bank_get(self._h, C.c_void_p(s.ctypes.data), s.size, C.c_void_p(buf.ctypes.data), buf.size), "bank_get")
+        return buf
+
+    def bank_status(self, reset=False):
+        """(refused_calls, entry, reason) after the queued bank calls: the recalls the device has refused since the last reset, and
+        of the most recent one its lowest bad list entry (-1: none) and the reason (BANK_*; 0: none)"""
+        refused, entry, reason = C.c_int64(0), C.c_int64(-1), C.c_int(0)
+        self._check(self._lib.fxb_bank_status(self._h, C.byref(refused), C.byref(entry), C.byref(reason), 1 if reset else 0), "bank_status")
+        return int(refused.value), int(entry.value), int(reason.value)
 
     def set_tram_list(self, which, instances, first, values, logical=False):
         """A window of delay line `which` (0 iTRAM, 1 xTRAM) of the listed instances only (include/fx8010_amd.h "Delay-line windows

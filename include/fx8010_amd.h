@@ -256,6 +256,67 @@ int fxb_load_instances(fxb_handle* h, const int64_t* list, int64_t count, const 
  *   A program without delay lines, or one that executes no delay-line instruction, goes the way of fxb_load_instances; otherwise
  *   FXB_INFO_INSTANCE_ROTATIONS counts the launches and FXB_INFO_INSTANCE_SCATTERS does not.  Returns as fxb_load_instances. */
 int fxb_load_instances_rotated(fxb_handle* h, const int64_t* list, int64_t count, const void* buf, int64_t bytes);
+/* Record banks: instance records kept on the GPU and recalled by list - a note-on from a preset, a checkpoint and its recall, a
+ * winner forked into its group after more blocks have run - queued behind the blocks like the other sets by list.  A BANK is
+ * n_slots packed records of W = FXB_INFO_INSTANCE_WORDS words in device memory of the handle's GPU, owned by the handle: one bank
+ * per handle.  Only the list entries cross PCIe in a store or a recall; no record and no position row does, and neither call waits
+ * for a queued block.  Three kernels (fx_bank_gather, fx_bank_rotations, fx_bank_scatter_rot) move the words as bit patterns.
+ *
+ * fxb_bank_create: a bank of n_slots >= 1 slots, zero-filled; an existing bank is replaced (nothing of it is kept), n_slots == 0
+ *   frees it.  FX_E_NOTREADY without a program, FX_E_ARG for n_slots outside 0..2^31-1, FX_E_MEMORY with nothing changed - the old
+ *   bank included - when the allocation fails.  A program load (fxb_load_file / fxb_load_text) and fxb_destroy free the bank: its
+ *   records are those of the program that was.  fxb_bank_slots: n_slots, 0 without a bank.
+ * fxb_bank_store: slot slots[k] takes the record of instance list[k], bit for bit - the words fxb_save_instances would write.
+ *   Instances may repeat, slots may not.  Stream-ordered inside the frame of the sets by list: behind every block queued so far on
+ *   whichever stream, in front of every later one; fxb_sync covers it.  The only host wait is the frame's own, for the previous
+ *   call by list.  On a handle of several shards it blocks (below).
+ * fxb_bank_recall: instance list[k] takes the record in slot slots[k] under exactly the rule of fxb_load_instances_rotated - every
+ *   state row but the four position rows, the delay memory rotated per record and per line by d, with that call's definition of d,
+ *   of a ring and of which position kinds count, the FX_OPT_TRAM_DANE model included.  The DEVICE works out d, from the record's
+ *   position words in the bank and the position rows the destination holds when the kernel runs: no position is copied to the
+ *   host, nothing is waited for, the call returns 0 once queued.  Slots may repeat (fan-out), destinations may not.  A program
+ *   that executes no delay-line instruction takes the plain scatter, position words included.
+ *   The three refusals of the rotated load that depend on the record are the device's here: a record position word outside
+ *   0..Z-1 (FXB_BANK_BAD_POSITION), d_w != d_r (FXB_BANK_PHASE), d != 0 on a line that is no ring (FXB_BANK_NO_RING).  They are
+ *   all or nothing per call: a first small kernel works out the rotations and counts the bad entries into a device cell, the
+ *   scatter reads that cell and every workgroup leaves without a store if it is not zero.  A refused recall changes no word of
+ *   the batch and still returns 0.  (The host has noted its registers as for a recall that ran: at most a register row more.)
+ * fxb_bank_status: waits for the queued bank calls, then reports how many recalls the device has refused since the last reset,
+ *   and of the most recent refused one the lowest bad list entry (-1: none) and its reason (FXB_BANK_*; 0: none; an entry bad on
+ *   both lines reports iTRAM's).  Any of the three pointers may be null; reset != 0 zeroes the count afterwards.
+ * fxb_bank_put / fxb_bank_get: slots from and to the instance-image format above - record k of the image and slot slots[k] - with
+ *   the header and the checks of fxb_load_instances / fxb_save_instances (fxb_instance_image_size(h, count) bytes).  Synchronous,
+ *   behind everything queued.  A store followed by a get gives the bytes of fxb_save_instances; an image of fxb_save_instances
+ *   that is put and recalled leaves what fxb_load_instances_rotated leaves.  put: slots may not repeat; get: they may.  They are
+ *   also the door to another handle's bank.
+ * Registers: the host keeps, per slot, what it knows of every register that is neither tracked nor kept per instance by the
+ *   program itself - the word (a put knows the image's; a store knows the bits of a register the host holds as one value at that
+ *   moment) or "unknown".  A recall makes a register per-instance, as if fxb_set_register_i had written it, unless every recalled
+ *   slot is known to hold the bits the host holds now: storing and recalling voices whose controls were never moved asks for no
+ *   other code (FXB_INFO_NUM_LANE_REGS stays), and a recall across a broadcast fxb_set_register keeps the stored value in the
+ *   recalled voice and the broadcast one in the others.
+ * Sharded handles: every shard holds its own copy of the bank (FXB_INFO_BANK_BYTES sums them), so any instance recalls any slot
+ *   without traffic between devices.  put goes to every shard.  store gathers on the shard that owns the instance and then copies
+ *   the stored slots to the other shards through pinned host memory: with more than one shard it blocks, as a crossing pair of
+ *   fxb_copy_instances does.  recall is split by shard and stays stream-ordered on each; THE GATE HOLDS PER SHARD - a bad entry
+ *   stops the part of the call that fell to its shard, the other shards' parts run - the refused count sums the shards (a call
+ *   refused on two shards counts twice) and `entry` is in the caller's numbering: an index into the list as it was passed.
+ * Bank calls leave meters, armed control tracks and the FXB_INFO_*_BLOCKS counters alone.  FXB_INFO_BANK_STORES / _RECALLS count
+ *   the launches of fx_bank_gather / fx_bank_scatter_rot - a refused recall has launched - and FXB_INFO_INSTANCE_* do not move.
+ * 0, FX_E_NOTREADY without a program, or FX_E_ARG with nothing launched, nothing changed and the reason in fxb_last_error: no
+ * bank, count < 0, a null list with count > 0, a slot outside 0..n_slots-1, an instance outside 0..N-1, a repeated slot in store
+ * or put, a repeated destination in recall, a short buffer, an image of another program, kind or version.  count == 0 returns 0
+ * on a handle with a bank. */
+#define FXB_BANK_BAD_POSITION 1
+#define FXB_BANK_PHASE 2
+#define FXB_BANK_NO_RING 3
+int fxb_bank_create(fxb_handle* h, int64_t n_slots);
+int64_t fxb_bank_slots(fxb_handle* h);
+int fxb_bank_store(fxb_handle* h, const int64_t* slots, const int64_t* list, int64_t count);
+int fxb_bank_recall(fxb_handle* h, const int64_t* slots, const int64_t* list, int64_t count);
+int fxb_bank_put(fxb_handle* h, const int64_t* slots, int64_t count, const void* image, int64_t bytes);
+int fxb_bank_get(fxb_handle* h, const int64_t* slots, int64_t count, void* buf, int64_t cap);
+int fxb_bank_status(fxb_handle* h, int64_t* refused_calls, int64_t* entry, int* reason, int reset);
 /* Register sets by list: the parameters of the program itself - a cutoff, a decay, a pitch per voice - for the instances a host
  * moves, scattered on the GPU behind the queued blocks.  fxb_set_register_i waits on the host for every queued block and copies
  * four bytes; fxb_set_register_array moves all N values of a register.  These two move n_keys * count words with one launch.
@@ -1047,6 +1108,10 @@ enum {
     FXB_INFO_METER_LEVEL_LAUNCHES = 64,  /* meter launches that took the level rows (fx_meter_level, fx_meter_target_level) since creation (summed over shards) */
     FXB_INFO_METER_LEVEL_SELECTS = 65,   /* calls of fxb_meter_select_level that launched (fx_level_count / fx_meter_scan / fx_level_emit) since creation (summed over shards) */
     FXB_INFO_METER_LEVEL_LIST_READS = 66, /* calls of fxb_meter_read_level_list that launched (fx_level_gather) since creation (summed over shards) */
+    FXB_INFO_BANK_SLOTS = 67,            /* slots of the record bank (fxb_bank_create), 0 without one; every shard holds them all: not summed */
+    FXB_INFO_BANK_STORES = 68,           /* launches of the kernel fx_bank_gather - by fxb_bank_store - since creation (summed over shards) */
+    FXB_INFO_BANK_RECALLS = 69,          /* launches of the kernel fx_bank_scatter_rot - by fxb_bank_recall, refused ones included - since creation (summed over shards) */
+    FXB_INFO_BANK_BYTES = 70,            /* device memory of the bank's slots: n_slots * W * 4 (summed over shards: each holds a copy) */
     FXB_INFO_TRACK_LIST_EXPANDS = 60   /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
 };
 int64_t fxb_info(fxb_handle* h, int what);
