@@ -1004,6 +1004,9 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_METER_LEVEL_LAUNCHES) return meterLevelLaunches_;
     if (what == FXB_INFO_METER_LEVEL_SELECTS) return levelSelects_;
     if (what == FXB_INFO_METER_LEVEL_LIST_READS) return levelListReads_;
+    if (what == FXB_INFO_METER_RANKS) return meterRanks_;
+    if (what == FXB_INFO_METER_MATCH_RANKS) return matchRanks_;
+    if (what == FXB_INFO_METER_LEVEL_RANKS) return levelRanks_;
     if (what == FXB_INFO_BANK_SLOTS) return bankSlots_;
     if (what == FXB_INFO_BANK_STORES) return bankStores_;
     if (what == FXB_INFO_BANK_RECALLS) return bankRecalls_;

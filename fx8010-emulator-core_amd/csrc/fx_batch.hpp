@@ -28,6 +28,7 @@
 #include "fx_kernel.hpp"
 #include "fx_meter.hpp"
 #include "fx_meter_list.hpp"
+#include "fx_meter_rank.hpp"
 #include "fx_knobs.hpp"
 #include "fx_model.hpp"
 
@@ -432,6 +433,16 @@ public:
     // select over V = the channel maximum of `level` (stat 0) or the channel MINIMUM of `quiet` (stat 1): everything else as meterSelect
     static int checkLevelSelect(int stat, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
     int64_t levelSelect(int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
+    // Meter ranks (fx_meter_rank.hpp; include/fx8010_amd.h "Meter ranks"; fx_batch_meter_rank.cpp).  Split check / reserve / act
+    // like the selects.  family: kRankMeter / kRankMatch / kRankLevel - the rows, the range of `stat`, the counter.  checkMeterRank
+    // holds the refusals that read nothing but the arguments.  reserveMeterRank grows the staging of the meter queries by list to
+    // what this batch's part needs (FX_E_MEMORY changes nothing; FX_E_ARG while metering is off).  meterRank looks at the local
+    // columns first .. first + nRange - 1 and writes the first R = min(M, k) candidates under the order (V, n) - V descending with
+    // `largest`, ties to the smaller number - as firstGlobal + (column - first) to `list` and their V to `value` (may be null), in
+    // rank order; nothing beyond R is touched; it returns M.  Synchronous; changes nothing on the device but the staging.
+    static int checkMeterRank(int family, int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, unsigned flags, std::string* why);
+    int reserveMeterRank(int64_t nRange, int64_t k);
+    int64_t meterRank(int family, int stat, int64_t k, double threshold, bool below, bool largest, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, double* value);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -983,6 +994,7 @@ private:
     int zeroLevelRows();   // queued on stream_ and waited for
     LevelParams levelParams() const { return LevelParams{dLevel_, levelRelease_, levelFloor_}; }
     int64_t meterLevelLaunches_ = 0, levelSelects_ = 0, levelListReads_ = 0;   // FXB_INFO_METER_LEVEL_LAUNCHES / _LEVEL_SELECTS / _LEVEL_LIST_READS
+    int64_t meterRanks_ = 0, matchRanks_ = 0, levelRanks_ = 0;   // FXB_INFO_METER_RANKS / _MATCH_RANKS / _LEVEL_RANKS (fx_batch_meter_rank.cpp)
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

@@ -305,6 +305,15 @@ int64_t fxb_meter_target_pos(fxb_handle* h) { return h ? guard(&h->batch.front()
 int fxb_meter_read_match(fxb_handle* h, double* err, double* cross, int reset) {
     return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadMatch(err, cross, reset != 0); }) : FX_E_ARG;
 }
+int64_t fxb_meter_rank(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterRank(fx::kRankMeter, stat, k, threshold, first, n_range, list, value, flags); }) : (int64_t)FX_E_ARG;
+}
+int64_t fxb_meter_rank_match(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterRank(fx::kRankMatch, stat, k, threshold, first, n_range, list, value, flags); }) : (int64_t)FX_E_ARG;
+}
+int64_t fxb_meter_rank_level(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterRank(fx::kRankLevel, stat, k, threshold, first, n_range, list, value, flags); }) : (int64_t)FX_E_ARG;
+}
 int64_t fxb_meter_select_match(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
     return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelectMatch(stat, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
 }

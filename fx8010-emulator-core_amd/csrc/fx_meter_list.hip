@@ -49,6 +49,7 @@
 
 #include "fx_meter.hpp"
 #include "fx_meter_list.hpp"
+#include "fx_meter_value.hpp"
 
 namespace fx {
 
@@ -58,38 +59,19 @@ constexpr int kLanes = kMeterSelectChunk;
 constexpr int kWaves = kLanes / 64;
 static_assert(kMeterScanWidth == kLanes, "the scan is one workgroup of that many lanes");
 
-// whether instance first + i of the range matches; i is the lane's index in the range
+// whether instance first + i of the range matches; i is the lane's index in the range.  V(n) is taken by fx_meter_value.hpp, the
+// one place that defines it for the selects, fx_meter_best and the ranks (fx_meter_rank.hip)
 __device__ __forceinline__ bool meterMatches(const MeterSelectArgs& a, long long i) {
     if (i >= a.nRange) return false;
     const long long col = a.first + i;
     if (col >= a.n) return false;   // (cannot be: first + nRange <= n.  The padding never matches.)
-    const char* ch = static_cast<const char*>(a.rows);
-    double best = 0.0;
-    for (int c = 0; c < a.channels; ++c, ch += meterChannelBytes(a.nPad)) {
-        double v;
-        if (a.stat == 0) v = reinterpret_cast<const double*>(ch + meterEnergyOff(a.nPad))[col];
-        else if (a.stat == 1) v = (double)reinterpret_cast<const float*>(ch + meterPeakOff(a.nPad))[col];
-        else if (a.stat == 2) v = (double)reinterpret_cast<const uint32_t*>(ch + meterFullScaleOff(a.nPad))[col];
-        else v = (double)reinterpret_cast<const uint32_t*>(ch + meterNonfiniteOff(a.nPad))[col];
-        best = (c == 0 || v > best) ? v : best;
-    }
+    const double best = meterValue(a.rows, a.nPad, a.channels, a.stat, col);
     return a.below ? best < a.threshold : best >= a.threshold;
 }
 
 // (the bodies of the count and the emit take the predicate through their argument type: matchesRange is overloaded, so the
 // select over the match rows of a target - MatchSelectArgs, below - runs the same code with the channel-sum predicate)
 __device__ __forceinline__ bool matchesRange(const MeterSelectArgs& a, long long i) { return meterMatches(a, i); }
-
-// V(n) over the match rows: ((v0 + v1) + v2) + v3 in fp64, in channel order, starting from v0
-__device__ __forceinline__ double matchValue(const void* rows, long long nPad, int channels, int stat, long long col) {
-    const char* ch = static_cast<const char*>(rows) + (stat == 0 ? matchErrOff(nPad) : matchCrossOff(nPad));
-    double sum = reinterpret_cast<const double*>(ch)[col];
-    for (int c = 1; c < channels; ++c) {
-        ch += matchChannelBytes(nPad);
-        sum = sum + reinterpret_cast<const double*>(ch)[col];
-    }
-    return sum;
-}
 
 __device__ __forceinline__ bool matchesRange(const MatchSelectArgs& a, long long i) {
     if (i >= a.nRange) return false;
@@ -104,17 +86,7 @@ __device__ __forceinline__ bool matchesRange(const LevelSelectArgs& a, long long
     if (i >= a.nRange) return false;
     const long long col = a.first + i;
     if (col >= a.n) return false;
-    const char* ch = static_cast<const char*>(a.rows);
-    double best = 0.0;
-    for (int c = 0; c < a.channels; ++c, ch += levelChannelBytes(a.nPad)) {
-        if (a.stat == 0) {
-            const double v = (double)reinterpret_cast<const float*>(ch + levelLevelOff(a.nPad))[col];
-            best = (c == 0 || v > best) ? v : best;
-        } else {
-            const double v = (double)reinterpret_cast<const uint32_t*>(ch + levelQuietOff(a.nPad))[col];
-            best = (c == 0 || v < best) ? v : best;
-        }
-    }
+    const double best = levelValue(a.rows, a.nPad, a.channels, a.stat, col);
     return a.below ? best < a.threshold : best >= a.threshold;
 }
 

@@ -435,6 +435,64 @@ int64_t Sharded::selectRange(SelectRows rows, int stat, double threshold, int64_
     return total;
 }
 
+int64_t Sharded::meterRank(int family, int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterRank(family, stat, k, threshold, first, nRange, n_, list, flags, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (family == kRankMatch && !front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
+    if (family == kRankLevel && !front().meterLevelOn()) { lastError_ = "level meters: the mode is off (fxb_meter_set_level)"; return FX_E_ARG; }
+    if (nRange == 0) return 0;
+    const bool below = (flags & FXB_METER_BELOW) != 0, largest = (flags & FXB_METER_LARGEST) != 0;
+    if (shards_.size() == 1) {
+        if (const int rc = runOn(0, [&](Batch& b) { return b.reserveMeterRank(nRange, k); })) return rc;
+        int64_t m = 0;
+        const int rc = runOn(0, [&](Batch& b) {
+            m = b.meterRank(family, stat, k, threshold, below, largest, first, nRange, first, list, value);
+            return m < 0 ? (int)m : 0;
+        });
+        return rc != 0 ? rc : m;
+    }
+    // the part of the range every shard owns (local numbers) and a block of its own for its min(k, part) pairs: what a shard finds
+    // depends on no other shard, so all of them run side by side
+    struct Part { int64_t first = 0, count = 0, m = 0; std::vector<int64_t> found; std::vector<double> value; };
+    std::vector<Part> parts(shards_.size());
+    for (size_t s = 0; s < shards_.size(); ++s) {
+        const int64_t lo = std::max(first, shards_[s]->first), hi = std::min(first + nRange, shards_[s]->first + shards_[s]->count);
+        if (hi <= lo) continue;
+        parts[s].first = lo - shards_[s]->first;
+        parts[s].count = hi - lo;
+        parts[s].found.resize((size_t)std::min(k, parts[s].count));
+        parts[s].value.resize(parts[s].found.size());
+    }
+    if (const int rc = fan([&](int s, Batch& b) { return b.reserveMeterRank(parts[(size_t)s].count, k); })) return rc;
+    const int rc = fan([&](int s, Batch& b) {
+        Part& p = parts[(size_t)s];
+        if (p.count == 0) return 0;
+        p.m = b.meterRank(family, stat, k, threshold, below, largest, p.first, p.count, shards_[(size_t)s]->first + p.first, p.found.data(), p.value.data());
+        return p.m < 0 ? (int)p.m : 0;
+    });
+    if (rc != 0) return rc;
+    // the merge: every part is in rank order already; the head of the part that comes first under the order is taken, k times
+    int64_t total = 0, written = 0;
+    std::vector<size_t> at(parts.size(), 0);
+    for (const Part& p : parts) total += p.m;
+    while (written < std::min(k, total)) {
+        int best = -1;
+        for (size_t s = 0; s < parts.size(); ++s) {
+            const Part& p = parts[s];
+            if (at[s] >= (size_t)std::min(p.m, (int64_t)p.found.size())) continue;
+            if (best < 0 || rankBefore(p.value[at[s]], p.found[at[s]], parts[(size_t)best].value[at[(size_t)best]], parts[(size_t)best].found[at[(size_t)best]], largest)) best = (int)s;
+        }
+        if (best < 0) break;   // (cannot be: the parts hold min(k, M_s) pairs each, together at least min(k, total))
+        list[written] = parts[(size_t)best].found[at[(size_t)best]];
+        if (value) value[written] = parts[(size_t)best].value[at[(size_t)best]];
+        ++at[(size_t)best];
+        ++written;
+    }
+    return total;
+}
+
 int Sharded::meterReadList(const int64_t* list, int64_t count, double* energy, float* peak, uint32_t* fullScale, uint32_t* nonfinite, bool reset) {
     Serial serial(api_);
     lastError_.clear();
@@ -1225,6 +1283,7 @@ int64_t Sharded::info(int what) {
         what == FXB_INFO_METER_SELECTS || what == FXB_INFO_METER_LIST_READS || what == FXB_INFO_METER_LIST_RESETS || what == FXB_INFO_TRACK_LIST_EXPANDS ||
         what == FXB_INFO_METER_TARGET_LAUNCHES || what == FXB_INFO_METER_MATCH_SELECTS || what == FXB_INFO_METER_MATCH_BESTS ||
         what == FXB_INFO_METER_LEVEL_LAUNCHES || what == FXB_INFO_METER_LEVEL_SELECTS || what == FXB_INFO_METER_LEVEL_LIST_READS ||
+        what == FXB_INFO_METER_RANKS || what == FXB_INFO_METER_MATCH_RANKS || what == FXB_INFO_METER_LEVEL_RANKS ||
         what == FXB_INFO_BANK_STORES || what == FXB_INFO_BANK_RECALLS || what == FXB_INFO_BANK_BYTES ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;

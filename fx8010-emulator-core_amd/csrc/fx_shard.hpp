@@ -114,6 +114,11 @@ public:
     int meterReadLevel(float* level, uint32_t* quiet, bool reset);
     int meterReadLevelList(const int64_t* list, int64_t count, float* level, uint32_t* quiet, bool reset);
     int64_t meterSelectLevel(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
+    // meter ranks (Batch "Meter ranks"; family: kRankMeter / kRankMatch / kRankLevel): the arguments are checked for the whole
+    // handle; every shard reserves the staging of its part of the range before any shard launches; each shard answers with its own
+    // first min(k, M_s) pairs, and the parts are merged under the same total order on global instance numbers - the first k of
+    // the whole range are among them.  The return value is the sum of the M_s; a shard whose part is empty launches nothing.
+    int64_t meterRank(int family, int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags);
     // bus gains (Batch::busSetGains ...): `gains` is [channels][all instances] by global instance, checked as a whole (every value
     // finite) before any shard is posted; every shard reserves its blocks first and only when all of them could is any shard's
     // state changed (FX_E_MEMORY leaves the gains as they were everywhere); null turns them off.  get assembles the same layout.

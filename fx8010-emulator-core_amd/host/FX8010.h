@@ -384,6 +384,25 @@ public:
         if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterSelectLevel: ") + fxb_last_error(h_));
         return m;
     }
+    // Meter ranks (include/fx8010_amd.h "Meter ranks"): the first min(M, k) candidates of first .. first + nRange - 1 under the order
+    // (V, n) - V descending with FXB_METER_LARGEST, ties to the smaller instance number - into list (and their V into value, which
+    // may be null), in rank order; returns M.  meterRank over the four accumulators, meterRankMatch over the match rows of a target,
+    // meterRankLevel over the level rows.
+    int64_t meterRank(int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags = 0) {
+        const int64_t m = fxb_meter_rank(h_, stat, k, threshold, first, nRange, list, value, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterRank: ") + fxb_last_error(h_));
+        return m;
+    }
+    int64_t meterRankMatch(int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags = 0) {
+        const int64_t m = fxb_meter_rank_match(h_, stat, k, threshold, first, nRange, list, value, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterRankMatch: ") + fxb_last_error(h_));
+        return m;
+    }
+    int64_t meterRankLevel(int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags = 0) {
+        const int64_t m = fxb_meter_rank_level(h_, stat, k, threshold, first, nRange, list, value, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterRankLevel: ") + fxb_last_error(h_));
+        return m;
+    }
     // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
     // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
     // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and

@@ -33,12 +33,14 @@ INFO = {
     "meter_target_launches": 61, "meter_match_selects": 62, "meter_match_bests": 63,
     "meter_level_launches": 64, "meter_level_selects": 65, "meter_level_list_reads": 66,
     "bank_slots": 67, "bank_stores": 68, "bank_recalls": 69, "bank_bytes": 70,
+    "meter_ranks": 71, "meter_match_ranks": 72, "meter_level_ranks": 73,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
 TRAM_LOGICAL, TRAM_BROADCAST = 1, 2  # FXB_TRAM_* of include/fx8010_amd.h
 METER_ENERGY, METER_PEAK, METER_FULL_SCALE, METER_NONFINITE = 0, 1, 2, 3  # FXB_METER_* of include/fx8010_amd.h: the `stat` of meter_select
 METER_BELOW = 1
+METER_LARGEST = 2  # FXB_METER_LARGEST: the flag of the meter_rank calls (the same bit as MATCH_LARGEST)
 METER_TARGET_LOOP = 1  # FXB_METER_TARGET_LOOP: the flag of meter_set_target
 MATCH_ERROR, MATCH_CROSS = 0, 1  # FXB_MATCH_*: the `stat` of meter_select_match and meter_best
 MATCH_LARGEST = 2  # FXB_MATCH_LARGEST: the flag of meter_best
@@ -64,6 +66,7 @@ SYMBOLS = [
     "fxb_meter_enable", "fxb_meter_read", "fxb_meter_samples", "fxb_meter_select", "fxb_meter_read_list", "fxb_meter_reset_list",
     "fxb_meter_set_target", "fxb_meter_clear_target", "fxb_meter_target_seek", "fxb_meter_target_pos", "fxb_meter_read_match", "fxb_meter_select_match", "fxb_meter_best",
     "fxb_meter_set_level", "fxb_meter_clear_level", "fxb_meter_get_level", "fxb_meter_read_level", "fxb_meter_read_level_list", "fxb_meter_select_level",
+    "fxb_meter_rank", "fxb_meter_rank_match", "fxb_meter_rank_level",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -141,6 +144,8 @@ def load():
     sig("fxb_meter_read_match", i32, vp, vp, vp, i32); sig("fxb_meter_select_match", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_best", i32, vp, i32, i64, vp, vp, C.c_uint)
     sig("fxb_meter_set_level", i32, vp, f32, f32, C.c_uint); sig("fxb_meter_clear_level", i32, vp); sig("fxb_meter_get_level", i32, vp, vp, vp)
     sig("fxb_meter_read_level", i32, vp, vp, vp, i32); sig("fxb_meter_read_level_list", i32, vp, vp, i64, vp, vp, i32); sig("fxb_meter_select_level", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint)
+    for name in ("fxb_meter_rank", "fxb_meter_rank_match", "fxb_meter_rank_level"):
+        sig(name, i64, vp, i32, i64, C.c_double, i64, i64, vp, vp, C.c_uint)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -1137,6 +1142,32 @@ class Batch(_Reports):
         m = self._check(int(self._lib.fxb_meter_select_level(self._h, int(stat), float(threshold), first, n_range, C.c_void_p(out.ctypes.data) if out.size else None,
                                                              cap, METER_BELOW if below else 0)), "meter_select_level")
         return out[:min(m, out.size)], m
+
+    def _meter_rank(self, name, stat, k, threshold, below, largest, first, n_range):
+        first, k = int(first), int(k)
+        n_range = self.n - first if n_range is None else int(n_range)
+        room = max(min(k, n_range), 0)
+        lst, val = np.empty(max(room, 1), dtype=np.int64), np.empty(max(room, 1), dtype=np.float64)   # (never null: k > 0 over an empty range is no refusal)
+        m = self._check(int(getattr(self._lib, "fxb_" + name)(self._h, int(stat), k, float(threshold), first, n_range, C.c_void_p(lst.ctypes.data),
+                                                              C.c_void_p(val.ctypes.data), (METER_BELOW if below else 0) | (METER_LARGEST if largest else 0))), name)
+        r = min(m, room)
+        return m, lst[:r], val[:r]
+
+    def meter_rank(self, stat, k, threshold=-np.inf, below=False, largest=False, first=0, n_range=None):
+        """The first k instances of first .. first + n_range - 1 under the order (V, n) - V as meter_select takes it, ascending (with
+        `largest` descending), ties to the smaller instance number - among those meter_select would match (V >= threshold, with
+        `below` V < threshold; the default takes the whole range), chosen on the device.  (M, list, values): M candidates, the
+        min(M, k) instance numbers in rank order and their V."""
+        return self._meter_rank("meter_rank", stat, k, threshold, below, largest, first, n_range)
+
+    def meter_rank_match(self, stat, k, threshold=-np.inf, below=False, largest=False, first=0, n_range=None):
+        """meter_rank over the match rows of a target: V is the channel sum of MATCH_ERROR or MATCH_CROSS.  (M, list, values)."""
+        return self._meter_rank("meter_rank_match", stat, k, threshold, below, largest, first, n_range)
+
+    def meter_rank_level(self, stat, k, threshold=-np.inf, below=False, largest=False, first=0, n_range=None):
+        """meter_rank over the level meters: V is the channel maximum of the envelope (LEVEL_ENVELOPE) or the channel MINIMUM of the
+        quiet run (LEVEL_QUIET) - the k quietest voices are meter_rank_level(LEVEL_ENVELOPE, k).  (M, list, values)."""
+        return self._meter_rank("meter_rank_level", stat, k, threshold, below, largest, first, n_range)
 
     def meter_samples(self):
         """sample periods metered since the last reset"""

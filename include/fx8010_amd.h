@@ -1003,6 +1003,45 @@ int     fxb_meter_get_level(fxb_handle* h, float* release, float* floor);       
 int     fxb_meter_read_level(fxb_handle* h, float* level, uint32_t* quiet, int reset);          /* [C][N]; pointers may be NULL */
 int     fxb_meter_read_level_list(fxb_handle* h, const int64_t* list, int64_t count, float* level, uint32_t* quiet, int reset); /* [C][count] */
 int64_t fxb_meter_select_level(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
+/* Meter ranks: the K quietest, loudest or closest voices, chosen on the device.  The selects answer "which voices pass this
+ * threshold" and fxb_meter_best "which one voice of each group is closest"; a rank answers the question a voice pool asks when it
+ * is full (a note-on arrives, no voice is below the floor: which K have the lowest envelope, whatever it is?), a fitting loop after
+ * every sweep (the K best candidates of the whole range) and a diagnostic (the ten loudest).  It is an order statistic, and the
+ * answer is K numbers - never the rows of every instance and a sort on the host.
+ *
+ * The definition.  fxb_meter_rank, fxb_meter_rank_match and fxb_meter_rank_level take (h, stat, k, threshold, first, n_range,
+ *   list, value, flags):
+ *   - V(n) is exactly the V(n) of the select of the same family, taken by the same device code: for the meter stats the fp64
+ *     maximum over the channels; for the match stats the fp64 sum in channel order, starting from v(0,n); for FXB_LEVEL_ENVELOPE
+ *     the maximum over the channels; for FXB_LEVEL_QUIET the minimum over the channels.
+ *   - Candidates are the instances n in first .. first + n_range - 1 that the select would match: V(n) >= threshold, or with
+ *     FXB_METER_BELOW V(n) < threshold.  threshold = -Inf without BELOW takes the whole range.  M is the number of candidates.
+ *   - Candidates are ordered by the total order (V, n): V ascending as real numbers, so -0.0 equals +0.0, and ties go to the
+ *     smaller instance number.  With FXB_METER_LARGEST the order is V descending, ties still to the smaller instance number.
+ *   - The call writes the first R = min(M, k) candidates of that order to list[0..R-1] in rank order.  Their V goes to
+ *     value[0..R-1] when `value` is not NULL.  Neither array is touched beyond R.  The call returns M, as the selects do.
+ *   - k == 0 is a count query, and n_range == 0 returns 0 without a launch.
+ *   - No V is ever NaN (argued per family above), so the order is total.
+ *   - The call is synchronous and changes nothing, like fxb_meter_select.  It covers a list reset still in flight.
+ * Refusals.  FX_E_ARG, with nothing launched: everything the matching select refuses (the mode off - metering, the target, the
+ *   level meters -, `stat` out of the family's range, a NaN threshold, the range rules, an unknown flag bit); k < 0; a NULL `list`
+ *   with k > 0.  FX_E_MEMORY when the staging cannot be allocated: it is grown on demand, freed with the handle and sized by
+ *   min(k, n_range) - 16 bytes per pair - plus 16 bytes per chunk of 256 instances and a fixed 16 KB of histograms; nothing has
+ *   changed afterwards.
+ * The device side is a selection, not a sort: a radix select over 64-bit keys (V + 0.0 with the sign-flip transform, complemented
+ *   for LARGEST) finds the key of the k-th candidate in eight passes of eight bits, then the count / scan / emit pattern of the
+ *   selects writes the winners - a tie at the k-th key goes to the first of the equals by instance number.  The number of launches
+ *   (eleven kernels behind one memset; ten for a count query) depends neither on N nor on the data; there is one wait, at the end;
+ *   min(M, k) * 16 bytes and four words cross PCIe (for M < k: min(k, 4 096) pairs, so that the wait stays one).  The only atomics
+ *   are integer adds into histogram bins, whose sums no order can change: the same bits run to run.
+ * Sharded handles: each shard answers for its part of the range with its own first min(k, M_s) pairs, and the host merges the parts
+ *   under the same total order on global instance numbers; the result equals the single handle's word for word.  A shard whose
+ *   part is empty launches nothing.  The return value is the sum of the M_s.
+ * FXB_INFO_METER_RANKS / _MATCH_RANKS / _LEVEL_RANKS count the calls that launched, summed over shards. */
+#define FXB_METER_LARGEST (1u << 1)   /* same bit as FXB_MATCH_LARGEST */
+int64_t fxb_meter_rank(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);
+int64_t fxb_meter_rank_match(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);   /* stat: FXB_MATCH_ERROR / _CROSS; needs a target */
+int64_t fxb_meter_rank_level(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);   /* stat: FXB_LEVEL_ENVELOPE / _QUIET; needs level meters */
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -1112,7 +1151,10 @@ enum {
     FXB_INFO_BANK_STORES = 68,           /* launches of the kernel fx_bank_gather - by fxb_bank_store - since creation (summed over shards) */
     FXB_INFO_BANK_RECALLS = 69,          /* launches of the kernel fx_bank_scatter_rot - by fxb_bank_recall, refused ones included - since creation (summed over shards) */
     FXB_INFO_BANK_BYTES = 70,            /* device memory of the bank's slots: n_slots * W * 4 (summed over shards: each holds a copy) */
-    FXB_INFO_TRACK_LIST_EXPANDS = 60   /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
+    FXB_INFO_TRACK_LIST_EXPANDS = 60,  /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
+    FXB_INFO_METER_RANKS = 71,           /* calls of fxb_meter_rank that launched (fx_rank_hist / _count / _scan / _emit) since creation (summed over shards) */
+    FXB_INFO_METER_MATCH_RANKS = 72,     /* calls of fxb_meter_rank_match that launched since creation (summed over shards) */
+    FXB_INFO_METER_LEVEL_RANKS = 73      /* calls of fxb_meter_rank_level that launched since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
