@@ -82,6 +82,8 @@ Batch::~Batch() {
     releaseMeterTarget();
     (void)hipFree(dLevel_);
     releaseMeterLevel();
+    (void)hipFree(dTone_);
+    releaseMeterTones();
     (void)hipFree(dGain_[0]);
     (void)hipFree(dGain_[1]);
     if (hGain_) (void)hipHostFree(hGain_);
@@ -865,6 +867,8 @@ int Batch::meterReset() {
     if (e == hipSuccess && dMatch_) e = hipMemsetAsync(dMatch_, 0, matchChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
     // (... and the two level rows; the mode and its parameters stay)
     if (e == hipSuccess && dLevel_) e = hipMemsetAsync(dLevel_, 0, levelChannelBytes(nPad_) * (size_t)prog_.numChannels, stream_);
+    // (... and the tone rows behind their header; the mode and its coefficients stay)
+    if (e == hipSuccess && dTone_) e = hipMemsetAsync(static_cast<char*>(dTone_) + kToneHeaderBytes, 0, toneRowsBytes(nPad_, prog_.numChannels, toneCount_), stream_);
     if (e == hipSuccess) e = hipStreamSynchronize(stream_);
     meterSamples_ = 0;
     return e == hipSuccess ? 0 : hipFail(e, "zeroing the meter rows");
@@ -878,6 +882,7 @@ int Batch::meterEnable(bool on) {
     if (!on) {
         (void)clearMeterTarget();
         (void)clearMeterLevel();
+        (void)clearMeterTones();
         (void)hipFree(dMeter_);
         dMeter_ = nullptr;
         meterSamples_ = 0;
@@ -1011,6 +1016,10 @@ int64_t Batch::info(int what) {
     if (what == FXB_INFO_BANK_STORES) return bankStores_;
     if (what == FXB_INFO_BANK_RECALLS) return bankRecalls_;
     if (what == FXB_INFO_BANK_BYTES) return bankSlots_ * bankWords_ * 4;
+    if (what == FXB_INFO_METER_TONE_LAUNCHES) return meterToneLaunches_;
+    if (what == FXB_INFO_METER_TONE_SELECTS) return toneSelects_;
+    if (what == FXB_INFO_METER_TONE_LIST_READS) return toneListReads_;
+    if (what == FXB_INFO_METER_TONE_RANKS) return toneRanks_;
     if (what == FXB_INFO_WAVES_PER_WG) return (c_.useAsm && c_.useXlate) ? c_.stages : 1;
     if (ensureLowered() != 0) return -1;
     switch (what) {

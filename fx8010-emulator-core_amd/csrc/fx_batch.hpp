@@ -29,6 +29,7 @@
 #include "fx_meter.hpp"
 #include "fx_meter_list.hpp"
 #include "fx_meter_rank.hpp"
+#include "fx_meter_tone.hpp"
 #include "fx_knobs.hpp"
 #include "fx_model.hpp"
 
@@ -443,6 +444,28 @@ public:
     static int checkMeterRank(int family, int stat, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, unsigned flags, std::string* why);
     int reserveMeterRank(int64_t nRange, int64_t k);
     int64_t meterRank(int family, int stat, int64_t k, double threshold, bool below, bool largest, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, double* value);
+    // Tone meters (fx_meter_tone.hpp; include/fx8010_amd.h "Tone meters"; fx_batch_meter_tone.cpp).  Split check / reserve / act
+    // like the level meters.  checkMeterTones refuses for the whole handle and canonicalises -0.0 to +0.0.  reserveMeterTones is
+    // the allocating half - a tone block for `tones` tones, kept aside; FX_E_MEMORY or FX_E_ARG (metering off) changes nothing.
+    // setMeterTones waits as sync() does, takes the block into force with its header written and its rows zeroed and frees the
+    // block it replaces: the accumulators of other coefficients mean nothing.  While the mode is on launchBlock queues
+    // fx_meter_tone<K> behind the meter launch of the block, with the coefficients by value.  The reads, the select and the rank
+    // are synchronous and share the staging of the meter queries by list (reserveToneList: a packed side of 24 bytes per tone,
+    // channel and entry).
+    static int checkMeterTones(int tones, const double* coeff, unsigned flags, double* canonical, std::string* why);
+    int reserveMeterTones(int tones);
+    void releaseMeterTones();
+    int setMeterTones(int tones, const double* coeff);
+    int clearMeterTones();
+    int meterTones() const { return dTone_ ? toneCount_ : 0; }   // 0: the mode is off
+    int getMeterTones(int* tones, double* coeff);
+    int meterReadTones(double* s1, double* s2, double* power, bool reset, int64_t rowPitch = 0);
+    int reserveToneList(int64_t count);
+    int meterReadTonesList(const int64_t* list, const int64_t* pos, int64_t count, int64_t total, double* s1, double* s2, double* power, bool reset);
+    // select over V = the channel maximum of P(tone): everything else as meterSelect.  (the tone is checked against K by the caller
+    // that knows it: Sharded for the handle, runSelect for this batch)
+    static int checkToneSelect(int tone, double threshold, int64_t first, int64_t nRange, int64_t n, const int64_t* list, int64_t cap, unsigned flags, std::string* why);
+    int64_t toneSelect(int tone, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
     // one instance's delay memory as the reference holds it (which: 0 smallDelayBuffer, 1 largeDelayBuffer), and its positions
     int getTramAt(int which, int64_t inst, float* out, int nSlots);
     int getCursorsAt(int64_t inst, int32_t out4[4]);
@@ -973,7 +996,7 @@ private:
     Block<unsigned long long> meterStage_, hMeterStage_;
     int reserveMeterStage(size_t words, bool needEvent);
     int64_t meterSelects_ = 0, meterListReads_ = 0, meterListResets_ = 0;   // FXB_INFO_METER_SELECTS / _LIST_READS / _LIST_RESETS
-    enum class SelectRows { kMeter, kMatch, kLevel };   // which rows a select looks at, and with which predicate
+    enum class SelectRows { kMeter, kMatch, kLevel, kTone };   // which rows a select looks at, and with which predicate
     int64_t runSelect(SelectRows rows, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap);
     // target meters (fx_batch_meter_target.cpp): the target block and the match rows in force (null: no target), the blocks a
     // set has reserved and not yet taken, the shape of the target, and the position of the next queued block
@@ -995,6 +1018,16 @@ private:
     LevelParams levelParams() const { return LevelParams{dLevel_, levelRelease_, levelFloor_}; }
     int64_t meterLevelLaunches_ = 0, levelSelects_ = 0, levelListReads_ = 0;   // FXB_INFO_METER_LEVEL_LAUNCHES / _LEVEL_SELECTS / _LEVEL_LIST_READS
     int64_t meterRanks_ = 0, matchRanks_ = 0, levelRanks_ = 0;   // FXB_INFO_METER_RANKS / _MATCH_RANKS / _LEVEL_RANKS (fx_batch_meter_rank.cpp)
+    // tone meters (fx_batch_meter_tone.cpp): the tone block in force (null: the mode is off), the block a set has reserved and not
+    // yet taken with the tone count it was sized for, and the mode: K and the coefficients of the launches queued from now on
+    void* dTone_ = nullptr;
+    void* toneNew_ = nullptr;
+    int toneNewCount_ = 0;
+    int toneCount_ = 0;
+    double toneCoeff_[kMeterMaxTones] = {};
+    int zeroToneRows();   // queued on stream_ and waited for
+    int launchToneMeter(const MeterArgs& m, hipStream_t s);   // of the block that is about to be metered
+    int64_t meterToneLaunches_ = 0, toneSelects_ = 0, toneListReads_ = 0, toneRanks_ = 0;   // FXB_INFO_METER_TONE_LAUNCHES / _TONE_SELECTS / _TONE_LIST_READS / _TONE_RANKS
     // a delay line as fxb_load_instances_rotated sees it: size Z, allocated slots, and which position kinds the program has an
     // instruction of (whether or not it is ever executed: a kind whose only instruction sits in a SKIP shadow that is always taken
     // counts, so such a record is compared - and may be refused - rather than loaded unseen)

@@ -340,6 +340,10 @@ int Batch::launchBlock(const float* dIn, float* dOut, int nSamples, hipStream_t 
                 ++meterLaunches_;
             }
             meterSamples_ += nSamples;
+            // tone meters: a launch of its own behind whichever of the four ran, reading the same block, in front of ev1_
+            if (dTone_) {
+                if ((rc = launchToneMeter(m, s)) != 0) return rc;
+            }
         }
         if (e == hipSuccess && timed) e = hipEventRecord(ev1_, s);
         // A workgroup of several wavefronts that the device will not start (registers x wavefronts beyond a CU, LDS): the plain

@@ -65,12 +65,14 @@ int64_t Batch::meterSelect(int stat, double threshold, bool below, int64_t first
 }
 
 // rows: kMatch is the select over the match rows of a target (fx_batch_meter_target.cpp), kLevel the one over the level rows
-// (fx_batch_meter_level.cpp) - the same staging, copies and counts of words, another predicate on the device
+// (fx_batch_meter_level.cpp), kTone the one over the tone rows (fx_batch_meter_tone.cpp) - the same staging, copies and counts of words, another predicate on the device
 int64_t Batch::runSelect(SelectRows rows, int stat, double threshold, bool below, int64_t first, int64_t nRange, int64_t firstGlobal, int64_t* list, int64_t cap) {
     (void)hipSetDevice(device_);
     if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
     if (rows == SelectRows::kMatch && !dTarget_) return fail(FX_E_ARG, "meter target: no target is set (fxb_meter_set_target)");
     if (rows == SelectRows::kLevel && !dLevel_) return fail(FX_E_ARG, "level meters: the mode is off (fxb_meter_set_level)");
+    if (rows == SelectRows::kTone && !dTone_) return fail(FX_E_ARG, "tone meters: the mode is off (fxb_meter_set_tones)");
+    if (rows == SelectRows::kTone && (stat < 0 || stat >= toneCount_)) return fail(FX_E_ARG, "meter_select_tone: tone must lie in 0 .. n_tones - 1");
     if (nRange == 0) return 0;
     if (selectWords(nRange, cap) > meterStage_.cap || selectWords(nRange, cap) > hMeterStage_.cap) return fail(FX_E_ARG, "meter_select: no staging reserved (reserveMeterSelect)");
     const int rc = sync();
@@ -99,6 +101,9 @@ int64_t Batch::runSelect(SelectRows rows, int stat, double threshold, bool below
     } else if (rows == SelectRows::kLevel) {
         const LevelSelectArgs b{dLevel_, a.offsets, a.list, a.n, a.nPad, a.first, a.nRange, a.firstGlobal, a.cap, a.threshold, a.channels, a.stat, a.below};
         if ((e = launchLevelSelect(b, stream_)) == hipSuccess) ++levelSelects_;
+    } else if (rows == SelectRows::kTone) {
+        const ToneSelectArgs b{dTone_, a.offsets, a.list, a.n, a.nPad, a.first, a.nRange, a.firstGlobal, a.cap, a.threshold, a.channels, a.stat, a.below};
+        if ((e = launchToneSelect(b, stream_)) == hipSuccess) ++toneSelects_;
     } else if ((e = launchMeterSelect(a, stream_)) == hipSuccess) {
         ++meterSelects_;
     }
@@ -192,6 +197,11 @@ int Batch::meterResetList(const int64_t* list, int64_t count) {
     if (e == hipSuccess && dLevel_) {
         a.rows = dLevel_;
         e = launchLevelZero(a, stream_);
+    }
+    // (... and those of the tone rows: stores only, inside the same frame)
+    if (e == hipSuccess && dTone_) {
+        a.rows = dTone_;
+        e = launchToneZero(a, stream_);
     }
     if (const int failed = closeInstCall(e, "meter_reset_list: queueing the zeroing")) return failed;
     ++meterListResets_;

@@ -1,6 +1,6 @@
 // fx_batch_meter_rank.cpp — the meter ranks of one batch: the first k candidates of a range under the order (V, n), chosen on the
 // device (include/fx8010_amd.h "Meter ranks", fx_batch.hpp "Meter ranks", kernels: fx_meter_rank.hip).  One implementation serves
-// the three families - the four accumulators, the match rows of a target, the level rows: the family picks the rows, the range of
+// the four families - the four accumulators, the match rows of a target, the level rows, the tone rows: the family picks the rows, the range of
 // `stat` and the counter.
 //
 // Split check / reserve / act like the level meters (fx_batch_meter_level.cpp), so that a sharded handle can ask every shard before
@@ -22,7 +22,7 @@
 namespace fx {
 
 namespace {
-const char* const kRankNames[3] = {"meter_rank", "meter_rank_match", "meter_rank_level"};
+const char* const kRankNames[4] = {"meter_rank", "meter_rank_match", "meter_rank_level", "meter_rank_tone"};
 // pairs that travel with the result words in the one copy when M is not known to be smaller: all of them up to this many; a
 // longer list is fetched in a second copy once R is known
 constexpr int64_t kRankHead = 4096;
@@ -33,6 +33,7 @@ int Batch::checkMeterRank(int family, int stat, int64_t k, double threshold, int
     if (family == kRankMeter && (stat < FXB_METER_ENERGY || stat > FXB_METER_NONFINITE)) { *why = who + ": stat must be 0..3 (FXB_METER_ENERGY .. FXB_METER_NONFINITE)"; return FX_E_ARG; }
     if (family == kRankMatch && (stat < FXB_MATCH_ERROR || stat > FXB_MATCH_CROSS)) { *why = who + ": stat must be 0 or 1 (FXB_MATCH_ERROR, FXB_MATCH_CROSS)"; return FX_E_ARG; }
     if (family == kRankLevel && (stat < FXB_LEVEL_ENVELOPE || stat > FXB_LEVEL_QUIET)) { *why = who + ": stat must be 0 or 1 (FXB_LEVEL_ENVELOPE, FXB_LEVEL_QUIET)"; return FX_E_ARG; }
+    if (family == kRankTone && (stat < 0 || stat >= kMeterMaxTones)) { *why = who + ": tone must lie in 0 .. n_tones - 1"; return FX_E_ARG; }
     if (flags & ~(unsigned)(FXB_METER_BELOW | FXB_METER_LARGEST)) { *why = who + ": flags has an unknown bit"; return FX_E_ARG; }
     if (std::isnan(threshold)) { *why = who + ": the threshold is NaN"; return FX_E_ARG; }
     if (first < 0 || nRange < 0 || first > n || nRange > n - first) { *why = who + ": first .. first + n_range - 1 must lie in 0.." + std::to_string(n - 1); return FX_E_ARG; }
@@ -48,6 +49,8 @@ int64_t Batch::meterRank(int family, int stat, int64_t k, double threshold, bool
     if (!dMeter_) return fail(FX_E_ARG, "meters: metering is off (fxb_meter_enable)");
     if (family == kRankMatch && !dTarget_) return fail(FX_E_ARG, "meter target: no target is set (fxb_meter_set_target)");
     if (family == kRankLevel && !dLevel_) return fail(FX_E_ARG, "level meters: the mode is off (fxb_meter_set_level)");
+    if (family == kRankTone && !dTone_) return fail(FX_E_ARG, "tone meters: the mode is off (fxb_meter_set_tones)");
+    if (family == kRankTone && (stat < 0 || stat >= toneCount_)) return fail(FX_E_ARG, "meter_rank_tone: tone must lie in 0 .. n_tones - 1");
     if (nRange == 0) return 0;
     const int64_t room = std::min(k, nRange);
     const size_t words = meterRankStageWords(nRange, room);
@@ -55,7 +58,7 @@ int64_t Batch::meterRank(int family, int stat, int64_t k, double threshold, bool
     const int rc = sync();
     if (rc != 0) return rc;
     MeterRankArgs a{};
-    a.rows = family == kRankMatch ? dMatch_ : family == kRankLevel ? dLevel_ : dMeter_;
+    a.rows = family == kRankMatch ? dMatch_ : family == kRankLevel ? dLevel_ : family == kRankTone ? dTone_ : dMeter_;
     a.stage = meterStage_.p;
     a.n = n_;
     a.nPad = nPad_;
@@ -70,8 +73,8 @@ int64_t Batch::meterRank(int family, int stat, int64_t k, double threshold, bool
     a.stat = stat;
     a.below = below ? 1 : 0;
     a.largest = largest ? 1 : 0;
-    hipError_t e = launchMeterRank(a, stream_);
-    if (e == hipSuccess) ++(family == kRankMatch ? matchRanks_ : family == kRankLevel ? levelRanks_ : meterRanks_);
+    hipError_t e = family == kRankTone ? launchToneRank(a, stream_) : launchMeterRank(a, stream_);
+    if (e == hipSuccess) ++(family == kRankMatch ? matchRanks_ : family == kRankLevel ? levelRanks_ : family == kRankTone ? toneRanks_ : meterRanks_);
     // the result words and the pairs behind them in one copy; the rest of a list above kRankHead once R says how long it is
     const int64_t head = std::min(room, kRankHead);
     unsigned long long* const h = hMeterStage_.p;

@@ -336,6 +336,25 @@ int fxb_meter_read_level_list(fxb_handle* h, const int64_t* list, int64_t count,
 int64_t fxb_meter_select_level(fxb_handle* h, int stat, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
     return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelectLevel(stat, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
 }
+int fxb_meter_set_tones(fxb_handle* h, int n_tones, const double* coeff, unsigned flags) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterSetTones(n_tones, coeff, flags); }) : FX_E_ARG;
+}
+int fxb_meter_clear_tones(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterClearTones(); }) : FX_E_ARG; }
+int fxb_meter_get_tones(fxb_handle* h, int* n_tones, double* coeff) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterGetTones(n_tones, coeff); }) : FX_E_ARG;
+}
+int fxb_meter_read_tones(fxb_handle* h, double* s1, double* s2, double* power, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadTones(s1, s2, power, reset != 0); }) : FX_E_ARG;
+}
+int fxb_meter_read_tones_list(fxb_handle* h, const int64_t* list, int64_t n_list, double* s1, double* s2, double* power, int reset) {
+    return h ? guardCode(&h->batch.front(), [&] { return h->batch.meterReadTonesList(list, n_list, s1, s2, power, reset != 0); }) : FX_E_ARG;
+}
+int64_t fxb_meter_select_tone(fxb_handle* h, int tone, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSelectTone(tone, threshold, first, n_range, list, cap, flags); }) : (int64_t)FX_E_ARG;
+}
+int64_t fxb_meter_rank_tone(fxb_handle* h, int tone, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags) {
+    return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterRank(fx::kRankTone, tone, k, threshold, first, n_range, list, value, flags); }) : (int64_t)FX_E_ARG;
+}
 int64_t fxb_meter_samples(fxb_handle* h) { return h ? guard(&h->batch.front(), (int64_t)FX_E_PROGRAM, [&] { return h->batch.meterSamples(); }) : FX_E_ARG; }
 int fxb_sync(fxb_handle* h) { return h ? guardCode(&h->batch.front(), [&] { return h->batch.sync(); }) : FX_E_ARG; }
 int fxb_prepare(fxb_handle* h, int n_samples, int wait) { return h ? guard(&h->batch.front(), FX_E_PROGRAM, [&] { return h->batch.prepare(n_samples, wait != 0); }) : FX_E_ARG; }

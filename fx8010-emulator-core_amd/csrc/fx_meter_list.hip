@@ -45,6 +45,10 @@
 // the quiet run, both exact in fp64.  fx_level_gather / fx_level_zero are the one-lane-per-list-entry form of meterColumns on the
 // two level rows: the lane that has read a column stores its zeros.  Resource usage as above: fx_level_count 10 / 0 / 16,
 // fx_level_emit 14 / 0 / 16, fx_level_gather 11 / 0 / 0, fx_level_zero 6 / 0 / 0; eight wavefronts per SIMD each.
+//
+// The select over the tone rows (fx_meter_tone.hpp): fx_tone_count / fx_tone_emit are the two bodies with a fourth predicate,
+// picked by ToneSelectArgs: V is the maximum over the channels of tonePower.  Resource usage as above: fx_tone_count 14 / 0 / 16,
+// fx_tone_emit 16 / 0 / 16; eight wavefronts per SIMD each.
 #include <hip/hip_runtime.h>
 
 #include "fx_meter.hpp"
@@ -90,6 +94,15 @@ __device__ __forceinline__ bool matchesRange(const LevelSelectArgs& a, long long
     return a.below ? best < a.threshold : best >= a.threshold;
 }
 
+// V(n) over the tone rows: the maximum over the channels of P of tone `stat`
+__device__ __forceinline__ bool matchesRange(const ToneSelectArgs& a, long long i) {
+    if (i >= a.nRange) return false;
+    const long long col = a.first + i;
+    if (col >= a.n) return false;
+    const double best = toneValue(a.rows, a.nPad, a.channels, a.stat, col);
+    return a.below ? best < a.threshold : best >= a.threshold;
+}
+
 template <class Args>
 __device__ __forceinline__ void selectCount(const Args& a) {
     __shared__ unsigned waveCount[kWaves];
@@ -108,6 +121,7 @@ __device__ __forceinline__ void selectCount(const Args& a) {
 __global__ __launch_bounds__(kLanes) void fx_meter_count(MeterSelectArgs a) { selectCount(a); }
 __global__ __launch_bounds__(kLanes) void fx_match_count(MatchSelectArgs a) { selectCount(a); }
 __global__ __launch_bounds__(kLanes) void fx_level_count(LevelSelectArgs a) { selectCount(a); }
+__global__ __launch_bounds__(kLanes) void fx_tone_count(ToneSelectArgs a) { selectCount(a); }
 
 // one workgroup: offsets[0 .. chunks - 1] counts -> their exclusive scan, offsets[chunks] = the total.  Lane t owns the `per`
 // consecutive counts from t * per on: the loads of one lane are independent, so their latencies overlap
@@ -156,6 +170,7 @@ __device__ __forceinline__ void selectEmit(const Args& a) {
 __global__ __launch_bounds__(kLanes) void fx_meter_emit(MeterSelectArgs a) { selectEmit(a); }
 __global__ __launch_bounds__(kLanes) void fx_match_emit(MatchSelectArgs a) { selectEmit(a); }
 __global__ __launch_bounds__(kLanes) void fx_level_emit(LevelSelectArgs a) { selectEmit(a); }
+__global__ __launch_bounds__(kLanes) void fx_tone_emit(ToneSelectArgs a) { selectEmit(a); }
 
 // fx_meter_best: wavefront w of the grid owns group firstGroup + w.  Its local members are the columns lo .. hi - 1; lane l
 // looks at lo + l, lo + l + 64, ... and keeps the best (V, n).  kNone marks a lane that has seen no member (a group below 64).
@@ -328,6 +343,21 @@ hipError_t launchLevelSelect(const LevelSelectArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
     if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
     hipLaunchKernelGGL(fx_level_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchToneSelect(const ToneSelectArgs& a, hipStream_t stream) {
+    if (!a.rows || !a.offsets || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.stat < 0 || a.stat >= kMeterMaxTones) return hipErrorInvalidValue;
+    if (a.first < 0 || a.nRange < 1 || a.first > a.n - a.nRange || a.cap < 0 || (a.cap > 0 && !a.list) || a.threshold != a.threshold) return hipErrorInvalidValue;
+    const long long chunks = meterSelectChunks(a.nRange);
+    if (chunks >= ((long long)1 << 31)) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(fx_tone_count, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fx_meter_scan, dim3(1), dim3(kLanes), 0, stream, a.offsets, chunks);
+    if ((e = hipGetLastError()) != hipSuccess || a.cap == 0) return e;   // (a count query emits nothing)
+    hipLaunchKernelGGL(fx_tone_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
     return hipGetLastError();
 }
 

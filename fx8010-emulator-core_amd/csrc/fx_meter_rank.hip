@@ -1,5 +1,5 @@
 // fx_meter_rank.hip — the kernels behind the meter ranks (fx_meter_rank.hpp): the first k candidates of a range under the order
-// (V, n), chosen on the device.  gfx950, wave64, workgroups of 256 lanes, a chunk of 256 instances per workgroup as in the selects.
+// (V, n), chosen on the device - V of one of four families (fx_meter_value.hpp).  gfx950, wave64, workgroups of 256 lanes, a chunk of 256 instances per workgroup as in the selects.
 // Plain HIP C++, vector loads and stores only.
 //
 // The key.  V + 0.0 (so that -0.0 cannot appear), its bits with the sign-flip transform - a negative value has all bits
@@ -24,8 +24,9 @@
 // run.  The host sorts the R pairs into rank order.
 //
 // Resource usage (-O3, gfx950, from -Rpass-analysis=kernel-resource-usage), VGPRs / SGPRs / scratch bytes per lane / LDS bytes per
-// workgroup: fx_rank_hist 17 / 44 / 0 / 3 088, fx_rank_count 16 / 37 / 0 / 2 096, fx_rank_scan 26 / 34 / 0 / 2 048, fx_rank_emit
-// 38 / 42 / 0 / 32; eight wavefronts per SIMD each.
+// workgroup: fx_rank_hist 24 / 44 / 0 / 3 088, fx_rank_count 20 / 41 / 0 / 2 096, fx_rank_scan 26 / 34 / 0 / 2 048, fx_rank_emit
+// 38 / 44 / 0 / 32; eight wavefronts per SIMD each (with the fourth family, the tone rows of fx_meter_tone.hpp, compiled in; 17,
+// 16, 26 and 38 VGPRs with three).
 #include <hip/hip_runtime.h>
 
 #include "fx_meter.hpp"
@@ -52,7 +53,8 @@ __device__ __forceinline__ RankLane rankLane(const MeterRankArgs& a, long long i
     const long long col = a.first + i;
     if (col >= a.n) return r;   // (cannot be: first + nRange <= n.  The padding is never a candidate.)
     const double v = a.family == kRankMeter ? meterValue(a.rows, a.nPad, a.channels, a.stat, col)
-                     : a.family == kRankMatch ? matchValue(a.rows, a.nPad, a.channels, a.stat, col) : levelValue(a.rows, a.nPad, a.channels, a.stat, col);
+                     : a.family == kRankMatch ? matchValue(a.rows, a.nPad, a.channels, a.stat, col)
+                     : a.family == kRankLevel ? levelValue(a.rows, a.nPad, a.channels, a.stat, col) : toneValue(a.rows, a.nPad, a.channels, a.stat, col);
     r.cand = a.below ? v < a.threshold : v >= a.threshold;
     unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
     u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
@@ -214,8 +216,8 @@ __global__ __launch_bounds__(kLanes) void fx_rank_emit(MeterRankArgs a) {
 }  // namespace
 
 hipError_t launchMeterRank(const MeterRankArgs& a, hipStream_t stream) {
-    if (!a.rows || !a.stage || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.family < kRankMeter || a.family > kRankLevel) return hipErrorInvalidValue;
-    if (a.stat < 0 || a.stat > (a.family == kRankMeter ? 3 : 1)) return hipErrorInvalidValue;
+    if (!a.rows || !a.stage || a.n < 1 || a.nPad < a.n || a.channels < 1 || a.channels > 4 || a.family < kRankMeter || a.family > kRankTone) return hipErrorInvalidValue;
+    if (a.stat < 0 || a.stat > (a.family == kRankMeter ? 3 : a.family == kRankTone ? kMeterMaxTones - 1 : 1)) return hipErrorInvalidValue;
     if (a.first < 0 || a.nRange < 1 || a.first > a.n - a.nRange || a.k < 0 || a.room != (a.k < a.nRange ? a.k : a.nRange) || a.threshold != a.threshold) return hipErrorInvalidValue;
     const long long chunks = meterSelectChunks(a.nRange);
     if (chunks >= ((long long)1 << 31)) return hipErrorInvalidValue;
@@ -233,5 +235,8 @@ hipError_t launchMeterRank(const MeterRankArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(fx_rank_emit, dim3((unsigned)chunks), dim3(kLanes), 0, stream, a);
     return hipGetLastError();
 }
+
+// (the tone family, fx_meter_tone.hpp: the same launches)
+hipError_t launchToneRank(const MeterRankArgs& a, hipStream_t stream) { return a.family == kRankTone ? launchMeterRank(a, stream) : hipErrorInvalidValue; }
 
 }  // namespace fx

@@ -23,7 +23,7 @@ constexpr int kMeterRankPasses = 64 / kMeterRankDigitBits;         // digits of 
 constexpr int kMeterRankBins = 1 << kMeterRankDigitBits;           // = the lanes of a workgroup: one bin per lane in the pick
 static_assert(kMeterRankBins == kMeterSelectChunk, "the pick scans the bins with one lane each");
 
-enum { kRankMeter = 0, kRankMatch = 1, kRankLevel = 2 };           // MeterRankArgs::family
+enum { kRankMeter = 0, kRankMatch = 1, kRankLevel = 2, kRankTone = 3 };   // MeterRankArgs::family
 
 // The staging block of one rank, 64-bit words, in this order (the part the host copies back comes first):
 //   result   [kRankResultWords]          M (the candidates), R = min(k, M) (the pairs written), T (the key of the R-th), the number
@@ -43,7 +43,7 @@ constexpr size_t rankEqualOff(long long nRange, long long room) { return rankBel
 constexpr size_t meterRankStageWords(long long nRange, long long room) { return rankEqualOff(nRange, room) + (size_t)meterSelectChunks(nRange); }
 
 struct MeterRankArgs {
-    const void* rows;              // [channels] x the rows of the family (device memory): accumulator, match or level rows
+    const void* rows;              // [channels] x the rows of the family (device memory): accumulator, match or level rows; the tone block
     unsigned long long* stage;     // device memory, meterRankStageWords(nRange, room) words, laid out as above
     long long n, nPad;             // instances, and the pitch of a row
     long long first, nRange;       // LOCAL columns first .. first + nRange - 1 are looked at; first + nRange <= n
@@ -52,8 +52,8 @@ struct MeterRankArgs {
     long long room;                // min(k, nRange): pairs the staging has room for
     double threshold;              // not NaN; +-Inf allowed
     int channels;                  // 1..4
-    int family;                    // kRankMeter / kRankMatch / kRankLevel
-    int stat;                      // the family's: 0..3, 0..1, 0..1
+    int family;                    // kRankMeter / kRankMatch / kRankLevel / kRankTone
+    int stat;                      // the family's: 0..3, 0..1, 0..1, the tone 0..K-1
     int below;                     // 0: V >= threshold is a candidate; 1: V < threshold
     int largest;                   // 0: V ascending; 1: V descending.  Ties go to the smaller instance number either way
 };

@@ -379,21 +379,29 @@ int64_t Sharded::meterSelectLevel(int stat, double threshold, int64_t first, int
     return selectRange(SelectRows::kLevel, stat, threshold, first, nRange, list, cap, flags);
 }
 
-// rows: kMatch over the match rows of a target (Batch::matchSelect), kLevel over the level rows (Batch::levelSelect) - other
+int64_t Sharded::meterSelectTone(int tone, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
+    return selectRange(SelectRows::kTone, tone, threshold, first, nRange, list, cap, flags);
+}
+
+// rows: kMatch over the match rows of a target (Batch::matchSelect), kLevel over the level rows (Batch::levelSelect), kTone over
+// the tone rows (Batch::toneSelect) - other
 // refusals and another predicate, the same ranges and joins
 int64_t Sharded::selectRange(SelectRows rows, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags) {
     Serial serial(api_);
     lastError_.clear();
-    const bool match = rows == SelectRows::kMatch, level = rows == SelectRows::kLevel;
-    if ((match ? Batch::checkMatchSelect : level ? Batch::checkLevelSelect : Batch::checkMeterSelect)(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
+    const bool match = rows == SelectRows::kMatch, level = rows == SelectRows::kLevel, tone = rows == SelectRows::kTone;
+    if ((match ? Batch::checkMatchSelect : level ? Batch::checkLevelSelect : tone ? Batch::checkToneSelect : Batch::checkMeterSelect)(stat, threshold, first, nRange, n_, list, cap, flags, &lastError_) != 0) return FX_E_ARG;
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
     if (match && !front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
     if (level && !front().meterLevelOn()) { lastError_ = "level meters: the mode is off (fxb_meter_set_level)"; return FX_E_ARG; }
+    if (tone && front().meterTones() == 0) { lastError_ = "tone meters: the mode is off (fxb_meter_set_tones)"; return FX_E_ARG; }
+    if (tone && stat >= front().meterTones()) { lastError_ = "meter_select_tone: tone must lie in 0 .. n_tones - 1"; return FX_E_ARG; }
     if (nRange == 0) return 0;
     const bool below = (flags & FXB_METER_BELOW) != 0;
     const auto select = [&](Batch& b, int64_t from, int64_t count, int64_t firstGlobal, int64_t* out) {
         return match ? b.matchSelect(stat, threshold, below, from, count, firstGlobal, out, cap)
-                     : level ? b.levelSelect(stat, threshold, below, from, count, firstGlobal, out, cap) : b.meterSelect(stat, threshold, below, from, count, firstGlobal, out, cap);
+                     : level ? b.levelSelect(stat, threshold, below, from, count, firstGlobal, out, cap)
+                     : tone  ? b.toneSelect(stat, threshold, below, from, count, firstGlobal, out, cap) : b.meterSelect(stat, threshold, below, from, count, firstGlobal, out, cap);
     };
     if (shards_.size() == 1) {
         if (const int rc = runOn(0, [&](Batch& b) { return b.reserveMeterSelect(nRange, cap); })) return rc;
@@ -442,6 +450,8 @@ int64_t Sharded::meterRank(int family, int stat, int64_t k, double threshold, in
     if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
     if (family == kRankMatch && !front().meterTargetSet()) { lastError_ = "meter target: no target is set (fxb_meter_set_target)"; return FX_E_ARG; }
     if (family == kRankLevel && !front().meterLevelOn()) { lastError_ = "level meters: the mode is off (fxb_meter_set_level)"; return FX_E_ARG; }
+    if (family == kRankTone && front().meterTones() == 0) { lastError_ = "tone meters: the mode is off (fxb_meter_set_tones)"; return FX_E_ARG; }
+    if (family == kRankTone && stat >= front().meterTones()) { lastError_ = "meter_rank_tone: tone must lie in 0 .. n_tones - 1"; return FX_E_ARG; }
     if (nRange == 0) return 0;
     const bool below = (flags & FXB_METER_BELOW) != 0, largest = (flags & FXB_METER_LARGEST) != 0;
     if (shards_.size() == 1) {
@@ -553,6 +563,46 @@ int Sharded::meterReadLevelList(const int64_t* list, int64_t count, float* level
     // every shard is asked for its staging first: with reset, no shard zeroes a word unless all of them can answer
     if (const int rc = fan([&](int k, Batch& b) { return b.reserveMeterList(l.count(k), true); })) return rc;
     return fan([&](int k, Batch& b) { return b.meterReadLevelList(l.list(k), l.pos(k), l.count(k), count, level, quiet, reset); });
+}
+
+int Sharded::meterSetTones(int tones, const double* coeff, unsigned flags) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    double canonical[kMeterMaxTones] = {};
+    if (Batch::checkMeterTones(tones, coeff, flags, canonical, &lastError_) != 0) return FX_E_ARG;
+    if (const int rc = reserveOnAll([tones](int, Batch& b) { return b.reserveMeterTones(tones); }, [](Batch& b) { b.releaseMeterTones(); })) return rc;
+    return fan([&](int, Batch& b) { return b.setMeterTones(tones, canonical); });
+}
+int Sharded::meterClearTones() {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([](int, Batch& b) { return b.clearMeterTones(); });
+}
+int Sharded::meterGetTones(int* tones, double* coeff) {
+    Serial serial(api_);
+    lastError_.clear();
+    return runOn(0, [&](Batch& b) { return b.getMeterTones(tones, coeff); });
+}
+int Sharded::meterReadTones(double* s1, double* s2, double* power, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    return fan([&](int k, Batch& b) {
+        const int64_t first = shards_[(size_t)k]->first;
+        return b.meterReadTones(s1 ? s1 + first : nullptr, s2 ? s2 + first : nullptr, power ? power + first : nullptr, reset, n_);
+    });
+}
+int Sharded::meterReadTonesList(const int64_t* list, int64_t count, double* s1, double* s2, double* power, bool reset) {
+    Serial serial(api_);
+    lastError_.clear();
+    if (Batch::checkMeterList("meter_read_tones_list", list, count, n_, reset, &lastError_) != 0) return FX_E_ARG;
+    if (!front().metering()) { lastError_ = "meters: metering is off (fxb_meter_enable)"; return FX_E_ARG; }
+    if (front().meterTones() == 0) { lastError_ = "tone meters: the mode is off (fxb_meter_set_tones)"; return FX_E_ARG; }
+    if (count == 0) return 0;
+    const ShardLists l(*this, list, count);
+    // every shard is asked for its staging first: with reset, no shard zeroes a word unless all of them can answer
+    if (const int rc = fan([&](int k, Batch& b) { return b.reserveToneList(l.count(k)); })) return rc;
+    return fan([&](int k, Batch& b) { return b.meterReadTonesList(l.list(k), l.pos(k), l.count(k), count, s1, s2, power, reset); });
 }
 
 int Sharded::meterSetTarget(const float* target, int64_t nSamples, int64_t group, unsigned flags) {
@@ -1284,6 +1334,7 @@ int64_t Sharded::info(int what) {
         what == FXB_INFO_METER_TARGET_LAUNCHES || what == FXB_INFO_METER_MATCH_SELECTS || what == FXB_INFO_METER_MATCH_BESTS ||
         what == FXB_INFO_METER_LEVEL_LAUNCHES || what == FXB_INFO_METER_LEVEL_SELECTS || what == FXB_INFO_METER_LEVEL_LIST_READS ||
         what == FXB_INFO_METER_RANKS || what == FXB_INFO_METER_MATCH_RANKS || what == FXB_INFO_METER_LEVEL_RANKS ||
+        what == FXB_INFO_METER_TONE_LAUNCHES || what == FXB_INFO_METER_TONE_SELECTS || what == FXB_INFO_METER_TONE_LIST_READS || what == FXB_INFO_METER_TONE_RANKS ||
         what == FXB_INFO_BANK_STORES || what == FXB_INFO_BANK_RECALLS || what == FXB_INFO_BANK_BYTES ||
         what == FXB_INFO_XLATE_QUIET_LEFT || what == FXB_INFO_XLATE_QUIET_REPAIRS) {
         int64_t sum = 0;

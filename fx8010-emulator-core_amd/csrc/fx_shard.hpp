@@ -114,6 +114,16 @@ public:
     int meterReadLevel(float* level, uint32_t* quiet, bool reset);
     int meterReadLevelList(const int64_t* list, int64_t count, float* level, uint32_t* quiet, bool reset);
     int64_t meterSelectLevel(int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
+    // tone meters (Batch "Tone meters"): the arguments are checked for the whole handle; every shard reserves its tone block
+    // before any shard changes - FX_E_MEMORY leaves the mode as it was everywhere.  get is shard 0's.  readTones gives each shard
+    // its columns like meterReadLevel, readTonesList its entries like meterReadLevelList; selectTone is meterSelect with the tone
+    // predicate; the rank goes through meterRank with the family kRankTone.
+    int meterSetTones(int tones, const double* coeff, unsigned flags);
+    int meterClearTones();
+    int meterGetTones(int* tones, double* coeff);
+    int meterReadTones(double* s1, double* s2, double* power, bool reset);
+    int meterReadTonesList(const int64_t* list, int64_t count, double* s1, double* s2, double* power, bool reset);
+    int64_t meterSelectTone(int tone, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     // meter ranks (Batch "Meter ranks"; family: kRankMeter / kRankMatch / kRankLevel): the arguments are checked for the whole
     // handle; every shard reserves the staging of its part of the range before any shard launches; each shard answers with its own
     // first min(k, M_s) pairs, and the parts are merged under the same total order on global instance numbers - the first k of
@@ -222,7 +232,7 @@ public:
 
 private:
     int loadRecords(const int64_t* list, int64_t count, const void* buf, int64_t bytes, bool rotated);
-    enum class SelectRows { kMeter, kMatch, kLevel };
+    enum class SelectRows { kMeter, kMatch, kLevel, kTone };
     int64_t selectRange(SelectRows rows, int stat, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags);
     int registersList(bool set, const char* const* keys, int nKeys, const int64_t* list, int64_t count, const float* in, float* out);
     int tramList(int which, const int64_t* list, int64_t count, int first, int nWords, const float* in, float* out, unsigned flags, bool set);

@@ -403,6 +403,39 @@ public:
         if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterRankLevel: ") + fxb_last_error(h_));
         return m;
     }
+    // Tone meters (include/fx8010_amd.h "Tone meters"): a Goertzel recurrence per probe frequency, channel and instance; each
+    // coefficient is c = 2 cos(2 pi f / fs).  meterReadTones fills [tones][channels][instances] arrays of doubles (any may be
+    // null), meterReadTonesList [tones][channels][list.size()]; meterSelectTone / meterRankTone are meterSelect / fxb_meter_rank
+    // over the channel maximum of the power at `tone`.
+    void meterSetTones(const std::vector<double>& coeff) {
+        if (fxb_meter_set_tones(h_, (int)coeff.size(), coeff.data(), 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterSetTones: ") + fxb_last_error(h_));
+    }
+    std::vector<double> meterGetTones() {
+        int n = 0;
+        std::vector<double> coeff(FXB_METER_MAX_TONES);
+        if (fxb_meter_get_tones(h_, &n, coeff.data()) < 0) throw std::runtime_error(std::string("FX8010Batch::meterGetTones: ") + fxb_last_error(h_));
+        coeff.resize((size_t)n);
+        return coeff;
+    }
+    void meterClearTones() {
+        if (fxb_meter_clear_tones(h_) < 0) throw std::runtime_error(std::string("FX8010Batch::meterClearTones: ") + fxb_last_error(h_));
+    }
+    void meterReadTones(double* s1, double* s2, double* power, bool reset = false) {
+        if (fxb_meter_read_tones(h_, s1, s2, power, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterReadTones: ") + fxb_last_error(h_));
+    }
+    void meterReadTonesList(const std::vector<int64_t>& list, double* s1, double* s2, double* power, bool reset = false) {
+        if (fxb_meter_read_tones_list(h_, list.data(), (int64_t)list.size(), s1, s2, power, reset ? 1 : 0) < 0) throw std::runtime_error(std::string("FX8010Batch::meterReadTonesList: ") + fxb_last_error(h_));
+    }
+    int64_t meterSelectTone(int tone, double threshold, int64_t first, int64_t nRange, int64_t* list, int64_t cap, unsigned flags = 0) {
+        const int64_t m = fxb_meter_select_tone(h_, tone, threshold, first, nRange, list, cap, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterSelectTone: ") + fxb_last_error(h_));
+        return m;
+    }
+    int64_t meterRankTone(int tone, int64_t k, double threshold, int64_t first, int64_t nRange, int64_t* list, double* value, unsigned flags = 0) {
+        const int64_t m = fxb_meter_rank_tone(h_, tone, k, threshold, first, nRange, list, value, flags);
+        if (m < 0) throw std::runtime_error(std::string("FX8010Batch::meterRankTone: ") + fxb_last_error(h_));
+        return m;
+    }
     // Per-instance state by list (include/fx8010_amd.h "Per-instance state"): dst[k] becomes a copy of src[k]; the listed instances
     // become fresh ones (registers as last broadcast, delay memory cleared, delay-line positions kept); their records to an image
     // of fxb_instance_image_size bytes and back into any batch with the same program that has run as many samples.  Copy and

@@ -34,6 +34,7 @@ INFO = {
     "meter_level_launches": 64, "meter_level_selects": 65, "meter_level_list_reads": 66,
     "bank_slots": 67, "bank_stores": 68, "bank_recalls": 69, "bank_bytes": 70,
     "meter_ranks": 71, "meter_match_ranks": 72, "meter_level_ranks": 73,
+    "meter_tone_launches": 74, "meter_tone_selects": 75, "meter_tone_list_reads": 76, "meter_tone_ranks": 77,
 }
 
 BUS_SHARED_IN, BUS_MIX_OUT = 1, 2  # FXB_BUS_* of include/fx8010_amd.h
@@ -44,6 +45,7 @@ METER_LARGEST = 2  # FXB_METER_LARGEST: the flag of the meter_rank calls (the sa
 METER_TARGET_LOOP = 1  # FXB_METER_TARGET_LOOP: the flag of meter_set_target
 MATCH_ERROR, MATCH_CROSS = 0, 1  # FXB_MATCH_*: the `stat` of meter_select_match and meter_best
 MATCH_LARGEST = 2  # FXB_MATCH_LARGEST: the flag of meter_best
+METER_MAX_TONES = 8  # FXB_METER_MAX_TONES: the tones of meter_set_tones
 LEVEL_ENVELOPE, LEVEL_QUIET = 0, 1  # FXB_LEVEL_*: the `stat` of meter_select_level
 BANK_BAD_POSITION, BANK_PHASE, BANK_NO_RING = 1, 2, 3  # FXB_BANK_*: the `reason` of bank_status
 
@@ -67,6 +69,7 @@ SYMBOLS = [
     "fxb_meter_set_target", "fxb_meter_clear_target", "fxb_meter_target_seek", "fxb_meter_target_pos", "fxb_meter_read_match", "fxb_meter_select_match", "fxb_meter_best",
     "fxb_meter_set_level", "fxb_meter_clear_level", "fxb_meter_get_level", "fxb_meter_read_level", "fxb_meter_read_level_list", "fxb_meter_select_level",
     "fxb_meter_rank", "fxb_meter_rank_match", "fxb_meter_rank_level",
+    "fxb_meter_set_tones", "fxb_meter_get_tones", "fxb_meter_clear_tones", "fxb_meter_read_tones", "fxb_meter_read_tones_list", "fxb_meter_select_tone", "fxb_meter_rank_tone",
     "fxb_instruction_counter", "fxb_instruction_counter_i", "fxb_ood_flags", "fxb_error_count", "fxb_error_desc",
     "fxb_error_row", "fxb_control_count", "fxb_control_at", "fxb_meta_get", "fxb_ready", "fxb_last_error", "fxb_tier_note",
     "fxb_last_kernel_ms", "fxb_info", "fxb_device_count", "fxb_version", "fxb_host_alloc", "fxb_host_free",
@@ -144,8 +147,10 @@ def load():
     sig("fxb_meter_read_match", i32, vp, vp, vp, i32); sig("fxb_meter_select_match", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint); sig("fxb_meter_best", i32, vp, i32, i64, vp, vp, C.c_uint)
     sig("fxb_meter_set_level", i32, vp, f32, f32, C.c_uint); sig("fxb_meter_clear_level", i32, vp); sig("fxb_meter_get_level", i32, vp, vp, vp)
     sig("fxb_meter_read_level", i32, vp, vp, vp, i32); sig("fxb_meter_read_level_list", i32, vp, vp, i64, vp, vp, i32); sig("fxb_meter_select_level", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint)
-    for name in ("fxb_meter_rank", "fxb_meter_rank_match", "fxb_meter_rank_level"):
+    for name in ("fxb_meter_rank", "fxb_meter_rank_match", "fxb_meter_rank_level", "fxb_meter_rank_tone"):
         sig(name, i64, vp, i32, i64, C.c_double, i64, i64, vp, vp, C.c_uint)
+    sig("fxb_meter_set_tones", i32, vp, i32, vp, C.c_uint); sig("fxb_meter_get_tones", i32, vp, vp, vp); sig("fxb_meter_clear_tones", i32, vp)
+    sig("fxb_meter_read_tones", i32, vp, vp, vp, vp, i32); sig("fxb_meter_read_tones_list", i32, vp, vp, i64, vp, vp, vp, i32); sig("fxb_meter_select_tone", i64, vp, i32, C.c_double, i64, i64, vp, i64, C.c_uint)
     sig("fxb_instruction_counter", i64, vp); sig("fxb_instruction_counter_i", i64, vp, i64)
     sig("fxb_ood_flags", C.c_uint32, vp); sig("fxb_ready", i32, vp); sig("fxb_last_error", cp, vp); sig("fxb_tier_note", i32, vp, C.c_char_p, i32)
     sig("fxb_last_kernel_ms", f32, vp); sig("fxb_info", i64, vp, i32)
@@ -1168,6 +1173,60 @@ class Batch(_Reports):
         """meter_rank over the level meters: V is the channel maximum of the envelope (LEVEL_ENVELOPE) or the channel MINIMUM of the
         quiet run (LEVEL_QUIET) - the k quietest voices are meter_rank_level(LEVEL_ENVELOPE, k).  (M, list, values)."""
         return self._meter_rank("meter_rank_level", stat, k, threshold, below, largest, first, n_range)
+
+    def meter_set_tones(self, coeff):
+        """Turn the tone meters on (include/fx8010_amd.h "Tone meters"): from now on every block's meter launch is followed by a
+        Goertzel recurrence per (tone, channel, instance) - s0 = (y + c * s1) - s2 in fp64, nothing fused - for the 1 .. 8
+        coefficients given, each c = 2 * cos(2 * pi * f / fs) with -2 <= c <= 2.  Every call waits as sync() does and takes the
+        rows into force zeroed."""
+        c = np.ascontiguousarray(coeff, dtype=np.float64).reshape(-1)
+        return self._check(self._lib.fxb_meter_set_tones(self._h, int(c.size), C.c_void_p(c.ctypes.data) if c.size else None, 0), "meter_set_tones")
+
+    def meter_clear_tones(self):
+        """Turn the tone meters off: the rows are freed; the other meters go on."""
+        return self._check(self._lib.fxb_meter_clear_tones(self._h), "meter_clear_tones")
+
+    def meter_get_tones(self):
+        """the coefficients in force, float64 [K]; an error while the tone meters are off"""
+        n, c = C.c_int(0), np.zeros(METER_MAX_TONES, dtype=np.float64)
+        self._check(self._lib.fxb_meter_get_tones(self._h, C.byref(n), C.c_void_p(c.ctypes.data)), "meter_get_tones")
+        return c[:n.value].copy()
+
+    def _tone_rows(self, width):
+        shape = (int(self.meter_get_tones().size), self.channels, width)
+        return {k: np.empty(shape, dtype=np.float64) for k in ("s1", "s2", "power")}
+
+    def meter_read_tones(self, reset=False):
+        """{"s1", "s2", "power"}, each float64 [K, channels, N] by global instance: the two words of every recurrence and
+        P = (s1*s1 + s2*s2) - (c*s1)*s2, about (A * n / 2) ** 2 after n samples of a sine of amplitude A at the probed bin.
+        Synchronous; reset zeroes the tone rows only."""
+        out = self._tone_rows(self.n)
+        self._check(self._lib.fxb_meter_read_tones(self._h, C.c_void_p(out["s1"].ctypes.data), C.c_void_p(out["s2"].ctypes.data), C.c_void_p(out["power"].ctypes.data), 1 if reset else 0), "meter_read_tones")
+        return out
+
+    def meter_read_tones_list(self, instances, reset=False):
+        """{"s1", "s2", "power"}, each [K, channels, len(instances)]: the tone meters of the listed instances, gathered on the
+        device.  An instance may repeat unless reset is set."""
+        lst = self._instance_list(instances)
+        out = self._tone_rows(int(lst.size))
+        ptrs = [C.c_void_p(out[k].ctypes.data) if lst.size else None for k in ("s1", "s2", "power")]
+        self._check(self._lib.fxb_meter_read_tones_list(self._h, C.c_void_p(lst.ctypes.data) if lst.size else None, int(lst.size), ptrs[0], ptrs[1], ptrs[2], 1 if reset else 0), "meter_read_tones_list")
+        return out
+
+    def meter_select_tone(self, tone, threshold, below=False, first=0, n_range=None, cap=None):
+        """meter_select over the tone meters: V is the maximum over the channels of the power at `tone`.  (list, M)."""
+        first = int(first)
+        n_range = self.n - first if n_range is None else int(n_range)
+        cap = n_range if cap is None else int(cap)
+        out = np.empty(max(min(cap, n_range), 0), dtype=np.int64)
+        m = self._check(int(self._lib.fxb_meter_select_tone(self._h, int(tone), float(threshold), first, n_range, C.c_void_p(out.ctypes.data) if out.size else None,
+                                                            cap, METER_BELOW if below else 0)), "meter_select_tone")
+        return out[:min(m, out.size)], m
+
+    def meter_rank_tone(self, tone, k, threshold=-np.inf, below=False, largest=False, first=0, n_range=None):
+        """meter_rank over the tone meters: V is the maximum over the channels of the power at `tone` - the k voices that ring
+        loudest at a pitch are meter_rank_tone(tone, k, largest=True).  (M, list, values)."""
+        return self._meter_rank("meter_rank_tone", tone, k, threshold, below, largest, first, n_range)
 
     def meter_samples(self):
         """sample periods metered since the last reset"""

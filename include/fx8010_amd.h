@@ -1042,6 +1042,58 @@ int64_t fxb_meter_select_level(fxb_handle* h, int stat, double threshold, int64_
 int64_t fxb_meter_rank(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);
 int64_t fxb_meter_rank_match(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);   /* stat: FXB_MATCH_ERROR / _CROSS; needs a target */
 int64_t fxb_meter_rank_level(fxb_handle* h, int stat, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);   /* stat: FXB_LEVEL_ENVELOPE / _QUIET; needs level meters */
+/* Tone meters: per-instance power at K probe frequencies, on the device.  Every other figure the device keeps per instance is
+ * broadband; the tone meters say where in the spectrum the energy sits - the gain of every variant of a sweep at a handful of
+ * frequencies, the voices that ring at a note's pitch or carry hum, the variants of a feedback network that build up at a
+ * resonance.  The answer is a Goertzel recurrence per (tone, channel, instance): two fp64 words of state and three fp64 operations
+ * per sample, no table and no position - the phase lives in the state - so the figures do not depend on how a stream is cut.  With
+ * the mode off nothing changes: the same kernels, the same arguments, no allocation.
+ *
+ * The definition.  fxb_meter_set_tones(h, n_tones, coeff, flags) turns the mode on.  1 <= n_tones <= FXB_METER_MAX_TONES;
+ *   coeff[k] is a finite double with -2 <= coeff[k] <= 2 (-0.0 is taken as +0.0); `flags` must be 0.  The caller computes
+ *   c = 2 cos(2 pi f / fs); the library takes the double as given, so no libm call is part of the definition.  Each (tone k,
+ *   channel c, instance n) gets two fp64 words s1 and s2, +0.0 after a reset.  For every output word y of that column, in sample
+ *   order, with fin exactly that of "Output meters":
+ *       x  = fin ? (double)y : +0.0     (the signed word; a NaN or an infinity contributes nothing, but time still passes)
+ *       p  = c * s1                     (one fp64 multiply)
+ *       q  = x + p                      (one fp64 add)
+ *       s0 = q - s2                     (one fp64 subtract)
+ *       s2 = s1 ;  s1 = s0
+ *   Nothing is fused: the library is built with -ffp-contract=off and the contract depends on it.  The figure is
+ *       P = (s1*s1 + s2*s2) - (c*s1)*s2
+ *   five fp64 operations in exactly that order.  After n samples of A sin(2 pi k t / n + phi) probed at bin k (c = 2 cos(2 pi k /
+ *   n)), P is about (A n / 2)^2.  With |c| <= 2 the impulse response of the recurrence is bounded by its index, so |s1| <=
+ *   n (n + 1) / 2 * max|y|: from fp32 inputs no reachable sample count makes a word non-finite or P a NaN (the ranks' rule "no V
+ *   is ever NaN" rests on this), and that is why coefficients beyond +-2 are refused.  P may come out a few ulps negative; it is
+ *   ordered as the real number it is.  The four existing accumulators, the match rows and the level rows are taken exactly as
+ *   without the mode.
+ *
+ * fxb_meter_set_tones needs metering on (FX_E_ARG otherwise).  Every successful call waits as fxb_sync does and takes the rows
+ *   into force zeroed: accumulators of other coefficients mean nothing.  The tone block - a header with the coefficients, then
+ *   [num_channels][n_tones][2][nPad] doubles - is allocated on every shard before any shard changes: FX_E_MEMORY leaves the mode as
+ *   it was everywhere.  All allocation of the feature happens here, never in a block.  A refusal changes nothing.  While the mode
+ *   is on, every block's meter launch is followed by one launch of fx_meter_tone on the same stream, with the coefficients by value.
+ * fxb_meter_get_tones: the mode in force - *n_tones and coeff[0 .. n_tones - 1] (either pointer may be NULL; coeff must have room
+ *   for FXB_METER_MAX_TONES); FX_E_ARG while the mode is off.  fxb_meter_clear_tones and fxb_meter_enable(h, 0) free the rows.
+ * Resets.  fxb_meter_read(..., reset = 1) and a program load zero the tone rows with the others and keep the mode.
+ *   fxb_meter_reset_list zeroes the listed columns by one more stores-only launch (fx_tone_zero) inside the same event frame as
+ *   its siblings.  Instance copy, reset, save, load and the record bank leave the tone rows alone; the state image does not hold them.
+ * fxb_meter_read_tones: s1, s2, power are [n_tones][num_channels][N] doubles by (global) instance; any of the three may be NULL.
+ *   Waits as fxb_sync does.  reset != 0 zeroes only the tone rows.  `power` is P, computed by the one function that defines it.
+ * fxb_meter_read_tones_list: [n_tones][num_channels][n_list], with the list rules of fxb_meter_read_level_list: a list may repeat
+ *   an instance unless reset != 0; with reset, the lane that has read a column stores its zeros.
+ * fxb_meter_select_tone / fxb_meter_rank_tone: fxb_meter_select's and fxb_meter_rank's contracts over V(n) = the maximum over the
+ *   channels of P(tone, c, n).  `tone` outside 0 .. n_tones - 1 is FX_E_ARG; so is the mode off.
+ * FXB_INFO_METER_TONE_LAUNCHES counts the launches of fx_meter_tone; FXB_INFO_METER_TONE_SELECTS / _TONE_LIST_READS / _TONE_RANKS
+ *   the calls that launched.  All are summed over shards. */
+#define FXB_METER_MAX_TONES 8
+int     fxb_meter_set_tones(fxb_handle* h, int n_tones, const double* coeff, unsigned flags);
+int     fxb_meter_get_tones(fxb_handle* h, int* n_tones, double* coeff);           /* FX_E_ARG while tone meters are off */
+int     fxb_meter_clear_tones(fxb_handle* h);
+int     fxb_meter_read_tones(fxb_handle* h, double* s1, double* s2, double* power, int reset);     /* [K][C][N]; pointers may be NULL */
+int     fxb_meter_read_tones_list(fxb_handle* h, const int64_t* list, int64_t n_list, double* s1, double* s2, double* power, int reset); /* [K][C][n_list] */
+int64_t fxb_meter_select_tone(fxb_handle* h, int tone, double threshold, int64_t first, int64_t n_range, int64_t* list, int64_t cap, unsigned flags);
+int64_t fxb_meter_rank_tone(fxb_handle* h, int tone, int64_t k, double threshold, int64_t first, int64_t n_range, int64_t* list, double* value, unsigned flags);
 int fxb_sync(fxb_handle* h);
 /* executed instructions (reference counting: END and SKIP count, skipped ones do not):
  * summed over all instances / of one instance */
@@ -1154,7 +1206,11 @@ enum {
     FXB_INFO_TRACK_LIST_EXPANDS = 60,  /* blocks that launched the expansion of list schedules (fx_track_hold, fx_track_scatter): once per block and shard, summed over shards */
     FXB_INFO_METER_RANKS = 71,           /* calls of fxb_meter_rank that launched (fx_rank_hist / _count / _scan / _emit) since creation (summed over shards) */
     FXB_INFO_METER_MATCH_RANKS = 72,     /* calls of fxb_meter_rank_match that launched since creation (summed over shards) */
-    FXB_INFO_METER_LEVEL_RANKS = 73      /* calls of fxb_meter_rank_level that launched since creation (summed over shards) */
+    FXB_INFO_METER_LEVEL_RANKS = 73,     /* calls of fxb_meter_rank_level that launched since creation (summed over shards) */
+    FXB_INFO_METER_TONE_LAUNCHES = 74,   /* launches of the kernel fx_meter_tone - behind the meter launch of a block while tone meters are on (fxb_meter_set_tones) - since creation (summed over shards) */
+    FXB_INFO_METER_TONE_SELECTS = 75,    /* calls of fxb_meter_select_tone that launched (fx_tone_count / fx_meter_scan / fx_tone_emit) since creation (summed over shards) */
+    FXB_INFO_METER_TONE_LIST_READS = 76, /* calls of fxb_meter_read_tones_list that launched (fx_tone_gather) since creation (summed over shards) */
+    FXB_INFO_METER_TONE_RANKS = 77       /* calls of fxb_meter_rank_tone that launched since creation (summed over shards) */
 };
 int64_t fxb_info(fxb_handle* h, int what);
 /* Which tier runs the program as it stands, in words - "translated to gfx950 code (fx_xlate_v128, 8 stages)", "interpreter
